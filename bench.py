@@ -10,11 +10,23 @@ gather of every rank's packed post-NMS detections to rank 0 over RCCL — the no
 channel plan, synth.py) are broadcast from rank 0 once before timing.  Weak scaling:
 64 frames per GPU at every N.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--dump-outputs DIR] [--full]
 N>1 is launched by the driver through torch.distributed.run (one process per GPU); when
 started by hand with --gpus N>1 it relaunches itself that way.
 
-Rank 0 prints one JSON line: images/s for the whole job, plus
+A plain run does only what the headline needs: set-up, W warm-up steps, the pre-heat, the K
+timed steps, then rank 0 prints one JSON line: images/s for the whole job (`value`), the
+milliseconds one timed step took (`ms_per_step`), the per-rank breakdown of those steps.
+--dump-outputs DIR (rank 0) writes what the last timed step returned, as .npy: detections
+[P, 6] float64 (class, score, left, top, right, bottom; image-major), counts [images]
+float64 (negative: that image's error code) and outputs [B,13,13,125] float32, rank 0's raw
+network output of that step; with --gather outputs, outputs is the gathered [images,13,13,125].
+Frames and weights are seeded: the same arguments give the same inputs in every run.
+
+--full adds to the line every other measurement (HIP events and clock stamps inside the timed
+region, then runs of their own: the sustained window that checks the headline (`stable`; when
+it is more than 2 % slower, `value` is the lower of the two rates), the dominant kernel's
+shader clock, batch-1 latency, end-to-end from host frames, the unfused and fp16 plans), and
   roofline      the dominant kernel (conv7's GEMM, M=64*169, N=1024, K=9216): executed flops /
                 its mean HIP-event duration inside the timed region, vs the MFMA peak it runs on
                 (MI355X_MICROARCH.md): the x3 conv (default) executes 6 x 2*M*N*K bf16 MFMA flops
@@ -61,6 +73,14 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64, help="frames per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (roofline, per-kernel times, sustained "
+                         "window, shader clock, batch-1 latency, end-to-end, unfused / fp32-MFMA / fp16 plans, "
+                         "CPU baseline); the --no-*, --kernels, --sustained and --cpu-seconds options select "
+                         "among these and have no effect without it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step returned to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a fixed seeded sample of a larger array)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="bound on the CPU-baseline sample")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency measurement")
@@ -75,14 +95,50 @@ def parse():
                     help="seconds of back-to-back steps before the timed region (the clock the chip holds "
                          "under sustained load: MI355X_MICROARCH DVFS give-back), independent of --warmup")
     ap.add_argument("--sustained", type=float, default=2.0,
-                    help="seconds of steps after the timed region for the `sustained` field (0: skip)")
+                    help="--full: seconds of steps after the timed region for the `sustained` field (0: skip)")
     ap.add_argument("--gather", choices=("detections", "outputs"), default="detections",
                     help="per step, gather post-NMS detections (on-GPU postprocessing, the north star's "
                          "detection gather) or the raw [n,13,13,125] outputs to rank 0")
     ap.add_argument("--dump-detections", default=None,
                     help="rank 0 writes the last timed step's gathered detections (packed rows, counts) "
                          "to this .npz (tests: multi-rank detections vs a single-process run)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.kernels and not args.full:
+        ap.error("--kernels needs --full")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: bound on all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array of `arrays` (name -> numpy) as path/<name>.npy, float32 kept,
+    everything else as float64.  Above DUMP_BYTES in all, an array larger than its equal share
+    is cut to a fixed sample of its elements (seeded, sorted flat indices, the same in every
+    run), written flat."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    share = DUMP_BYTES // max(len(arrays), 1)
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_BYTES
+    for k, a in arrays.items():
+        if over and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, size=share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def detections_as_float(dets_u8, counts):
+    """Gathered packed detections ([P, 40] uint8 dnn_detection rows, counts) -> ([P, 6] float64:
+    class, score, left, top, right, bottom; counts as float64)."""
+    import numpy as np
+    import dist as D
+    rows = np.ascontiguousarray(dets_u8).reshape(-1, 40).view(D.DETECTION_DTYPE).reshape(-1)
+    cols = [rows[f].astype(np.float64) for f in ("cls", "score", "left", "top", "right", "bottom")]
+    return np.stack(cols, 1).reshape(-1, 6), np.asarray(counts, dtype=np.float64)
 
 
 def relaunch(args):
@@ -547,7 +603,10 @@ def main():
         dbufs = [yolo_post.DetectionBuffers(runner.shard_cap, dev) for _ in range(runner.slots)]
         dbuf = dbufs[0]
 
+        last_out = [None]  # the output slot of the latest step whose postprocess was enqueued
+
         def post(out, n, slot, post_stream):
+            last_out[0] = out
             dbufs[slot].run(out.data_ptr(), n, post_stream)
             return dbufs[slot].pack(n, post_stream)
 
@@ -616,35 +675,48 @@ def main():
     # HIP events around the dominant kernel only (an event packet between every kernel costs
     # the step ~1 %); --kernels: around every kernel, for the per-kernel table.  Two clock-stamp
     # launches on the run stream bracket the timed forwards (the shader clock over the region)
-    clk = torch.zeros((2, CLOCK_WGS, 4), dtype=torch.int64, device=dev)
-    dnn_hip.clock_stamp(clk[0].data_ptr(), CLOCK_WGS, stream)  # (first launch outside the timed region)
-    plan.timing_begin(args.steps, only=None if args.kernels else DOMINANT)
+    # (--full only: a plain run puts nothing but the steps themselves into the timed region)
+    if args.full:
+        clk = torch.zeros((2, CLOCK_WGS, 4), dtype=torch.int64, device=dev)
+        dnn_hip.clock_stamp(clk[0].data_ptr(), CLOCK_WGS, stream)  # (first launch outside the timed region)
+        plan.timing_begin(args.steps, only=None if args.kernels else DOMINANT)
     torch.cuda.synchronize()
     if distributed:
         tdist.barrier()
     t0 = time.perf_counter()
-    dnn_hip.clock_stamp(clk[0].data_ptr(), CLOCK_WGS, stream)
-    full = None
+    if args.full:
+        dnn_hip.clock_stamp(clk[0].data_ptr(), CLOCK_WGS, stream)
+    last = None  # what the latest finished step returned on rank 0
     for _ in range(args.steps):
         r = one_step()
-        full = r if r is not None else full
-    dnn_hip.clock_stamp(clk[1].data_ptr(), CLOCK_WGS, stream)
+        last = r if r is not None else last
+    if args.full:
+        dnn_hip.clock_stamp(clk[1].data_ptr(), CLOCK_WGS, stream)
     r = drain()
-    full = r if r is not None else full
+    last = r if r is not None else last
     torch.cuda.synchronize()
     if distributed:
         tdist.barrier()
     elapsed = time.perf_counter() - t0
-    ms_dom, cnt_dom = plan.timing_end()
-    if args.kernels:
-        ms, cnt = ms_dom, cnt_dom
-    else:  # per-kernel table from 5 forwards after the timed region (events around every kernel)
-        plan.timing_begin(5)
-        for _ in range(5):
-            compute(frames, runner.out, B)
-        ms, cnt = plan.timing_end()
-        kidx = [k["name"] for k in plan.kernels()].index(DOMINANT)
-        ms[kidx], cnt[kidx] = ms_dom[kidx], cnt_dom[kidx]  # the dominant kernel: timed-region events
+    if rank == 0 and args.dump_outputs:
+        # now, before any later measurement reuses the output slots: the last timed step's result
+        if args.gather == "detections":
+            dets_f, counts_f = detections_as_float(*last)
+            dump_outputs(args.dump_outputs, {"detections": dets_f, "counts": counts_f,
+                                             "outputs": last_out[0][:runner.count].cpu().numpy()})
+        else:
+            dump_outputs(args.dump_outputs, {"outputs": last.cpu().numpy()})
+    if args.full:
+        ms_dom, cnt_dom = plan.timing_end()
+        if args.kernels:
+            ms, cnt = ms_dom, cnt_dom
+        else:  # per-kernel table from 5 forwards after the timed region (events around every kernel)
+            plan.timing_begin(5)
+            for _ in range(5):
+                compute(frames, runner.out, B)
+            ms, cnt = plan.timing_end()
+            kidx = [k["name"] for k in plan.kernels()].index(DOMINANT)
+            ms[kidx], cnt[kidx] = ms_dom[kidx], cnt_dom[kidx]  # the dominant kernel: timed-region events
     # per-rank breakdown of the timed steps (means per step, ms), gathered to every rank
     keys = ("wall_ms", "forward_ms", "post_ms", "gather_ms", "gather_span_ms", "host_blocked_ms")
     st = runner.stats() if args.gather == "detections" else {}
@@ -661,7 +733,7 @@ def main():
     # sustained: >= --sustained seconds of steps right after the timed region (same loop, events
     # around the dominant kernel only): the steady-state rate the headline must match
     sustained = None
-    n_sus = steps_for(args.sustained)
+    n_sus = steps_for(args.sustained) if args.full else 0
     if n_sus:
         if distributed:
             tdist.barrier()
@@ -691,84 +763,66 @@ def main():
     # the dominant kernel's own shader clock: clock stamps right before and after it in each of
     # a few further steps (outside its HIP-event window; a separate window, so the stamp launches
     # never touch the timed or sustained steps)
-    clk_region = dnn_hip.sclk_from_stamps(clk[0].cpu().numpy(), clk[1].cpu().numpy())
-    n_clk = 20
-    kbuf = torch.zeros((n_clk, 2, CLOCK_WGS, 4), dtype=torch.int64, device=dev)
-    plan.clock_begin(DOMINANT, kbuf.data_ptr(), n_clk, CLOCK_WGS)
-    for _ in range(n_clk):
-        one_step()
-    drain()
-    torch.cuda.synchronize()
-    runs_clk = plan.clock_end()
-    kb = kbuf.cpu().numpy()
-    per_run = [dnn_hip.sclk_from_stamps(kb[i, 0], kb[i, 1]) for i in range(runs_clk)]
-    per_run = [c for c in per_run if c]
-    clk_kernel = None
-    if per_run:
-        med = lambda v: sorted(v)[len(v) // 2]
-        clk_kernel = {"mean": med([c["mean"] for c in per_run]), "min": med([c["min"] for c in per_run]),
-                      "max": med([c["max"] for c in per_run]), "runs": len(per_run),
-                      "window_us": med([c["window_us"] for c in per_run]),
-                      "per_xcd": {str(x): round(med([c["per_xcd"][x] for c in per_run if x in c["per_xcd"]]), 4)
-                                  for x in per_run[0]["per_xcd"]}}
-
-    post_ms = None
-    if args.gather == "detections":  # the postprocess kernel alone, for the per-kernel table
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(10):
-            dbuf.run(runner.out.data_ptr(), runner.count, stream)
-        e1.record()
+    clk_region = clk_kernel = post_ms = None
+    if args.full:
+        clk_region = dnn_hip.sclk_from_stamps(clk[0].cpu().numpy(), clk[1].cpu().numpy())
+        n_clk = 20
+        kbuf = torch.zeros((n_clk, 2, CLOCK_WGS, 4), dtype=torch.int64, device=dev)
+        plan.clock_begin(DOMINANT, kbuf.data_ptr(), n_clk, CLOCK_WGS)
+        for _ in range(n_clk):
+            one_step()
+        drain()
         torch.cuda.synchronize()
-        post_ms = e0.elapsed_time(e1) / 10
+        runs_clk = plan.clock_end()
+        kb = kbuf.cpu().numpy()
+        per_run = [dnn_hip.sclk_from_stamps(kb[i, 0], kb[i, 1]) for i in range(runs_clk)]
+        per_run = [c for c in per_run if c]
+        if per_run:
+            med = lambda v: sorted(v)[len(v) // 2]
+            clk_kernel = {"mean": med([c["mean"] for c in per_run]), "min": med([c["min"] for c in per_run]),
+                          "max": med([c["max"] for c in per_run]), "runs": len(per_run),
+                          "window_us": med([c["window_us"] for c in per_run]),
+                          "per_xcd": {str(x): round(med([c["per_xcd"][x] for c in per_run if x in c["per_xcd"]]), 4)
+                                      for x in per_run[0]["per_xcd"]}}
+
+        if args.gather == "detections":  # the postprocess kernel alone, for the per-kernel table
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(10):
+                dbuf.run(runner.out.data_ptr(), runner.count, stream)
+            e1.record()
+            torch.cuda.synchronize()
+            post_ms = e0.elapsed_time(e1) / 10
+    x3 = False
     if rank == 0:
         if args.gather == "detections":
-            dets_u8, counts = full
+            dets_u8, counts = last
             assert len(counts) == B * world
             n_det = int(np.clip(counts, 0, None).sum())
             if args.dump_detections:
                 np.savez(args.dump_detections, dets=np.ascontiguousarray(dets_u8), counts=np.asarray(counts))
         else:
-            assert full is not None and full.shape[0] == B * world
-        kinfo = plan.kernels()
-        by_name = {k["name"]: (k, ms[i], cnt[i]) for i, k in enumerate(kinfo)}
-        k, kms, kc = by_name[DOMINANT]
-        avg_s = kms / max(kc, 1) / 1e3
+            assert last is not None and last.shape[0] == B * world
         # the x3 conv (default for conv6/conv7 on the fp32 path) executes 6 bf16 MFMA products
-        # per fp32 product: its roofline is the bf16 MFMA peak over the executed flops
+        # per fp32 product
         desc = plan.describe().splitlines()
         dom_layer = [ln for ln in desc if ln.startswith("conv")][int(DOMINANT[4:DOMINANT.index(".")])]
         x3 = "patch_x3" in dom_layer
-        mult, peak = (X3_PRODUCTS, BF16_MFMA_PEAK_TFLOPS) if x3 else (1, FP32_MFMA_PEAK_TFLOPS)
-        if args.precision == "fp16":  # (config 5 as the main line: one fp16 MFMA product per product)
-            mult, peak = 1, FP16_MFMA_PEAK_TFLOPS
-        achieved = mult * k["flops"] / avg_s / 1e12
-        prof = pmc_entry(DOMINANT, "pmc_summary_fp16.json" if args.precision == "fp16" else "pmc_summary.json")
-        traffic = prof.get("hbm_bytes_per_launch")
-        # split-K layers (conv6/conv7) finish in a separate ordered reduce + epilogue kernel:
-        # the conv-level figures below charge its time to the GEMM
-        red = by_name.get(DOMINANT.replace(".gemm", ".reduce"))
-        red_s = red[1] / max(red[2], 1) / 1e3 if red else 0.0
-        mfma = (".gemm", ".patch", ".reduce")  # the MFMA conv kernels (+ their split-K reduces)
-        gemm_fl = sum(v[0]["flops"] for n, v in by_name.items() if n.endswith(mfma))
-        gemm_s = sum(v[1] / max(v[2], 1) for n, v in by_name.items() if n.endswith(mfma)) / 1e3
-        conv67 = [by_name[n] for n in ("conv6.gemm", "conv6.reduce", "conv7.gemm", "conv7.reduce") if n in by_name]
-        c67_fl = sum(v[0]["flops"] for v in conv67)
-        c67_s = sum(v[1] / max(v[2], 1) for v in conv67) / 1e3
-        total_kernel_ms = sum(m / max(c, 1) for m, c in zip(ms, cnt))
         value = timed_value = B * world * args.steps / elapsed
         value_source = f"{args.steps} timed steps after a {preheat_s:.1f} s pre-heat"
-        stable = True
-        if sustained and abs(value - sustained["images_per_s"]) > 0.02 * sustained["images_per_s"]:
-            # the two windows disagree: the run is marked unstable, and the headline is the LOWER of
-            # the two rates (a faster sustained window never replaces the timed one)
-            stable = False
-            if sustained["images_per_s"] < value:
-                value = sustained["images_per_s"]
-                value_source = (f"sustained ({sustained['steps']} steps): more than 2 % below the "
-                                f"{args.steps} timed steps, the lower of the two")
-            else:
-                value_source += " (the sustained window ran more than 2 % faster; the timed value is kept)"
+        stable = None  # (--full: whether the sustained window agrees with the timed steps)
+        if sustained:
+            stable = True
+            if abs(value - sustained["images_per_s"]) > 0.02 * sustained["images_per_s"]:
+                # the two windows disagree: the run is marked unstable, and the headline is the LOWER of
+                # the two rates (a faster sustained window never replaces the timed one)
+                stable = False
+                if sustained["images_per_s"] < value:
+                    value = sustained["images_per_s"]
+                    value_source = (f"sustained ({sustained['steps']} steps): more than 2 % below the "
+                                    f"{args.steps} timed steps, the lower of the two")
+                else:
+                    value_source += " (the sustained window ran more than 2 % faster; the timed value is kept)"
         res = {
             "metric": "YOLOv2-tiny 416×416 images/sec at 1/2/4/8 GPU; conv MFMA % of fp32 peak",
             "value": round(value, 2),
@@ -776,7 +830,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
-            "ms_per_step": round(B * world / value * 1e3, 4),
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),  # one timed step (max over ranks)
             "value_source": value_source,
             "timed_value": round(timed_value, 2),
             "stable": stable,
@@ -794,6 +848,38 @@ def main():
                                       else "raw outputs gathered to rank 0"),
                        "model": "yolov2-tiny (9 conv, 6 maxpool)", "global_batch": B * world,
                        "per_gpu_batch": B, "seq_len": None, "parallelism": f"dp{world}"},
+            "full": args.full,
+            "dist_backend": ("rccl" if backend == "nccl" else backend) if distributed else None,
+            "per_rank": [dict(rank=r, **{k: (round(v, 4) if v == v else None) for k, v in zip(keys, vals)})
+                         for r, vals in enumerate(per_rank)],
+        }
+        if args.gather == "detections":
+            res["postprocess"] = {"detections_last_step": n_det,
+                                  "gathered_bytes_last_step": int(dets_u8.nbytes + counts.nbytes)}
+    if rank == 0 and args.full:
+        kinfo = plan.kernels()
+        by_name = {k["name"]: (k, ms[i], cnt[i]) for i, k in enumerate(kinfo)}
+        k, kms, kc = by_name[DOMINANT]
+        avg_s = kms / max(kc, 1) / 1e3
+        # the x3 conv's roofline is the bf16 MFMA peak over the executed flops
+        mult, peak = (X3_PRODUCTS, BF16_MFMA_PEAK_TFLOPS) if x3 else (1, FP32_MFMA_PEAK_TFLOPS)
+        if args.precision == "fp16":  # (config 5 as the main line: one fp16 MFMA product per product)
+            mult, peak = 1, FP16_MFMA_PEAK_TFLOPS
+        achieved = mult * k["flops"] / avg_s / 1e12
+        prof = pmc_entry(DOMINANT, "pmc_summary_fp16.json" if args.precision == "fp16" else "pmc_summary.json")
+        traffic = prof.get("hbm_bytes_per_launch")
+        # split-K layers (conv6/conv7) finish in a separate ordered reduce + epilogue kernel:
+        # the conv-level figures below charge its time to the GEMM
+        red = by_name.get(DOMINANT.replace(".gemm", ".reduce"))
+        red_s = red[1] / max(red[2], 1) / 1e3 if red else 0.0
+        mfma = (".gemm", ".patch", ".reduce")  # the MFMA conv kernels (+ their split-K reduces)
+        gemm_fl = sum(v[0]["flops"] for n, v in by_name.items() if n.endswith(mfma))
+        gemm_s = sum(v[1] / max(v[2], 1) for n, v in by_name.items() if n.endswith(mfma)) / 1e3
+        conv67 = [by_name[n] for n in ("conv6.gemm", "conv6.reduce", "conv7.gemm", "conv7.reduce") if n in by_name]
+        c67_fl = sum(v[0]["flops"] for v in conv67)
+        c67_s = sum(v[1] / max(v[2], 1) for v in conv67) / 1e3
+        total_kernel_ms = sum(m / max(c, 1) for m, c in zip(ms, cnt))
+        res.update({
             "roofline": {"kernel": DOMINANT, "bound": "mfma", "achieved": round(achieved, 2),
                          "peak": peak, "unit": "TFLOP/s", "frac": round(achieved / peak, 4), "traffic": traffic,
                          "mfma": ("v_mfma_f32_16x16x32_bf16, executed flops = 6 x algorithmic (x3 splits)" if x3
@@ -838,13 +924,9 @@ def main():
             "kernel_timing": ("HIP events around every kernel in the timed region" if args.kernels else
                               f"{DOMINANT}: HIP events around it in the timed region; the other kernels: "
                               "5 forwards after it, events around every kernel"),
-            "dist_backend": ("rccl" if backend == "nccl" else backend) if distributed else None,
-            "per_rank": [dict(rank=r, **{k: (round(v, 4) if v == v else None) for k, v in zip(keys, vals)})
-                         for r, vals in enumerate(per_rank)],
-        }
+        })
         if args.gather == "detections":
-            res["postprocess"] = {"ms": round(post_ms, 4), "detections_last_step": n_det,
-                                  "gathered_bytes_last_step": int(dets_u8.nbytes + counts.nbytes)}
+            res["postprocess"]["ms"] = round(post_ms, 4)
         if args.kernels:
             res["kernels"] = {n: {"ms": round(v[1] / max(v[2], 1), 4),
                                   "tflops": round(v[0]["flops"] / (v[1] / max(v[2], 1) / 1e3) / 1e12, 2)
@@ -852,7 +934,8 @@ def main():
                                   "gbs": round(v[0]["bytes"] / (v[1] / max(v[2], 1) / 1e3) / 1e9, 1)}
                               for n, v in by_name.items()}
 
-    if rank == 0 and world == 1 and not args.no_latency:
+    extras = rank == 0 and world == 1 and args.full  # single-GPU measurements beside the headline
+    if extras and not args.no_latency:
         lat = latency_b1(dnn_hip, yolo_graph, ws, dev)
         inv = latency_b1(dnn_hip, yolo_graph, ws, dev, latency=False)
         yb = torch.empty((B, 13, 13, 125), device=dev)
@@ -862,16 +945,17 @@ def main():
         lat.pop("_x")
         lat["batch_plan_at_batch1"] = inv
         res["latency_b1"] = lat
-    if rank == 0 and world == 1 and not args.no_e2e:
+    if extras and not args.no_e2e:
         res["end_to_end_host_frames"] = end_to_end(plan, B, dev, stream)
-    if rank == 0 and world == 1 and args.precision == "fp32" and not args.no_unfused:
+    if extras and args.precision == "fp32" and not args.no_unfused:
         res["unfused"] = unfused_im2col(dnn_hip, yolo_graph, ws, dev, frames, stream, B)
-    if rank == 0 and world == 1 and args.precision == "fp32" and not args.no_fp32_mfma and x3:
+    if extras and args.precision == "fp32" and not args.no_fp32_mfma and x3:
         res["fp32_mfma"] = fp32_mfma_config(dnn_hip, yolo_graph, ws, dev, frames, runner.out, stream, B)
-    if rank == 0 and world == 1 and args.precision == "fp32" and not args.no_fp16:
+    if extras and args.precision == "fp32" and not args.no_fp16:
         res["fp16"] = fp16_config(dnn_hip, yolo_graph, ws, dev, frames, runner.out, plan, stream, B)
-    if rank == 0:
+    if rank == 0 and args.full:
         res["cpu_baseline"] = None if (world > 1 or args.no_cpu) else cpu_baseline(args.cpu_seconds)
+    if rank == 0:
         print(json.dumps(res), flush=True)
 
     plan.close()

@@ -18,7 +18,8 @@ from conftest import REPO
 def test_bench_two_ranks_one_gpu(gather):
     env = dict(os.environ, DNN_BENCH_SHARED_GPU="1", DNN_BENCH_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--batch", "8", "--steps", "2",
-           "--warmup", "1", "--no-cpu", "--no-latency", "--no-e2e", "--no-fp16", "--no-unfused", "--gather", gather]
+           "--warmup", "1", "--full", "--no-cpu", "--no-latency", "--no-e2e", "--no-fp16", "--no-unfused",
+           "--gather", gather]
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -41,7 +42,7 @@ def test_bench_eight_ranks_one_gpu(mode):
     collectives stand in for RCCL (one card).  The JSON line carries all 8 ranks."""
     env = dict(os.environ, DNN_BENCH_SHARED_GPU="1", DNN_BENCH_BACKEND="gloo", DNN_BENCH_GATHER_MODE=mode)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--batch", "4", "--steps", "4",
-           "--warmup", "2", "--no-cpu", "--no-latency", "--no-e2e", "--no-fp16", "--no-unfused"]
+           "--warmup", "2", "--full", "--no-cpu", "--no-latency", "--no-e2e", "--no-fp16", "--no-unfused"]
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -86,7 +87,7 @@ def test_bench_under_torchrun_world1_rccl():
     """bench.py as the driver launches it for N > 1 (torch.distributed.run), at one rank:
     RCCL group, broadcast, detection gathers and the per-rank breakdown in the JSON line."""
     r = _torchrun([os.path.join(REPO, "bench.py"), "--gpus", "1", "--batch", "8", "--steps", "3", "--warmup", "1",
-                   "--no-cpu", "--no-latency", "--no-e2e", "--no-fp16", "--no-unfused"])
+                   "--full", "--no-cpu", "--no-latency", "--no-e2e", "--no-fp16", "--no-unfused"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-3000:]
@@ -116,8 +117,8 @@ def test_bench_eight_ranks_batch64_detections_match_single_process(tmp_path):
     dump = str(tmp_path / "dets.npz")
     env = dict(os.environ, DNN_BENCH_SHARED_GPU="1", DNN_BENCH_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--batch", "64", "--steps", "2",
-           "--warmup", "1", "--preheat", "0", "--sustained", "0", "--no-cpu", "--no-latency", "--no-e2e",
-           "--no-fp16", "--no-unfused", "--no-fp32-mfma", "--dump-detections", dump]
+           "--warmup", "1", "--preheat", "0", "--sustained", "0", "--full", "--no-cpu", "--no-latency",
+           "--no-e2e", "--no-fp16", "--no-unfused", "--no-fp32-mfma", "--dump-detections", dump]
     r = subprocess.run(cmd, env=env, cwd=REPO, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -149,3 +150,60 @@ def test_bench_eight_ranks_batch64_detections_match_single_process(tmp_path):
     assert np.array_equal(got["counts"], want_c)
     assert int(np.clip(want_c, 0, None).sum()) > 0 and got["dets"].shape == want_d.shape
     assert got["dets"].tobytes() == want_d.tobytes()
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_last_step_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run (no --full) prints the headline line alone, none of the
+    measurements that take runs of their own, and --dump-outputs writes what its last timed
+    step returned: the raw outputs, the detections as [P, 6] float64 rows and the per-image
+    counts.  They equal, element for element, the same seeded frames (bench.py's rank 0) run
+    in this process through a plan of the same batch, postprocessed and packed."""
+    import numpy as np
+    import torch
+
+    import dist as D
+    import dnn_hip
+    import synth
+    import yolo_graph
+    import yolo_post
+    B = 8
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--batch", str(B), "--steps", "3",
+           "--warmup", "1", "--preheat", "0", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-3000:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["unit"] == "images/s" and d["higher_is_better"] is True and d["full"] is False
+    assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(B / d["ms_per_step"] * 1e3, rel=1e-3)
+    for key in ("roofline", "sustained", "latency_b1", "end_to_end_host_frames", "unfused", "fp32_mfma", "fp16",
+                "cpu_baseline", "kernels"):
+        assert not d.get(key), key
+    assert sorted(os.listdir(out_dir)) == ["counts.npy", "detections.npy", "outputs.npy"]
+    got = {n: np.load(out_dir / (n + ".npy")) for n in ("counts", "detections", "outputs")}
+    assert got["outputs"].dtype == np.float32 and got["outputs"].shape == (B, 13, 13, 125)
+    assert got["detections"].dtype == np.float64 and got["counts"].dtype == np.float64
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+
+    dev = torch.device("cuda", 0)
+    g, _ = yolo_graph.build_graph(dnn_hip.DnnGraphBuilder, synth.yolo_weights(), in_shape=(B, 416, 416, 3))
+    plan = dnn_hip.Plan.from_graph(g, device=0)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(1234)  # bench.py's frames of rank 0
+    frames = torch.rand((B, 416, 416, 3), generator=gen, device=dev, dtype=torch.float32)
+    out = torch.empty((B, 13, 13, 125), device=dev)
+    db = yolo_post.DetectionBuffers(B, dev)
+    s = torch.cuda.current_stream(dev).cuda_stream
+    plan.run_device(B, frames.data_ptr(), out.data_ptr(), s)
+    db.run(out.data_ptr(), B, s)
+    packed, total, cnt = db.pack(B, s)
+    torch.cuda.synchronize()
+    plan.close()
+    assert np.array_equal(got["outputs"], out.cpu().numpy())
+    want_c = cnt[:B].cpu().numpy()
+    assert int(np.clip(want_c, 0, None).sum()) > 0 and np.array_equal(got["counts"], want_c.astype(np.float64))
+    rows = packed[:int(total.item())].cpu().numpy().view(D.DETECTION_DTYPE).reshape(-1)
+    want_d = np.stack([rows[f].astype(np.float64) for f in ("cls", "score", "left", "top", "right", "bottom")], 1)
+    assert np.array_equal(got["detections"], want_d)

@@ -4,7 +4,7 @@
 #   bash tools/gpu_job.sh TASK [ARGS...]
 # Tasks (output under gpurun_out/$OUT, default gpurun_out/job):
 #   tests [PYTEST_ARGS...]     pytest -m gpu (extra args passed through, e.g. -k x3)
-#   bench [BENCH_ARGS...]      one bench.py line (fp32 forward only unless args say otherwise)
+#   bench [BENCH_ARGS...]      one bench.py --full line (every measurement unless args say otherwise)
 #   ab VAR V1 V2 [BENCH_ARGS]  bench.py --kernels with env VAR=V1, then VAR=V2, then V1 again
 #   sweep VAR V1 V2 ...        bench.py --kernels (forward only) for each value of env VAR, then V1 again
 #   lat VAR V1 V2 ...          the batch-1 latency plan (latency_b1) for each value of env VAR
@@ -22,7 +22,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${OUT:-job}
 mkdir -p "$O"
 cd "$R" || exit 1
-FAST="--no-cpu --no-latency --no-fp16 --no-unfused --no-e2e --no-fp32-mfma"
+FAST="--full --no-cpu --no-latency --no-fp16 --no-unfused --no-e2e --no-fp32-mfma"
 # counter passes serialise every dispatch: no pre-heat / sustained windows there (the kernel-trace
 # passes keep them, so their durations are the steady-state ones)
 NOHEAT="--preheat 0 --sustained 0"
@@ -37,7 +37,7 @@ run_tests() {
 
 run_bench() {  # $1 = log name, rest = bench args
   local name=$1; shift
-  timeout -k 10 400 python bench.py "$@" > "$O/$name.log" 2>&1 || { tail -20 "$O/$name.log"; return 1; }
+  timeout -k 10 400 python bench.py --full "$@" > "$O/$name.log" 2>&1 || { tail -20 "$O/$name.log"; return 1; }
   tail -1 "$O/$name.log" > "$O/$name.json"
   python - "$O/$name.json" <<'EOF'
 import json, sys
@@ -78,7 +78,7 @@ case $task in
     var=$1; shift
     for v in "$@"; do
       export "$var=$v"
-      timeout -k 10 400 python bench.py --no-cpu --no-fp16 --no-unfused --no-e2e --no-fp32-mfma --steps 3 --warmup 1 \
+      timeout -k 10 400 python bench.py --full --no-cpu --no-fp16 --no-unfused --no-e2e --no-fp32-mfma --steps 3 --warmup 1 \
         > "$O/lat_$v.log" 2>&1 || { tail -20 "$O/lat_$v.log"; exit 1; }
       tail -1 "$O/lat_$v.log" > "$O/lat_$v.json"
       python - "$O/lat_$v.json" "$var=$v" <<'EOF2'
@@ -90,7 +90,7 @@ EOF2
     done
     ;;
   lattrace)
-    prof lattrace --kernel-trace -- --steps 1 --warmup 1 --no-cpu --no-fp16 --no-unfused --no-e2e --no-fp32-mfma "$@" || exit 1
+    prof lattrace --kernel-trace -- --steps 1 --warmup 1 --full --no-cpu --no-fp16 --no-unfused --no-e2e --no-fp32-mfma "$@" || exit 1
     python tools/trace_by_grid.py $(find "$O/lattrace" -name "*kernel_trace.csv") --min-count 100 > "$O/lattrace.txt" && cat "$O/lattrace.txt"
     ;;
   trace) prof trace --kernel-trace --stats -- --steps 10 --warmup 3 $FAST "$@" ;;
