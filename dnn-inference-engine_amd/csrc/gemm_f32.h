@@ -309,6 +309,24 @@ gemm_f32_mfma_kernel(const float* __restrict__ A, int lda, const float* __restri
   const int a_base = (wm * WTM + fr) * LS + fk;
   const int b_base = (wn * WTN + fr) * LS + fk;
 
+  // BN == 16 (the explicit GEMM of N <= 16 layers, which has no split-K and no implicit twin
+  // whose bits it must match): K beyond LONGK is summed in chunks of LONGK, each chunk from zero
+  // and the chunks into `tot`, so the fp32 chain an output goes through stays <= LONGK / 4 MFMAs
+  // + K / LONGK adds (one chain over K = 9216 measured 2.45e-6 normwise against the float64
+  // oracle, over the 2e-6 per-layer bar).  K <= LONGK: no fold, the same bits as before.
+  constexpr int LONGK = 1024;
+  constexpr bool FOLD = BN == 16;
+  const bool fold = FOLD && K > LONGK;
+  acc_t tot[FOLD ? TM : 1][FOLD ? TN : 1];
+  if constexpr (FOLD) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < MM::REGS; ++r) tot[i][j][r] = 0.f;
+  }
+
   const int nk = K / BK;
   gload(0);
   sstore(smem, smem + BM * LS);
@@ -332,6 +350,20 @@ gemm_f32_mfma_kernel(const float* __restrict__ A, int lda, const float* __restri
         for (int i = 0; i < TM; ++i)
 #pragma unroll
           for (int j = 0; j < TN; ++j) acc[i][j] = MM::op(af[i][s], bf[j][s], acc[i][j]);
+    }
+    if constexpr (FOLD) {
+      // a chunk ends (the last one too: the output is tot); uniform over the workgroup
+      if (fold && ((kt + 1) % (LONGK / BK) == 0 || kt + 1 == nk)) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < MM::REGS; ++r) {
+              tot[i][j][r] += acc[i][j][r];
+              acc[i][j][r] = kt + 1 == nk ? tot[i][j][r] : 0.f;
+            }
+      }
     }
     if (kt + 1 < nk) {
       float* Asn = smem + ((kt + 1) & 1) * (BM + BN) * LS;

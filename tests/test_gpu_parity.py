@@ -455,6 +455,13 @@ def test_yolo_batch64_golden_indices_and_batch_invariance(yolo_weights, golden_f
     plan = eng.plan()
     y5 = plan.run_host(x[:5])
     assert np.array_equal(y5, y[:5])
+    # ... and on five OTHER frames: rows 0-4 of every activation now differ from what the
+    # 64-frame run left there, rows 5-63 are stale; nothing stale may reach the output
+    x5 = synth.frames([300, 301, 302, 303, 304])
+    z5 = plan.run_host(x5)
+    for i in range(5):
+        assert np.array_equal(z5[i:i + 1], yolo_b1.run(x5[i:i + 1])), i
+    assert not np.array_equal(z5, y5)
     assert plan.run_host(x[:0]).shape == (0, 13, 13, 125)
 
 
