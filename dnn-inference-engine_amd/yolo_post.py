@@ -9,8 +9,17 @@ decode + threshold + sort + greedy NMS, one workgroup per image.  `detect_batch`
 whole [B,13,13,125] batch in one launch, and `DetectionBuffers` keeps the outputs on the
 device for the multi-GPU detection gather (dist.py).  There is no CPU fallback: a missing
 library raises (dnn_hip.load_library).
+
+Any other head — another grid (input size / 32), anchor list or class count — is described by
+a `YoloHead` and passed as `head=` to the same functions; they then run
+`dnn_yolo_postprocess_head` (csrc/postprocess_head.hip).  `head=None` is the path above.
+
+    head = YoloHead.for_input(608, 608)              # 19 x 19 cells, VOC anchors and classes
+    rows = detect_batch(pred, head=head)             # pred [B,19,19,125]
 """
 import ctypes
+
+import math
 
 import numpy as np
 
@@ -19,7 +28,10 @@ import dnn_hip
 N_BOXES = 845  # DNN_YOLO_BOXES: 13 * 13 * 5, the most detections an image can have
 PRED_FLOATS = 13 * 13 * 125
 
-# yolov2tiny.py:102-112 (data)
+MAX_BOXES, MAX_ANCHORS, MAX_CLASSES = 8192, 16, 128  # DNN_YOLO_MAX_* (include/dnn_hip_post.h)
+
+# yolov2tiny.py:102-115 (data)
+ANCHORS = (1.08, 1.19, 3.42, 4.41, 6.63, 11.38, 9.42, 5.11, 16.62, 10.52)
 CLASSES = ("aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "diningtable",
            "dog", "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor")
 COLORS = ((254.0, 254.0, 254), (239.88888888888889, 211.66666666666669, 127),
@@ -45,8 +57,26 @@ DETECTION_DTYPE = np.dtype([("cls", "<i4"), ("score", "<f4"), ("left", "<i8"), (
 assert DETECTION_DTYPE.itemsize == ctypes.sizeof(Detection) == 40
 
 
+class HeadStruct(ctypes.Structure):
+    """dnn_yolo_head (include/dnn_hip_post.h)."""
+    _fields_ = [("grid_h", ctypes.c_int), ("grid_w", ctypes.c_int), ("n_anchors", ctypes.c_int),
+                ("n_classes", ctypes.c_int), ("cell", ctypes.c_float), ("score_thr", ctypes.c_float),
+                ("iou_thr", ctypes.c_double), ("anchors", ctypes.c_float * 32)]
+
+
 def _bind(lib):
     vp, i = ctypes.c_void_p, ctypes.c_int
+    hp, u64 = ctypes.POINTER(HeadStruct), ctypes.c_ulonglong
+    lib.dnn_yolo_head_voc.restype = i
+    lib.dnn_yolo_head_voc.argtypes = [i, i, hp]
+    lib.dnn_yolo_head_boxes.restype = i
+    lib.dnn_yolo_head_boxes.argtypes = [hp]
+    lib.dnn_yolo_head_workspace.restype = i
+    lib.dnn_yolo_head_workspace.argtypes = [hp, i, ctypes.POINTER(u64)]
+    lib.dnn_yolo_postprocess_head.restype = i
+    lib.dnn_yolo_postprocess_head.argtypes = [hp, vp, i, vp, i, vp, vp, u64, vp]
+    lib.dnn_yolo_postprocess_head_host.restype = i
+    lib.dnn_yolo_postprocess_head_host.argtypes = [hp, vp, i, vp, i, vp]
     lib.dnn_yolo_postprocess.restype = i
     lib.dnn_yolo_postprocess.argtypes = [vp, i, vp, i, vp, vp]
     lib.dnn_yolo_postprocess_host.restype = i
@@ -61,6 +91,70 @@ _lib = _bind(dnn_hip.mylib)
 
 ERRORS = {-1: "a box corner is not finite or out of int64 range (the reference's int() raises there)",
           -2: "an IoU denominator is zero (the reference raises ZeroDivisionError)"}
+
+
+class YoloHead(object):
+    """What yolov2tiny.py:96-162 fixes for the 416 x 416 VOC model, as parameters: `grid` cells
+    (an int or (rows, cols)), `anchors` (w, h pairs in cells), `classes` (a tuple of names, or
+    a count), `cell` pixels per cell and the two thresholds.  Validates like the C side
+    (dnn_yolo_head_boxes) and raises ValueError."""
+
+    def __init__(self, grid, anchors=ANCHORS, classes=CLASSES, cell=32.0, score_thr=0.3, iou_thr=0.3):
+        try:
+            gh, gw = grid
+        except TypeError:
+            gh = gw = grid
+        if int(gh) != gh or int(gw) != gw:
+            raise ValueError(f"grid {grid!r}: whole numbers of cells expected")
+        self.grid_h, self.grid_w = int(gh), int(gw)
+        self.anchors = tuple(float(a) for a in anchors)
+        if isinstance(classes, (int, np.integer)):
+            self.names, self.n_classes = None, int(classes)
+        else:
+            self.names = tuple(classes)
+            self.n_classes = len(self.names)
+        self.cell, self.score_thr, self.iou_thr = float(cell), float(score_thr), float(iou_thr)
+        if len(self.anchors) % 2 or not 1 <= len(self.anchors) // 2 <= MAX_ANCHORS:
+            raise ValueError(f"{len(self.anchors)} anchor values: need (w, h) pairs for 1..{MAX_ANCHORS} anchors")
+        self.n_anchors = len(self.anchors) // 2
+        if not 1 <= self.n_classes <= MAX_CLASSES:
+            raise ValueError(f"{self.n_classes} classes: need 1..{MAX_CLASSES}")
+        if self.grid_h < 1 or self.grid_w < 1 or self.grid_h * self.grid_w * self.n_anchors > MAX_BOXES:
+            raise ValueError(f"{self.grid_h} x {self.grid_w} cells x {self.n_anchors} anchors: need 1..{MAX_BOXES} "
+                             "boxes")
+        if not (np.float32(self.score_thr) >= 0) or math.isnan(self.iou_thr):
+            raise ValueError(f"score_thr {score_thr!r} must be >= 0 and iou_thr {iou_thr!r} a number")
+        if not (np.float32(self.cell) > 0 and np.isfinite(np.float32(self.cell))):
+            raise ValueError(f"cell {cell!r} must be a finite number of pixels > 0")
+        if not np.all(np.isfinite(np.asarray(self.anchors, np.float32))):
+            raise ValueError("anchors must be finite")
+        self.boxes = self.grid_h * self.grid_w * self.n_anchors
+        self.n_out = self.n_anchors * (5 + self.n_classes)
+        self.pred_shape = (self.grid_h, self.grid_w, self.n_out)
+        self.pred_floats = self.grid_h * self.grid_w * self.n_out
+        self.c = HeadStruct(self.grid_h, self.grid_w, self.n_anchors, self.n_classes, self.cell, self.score_thr,
+                            self.iou_thr, (ctypes.c_float * 32)(*self.anchors))
+        n = _lib.dnn_yolo_head_boxes(ctypes.byref(self.c))
+        if n != self.boxes:
+            raise ValueError(f"dnn_yolo_head_boxes: {n}: {dnn_hip.last_error()}")
+
+    @classmethod
+    def for_input(cls, h, w, cell=32.0, **kw):
+        """The head of an h x w pixel input (yolov2tiny.py:129: 416 / 13 = 32): both must be
+        multiples of `cell`."""
+        if h < cell or w < cell or h % cell or w % cell:
+            raise ValueError(f"input {h} x {w}: height and width must be multiples of {cell:g}")
+        return cls((int(h // cell), int(w // cell)), cell=cell, **kw)
+
+    def workspace_bytes(self, n_images):
+        b = ctypes.c_ulonglong(0)
+        dnn_hip._check(_lib.dnn_yolo_head_workspace(ctypes.byref(self.c), n_images, ctypes.byref(b)),
+                       "dnn_yolo_head_workspace")
+        return int(b.value)
+
+    def __repr__(self):
+        return (f"YoloHead({self.grid_h}x{self.grid_w} cells, {self.n_anchors} anchors, {self.n_classes} classes, "
+                f"cell {self.cell:g}, score > {self.score_thr:g}, IoU > {self.iou_thr:g})")
 
 
 def _rows(dets, counts, max_det, raise_errors=True):
@@ -78,12 +172,25 @@ def _rows(dets, counts, max_det, raise_errors=True):
     return out
 
 
-def detect_batch(predictions, max_det=N_BOXES, raise_errors=True):
+def detect_batch(predictions, max_det=None, raise_errors=True, head=None):
     """[B,13,13,125] (or [13,13,125]) fp32 host predictions -> per image a list of
     (class, left, top, right, bottom, score) in the reference's output order.  An image on
     which the reference raises raises DnnHipError, or with raise_errors=False yields its
-    negative error code (ERRORS) in place of the list."""
+    negative error code (ERRORS) in place of the list.  With `head` (a YoloHead) the
+    predictions are [B, *head.pred_shape] and max_det defaults to head.boxes."""
     p = np.ascontiguousarray(predictions, dtype=np.float32)
+    if head is not None:
+        if p.size % head.pred_floats:
+            raise ValueError(f"predictions of shape {p.shape} are not [B,{','.join(map(str, head.pred_shape))}]")
+        n = p.size // head.pred_floats
+        max_det = head.boxes if max_det is None else max_det
+        dets = np.zeros((n, max_det), DETECTION_DTYPE)
+        counts = np.zeros(n, np.int32)
+        dnn_hip._check(_lib.dnn_yolo_postprocess_head_host(ctypes.byref(head.c), p.ctypes.data, n, dets.ctypes.data,
+                                                           max_det, counts.ctypes.data),
+                       "dnn_yolo_postprocess_head_host")
+        return _rows(dets, counts, max_det, raise_errors)
+    max_det = N_BOXES if max_det is None else max_det
     if p.size % PRED_FLOATS:
         raise ValueError(f"predictions of shape {p.shape} are not [B,13,13,125]")
     n = p.size // PRED_FLOATS
@@ -94,15 +201,25 @@ def detect_batch(predictions, max_det=N_BOXES, raise_errors=True):
     return _rows(dets, counts, max_det, raise_errors)
 
 
-def label_boxes(rows):
-    """(class, l, t, r, b, score) rows -> the reference's label_boxes tuples."""
-    return [(CLASSES[c], (l, t), (r, b), COLORS[c]) for c, l, t, r, b, _ in rows]
+def label_boxes(rows, head=None):
+    """(class, l, t, r, b, score) rows -> the reference's label_boxes tuples.  A head with
+    other classes than the 20 VOC names gives its own name (the class index where it has only
+    a count) and None as the colour: the reference's colours belong to the VOC list."""
+    if head is None or head.names == CLASSES:
+        return [(CLASSES[c], (l, t), (r, b), COLORS[c]) for c, l, t, r, b, _ in rows]
+    return [(head.names[c] if head.names else c, (l, t), (r, b), None) for c, l, t, r, b, _ in rows]
 
 
-def postprocessing(predictions):
+def postprocessing(predictions, head=None):
     """yolov2tiny.py:94-176: one image's [1,13,13,125] output -> [(class name, (left, top),
-    (right, bottom), color)] after the 0.3 threshold and greedy NMS."""
+    (right, bottom), color)] after the 0.3 threshold and greedy NMS.  With `head`, one image of
+    head.pred_shape and that head's thresholds."""
     p = np.asarray(predictions, dtype=np.float32)
+    if head is not None:
+        if p.size != head.pred_floats:
+            raise ValueError(f"postprocessing expects one {'x'.join(map(str, head.pred_shape))} prediction, "
+                             f"got shape {p.shape}")
+        return label_boxes(detect_batch(p, head=head)[0], head)
     if p.size != PRED_FLOATS:
         raise ValueError(f"postprocessing expects one 13x13x125 prediction, got shape {p.shape}")
     return label_boxes(detect_batch(p)[0])
@@ -112,17 +229,30 @@ class DetectionBuffers(object):
     """Device-side outputs for `n` images (torch tensors on `device`): dets [n, max_det, 40 B]
     as uint8 and counts [n] int32, filled by `run(pred_ptr, n, stream)` asynchronously;
     `pack(n, stream)` then compacts them image-major into packed [n * max_det, 40] with the
-    row count in total[0] (dnn_yolo_pack_detections), ready for dist.gather_detections."""
+    row count in total[0] (dnn_yolo_pack_detections), ready for dist.gather_detections.
+    With `head` (a YoloHead) `run` goes through dnn_yolo_postprocess_head, max_det defaults to
+    head.boxes and the buffers also own the workspace that entry needs."""
 
-    def __init__(self, n, device, max_det=N_BOXES):
+    def __init__(self, n, device, max_det=None, head=None):
         import torch
-        self.n, self.max_det = n, max_det
+        if max_det is None:
+            max_det = N_BOXES if head is None else head.boxes
+        self.n, self.max_det, self.head = n, max_det, head
+        if head is not None:
+            self.workspace = torch.zeros(head.workspace_bytes(n), dtype=torch.uint8, device=device)
         self.dets = torch.zeros((n, max_det, DETECTION_DTYPE.itemsize), dtype=torch.uint8, device=device)
         self.counts = torch.zeros(n, dtype=torch.int32, device=device)
         self.packed = torch.zeros((n * max_det, DETECTION_DTYPE.itemsize), dtype=torch.uint8, device=device)
         self.total = torch.zeros(1, dtype=torch.int32, device=device)
 
     def run(self, pred_ptr, n, stream):
+        if self.head is not None:
+            if n > self.n:
+                raise ValueError(f"{n} images > the {self.n} these buffers were sized for")
+            dnn_hip._check(_lib.dnn_yolo_postprocess_head(
+                ctypes.byref(self.head.c), pred_ptr, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
+                self.workspace.data_ptr(), self.workspace.numel(), stream), "dnn_yolo_postprocess_head")
+            return
         dnn_hip._check(_lib.dnn_yolo_postprocess(pred_ptr, n, self.dets.data_ptr(), self.max_det,
                                                  self.counts.data_ptr(), stream), "dnn_yolo_postprocess")
 
@@ -133,7 +263,10 @@ class DetectionBuffers(object):
         return self.packed, self.total, self.counts
 
     @staticmethod
-    def to_rows(dets_u8, counts, max_det=N_BOXES, raise_errors=True):
-        """Host copies (numpy uint8 [n, max_det, 40], int32 [n]) -> per-image rows."""
+    def to_rows(dets_u8, counts, max_det=None, raise_errors=True, head=None):
+        """Host copies (numpy uint8 [n, max_det, 40], int32 [n]) -> per-image rows; max_det
+        defaults to head.boxes when a head is given."""
+        if max_det is None:
+            max_det = N_BOXES if head is None else head.boxes
         d = np.ascontiguousarray(dets_u8).view(DETECTION_DTYPE).reshape(len(counts), max_det)
         return _rows(d, np.asarray(counts), max_det, raise_errors)

@@ -54,8 +54,10 @@ def _safe_load(data):
         raise WeightFileError(f"not a readable weight pickle: {e!r}") from e
 
 
-def validate(weights):
-    """Check the 9-layer structure and return it as fp32 contiguous arrays (new dicts)."""
+def validate(weights, n_out=125):
+    """Check the 9-layer structure and return it as fp32 contiguous arrays (new dicts).  The
+    last layer must be n_out wide: 125 for the VOC head, n_anchors * (5 + n_classes) for
+    another (yolo_post.YoloHead.n_out); None accepts any width."""
     if not isinstance(weights, (list, tuple)) or len(weights) != N_LAYERS:
         raise WeightFileError(f"expected a list of {N_LAYERS} layer dicts, got {type(weights).__name__} "
                               f"of length {len(weights) if hasattr(weights, '__len__') else '?'}")
@@ -83,20 +85,21 @@ def validate(weights):
                 raise WeightFileError(f"layer {i} {key}: shape {d[key].shape}, expected ({od},)")
         out.append(d)
         in_c = od
-    if in_c != 125:
-        raise WeightFileError(f"last layer has {in_c} outputs; YOLOv2-tiny VOC needs 125 (yolov2tiny.py:120)")
+    if n_out is not None and in_c != n_out:
+        what = "YOLOv2-tiny VOC needs 125 (yolov2tiny.py:120)" if n_out == 125 else f"this head needs {n_out}"
+        raise WeightFileError(f"last layer has {in_c} outputs; {what}")
     return out
 
 
-def load_y2t_weights(path):
+def load_y2t_weights(path, n_out=125):
     """Read and validate a YOLOv2-tiny weight pickle (Python-2 or -3 written)."""
     with open(path, "rb") as f:
-        return validate(_safe_load(f.read()))
+        return validate(_safe_load(f.read()), n_out)
 
 
-def save_y2t_weights(weights, path, protocol=2):
+def save_y2t_weights(weights, path, protocol=2, n_out=125):
     """Write `weights` in the reference's pickle format (protocol 2 is readable by the
     reference's Python 2.7 and 3.5 loaders too)."""
-    w = validate(weights)
+    w = validate(weights, n_out)
     with open(path, "wb") as f:
         pickle.dump([dict(d) for d in w], f, protocol=protocol)

@@ -54,6 +54,53 @@ int dnn_yolo_pack_detections(const dnn_detection* dets, const int* counts, int n
 /* Host pointers, synchronous (copies in, runs, copies out). */
 int dnn_yolo_postprocess_host(const float* pred, int n_images, dnn_detection* dets, int max_det, int* counts);
 
+/* ---- any YOLOv2 head: grid, anchors, classes -------------------------------------------
+ * yolov2tiny.py:94-177 fixes n_grid_cells = 13, n_classes = 20, the anchor list (:115),
+ * `* 32.0` (:132-136) and the two 0.3 thresholds (:154, :162) as named quantities; this
+ * struct carries them, so one set of weights can be postprocessed at any input size that is
+ * a multiple of 32.  Semantics are those above with 13 -> grid_h / grid_w, 5 -> n_anchors,
+ * 20 -> n_classes, 32.0 -> cell; anchors and cell are fp32, the softmax sum keeps numpy's
+ * float32 add.reduce order for the class count (sequential below 8, else 8 accumulators). */
+#define DNN_YOLO_MAX_BOXES 8192 /* grid_h * grid_w * n_anchors: 1280-pixel inputs, 5 anchors */
+#define DNN_YOLO_MAX_ANCHORS 16
+#define DNN_YOLO_MAX_CLASSES 128 /* numpy's add.reduce is unblocked up to 128 elements */
+
+typedef struct dnn_yolo_head {
+  int grid_h, grid_w; /* cells (yolov2tiny.py:97 n_grid_cells, per axis) */
+  int n_anchors;      /* 1..16  (yolov2tiny.py:98 n_b_boxes) */
+  int n_classes;      /* 1..128 (yolov2tiny.py:96 n_classes) */
+  float cell;         /* pixels per cell, 32 (yolov2tiny.py:132-136); > 0 */
+  float score_thr;    /* 0.3f (yolov2tiny.py:154); >= 0 so candidate scores are positive */
+  double iou_thr;     /* 0.3 (yolov2tiny.py:162, :218) */
+  float anchors[32];  /* (w, h) per anchor, in cells (yolov2tiny.py:115) */
+} dnn_yolo_head;
+
+/* yolov2tiny.py:96-115: the reference's constants (5 VOC anchors, 20 classes, 32 pixels per
+ * cell, both thresholds 0.3) at a grid_h x grid_w grid. */
+int dnn_yolo_head_voc(int grid_h, int grid_w, dnn_yolo_head* head);
+
+/* yolov2tiny.py:123-125 (the three nested loops): grid_h * grid_w * n_anchors, the most
+ * detections an image can have, or < 0 (message in dnn_last_error()) for an invalid head. */
+int dnn_yolo_head_boxes(const dnn_yolo_head* head);
+
+/* Bytes of device scratch dnn_yolo_postprocess_head needs for n_images images of this head:
+ * 40 bytes per decoded box (yolov2tiny.py:149-155: corners, score, class) when the boxes of
+ * one image do not fit in LDS beside the sort keys, else 0. */
+int dnn_yolo_head_workspace(const dnn_yolo_head* head, int n_images, unsigned long long* bytes);
+
+/* yolov2tiny.py:94-227 for any head.  Device pointers, asynchronous on `stream`.
+ * pred: [n_images][grid_h][grid_w][n_anchors * (5 + n_classes)] fp32; dets: [n_images][max_det];
+ * counts: [n_images], with the meaning above; workspace: 8-byte aligned, at least
+ * dnn_yolo_head_workspace() bytes (may be NULL when that is 0). */
+int dnn_yolo_postprocess_head(const dnn_yolo_head* head, const float* pred, int n_images, dnn_detection* dets,
+                              int max_det, int* counts, void* workspace, unsigned long long workspace_bytes,
+                              void* stream);
+
+/* yolov2tiny.py:94-227 for any head.  Host pointers, synchronous (allocates its scratch,
+ * copies in, runs, copies out). */
+int dnn_yolo_postprocess_head_host(const dnn_yolo_head* head, const float* pred, int n_images, dnn_detection* dets,
+                                   int max_det, int* counts);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
