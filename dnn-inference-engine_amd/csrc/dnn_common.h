@@ -304,6 +304,13 @@ bool conv1_patch_f16_supported(int C, int OC, int H, int W, int OH, int OW, int 
 int launch_conv1_patch_f16(const half_t* in, const half_t* Bt, int ldb, half_t* out, const DirectGeom& g,
                            const float* zero, const EpiParams& epi, hipStream_t s, int opad = 0);
 
+// route.hip: space-to-depth of a [n, H, W, Ca] (TensorFlow channel order, (dy*block + dx)*Ca + c),
+// channel concat with b [n, H/block, W/block, Cb] (NULL with Cb == 0), or both in one pass:
+// out [n, H/block, W/block, block*block*Ca + Cb], the b channels first with b_first.  block in
+// 1..8 (1: plain concat); 16-byte accesses when Ca % 4 == 0 and Cb % 4 == 0; every tensor < 2 GiB
+int launch_route(const float* a, const float* b, float* out, int n, int H, int W, int Ca, int block, int Cb,
+                 int b_first, hipStream_t stream);
+
 // element-wise ops of the per-op ABI
 int launch_bias_add(const float* in, const float* b, float* out, long long n, int C, hipStream_t s);
 int launch_bn_mvg(const float* in, const float* mean, const float* sq, const float* gamma, float* out,

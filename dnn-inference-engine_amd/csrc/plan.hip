@@ -20,6 +20,14 @@
 // between two workspace buffers.  DNN_HIP_FUSE=0 in the environment at plan creation
 // forces the explicit GEMM path with separate pools (for A/B checks); DNN_HIP_PATCH=0 keeps
 // PATCH-eligible layers on the implicit GEMM.
+//
+// Fork / join (fp32 plans): a stash entry names the current tensor as a slot, and the layer that
+// produces it writes it into the slot's own workspace region instead of an activation buffer, so
+// it outlives the ping-pong; a restore entry makes a slot the current tensor again; a route entry
+// (route.hip) folds the current tensor block x block into channels and concatenates it with a
+// slot's tensor.  Stash and restore launch nothing.  All three are plan layers, so the peepholes
+// of dnn_plan_add_conv / dnn_plan_add_max_pool, which rewrite layers.back(), stop at them: a
+// stashed tensor and both inputs of a route are always plain NHWC fp32.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -98,7 +106,7 @@ static const char* kModeName[] = {"gemm", "direct_a", "implicit", "direct", "pat
                                   "tile16"};
 
 struct PlanLayer {
-  int type = 0;  // 0 conv, 1 pool
+  int type = 0;  // 0 conv, 1 pool, 2 stash, 3 restore, 4 route (LAYER_*)
   // shapes (per image): input H,W,C -> conv/pool output OH,OW,OC (-> fused pool PH,PW)
   int H = 0, W = 0, C = 0, OH = 0, OW = 0, OC = 0;
   int kh = 0, kw = 0, sh = 1, sw = 1, pt = 0, pl = 0;
@@ -119,14 +127,31 @@ struct PlanLayer {
   bool have_host = false;
   std::vector<float> w, bias, mean, sq, gamma;
   int kernel_idx = 0;  // index of this layer's first kernel in the kernel list
+  // fork / join: the slot a stash defines, a restore switches to or a route reads as b (-1: none)
+  int slot = -1;
+  int block = 1, Cb = 0;    // route: space-to-depth block, channels of b
+  bool slot_first = false;  // route: b's channels come first
+  int to_region = -1;       // a writing layer followed by a stash: the slot region it writes
+  int dst_loc = 0;          // where this layer writes (LOC_*; layout())
   int out_h() const { return pool ? PH : OH; }
   int out_w() const { return pool ? PW : OW; }
+};
+
+enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4 };
+// where a tensor of a run lives: the caller's output / input, one of the two ping-pong activation
+// buffers, or slot region r (LOC_REGION + r)
+enum TensorLoc : int { LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, LOC_IN = 2, LOC_REGION = 3 };
+constexpr int kMaxSlots = 4;
+
+struct PlanSlot {
+  int h, w, c;  // per image
+  int loc;      // LOC_IN (a stash before any layer) or LOC_REGION + r
 };
 
 struct KernelDesc {
   std::string name;
   int layer;
-  int kind;             // 0 im2col, 1 gemm / conv, 2 pool
+  int kind;             // 0 im2col, 1 gemm / conv, 2 pool, 3 reduce / combine, 4 convert, 5 route
   double flops, bytes;  // algorithmic, full planned batch
 };
 
@@ -141,6 +166,12 @@ struct dnn_plan {
   bool latency = false;  // split K by M too (dnn_plan_set_latency_mode): batch-1 latency plans
   std::vector<PlanLayer> layers;
   std::vector<KernelDesc> kernels;
+  // fork / join: slots in stash order; regions (one per stashed layer output; slots of a restored
+  // or re-stashed tensor share one) as per-image floats, their float offsets inside the slot area
+  std::vector<PlanSlot> slots;
+  std::vector<size_t> region_elems, region_off;
+  int cur_src = LOC_IN;  // while adding: where the current tensor lives, -1 = the last layer's output
+  size_t slot_floats = 0;
   int device = -1;
   bool finalized = false;
   float* weights = nullptr;
@@ -198,7 +229,7 @@ static bool fp16_direct_out(const dnn_plan* p) {
 static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
-  int nconv = 0, npool = 0;  // kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7
+  int nconv = 0, npool = 0, nroute = 0;  // kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7
   p->kernels.clear();
   const double B = p->batch;
   for (size_t i = 0; i < p->layers.size(); ++i) {
@@ -236,7 +267,7 @@ static void layout(dnn_plan* p) {
       }
       if (L.mode == MODE_X3 && L.splits > 1) {  // raw partials; combined by the next pool, or:
         slab = std::max(slab, (size_t)L.splits * L.OH * L.OW * L.OC);
-        const bool pool_next = i + 1 < p->layers.size() && p->layers[i + 1].type == 1;
+        const bool pool_next = i + 1 < p->layers.size() && p->layers[i + 1].type == LAYER_POOL;
         if (!pool_next) {
           snprintf(nm, sizeof(nm), "conv%d.combine", nconv - 1);
           p->kernels.push_back({nm, (int)i, 3, (L.splits - 1) * M * L.OC, 4.0 * (L.splits + 1) * M * L.OC});
@@ -258,9 +289,35 @@ static void layout(dnn_plan* p) {
         p->kernels.push_back({nm, (int)i, 3, (L.splits - 1) * M * L.OC, 4.0 * (L.splits + 1) * M * L.OC});
       }
       if (L.pool) npool++;
-    } else {
+    } else if (L.type == LAYER_POOL) {
       snprintf(nm, sizeof(nm), "pool%d", npool++);
       p->kernels.push_back({nm, (int)i, 2, 0.0, in_b + out_b});
+    } else if (L.type == LAYER_ROUTE) {  // reads a and b, writes out: input bytes == output bytes
+      snprintf(nm, sizeof(nm), "route%d", nroute++);
+      p->kernels.push_back({nm, (int)i, 5, 0.0, 2.0 * out_b});
+    }  // (a stash or a restore launches nothing)
+  }
+  // where each layer writes.  Chains keep the ping-pong by layer parity; with fork / join entries
+  // a layer followed by a stash writes that slot's region, and any other one the activation
+  // buffer that does not hold its input (the only other live tensors are in slot regions)
+  {
+    bool fork = false;
+    for (auto& L : p->layers) fork = fork || L.type >= LAYER_STASH;
+    int cur = LOC_IN;
+    for (size_t i = 0; i < p->layers.size(); ++i) {
+      PlanLayer& L = p->layers[i];
+      if (L.type == LAYER_STASH) {
+        L.dst_loc = cur;
+      } else if (L.type == LAYER_RESTORE) {
+        L.dst_loc = cur = p->slots[L.slot].loc;
+      } else {
+        L.dst_loc = i + 1 == p->layers.size() ? LOC_OUT
+                    : !fork                   ? (int)(i & 1)
+                    : L.to_region >= 0        ? LOC_REGION + L.to_region
+                    : cur == LOC_ACT0         ? LOC_ACT1
+                                              : LOC_ACT0;
+        cur = L.dst_loc;
+      }
     }
   }
   if (p->fp16) {  // fp16 plans convert at the edges: fp32 frames in (unless conv0 is direct), fp32 out
@@ -287,8 +344,16 @@ static void layout(dnn_plan* p) {
       pad_total += align_up(p->fp16 ? (elems + 1) / 2 : elems * 3 / 2, 64);
     }
   p->pad_floats = pad_total;
+  // slot regions: the stashed tensors of the planned batch, after the pad area
+  p->region_off.assign(p->region_elems.size(), 0);
+  size_t slot_total = 0;
+  for (size_t r = 0; r < p->region_elems.size(); ++r) {
+    p->region_off[r] = slot_total;
+    slot_total += align_up(p->region_elems[r] * (size_t)p->batch, 64);
+  }
+  p->slot_floats = slot_total;
   p->ws_floats = 2 * p->act_floats + p->col_floats + p->slab_floats + p->ticket_floats + p->pad_floats +
-                 dnn_plan::kZeroFloats;
+                 p->slot_floats + dnn_plan::kZeroFloats;
 }
 
 extern "C" {
@@ -552,6 +617,7 @@ int dnn_plan_add_conv(dnn_plan* p, int kh, int kw, int od, int stride_h, int str
   p->cur_h = p->layers.back().OH;
   p->cur_w = p->layers.back().OW;
   p->cur_c = od;
+  p->cur_src = -1;
   return 0;
 }
 
@@ -669,7 +735,117 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
   p->layers.push_back(std::move(L));
   p->cur_h = p->layers.back().OH;
   p->cur_w = p->layers.back().OW;
+  p->cur_src = -1;
   return 0;
+}
+
+static void shape_only_layer(const dnn_plan* p, PlanLayer* L, int type) {
+  L->type = type;
+  L->H = L->OH = p->cur_h;
+  L->W = L->OW = p->cur_w;
+  L->C = L->OC = p->cur_c;
+}
+
+int dnn_plan_add_stash(dnn_plan* p, int* slot) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_stash: plan is NULL or finalized");
+  DNN_REQUIRE(slot != nullptr, "dnn_plan_add_stash: slot is NULL");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_stash: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE((int)p->slots.size() < kMaxSlots, "dnn_plan_add_stash: all %d slots are in use", kMaxSlots);
+  if (p->cur_src < 0) {  // the last layer's output: that layer writes a region of its own
+    p->layers.back().to_region = (int)p->region_elems.size();
+    p->cur_src = LOC_REGION + (int)p->region_elems.size();
+    p->region_elems.push_back((size_t)p->cur_h * p->cur_w * p->cur_c);
+  }  // (else the plan's input, or a tensor that already sits in a region)
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_STASH);
+  L.slot = (int)p->slots.size();
+  p->slots.push_back({p->cur_h, p->cur_w, p->cur_c, p->cur_src});
+  p->layers.push_back(std::move(L));
+  *slot = p->layers.back().slot;
+  return 0;
+}
+
+int dnn_plan_add_restore(dnn_plan* p, int slot) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_restore: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_restore: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(slot >= 0 && slot < (int)p->slots.size(), "dnn_plan_add_restore: unknown slot %d (%d defined)", slot,
+              (int)p->slots.size());
+  const PlanSlot& S = p->slots[slot];
+  p->cur_h = S.h;
+  p->cur_w = S.w;
+  p->cur_c = S.c;
+  p->cur_src = S.loc;
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_RESTORE);
+  L.slot = slot;
+  p->layers.push_back(std::move(L));
+  return 0;
+}
+
+int dnn_plan_add_route(dnn_plan* p, int block, int slot, int slot_first) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_route: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_route: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(block >= 1 && block <= 8, "dnn_plan_add_route: block %d outside 1..8", block);
+  DNN_REQUIRE(slot >= -1 && slot < (int)p->slots.size(), "dnn_plan_add_route: unknown slot %d (%d defined)", slot,
+              (int)p->slots.size());
+  DNN_REQUIRE(p->cur_h % block == 0 && p->cur_w % block == 0,
+              "dnn_plan_add_route: %dx%d input is not a multiple of block %d", p->cur_h, p->cur_w, block);
+  PlanLayer L;
+  L.type = LAYER_ROUTE;
+  L.H = p->cur_h;
+  L.W = p->cur_w;
+  L.C = p->cur_c;
+  L.OH = L.H / block;
+  L.OW = L.W / block;
+  L.block = block;
+  L.slot = slot;
+  L.slot_first = slot >= 0 && slot_first != 0;
+  if (slot >= 0) {
+    const PlanSlot& S = p->slots[slot];
+    DNN_REQUIRE(S.h == L.OH && S.w == L.OW, "dnn_plan_add_route: slot %d is %dx%d, the folded input %dx%d", slot, S.h,
+                S.w, L.OH, L.OW);
+    L.Cb = S.c;
+  }
+  L.OC = block * block * L.C + L.Cb;
+  p->layers.push_back(std::move(L));
+  p->cur_h = p->layers.back().OH;
+  p->cur_w = p->layers.back().OW;
+  p->cur_c = p->layers.back().OC;
+  p->cur_src = -1;
+  return 0;
+}
+
+int dnn_route_host(const float* a, const float* b, float* out, int n, int h, int w, int ca, int block, int cb,
+                   int b_first) {
+  DNN_REQUIRE(a && out, "dnn_route_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && ca > 0 && cb >= 0, "dnn_route_host: bad shape n=%d %dx%dx%d cb=%d", n, h, w,
+              ca, cb);
+  DNN_REQUIRE(block >= 1 && block <= 8, "dnn_route_host: block %d outside 1..8", block);
+  DNN_REQUIRE(h % block == 0 && w % block == 0, "dnn_route_host: %dx%d input is not a multiple of block %d", h, w,
+              block);
+  DNN_REQUIRE((b != nullptr) == (cb > 0), "dnn_route_host: b must be NULL exactly when cb == 0");
+  if (n == 0) return 0;
+  const size_t pix = (size_t)n * (h / block) * (w / block);
+  const size_t af = (size_t)n * h * w * ca, bf = pix * cb, of = pix * ((size_t)block * block * ca + cb);
+  DNN_REQUIRE(af * 4 < 0x80000000ULL && bf * 4 < 0x80000000ULL && of * 4 < 0x80000000ULL,
+              "dnn_route_host: a tensor of n=%d %dx%dx%d block %d cb=%d is >= 2 GiB; split the batch", n, h, w, ca,
+              block, cb);
+  const size_t a_off = 0, b_off = align_up(af, 64), o_off = b_off + align_up(bf, 64);
+  float* d = nullptr;
+  DNN_HIP_TRY(hipMalloc(&d, (o_off + of) * sizeof(float)));
+  int rc = 0;
+  if (hipMemcpy(d + a_off, a, af * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      (bf && hipMemcpy(d + b_off, b, bf * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) {
+    set_error("dnn_route_host: host to device copy failed");
+    rc = -1;
+  }
+  if (!rc) rc = launch_route(d + a_off, bf ? d + b_off : nullptr, d + o_off, n, h, w, ca, block, cb, b_first, nullptr);
+  if (!rc && hipMemcpy(out, d + o_off, of * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("dnn_route_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
+    rc = -1;
+  }
+  (void)hipFree(d);
+  return rc;
 }
 
 int dnn_plan_output_shape(const dnn_plan* p, int* batch, int* h, int* w, int* c) {
@@ -744,6 +920,9 @@ static int upload_weights(dnn_plan* p) {
 int dnn_plan_finalize(dnn_plan* p, int device, void* weights, void* workspace) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_finalize: plan is NULL or already finalized");
   DNN_REQUIRE(!p->layers.empty(), "dnn_plan_finalize: plan has no layers");
+  DNN_REQUIRE(p->layers.back().type != LAYER_STASH && p->layers.back().type != LAYER_RESTORE,
+              "dnn_plan_finalize: the plan ends in a %s: its output would not be written (end with a layer that "
+              "computes)", p->layers.back().type == LAYER_STASH ? "stash" : "restore");
   if (p->fp16)
     for (auto& L : p->layers) {
       DNN_REQUIRE(L.type != 0 || L.mode != MODE_GEMM,
@@ -761,6 +940,7 @@ int dnn_plan_finalize(dnn_plan* p, int device, void* weights, void* workspace) {
     for (auto& L : p->layers)
       if (L.out_padded)
         ok = ok && (unsigned long long)p->batch * (L.out_h() + 2) * (L.out_w() + 2) * L.OC * (p->fp16 ? 2 : 6) < lim;
+    for (size_t e : p->region_elems) ok = ok && (unsigned long long)p->batch * e * 4 < lim;
     DNN_REQUIRE(ok, "dnn_plan_finalize: batch %d makes an activation region >= 2 GiB; split the batch over plans",
                 p->batch);
   }
@@ -940,9 +1120,19 @@ int dnn_plan_run(dnn_plan* p, int n, const float* d_in, float* d_out, void* stre
   const float* cur = d_in;
   const int nl = (int)p->layers.size();
   unsigned short* padr = reinterpret_cast<unsigned short*>(slab + p->slab_floats + p->ticket_floats);
+  float* regions = slab + p->slab_floats + p->ticket_floats + p->pad_floats;
+  auto at = [&](int loc) -> float* {  // (LOC_IN is only ever read)
+    return loc == LOC_OUT ? d_out : loc == LOC_IN ? const_cast<float*>(d_in) : loc < LOC_IN ? act[loc]
+                                                                      : regions + p->region_off[loc - LOC_REGION];
+  };
   for (int i = 0; i < nl; ++i) {
     PlanLayer& L = p->layers[i];
-    float* dst = (i == nl - 1) ? d_out : act[i & 1];
+    if (L.type == LAYER_STASH) continue;  // its producer wrote the slot's region (or it is d_in)
+    if (L.type == LAYER_RESTORE) {
+      cur = at(L.dst_loc);
+      continue;
+    }
+    float* dst = at(L.dst_loc);  // chains: d_out for the last layer, else act[i & 1]
     // output in x3 split planes (the next layer is MODE_X3)
     unsigned short* dsplit = L.out_padded ? padr + L.pad_off * 2 : nullptr;
     int k = L.kernel_idx;
@@ -1023,7 +1213,7 @@ int dnn_plan_run(dnn_plan* p, int n, const float* d_in, float* d_out, void* stre
                          : launch_conv_x3(reinterpret_cast<const unsigned short*>(cur),
                                           reinterpret_cast<const unsigned short*>(wt), slab, nullptr, Mc, L.OC, L.Npad,
                                           L.K, L.H, L.W, L.C, epi, s, L.splits);
-            if (!rc && !(i + 1 < nl && p->layers[i + 1].type == 1)) {
+            if (!rc && !(i + 1 < nl && p->layers[i + 1].type == LAYER_POOL)) {
               PoolGeom id{n, L.OH, L.OW, L.OC, L.OH, L.OW, 1, 1, 1, 1, 0, 0, 0};
               if ((rc = record(p, ++k, s))) return rc;
               rc = launch_x3_combine(slab, L.splits, Mc * L.OC, epi, id, dsplit ? nullptr : dst, dsplit, s);
@@ -1044,6 +1234,10 @@ int dnn_plan_run(dnn_plan* p, int n, const float* d_in, float* d_out, void* stre
         if ((rc = record(p, ++k, s))) return rc;
         if ((rc = launch_splitk_reduce(slab, L.splits, Mc, L.OC, dst, L.OC, epi, s))) return rc;
       }
+    } else if (L.type == LAYER_ROUTE) {
+      if ((rc = record(p, k, s))) return rc;
+      const float* b = L.slot >= 0 ? at(p->slots[L.slot].loc) : nullptr;
+      if ((rc = launch_route(cur, b, dst, n, L.H, L.W, L.C, L.block, L.Cb, L.slot_first ? 1 : 0, s))) return rc;
     } else {
       PoolGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, 0};
       if ((rc = record(p, k, s))) return rc;
@@ -1148,6 +1342,15 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
                L.pool ? " +pool2x2s2" : L.pool1 ? " +pool2x2s1" : "", sk,
                L.splits > 1 ? (L.mode == MODE_X3 ? " x3-combine" : fused_splitk(p) ? " combine" : "") : "",
                p->fp16 ? " fp16" : "", p->latency ? " latency" : "");
+    } else if (L.type == LAYER_STASH || L.type == LAYER_RESTORE) {
+      snprintf(line, sizeof(line), "%s %dx%dx%d slot=%d\n", L.type == LAYER_STASH ? "stash" : "restore", L.H, L.W, L.C,
+               L.slot);
+    } else if (L.type == LAYER_ROUTE) {
+      char sb[64] = "";
+      if (L.slot >= 0)
+        snprintf(sb, sizeof(sb), " slot=%d (%dx%dx%d) %s", L.slot, L.OH, L.OW, L.Cb, L.slot_first ? "first" : "last");
+      snprintf(line, sizeof(line), "route %dx%dx%d -> %dx%dx%d block=%d%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.block,
+               sb);
     } else
       snprintf(line, sizeof(line), "pool %dx%dx%d -> %dx%dx%d k%dx%d s%d%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.kh,
                L.kw, L.sh, p->fp16 ? " fp16" : "");

@@ -13,7 +13,10 @@ engines by its import line (proj3/yolov2tiny.py:5):
 Execution.  `run` lowers the node chain ONCE to a device-resident plan
 (include/dnn_hip_plan.h): every Conv2D -> BiasAdd -> BatchNorm -> LeakyReLU run becomes
 one im2col + fp32-MFMA GEMM with the element-wise ops in its epilogue, every MaxPool2D
-one pool kernel; weights are uploaded once and activations stay in HBM.  With
+one pool kernel; weights are uploaded once and activations stay in HBM.  Two node kinds the
+reference lacks, `SpaceToDepth` and `Concat` (`create_space_to_depth`, `create_concat`), express
+YOLOv2's passthrough: a fork joined by a Concat lowers to stash / restore / route plan entries
+(the route kernel does the fold and the concat in one pass).  With
 `debug=True` (or a graph the plan cannot express) it instead runs node by node through
 the per-op C-ABI (`conv2d_mul`, `bias_add`, ... in libdnn_hip.so, include/dnn_hip.h),
 exactly like the reference, and saves every layer to ./intermediate/layer_{k}.npy
@@ -56,6 +59,10 @@ def _bind_plan_api(lib):
         "dnn_plan_destroy": (None, [vp]),
         "dnn_plan_add_conv": (i, [vp, i, i, i, i, i, i, vp, vp, vp, vp, vp, f, i]),
         "dnn_plan_add_max_pool": (i, [vp, i, i, i, i, i]),
+        "dnn_plan_add_stash": (i, [vp, P(i)]),
+        "dnn_plan_add_restore": (i, [vp, i]),
+        "dnn_plan_add_route": (i, [vp, i, i, i]),
+        "dnn_route_host": (i, [vp, vp, vp, i, i, i, i, i, i, i]),
         "dnn_plan_output_shape": (i, [vp, P(i), P(i), P(i), P(i)]),
         "dnn_plan_describe": (i, [vp, ctypes.c_char_p, i]),
         "dnn_plan_memory": (i, [vp, P(sz), P(sz)]),
@@ -240,7 +247,7 @@ class DnnGraphBuilder(object):
     def __init__(self):
         self.G = nx.DiGraph() if nx is not None else _DiGraph()
         self.name_num = {"conv2d": 0, "bias_add": 0, "max_pool2d": 0, "batch_norm": 0, "leaky_relu": 0,
-                         "input": 0}
+                         "input": 0, "space_to_depth": 0, "concat": 0}
         self.in_node = None
         self.out_node = None
 
@@ -287,6 +294,17 @@ class DnnGraphBuilder(object):
     def create_leaky_relu(self, in_node):
         out_node = LeakyReLU(self.get_name("leaky_relu"), in_node)
         self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_space_to_depth(self, in_node, block):
+        out_node = SpaceToDepth(self.get_name("space_to_depth"), in_node, block)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_concat(self, in_nodes):
+        out_node = Concat(self.get_name("concat"), in_nodes)
+        for in_node in out_node.in_nodes:
+            self.G.add_edge(in_node, out_node)
         return out_node
 
     def create_input(self, in_shape):
@@ -437,6 +455,60 @@ class LeakyReLU(DnnNode):
         _check_legacy(self.name)
 
 
+MAX_ROUTE_BLOCK = 8  # dnn_plan_add_route / dnn_route_host: block in 1..8
+MAX_SLOTS = 4        # dnn_plan_add_stash: slots per plan
+
+
+def _route_host(name, a, b, out, block, b_first=False):
+    """out = route(a, b, block) through dnn_route_host (include/dnn_hip_plan.h)."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    b = None if b is None else np.ascontiguousarray(b, dtype=np.float32)
+    n, h, w, ca = a.shape
+    rc = mylib.dnn_route_host(_vp(a), _vp(b), _vp(out), n, h, w, ca, int(block), 0 if b is None else b.shape[3],
+                              1 if b_first else 0)
+    _check(rc, name)
+
+
+class SpaceToDepth(DnnNode):
+    """Not in the reference (YOLOv2's passthrough needs it): [n, H, W, C] ->
+    [n, H/block, W/block, block*block*C] in TensorFlow's space_to_depth channel order,
+    out[n, h, w, (dy*block + dx)*C + c] = in[n, h*block + dy, w*block + dx, c] (not Darknet's
+    reorg order).  run() -> dnn_route_host."""
+
+    def __init__(self, name, in_node, block):
+        if len(in_node.result.shape) != 4 or int(block) != block or not 1 <= block <= MAX_ROUTE_BLOCK:
+            raise ValueError
+        batch, h, w, c = in_node.result.shape
+        if h % block or w % block:
+            raise ValueError
+        self.in_node = in_node
+        self.block = int(block)
+        self.result = np.zeros((batch, h // self.block, w // self.block, self.block * self.block * c), dtype='float32')
+        self.name = name
+
+    def run(self):
+        _route_host(self.name, self.in_node.result, None, self.result, self.block)
+
+
+class Concat(DnnNode):
+    """Not in the reference: channel concat of exactly two NHWC tensors of the same batch and
+    spatial size, in the order given.  run() -> dnn_route_host with block 1."""
+
+    def __init__(self, name, in_nodes):
+        in_nodes = list(in_nodes)
+        if len(in_nodes) != 2 or any(len(n.result.shape) != 4 for n in in_nodes):
+            raise ValueError
+        sa, sb = in_nodes[0].result.shape, in_nodes[1].result.shape
+        if tuple(sa[:3]) != tuple(sb[:3]):
+            raise ValueError
+        self.in_nodes = in_nodes
+        self.result = np.zeros(tuple(sa[:3]) + (sa[3] + sb[3],), dtype='float32')
+        self.name = name
+
+    def run(self):
+        _route_host(self.name, self.in_nodes[0].result, self.in_nodes[1].result, self.result, 1)
+
+
 class Input(DnnNode):
     """proj3/dnn_openblas.py:287-300 (unchanged contract)."""
 
@@ -470,44 +542,152 @@ class PoolEntry(object):
         self.nodes = [pool]
 
 
+class StashEntry(object):
+    """dnn_plan_add_stash: the current tensor becomes slot `slot` (no kernel)."""
+
+    def __init__(self, slot):
+        self.slot = slot
+        self.nodes = []
+
+
+class RestoreEntry(object):
+    """dnn_plan_add_restore: slot `slot` becomes the current tensor (no kernel)."""
+
+    def __init__(self, slot):
+        self.slot = slot
+        self.nodes = []
+
+
+class RouteEntry(object):
+    """dnn_plan_add_route: space_to_depth(current, block) concatenated with slot `slot`'s tensor
+    (-1: none), the slot's channels first with slot_first."""
+
+    def __init__(self, block, slot=-1, slot_first=False, nodes=()):
+        self.block, self.slot, self.slot_first = int(block), int(slot), bool(slot_first)
+        self.nodes = list(nodes)
+
+
+def _lower_one(g, nxt):
+    """The plan entry that starts at node `nxt`, and the last node it covers; None if `nxt` is
+    not the start of one."""
+    if isinstance(nxt, Conv2D):
+        e = ConvEntry(nxt)
+        cur = nxt
+        for kind in (BiasAdd, BatchNorm, LeakyReLU):
+            nn = list(g.G.successors(cur))
+            if g.is_out_node(cur) or len(nn) != 1 or not isinstance(nn[0], kind):
+                continue
+            cur = nn[0]
+            if kind is BiasAdd:
+                e.bias = cur
+            elif kind is BatchNorm:
+                e.bn = cur
+            else:
+                e.leaky = True
+            e.nodes.append(cur)
+        return e, cur
+    if isinstance(nxt, MaxPool2D):
+        return PoolEntry(nxt), nxt
+    if isinstance(nxt, SpaceToDepth):
+        return RouteEntry(nxt.block, nodes=[nxt]), nxt
+    return None  # a standalone element-wise op: not expressible as a fused entry
+
+
+def _lower_fork(g, x, heads, nslots):
+    """Node `x` has the two successors `heads`: lower the two chains up to the Concat that joins
+    them.  Returns (entries, the Concat, slots used so far), or None for anything but two plain
+    chains (either may be empty) meeting in one Concat."""
+    chains, joins = [], []
+    for cur in heads:
+        chain = []
+        while not (isinstance(cur, Concat) and len(list(g.G.predecessors(cur))) == 2):
+            succ = list(g.G.successors(cur))
+            if len(list(g.G.predecessors(cur))) != 1 or len(succ) != 1 or g.is_out_node(cur):
+                return None  # a nested fork, a join of another kind, or the output inside a branch
+            chain.append(cur)
+            cur = succ[0]
+        chains.append(chain)
+        joins.append(cur)
+    join = joins[0]
+    if joins[1] is not join:
+        return None
+    tails = [c[-1] if c else x for c in chains]
+    if tails[0] is join.in_nodes[1] and tails[1] is join.in_nodes[0]:
+        chains.reverse()
+    elif not (tails[0] is join.in_nodes[0] and tails[1] is join.in_nodes[1]):
+        return None
+    lowered = []  # the Concat's inputs in order
+    for chain in chains:
+        es, i = [], 0
+        while i < len(chain):
+            r = _lower_one(g, chain[i])
+            if r is None:
+                return None
+            es.append(r[0])
+            i += len(r[0].nodes)
+        lowered.append(es)
+
+    def ends_in_s2d(es):
+        return bool(es) and isinstance(es[-1], RouteEntry) and es[-1].slot < 0
+
+    # the branch lowered last is the route's `a` (the other one waits in a slot): the non-empty
+    # one, then the one that ends in a SpaceToDepth (it fuses into the route), then the second
+    if not lowered[0]:
+        last = 1
+    elif not lowered[1]:
+        last = 0
+    else:
+        last = 0 if ends_in_s2d(lowered[0]) and not ends_in_s2d(lowered[1]) else 1
+    first = 1 - last
+    x_slot = nslots
+    entries = [StashEntry(x_slot)]
+    nslots += 1
+    b_slot = x_slot
+    if lowered[first]:
+        b_slot = nslots
+        nslots += 1
+        entries += lowered[first] + [StashEntry(b_slot), RestoreEntry(x_slot)]
+    if nslots > MAX_SLOTS:
+        return None
+    tail = list(lowered[last])
+    block, nodes = 1, [join]
+    if ends_in_s2d(tail):
+        s2d = tail.pop()
+        block, nodes = s2d.block, s2d.nodes + [join]
+    entries += tail + [RouteEntry(block, b_slot, slot_first=(first == 0), nodes=nodes)]
+    return entries, join, nslots
+
+
 def lower_graph(g):
-    """Lower a builder graph to fused plan entries, or None if the graph is not a plain
-    chain the plan can express (then the node-by-node path runs)."""
+    """Lower a builder graph to fused plan entries, or None if the plan cannot express it (then
+    the node-by-node path runs).  Expressible: a chain of Conv2D (with its BiasAdd / BatchNorm /
+    LeakyReLU), MaxPool2D and SpaceToDepth, and forks of two such chains (either may be empty)
+    joined by one Concat, any number of them in sequence within the plan's slots; nested forks
+    are not."""
     if g.in_node is None or g.out_node is None:
         return None
     entries = []
+    nslots = 0
     node = g.in_node
-    succ = list(g.G.successors(node))
-    while True:
-        if len(succ) != 1 or g.is_out_node(node):
-            break
-        nxt = succ[0]
-        if len(list(g.G.predecessors(nxt))) != 1:
-            return None
-        if isinstance(nxt, Conv2D):
-            e = ConvEntry(nxt)
-            cur = nxt
-            for kind in (BiasAdd, BatchNorm, LeakyReLU):
-                nn = list(g.G.successors(cur))
-                if g.is_out_node(cur) or len(nn) != 1 or not isinstance(nn[0], kind):
-                    continue
-                cur = nn[0]
-                if kind is BiasAdd:
-                    e.bias = cur
-                elif kind is BatchNorm:
-                    e.bn = cur
-                else:
-                    e.leaky = True
-                e.nodes.append(cur)
-            entries.append(e)
-            node = cur
-        elif isinstance(nxt, MaxPool2D):
-            entries.append(PoolEntry(nxt))
-            node = nxt
-        else:
-            return None  # a standalone element-wise op: not expressible as a fused entry
+    while not g.is_out_node(node):
         succ = list(g.G.successors(node))
-    if not g.is_out_node(node) or not entries:
+        if len(succ) == 1:
+            if len(list(g.G.predecessors(succ[0]))) != 1:
+                return None
+            r = _lower_one(g, succ[0])
+            if r is None:
+                return None
+            entries.append(r[0])
+            node = r[1]
+        elif len(succ) == 2:
+            r = _lower_fork(g, node, succ, nslots)
+            if r is None:
+                return None
+            entries += r[0]
+            node, nslots = r[1], r[2]
+        else:
+            return None
+    if not entries:
         return None
     return entries
 
@@ -545,6 +725,22 @@ def _pad_code(padding):
     return 1 if padding == 'SAME' else 0
 
 
+def _add_structural(lib, h, e):
+    """Emit a StashEntry / RestoreEntry / RouteEntry; False if `e` is none of them."""
+    if isinstance(e, StashEntry):
+        slot = ctypes.c_int(-1)
+        _check(lib.dnn_plan_add_stash(h, ctypes.byref(slot)), "dnn_plan_add_stash", lib)
+        if slot.value != e.slot:
+            raise DnnHipError(f"dnn_plan_add_stash gave slot {slot.value}, the lowering expected {e.slot}")
+    elif isinstance(e, RestoreEntry):
+        _check(lib.dnn_plan_add_restore(h, e.slot), "dnn_plan_add_restore", lib)
+    elif isinstance(e, RouteEntry):
+        _check(lib.dnn_plan_add_route(h, e.block, e.slot, 1 if e.slot_first else 0), "dnn_plan_add_route", lib)
+    else:
+        return False
+    return True
+
+
 class Plan(object):
     """Owner of a dnn_plan handle (include/dnn_hip_plan.h)."""
 
@@ -564,6 +760,8 @@ class Plan(object):
             _check(self.lib.dnn_plan_set_latency_mode(self.h, 1), "dnn_plan_set_latency_mode", self.lib)
         self.entries = entries
         for e in entries:
+            if _add_structural(self.lib, self.h, e):
+                continue
             if isinstance(e, ConvEntry):
                 c = e.conv
                 kh, kw, _, od = c.kernel.shape
@@ -598,7 +796,7 @@ class Plan(object):
     def from_graph(cls, g, device=0, **kw):
         entries = lower_graph(g)
         if entries is None:
-            raise DnnHipError("graph is not a conv/pool chain the fused plan can express")
+            raise DnnHipError("graph is not a conv/pool chain (with Concat-joined forks) the fused plan can express")
         return cls(g.in_node.in_shape[0], tuple(g.in_node.in_shape[1:]), entries, device=device, **kw)
 
     @staticmethod
@@ -612,6 +810,8 @@ class Plan(object):
             if latency:
                 _check(lib.dnn_plan_set_latency_mode(h, 1), "dnn_plan_set_latency_mode", lib)
             for e in entries:
+                if _add_structural(lib, h, e):
+                    continue
                 if isinstance(e, ConvEntry):
                     kh, kw, _, od = e.conv.kernel.shape
                     _check(lib.dnn_plan_add_conv(h, kh, kw, od, int(e.conv.strides[1]), int(e.conv.strides[2]),

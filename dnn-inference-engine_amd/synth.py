@@ -97,6 +97,40 @@ def yolo_weights(seed=WEIGHT_SEED, channels=CHANNELS, in_c=IN_SHAPE[2]):
     return ws
 
 
+# full YOLOv2 (yolov2.py): (output channels, kernel size) of the 23 convs in the order yolov2.YOLO_V2
+# consumes them: Darknet-19's 18 trunk convs, conv19 / conv20, the 1x1 passthrough conv on the
+# 512-channel activation, the 3x3 conv after the concat and the linear 1x1 head
+YOLOV2_TRUNK = ((32, 3), (64, 3), (128, 3), (64, 1), (128, 3), (256, 3), (128, 1), (256, 3), (512, 3), (256, 1),
+                (512, 3), (256, 1), (512, 3), (1024, 3), (512, 1), (1024, 3), (512, 1), (1024, 3))
+YOLOV2_TAIL = ((1024, 3), (1024, 3))
+YOLOV2_PASSTHROUGH = (64, 1)
+YOLOV2_PASSTHROUGH_FROM = 12  # the passthrough reads trunk conv 12's output (26 x 26 x 512 at 416)
+YOLOV2_JOINED = (1024, 3)
+YOLOV2_N_OUT = 425            # 5 anchors x (5 + 80 COCO classes)
+
+
+def yolov2_weights(seed=WEIGHT_SEED, width_div=1, n_out=YOLOV2_N_OUT, in_c=IN_SHAPE[2]):
+    """The 23-entry weight list yolov2.YOLO_V2 consumes, from the same counter-based generators
+    (layer i draws from streams 10 i + j).  width_div divides every channel count except the
+    input's and the head's n_out (a narrow model of the same topology for tests)."""
+    def wd(c):
+        if c % width_div:
+            raise ValueError(f"width_div {width_div} does not divide {c}")
+        return c // width_div
+
+    ws = []
+    ic = in_c
+    for od, k in YOLOV2_TRUNK + YOLOV2_TAIL:
+        ws.append(layer_weights(len(ws), ic, wd(od), k=k, seed=seed))
+        ic = wd(od)
+    pt_in = wd(YOLOV2_TRUNK[YOLOV2_PASSTHROUGH_FROM][0])
+    ws.append(layer_weights(len(ws), pt_in, wd(YOLOV2_PASSTHROUGH[0]), k=YOLOV2_PASSTHROUGH[1], seed=seed))
+    ic = 4 * wd(YOLOV2_PASSTHROUGH[0]) + ic
+    ws.append(layer_weights(len(ws), ic, wd(YOLOV2_JOINED[0]), k=YOLOV2_JOINED[1], seed=seed))
+    ws.append(layer_weights(len(ws), wd(YOLOV2_JOINED[0]), n_out, k=1, seed=seed, bn=False))
+    return ws
+
+
 def yolo_zero_weights(channels=CHANNELS, in_c=IN_SHAPE[2]):
     """yolo_weights' shapes with zero values, without running the generator: what a
     non-root rank lays its plan out with before the weight broadcast fills it."""

@@ -8,7 +8,8 @@
  * MFMA GEMM with the three element-wise ops as its epilogue, evaluated in the reference's
  * operation order), each MaxPool2D one pool entry, and activations never leave HBM.
  * It is what `dnn_hip.DnnInferenceEngine.run` (the Python mirror of dnn_openblas.py)
- * lowers the graph to.
+ * lowers the graph to.  Beyond the reference's chains, stash / restore / route entries let a
+ * plan fork and join (YOLOv2's passthrough: space-to-depth + channel concat).
  *
  * Conventions: plain C ABI, cdecl, no torch types.  All tensors NHWC fp32 contiguous,
  * conv kernels HWIO (the pickle layout of proj3/yolov2tiny.py:30-77).  Functions return
@@ -67,6 +68,32 @@ int dnn_plan_add_conv(dnn_plan* plan, int kh, int kw, int od, int stride_h, int 
 /* Append a MaxPool2D (proj3/dnn_openblas.py:213-242). */
 int dnn_plan_add_max_pool(dnn_plan* plan, int kh, int kw, int stride_h, int stride_w, int padding);
 
+/* Fork / join entries (fp32 plans, batch and latency mode; on an fp16 plan each of the three
+ * fails).  The reference has no such nodes: they extend its chain to YOLOv2's passthrough.
+ *
+ * dnn_plan_add_stash: the current tensor becomes slot *slot (0, 1, ... in stash order, at most 4
+ * slots) and execution continues on it.  No kernel: the layer that produces the tensor writes it
+ * into the slot's region of the workspace (batch x H x W x C floats) instead of an activation
+ * buffer; a stash as the first entry names the caller's input.  A slot is written once per run.
+ * dnn_plan_add_restore: the current tensor and shape become the slot's.  No kernel.
+ * dnn_plan_add_route: current = route(a = current [H, W, C], b = slot's tensor, block):
+ *   space_to_depth of a, [H/block, W/block, block*block*C], in TensorFlow's NHWC channel order
+ *     s2d[h, w, (dy*block + dx)*C + c] = a[h*block + dy, w*block + dx, c]
+ *   (not Darknet's reorg order), concatenated on channels with b (whose spatial size must be
+ *   H/block x W/block), b's channels first if slot_first.  slot == -1: no b (pure space_to_depth);
+ *   block == 1: plain concat.  block in 1..8, H % block == 0, W % block == 0.  One kernel
+ *   ("route%d" in dnn_plan_kernel_info, 0 flops).
+ * A plan cannot end in a stash or a restore (dnn_plan_finalize fails). */
+int dnn_plan_add_stash(dnn_plan* plan, int* slot);
+int dnn_plan_add_restore(dnn_plan* plan, int slot);
+int dnn_plan_add_route(dnn_plan* plan, int block, int slot, int slot_first);
+
+/* The route kernel on host tensors: H2D copies, launch, D2H copy, synchronise.  a [n, h, w, ca],
+ * b [n, h/block, w/block, cb] (NULL with cb == 0), out [n, h/block, w/block, block*block*ca + cb];
+ * semantics as dnn_plan_add_route (b_first = slot_first).  Each tensor must be below 2 GiB. */
+int dnn_route_host(const float* a, const float* b, float* out, int n, int h, int w, int ca, int block, int cb,
+                   int b_first);
+
 /* Output shape of the plan so far (per image, plus the planned batch). */
 int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int* c);
 
@@ -74,13 +101,16 @@ int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int*
  * explicit im2col + GEMM, direct_a = 1x1 GEMM on the input, implicit = implicit GEMM,
  * direct = direct conv, patch = LDS-patch MFMA conv), GEMM config, whether a 2x2/s2 max
  * pool is fused and whether the GEMM is split along K (splitK=3: partials + an ordered
- * reduce/epilogue kernel).  A 2x2/s2 MaxPool2D directly after an implicit, patch or direct
- * conv is folded into it; set DNN_HIP_FUSE=0 in the environment before dnn_plan_create to
- * keep every conv explicit and every pool separate (DNN_HIP_PATCH=0: no patch mode). */
+ * reduce/epilogue kernel); a stash or restore line gives the tensor's shape and its slot, a
+ * route line both shapes, the block and the slot with its shape.  A 2x2/s2 MaxPool2D directly
+ * after an implicit, patch or direct conv is folded into it; set DNN_HIP_FUSE=0 in the
+ * environment before dnn_plan_create to keep every conv explicit and every pool separate
+ * (DNN_HIP_PATCH=0: no patch mode). */
 int dnn_plan_describe(const dnn_plan* plan, char* buf, int buf_len);
 
 /* Device bytes the plan needs: packed weights + epilogue params, and workspace
- * (two activation buffers + the im2col buffer) for the planned batch. */
+ * (two activation buffers + the im2col buffer + one region per stashed tensor) for the planned
+ * batch. */
 int dnn_plan_memory(const dnn_plan* plan, size_t* weight_bytes, size_t* workspace_bytes);
 
 /* Bind device memory and upload weights.  weights / workspace may be NULL, in which case
