@@ -66,6 +66,16 @@ enum EpiFlags : int {
                        // result into the zero-bordered split planes of an x3 conv's input
 };
 
+// the epilogue's activation (both leaky variants), shared by the conv epilogue and the shortcut
+__device__ __forceinline__ float apply_leaky(float v, int flags) {
+  if (flags & EPI_LEAKY_F64) v = v < 0.f ? (float)(0.1 * (double)v) : v;
+  if (flags & EPI_LEAKY_F32) {
+    float t = v * 0.1f;
+    v = v > t ? v : t;
+  }
+  return v;
+}
+
 struct EpiParams {
   const float* bias;   // [Npad]
   const float* mean;   // [Npad] (alpha for EPI_BN_AB)
@@ -310,6 +320,13 @@ int launch_conv1_patch_f16(const half_t* in, const half_t* Bt, int ldb, half_t* 
 // 1..8 (1: plain concat); 16-byte accesses when Ca % 4 == 0 and Cb % 4 == 0; every tensor < 2 GiB
 int launch_route(const float* a, const float* b, float* out, int n, int H, int W, int Ca, int block, int Cb,
                  int b_first, hipStream_t stream);
+
+// shortcut.hip: out[i] = act(a[i] + b[i]) over `count` floats (leaky 0 none, 1 / 2 the conv
+// epilogue's two variants; one fp32 add, bit-equal to a float32 a + b); out may alias neither input.
+int launch_shortcut(const float* a, const float* b, float* out, long long count, int leaky, hipStream_t stream);
+// nearest-neighbour upsample: out [n, H*factor, W*factor, C] = in [n, H, W, C] repeated, factor in
+// 1..8; 16-byte accesses when C % 4 == 0.  Every tensor < 2 GiB
+int launch_upsample(const float* in, float* out, int n, int H, int W, int C, int factor, hipStream_t stream);
 
 // element-wise ops of the per-op ABI
 int launch_bias_add(const float* in, const float* b, float* out, long long n, int C, hipStream_t s);

@@ -111,12 +111,7 @@ __device__ __forceinline__ float apply_epilogue(float v, float bias, float mean,
   if (flags & EPI_BIAS) v = v + bias;
   if (flags & EPI_BN) v = div_rn(v - mean, sq) * gamma;
   if (flags & EPI_BN_AB) v = v * mean - sq;
-  if (flags & EPI_LEAKY_F64) v = v < 0.f ? (float)(0.1 * (double)v) : v;
-  if (flags & EPI_LEAKY_F32) {
-    float t = v * 0.1f;
-    v = v > t ? v : t;
-  }
-  return v;
+  return apply_leaky(v, flags);
 }
 
 template <int MF>

@@ -28,8 +28,16 @@
 // slot's tensor.  Stash and restore launch nothing.  All three are plan layers, so the peepholes
 // of dnn_plan_add_conv / dnn_plan_add_max_pool, which rewrite layers.back(), stop at them: a
 // stashed tensor and both inputs of a route are always plain NHWC fp32.
+//
+// Residual and top-down plans: a shortcut entry (shortcut.hip) adds a slot's tensor to the current
+// one, an upsample entry repeats the current tensor's pixels, a release entry ends a slot's life.
+// A released slot number is handed out again by the next stash, and a region is handed out again
+// once no live slot names it and the current tensor has left it, but only to a producer added
+// after that point (region_free_from): a layer never writes a region that it, or a layer before
+// it, still reads.  Plans without a release are laid out exactly as before.
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -105,8 +113,12 @@ enum ConvMode : int { MODE_GEMM = 0, MODE_DIRECT_A = 1, MODE_IMPLICIT = 2, MODE_
 static const char* kModeName[] = {"gemm", "direct_a", "implicit", "direct", "patch", "patch16", "patch_x3", "x3_1x1",
                                   "tile16"};
 
+// where a tensor of a run lives: the caller's output / input, one of the two ping-pong activation
+// buffers, or slot region r (LOC_REGION + r)
+enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, LOC_IN = 2, LOC_REGION = 3 };
+
 struct PlanLayer {
-  int type = 0;  // 0 conv, 1 pool, 2 stash, 3 restore, 4 route (LAYER_*)
+  int type = 0;  // 0 conv, 1 pool, 2 stash, 3 restore, 4 route, 5 shortcut, 6 upsample, 7 release (LAYER_*)
   // shapes (per image): input H,W,C -> conv/pool output OH,OW,OC (-> fused pool PH,PW)
   int H = 0, W = 0, C = 0, OH = 0, OW = 0, OC = 0;
   int kh = 0, kw = 0, sh = 1, sw = 1, pt = 0, pl = 0;
@@ -132,26 +144,28 @@ struct PlanLayer {
   int block = 1, Cb = 0;    // route: space-to-depth block, channels of b
   bool slot_first = false;  // route: b's channels come first
   int to_region = -1;       // a writing layer followed by a stash: the slot region it writes
+  int slot_loc = LOC_NONE;  // where the slot's tensor lives when this entry is added (slot numbers are reused)
+  int factor = 1;           // upsample
+  int leaky = 0;            // shortcut: 0 none, 1 / 2 the conv epilogue's variants
   int dst_loc = 0;          // where this layer writes (LOC_*; layout())
   int out_h() const { return pool ? PH : OH; }
   int out_w() const { return pool ? PW : OW; }
 };
 
-enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4 };
-// where a tensor of a run lives: the caller's output / input, one of the two ping-pong activation
-// buffers, or slot region r (LOC_REGION + r)
-enum TensorLoc : int { LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, LOC_IN = 2, LOC_REGION = 3 };
+enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
+                       LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7 };
 constexpr int kMaxSlots = 4;
 
 struct PlanSlot {
   int h, w, c;  // per image
   int loc;      // LOC_IN (a stash before any layer) or LOC_REGION + r
+  bool live = true;  // false once released: its number is free for the next stash
 };
 
 struct KernelDesc {
   std::string name;
   int layer;
-  int kind;             // 0 im2col, 1 gemm / conv, 2 pool, 3 reduce / combine, 4 convert, 5 route
+  int kind;             // 0 im2col, 1 gemm / conv, 2 pool, 3 reduce / combine, 4 convert, 5 route, 6 shortcut, 7 upsample
   double flops, bytes;  // algorithmic, full planned batch
 };
 
@@ -166,10 +180,15 @@ struct dnn_plan {
   bool latency = false;  // split K by M too (dnn_plan_set_latency_mode): batch-1 latency plans
   std::vector<PlanLayer> layers;
   std::vector<KernelDesc> kernels;
-  // fork / join: slots in stash order; regions (one per stashed layer output; slots of a restored
-  // or re-stashed tensor share one) as per-image floats, their float offsets inside the slot area
+  // fork / join: slots by number (at most kMaxSlots, a released number is reused); regions (one
+  // per stashed layer output unless a free one fits; slots of a restored or re-stashed tensor share
+  // one) as per-image floats (the largest tensor a region ever holds), their float offsets inside
+  // the slot area
   std::vector<PlanSlot> slots;
   std::vector<size_t> region_elems, region_off;
+  // while adding: live slots naming each region, and the first layer index that may write it again
+  // (a region with no live slot whose tensor is no longer current; INT_MAX while it is still read)
+  std::vector<int> region_refs, region_free_from;
   int cur_src = LOC_IN;  // while adding: where the current tensor lives, -1 = the last layer's output
   size_t slot_floats = 0;
   int device = -1;
@@ -229,7 +248,7 @@ static bool fp16_direct_out(const dnn_plan* p) {
 static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
-  int nconv = 0, npool = 0, nroute = 0;  // kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7
+  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0;  // kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7
   p->kernels.clear();
   const double B = p->batch;
   for (size_t i = 0; i < p->layers.size(); ++i) {
@@ -295,7 +314,13 @@ static void layout(dnn_plan* p) {
     } else if (L.type == LAYER_ROUTE) {  // reads a and b, writes out: input bytes == output bytes
       snprintf(nm, sizeof(nm), "route%d", nroute++);
       p->kernels.push_back({nm, (int)i, 5, 0.0, 2.0 * out_b});
-    }  // (a stash or a restore launches nothing)
+    } else if (L.type == LAYER_SHORTCUT) {  // one add per output element; reads a and b, writes out
+      snprintf(nm, sizeof(nm), "shortcut%d", nshort++);
+      p->kernels.push_back({nm, (int)i, 6, out_b / 4.0, 3.0 * out_b});
+    } else if (L.type == LAYER_UPSAMPLE) {
+      snprintf(nm, sizeof(nm), "upsample%d", nup++);
+      p->kernels.push_back({nm, (int)i, 7, 0.0, in_b + out_b});
+    }  // (a stash, a restore or a release launches nothing)
   }
   // where each layer writes.  Chains keep the ping-pong by layer parity; with fork / join entries
   // a layer followed by a stash writes that slot's region, and any other one the activation
@@ -304,14 +329,16 @@ static void layout(dnn_plan* p) {
     bool fork = false;
     for (auto& L : p->layers) fork = fork || L.type >= LAYER_STASH;
     int cur = LOC_IN;
+    size_t last = p->layers.size();  // the last layer that is not a release writes the output
+    while (last > 0 && p->layers[last - 1].type == LAYER_RELEASE) --last;
     for (size_t i = 0; i < p->layers.size(); ++i) {
       PlanLayer& L = p->layers[i];
-      if (L.type == LAYER_STASH) {
+      if (L.type == LAYER_STASH || L.type == LAYER_RELEASE) {
         L.dst_loc = cur;
       } else if (L.type == LAYER_RESTORE) {
-        L.dst_loc = cur = p->slots[L.slot].loc;
+        L.dst_loc = cur = L.slot_loc;
       } else {
-        L.dst_loc = i + 1 == p->layers.size() ? LOC_OUT
+        L.dst_loc = i + 1 == last ? LOC_OUT
                     : !fork                   ? (int)(i & 1)
                     : L.to_region >= 0        ? LOC_REGION + L.to_region
                     : cur == LOC_ACT0         ? LOC_ACT1
@@ -354,6 +381,18 @@ static void layout(dnn_plan* p) {
   p->slot_floats = slot_total;
   p->ws_floats = 2 * p->act_floats + p->col_floats + p->slab_floats + p->ticket_floats + p->pad_floats +
                  p->slot_floats + dnn_plan::kZeroFloats;
+}
+
+// While adding: the layer about to be pushed (index layers.size()) consumes or replaces the current
+// tensor.  If that tensor sits in a region no live slot names, the region is free for the
+// producers after this layer.
+static void current_leaves(dnn_plan* p) {
+  const int r = p->cur_src - LOC_REGION;
+  if (r >= 0 && p->region_refs[r] == 0) p->region_free_from[r] = (int)p->layers.size() + 1;
+}
+
+static bool slot_is_live(const dnn_plan* p, int slot) {
+  return slot >= 0 && slot < (int)p->slots.size() && p->slots[slot].live;
 }
 
 extern "C" {
@@ -613,6 +652,7 @@ int dnn_plan_add_conv(dnn_plan* p, int kh, int kw, int od, int stride_h, int str
       }
     }
   }
+  current_leaves(p);
   p->layers.push_back(std::move(L));
   p->cur_h = p->layers.back().OH;
   p->cur_w = p->layers.back().OW;
@@ -732,6 +772,7 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
       return 0;
     }
   }
+  current_leaves(p);
   p->layers.push_back(std::move(L));
   p->cur_h = p->layers.back().OH;
   p->cur_w = p->layers.back().OW;
@@ -750,27 +791,82 @@ int dnn_plan_add_stash(dnn_plan* p, int* slot) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_stash: plan is NULL or finalized");
   DNN_REQUIRE(slot != nullptr, "dnn_plan_add_stash: slot is NULL");
   DNN_REQUIRE(!p->fp16, "dnn_plan_add_stash: fp32 plans only (this is an fp16 plan)");
-  DNN_REQUIRE((int)p->slots.size() < kMaxSlots, "dnn_plan_add_stash: all %d slots are in use", kMaxSlots);
-  if (p->cur_src < 0) {  // the last layer's output: that layer writes a region of its own
-    p->layers.back().to_region = (int)p->region_elems.size();
-    p->cur_src = LOC_REGION + (int)p->region_elems.size();
-    p->region_elems.push_back((size_t)p->cur_h * p->cur_w * p->cur_c);
+  int number = 0;  // the lowest free slot number
+  while (number < (int)p->slots.size() && p->slots[number].live) ++number;
+  DNN_REQUIRE(number < kMaxSlots, "dnn_plan_add_stash: all %d slots are in use", kMaxSlots);
+  if (p->cur_src < 0) {  // the last computing layer's output: that layer writes a slot region
+    int producer = (int)p->layers.size() - 1;  // (only release entries can follow it)
+    while (p->layers[producer].type == LAYER_RELEASE) --producer;
+    const size_t elems = (size_t)p->cur_h * p->cur_w * p->cur_c;
+    // a region freed before the producer was added: the smallest one that is large enough, else
+    // the largest one (it grows), else a new one
+    int r = -1;
+    for (int k = 0; k < (int)p->region_elems.size(); ++k) {
+      if (p->region_refs[k] != 0 || p->region_free_from[k] > producer) continue;
+      const size_t have = p->region_elems[k];
+      if (r < 0) {
+        r = k;
+        continue;
+      }
+      const size_t best = p->region_elems[r];
+      if (best >= elems ? (have >= elems && have < best) : have > best) r = k;
+    }
+    if (r < 0) {
+      r = (int)p->region_elems.size();
+      p->region_elems.push_back(elems);
+      p->region_refs.push_back(0);
+      p->region_free_from.push_back(INT_MAX);
+    } else {
+      p->region_elems[r] = std::max(p->region_elems[r], elems);
+      p->region_free_from[r] = INT_MAX;
+    }
+    p->layers[producer].to_region = r;
+    p->cur_src = LOC_REGION + r;
   }  // (else the plan's input, or a tensor that already sits in a region)
+  if (p->cur_src >= LOC_REGION) p->region_refs[p->cur_src - LOC_REGION]++;
   PlanLayer L;
   shape_only_layer(p, &L, LAYER_STASH);
-  L.slot = (int)p->slots.size();
-  p->slots.push_back({p->cur_h, p->cur_w, p->cur_c, p->cur_src});
+  L.slot = number;
+  L.slot_loc = p->cur_src;
+  const PlanSlot S{p->cur_h, p->cur_w, p->cur_c, p->cur_src, true};
+  if (number == (int)p->slots.size())
+    p->slots.push_back(S);
+  else
+    p->slots[number] = S;
   p->layers.push_back(std::move(L));
-  *slot = p->layers.back().slot;
+  *slot = number;
+  return 0;
+}
+
+int dnn_plan_add_release(dnn_plan* p, int slot) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_release: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_release: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(slot_is_live(p, slot), "dnn_plan_add_release: slot %d is unknown or already released", slot);
+  PlanSlot& S = p->slots[slot];
+  S.live = false;
+  const int r = S.loc - LOC_REGION;
+  // its region is free for the producers after this entry, unless the current tensor still sits in
+  // it: then from the layer that consumes it on (current_leaves)
+  if (r >= 0 && --p->region_refs[r] == 0)
+    p->region_free_from[r] = p->cur_src == S.loc ? INT_MAX : (int)p->layers.size() + 1;
+  PlanLayer L;
+  L.type = LAYER_RELEASE;
+  L.H = L.OH = S.h;
+  L.W = L.OW = S.w;
+  L.C = L.OC = S.c;
+  L.slot = slot;
+  L.slot_loc = S.loc;
+  p->layers.push_back(std::move(L));
   return 0;
 }
 
 int dnn_plan_add_restore(dnn_plan* p, int slot) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_restore: plan is NULL or finalized");
   DNN_REQUIRE(!p->fp16, "dnn_plan_add_restore: fp32 plans only (this is an fp16 plan)");
-  DNN_REQUIRE(slot >= 0 && slot < (int)p->slots.size(), "dnn_plan_add_restore: unknown slot %d (%d defined)", slot,
+  DNN_REQUIRE(slot_is_live(p, slot), "dnn_plan_add_restore: unknown or released slot %d (%d defined)", slot,
               (int)p->slots.size());
   const PlanSlot& S = p->slots[slot];
+  current_leaves(p);
   p->cur_h = S.h;
   p->cur_w = S.w;
   p->cur_c = S.c;
@@ -778,6 +874,7 @@ int dnn_plan_add_restore(dnn_plan* p, int slot) {
   PlanLayer L;
   shape_only_layer(p, &L, LAYER_RESTORE);
   L.slot = slot;
+  L.slot_loc = S.loc;
   p->layers.push_back(std::move(L));
   return 0;
 }
@@ -786,8 +883,8 @@ int dnn_plan_add_route(dnn_plan* p, int block, int slot, int slot_first) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_route: plan is NULL or finalized");
   DNN_REQUIRE(!p->fp16, "dnn_plan_add_route: fp32 plans only (this is an fp16 plan)");
   DNN_REQUIRE(block >= 1 && block <= 8, "dnn_plan_add_route: block %d outside 1..8", block);
-  DNN_REQUIRE(slot >= -1 && slot < (int)p->slots.size(), "dnn_plan_add_route: unknown slot %d (%d defined)", slot,
-              (int)p->slots.size());
+  DNN_REQUIRE(slot == -1 || slot_is_live(p, slot), "dnn_plan_add_route: unknown or released slot %d (%d defined)",
+              slot, (int)p->slots.size());
   DNN_REQUIRE(p->cur_h % block == 0 && p->cur_w % block == 0,
               "dnn_plan_add_route: %dx%d input is not a multiple of block %d", p->cur_h, p->cur_w, block);
   PlanLayer L;
@@ -805,12 +902,55 @@ int dnn_plan_add_route(dnn_plan* p, int block, int slot, int slot_first) {
     DNN_REQUIRE(S.h == L.OH && S.w == L.OW, "dnn_plan_add_route: slot %d is %dx%d, the folded input %dx%d", slot, S.h,
                 S.w, L.OH, L.OW);
     L.Cb = S.c;
+    L.slot_loc = S.loc;
   }
   L.OC = block * block * L.C + L.Cb;
+  current_leaves(p);
   p->layers.push_back(std::move(L));
   p->cur_h = p->layers.back().OH;
   p->cur_w = p->layers.back().OW;
   p->cur_c = p->layers.back().OC;
+  p->cur_src = -1;
+  return 0;
+}
+
+int dnn_plan_add_shortcut(dnn_plan* p, int slot, int leaky) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_shortcut: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_shortcut: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_plan_add_shortcut: leaky must be 0, 1 or 2");
+  DNN_REQUIRE(slot_is_live(p, slot), "dnn_plan_add_shortcut: unknown or released slot %d (%d defined)", slot,
+              (int)p->slots.size());
+  const PlanSlot& S = p->slots[slot];
+  DNN_REQUIRE(S.h == p->cur_h && S.w == p->cur_w && S.c == p->cur_c,
+              "dnn_plan_add_shortcut: slot %d is %dx%dx%d, the current tensor %dx%dx%d", slot, S.h, S.w, S.c, p->cur_h,
+              p->cur_w, p->cur_c);
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_SHORTCUT);
+  L.slot = slot;
+  L.slot_loc = S.loc;
+  L.leaky = leaky;
+  current_leaves(p);
+  p->layers.push_back(std::move(L));
+  p->cur_src = -1;
+  return 0;
+}
+
+int dnn_plan_add_upsample(dnn_plan* p, int factor) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_upsample: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_upsample: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(factor >= 1 && factor <= 8, "dnn_plan_add_upsample: factor %d outside 1..8", factor);
+  PlanLayer L;
+  L.type = LAYER_UPSAMPLE;
+  L.H = p->cur_h;
+  L.W = p->cur_w;
+  L.C = L.OC = p->cur_c;
+  L.OH = L.H * factor;
+  L.OW = L.W * factor;
+  L.factor = factor;
+  current_leaves(p);
+  p->layers.push_back(std::move(L));
+  p->cur_h = p->layers.back().OH;
+  p->cur_w = p->layers.back().OW;
   p->cur_src = -1;
   return 0;
 }
@@ -842,6 +982,58 @@ int dnn_route_host(const float* a, const float* b, float* out, int n, int h, int
   if (!rc) rc = launch_route(d + a_off, bf ? d + b_off : nullptr, d + o_off, n, h, w, ca, block, cb, b_first, nullptr);
   if (!rc && hipMemcpy(out, d + o_off, of * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
     set_error("dnn_route_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
+    rc = -1;
+  }
+  (void)hipFree(d);
+  return rc;
+}
+
+int dnn_shortcut_host(const float* a, const float* b, float* out, int n, int h, int w, int c, int leaky) {
+  DNN_REQUIRE(a && b && out, "dnn_shortcut_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_shortcut_host: bad shape n=%d %dx%dx%d", n, h, w, c);
+  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_shortcut_host: leaky must be 0, 1 or 2");
+  if (n == 0) return 0;
+  const size_t f = (size_t)n * h * w * c;
+  DNN_REQUIRE(f * 4 < 0x80000000ULL, "dnn_shortcut_host: a tensor of n=%d %dx%dx%d is >= 2 GiB; split the batch", n, h,
+              w, c);
+  const size_t step = align_up(f, 64);
+  float* d = nullptr;
+  DNN_HIP_TRY(hipMalloc(&d, (2 * step + f) * sizeof(float)));
+  int rc = 0;
+  if (hipMemcpy(d, a, f * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d + step, b, f * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("dnn_shortcut_host: host to device copy failed");
+    rc = -1;
+  }
+  if (!rc) rc = launch_shortcut(d, d + step, d + 2 * step, (long long)f, leaky, nullptr);
+  if (!rc && hipMemcpy(out, d + 2 * step, f * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("dnn_shortcut_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
+    rc = -1;
+  }
+  (void)hipFree(d);
+  return rc;
+}
+
+int dnn_upsample_host(const float* a, float* out, int n, int h, int w, int c, int factor) {
+  DNN_REQUIRE(a && out, "dnn_upsample_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_upsample_host: bad shape n=%d %dx%dx%d", n, h, w, c);
+  DNN_REQUIRE(factor >= 1 && factor <= 8, "dnn_upsample_host: factor %d outside 1..8", factor);
+  if (n == 0) return 0;
+  const size_t af = (size_t)n * h * w * c;
+  DNN_REQUIRE(af * 4 < 0x80000000ULL && af * factor * factor * 4 < 0x80000000ULL,
+              "dnn_upsample_host: the output of n=%d %dx%dx%d factor %d is >= 2 GiB; split the batch", n, h, w, c,
+              factor);
+  const size_t of = af * factor * factor, o_off = align_up(af, 64);
+  float* d = nullptr;
+  DNN_HIP_TRY(hipMalloc(&d, (o_off + of) * sizeof(float)));
+  int rc = 0;
+  if (hipMemcpy(d, a, af * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("dnn_upsample_host: host to device copy failed");
+    rc = -1;
+  }
+  if (!rc) rc = launch_upsample(d, d + o_off, n, h, w, c, factor, nullptr);
+  if (!rc && hipMemcpy(out, d + o_off, of * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("dnn_upsample_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
     rc = -1;
   }
   (void)hipFree(d);
@@ -920,9 +1112,15 @@ static int upload_weights(dnn_plan* p) {
 int dnn_plan_finalize(dnn_plan* p, int device, void* weights, void* workspace) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_finalize: plan is NULL or already finalized");
   DNN_REQUIRE(!p->layers.empty(), "dnn_plan_finalize: plan has no layers");
-  DNN_REQUIRE(p->layers.back().type != LAYER_STASH && p->layers.back().type != LAYER_RESTORE,
-              "dnn_plan_finalize: the plan ends in a %s: its output would not be written (end with a layer that "
-              "computes)", p->layers.back().type == LAYER_STASH ? "stash" : "restore");
+  {
+    size_t last = p->layers.size();  // (release entries after the last writer do not count)
+    while (last > 0 && p->layers[last - 1].type == LAYER_RELEASE) --last;
+    DNN_REQUIRE(last > 0, "dnn_plan_finalize: plan has no layer that computes");
+    const int t = p->layers[last - 1].type;
+    DNN_REQUIRE(t != LAYER_STASH && t != LAYER_RESTORE,
+                "dnn_plan_finalize: the plan ends in a %s: its output would not be written (end with a layer that "
+                "computes)", t == LAYER_STASH ? "stash" : "restore");
+  }
   if (p->fp16)
     for (auto& L : p->layers) {
       DNN_REQUIRE(L.type != 0 || L.mode != MODE_GEMM,
@@ -1127,7 +1325,8 @@ int dnn_plan_run(dnn_plan* p, int n, const float* d_in, float* d_out, void* stre
   };
   for (int i = 0; i < nl; ++i) {
     PlanLayer& L = p->layers[i];
-    if (L.type == LAYER_STASH) continue;  // its producer wrote the slot's region (or it is d_in)
+    // a stash: its producer wrote the slot's region (or it is d_in); a release: nothing to do
+    if (L.type == LAYER_STASH || L.type == LAYER_RELEASE) continue;
     if (L.type == LAYER_RESTORE) {
       cur = at(L.dst_loc);
       continue;
@@ -1236,8 +1435,14 @@ int dnn_plan_run(dnn_plan* p, int n, const float* d_in, float* d_out, void* stre
       }
     } else if (L.type == LAYER_ROUTE) {
       if ((rc = record(p, k, s))) return rc;
-      const float* b = L.slot >= 0 ? at(p->slots[L.slot].loc) : nullptr;
+      const float* b = L.slot >= 0 ? at(L.slot_loc) : nullptr;
       if ((rc = launch_route(cur, b, dst, n, L.H, L.W, L.C, L.block, L.Cb, L.slot_first ? 1 : 0, s))) return rc;
+    } else if (L.type == LAYER_SHORTCUT) {
+      if ((rc = record(p, k, s))) return rc;
+      if ((rc = launch_shortcut(cur, at(L.slot_loc), dst, (long long)n * L.H * L.W * L.C, L.leaky, s))) return rc;
+    } else if (L.type == LAYER_UPSAMPLE) {
+      if ((rc = record(p, k, s))) return rc;
+      if ((rc = launch_upsample(cur, dst, n, L.H, L.W, L.C, L.factor, s))) return rc;
     } else {
       PoolGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, 0};
       if ((rc = record(p, k, s))) return rc;
@@ -1351,6 +1556,14 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
         snprintf(sb, sizeof(sb), " slot=%d (%dx%dx%d) %s", L.slot, L.OH, L.OW, L.Cb, L.slot_first ? "first" : "last");
       snprintf(line, sizeof(line), "route %dx%dx%d -> %dx%dx%d block=%d%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.block,
                sb);
+    } else if (L.type == LAYER_SHORTCUT) {
+      snprintf(line, sizeof(line), "shortcut %dx%dx%d slot=%d act=%s\n", L.H, L.W, L.C, L.slot,
+               L.leaky == 1 ? "leaky" : L.leaky == 2 ? "leaky_f32" : "none");
+    } else if (L.type == LAYER_UPSAMPLE) {
+      snprintf(line, sizeof(line), "upsample %dx%dx%d -> %dx%dx%d factor=%d\n", L.H, L.W, L.C, L.OH, L.OW, L.OC,
+               L.factor);
+    } else if (L.type == LAYER_RELEASE) {
+      snprintf(line, sizeof(line), "release %dx%dx%d slot=%d\n", L.H, L.W, L.C, L.slot);
     } else
       snprintf(line, sizeof(line), "pool %dx%dx%d -> %dx%dx%d k%dx%d s%d%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.kh,
                L.kw, L.sh, p->fp16 ? " fp16" : "");

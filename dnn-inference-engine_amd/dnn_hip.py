@@ -16,7 +16,10 @@ one im2col + fp32-MFMA GEMM with the element-wise ops in its epilogue, every Max
 one pool kernel; weights are uploaded once and activations stay in HBM.  Two node kinds the
 reference lacks, `SpaceToDepth` and `Concat` (`create_space_to_depth`, `create_concat`), express
 YOLOv2's passthrough: a fork joined by a Concat lowers to stash / restore / route plan entries
-(the route kernel does the fold and the concat in one pass).  With
+(the route kernel does the fold and the concat in one pass).  Two more, `Add` and `Upsample`
+(`create_add`, `create_upsample`), express the residual block y = x + f(x) and the top-down
+merge: a fork joined by an Add lowers to stash / shortcut / release entries (a release hands the
+slot and its workspace region back, so any number of blocks fit in one plan).  With
 `debug=True` (or a graph the plan cannot express) it instead runs node by node through
 the per-op C-ABI (`conv2d_mul`, `bias_add`, ... in libdnn_hip.so, include/dnn_hip.h),
 exactly like the reference, and saves every layer to ./intermediate/layer_{k}.npy
@@ -63,6 +66,11 @@ def _bind_plan_api(lib):
         "dnn_plan_add_restore": (i, [vp, i]),
         "dnn_plan_add_route": (i, [vp, i, i, i]),
         "dnn_route_host": (i, [vp, vp, vp, i, i, i, i, i, i, i]),
+        "dnn_plan_add_shortcut": (i, [vp, i, i]),
+        "dnn_plan_add_upsample": (i, [vp, i]),
+        "dnn_plan_add_release": (i, [vp, i]),
+        "dnn_shortcut_host": (i, [vp, vp, vp, i, i, i, i, i]),
+        "dnn_upsample_host": (i, [vp, vp, i, i, i, i, i]),
         "dnn_plan_output_shape": (i, [vp, P(i), P(i), P(i), P(i)]),
         "dnn_plan_describe": (i, [vp, ctypes.c_char_p, i]),
         "dnn_plan_memory": (i, [vp, P(sz), P(sz)]),
@@ -247,7 +255,7 @@ class DnnGraphBuilder(object):
     def __init__(self):
         self.G = nx.DiGraph() if nx is not None else _DiGraph()
         self.name_num = {"conv2d": 0, "bias_add": 0, "max_pool2d": 0, "batch_norm": 0, "leaky_relu": 0,
-                         "input": 0, "space_to_depth": 0, "concat": 0}
+                         "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0}
         self.in_node = None
         self.out_node = None
 
@@ -305,6 +313,17 @@ class DnnGraphBuilder(object):
         out_node = Concat(self.get_name("concat"), in_nodes)
         for in_node in out_node.in_nodes:
             self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_add(self, in_nodes):
+        out_node = Add(self.get_name("add"), in_nodes)
+        for in_node in out_node.in_nodes:
+            self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_upsample(self, in_node, factor):
+        out_node = Upsample(self.get_name("upsample"), in_node, factor)
+        self.G.add_edge(in_node, out_node)
         return out_node
 
     def create_input(self, in_shape):
@@ -509,6 +528,51 @@ class Concat(DnnNode):
         _route_host(self.name, self.in_nodes[0].result, self.in_nodes[1].result, self.result, 1)
 
 
+MAX_UPSAMPLE_FACTOR = 8  # dnn_plan_add_upsample / dnn_upsample_host: factor in 1..8
+
+
+class Add(DnnNode):
+    """Not in the reference (the residual block y = x + f(x) needs it): the element-wise sum of
+    exactly two NHWC tensors of identical shape, one fp32 add per element.  run() ->
+    dnn_shortcut_host."""
+
+    def __init__(self, name, in_nodes):
+        in_nodes = list(in_nodes)
+        if len(in_nodes) != 2 or any(len(n.result.shape) != 4 for n in in_nodes):
+            raise ValueError
+        if tuple(in_nodes[0].result.shape) != tuple(in_nodes[1].result.shape):
+            raise ValueError
+        self.in_nodes = in_nodes
+        self.result = np.zeros(tuple(in_nodes[0].result.shape), dtype='float32')
+        self.name = name
+
+    def run(self):
+        a = np.ascontiguousarray(self.in_nodes[0].result, dtype=np.float32)
+        b = np.ascontiguousarray(self.in_nodes[1].result, dtype=np.float32)
+        rc = mylib.dnn_shortcut_host(_vp(a), _vp(b), _vp(self.result), *map(int, a.shape), 0)
+        _check(rc, self.name)
+
+
+class Upsample(DnnNode):
+    """Not in the reference (a top-down merge needs it): nearest-neighbour upsample,
+    [n, H, W, C] -> [n, H*factor, W*factor, C], out[n, h, w, c] = in[n, h // factor, w // factor, c].
+    run() -> dnn_upsample_host."""
+
+    def __init__(self, name, in_node, factor):
+        if len(in_node.result.shape) != 4 or int(factor) != factor or not 1 <= factor <= MAX_UPSAMPLE_FACTOR:
+            raise ValueError
+        batch, h, w, c = in_node.result.shape
+        self.in_node = in_node
+        self.factor = int(factor)
+        self.result = np.zeros((batch, h * self.factor, w * self.factor, c), dtype='float32')
+        self.name = name
+
+    def run(self):
+        a = np.ascontiguousarray(self.in_node.result, dtype=np.float32)
+        rc = mylib.dnn_upsample_host(_vp(a), _vp(self.result), *map(int, a.shape), self.factor)
+        _check(rc, self.name)
+
+
 class Input(DnnNode):
     """proj3/dnn_openblas.py:287-300 (unchanged contract)."""
 
@@ -567,6 +631,31 @@ class RouteEntry(object):
         self.nodes = list(nodes)
 
 
+class ShortcutEntry(object):
+    """dnn_plan_add_shortcut: current = act(current + slot `slot`'s tensor); `leaky` when a
+    LeakyReLU directly after the Add is folded in."""
+
+    def __init__(self, slot, leaky=False, nodes=()):
+        self.slot, self.leaky = int(slot), bool(leaky)
+        self.nodes = list(nodes)
+
+
+class ReleaseEntry(object):
+    """dnn_plan_add_release: slot `slot` stops being live; its number and region are reused."""
+
+    def __init__(self, slot):
+        self.slot = int(slot)
+        self.nodes = []
+
+
+class UpsampleEntry(object):
+    """dnn_plan_add_upsample: nearest-neighbour upsample of the current tensor by `factor`."""
+
+    def __init__(self, factor, nodes=()):
+        self.factor = int(factor)
+        self.nodes = list(nodes)
+
+
 def _lower_one(g, nxt):
     """The plan entry that starts at node `nxt`, and the last node it covers; None if `nxt` is
     not the start of one."""
@@ -590,17 +679,21 @@ def _lower_one(g, nxt):
         return PoolEntry(nxt), nxt
     if isinstance(nxt, SpaceToDepth):
         return RouteEntry(nxt.block, nodes=[nxt]), nxt
+    if isinstance(nxt, Upsample):
+        return UpsampleEntry(nxt.factor, nodes=[nxt]), nxt
     return None  # a standalone element-wise op: not expressible as a fused entry
 
 
 def _lower_fork(g, x, heads, nslots):
-    """Node `x` has the two successors `heads`: lower the two chains up to the Concat that joins
-    them.  Returns (entries, the Concat, slots used so far), or None for anything but two plain
-    chains (either may be empty) meeting in one Concat."""
+    """Node `x` has the two successors `heads`: lower the two chains up to the Concat or Add that
+    joins them.  Returns (entries, the last node covered, slots used so far), or None for anything
+    but two plain chains (either may be empty) meeting in one Concat or one Add.  A Concat keeps its
+    slots to the end of the plan; an Add block releases every slot it opens, so any number of them
+    fit in sequence."""
     chains, joins = [], []
     for cur in heads:
         chain = []
-        while not (isinstance(cur, Concat) and len(list(g.G.predecessors(cur))) == 2):
+        while not (isinstance(cur, (Concat, Add)) and len(list(g.G.predecessors(cur))) == 2):
             succ = list(g.G.successors(cur))
             if len(list(g.G.predecessors(cur))) != 1 or len(succ) != 1 or g.is_out_node(cur):
                 return None  # a nested fork, a join of another kind, or the output inside a branch
@@ -616,7 +709,7 @@ def _lower_fork(g, x, heads, nslots):
         chains.reverse()
     elif not (tails[0] is join.in_nodes[0] and tails[1] is join.in_nodes[1]):
         return None
-    lowered = []  # the Concat's inputs in order
+    lowered = []  # the join's inputs in order
     for chain in chains:
         es, i = [], 0
         while i < len(chain):
@@ -626,6 +719,8 @@ def _lower_fork(g, x, heads, nslots):
             es.append(r[0])
             i += len(r[0].nodes)
         lowered.append(es)
+    if isinstance(join, Add):
+        return _emit_add_block(g, join, lowered, nslots)
 
     def ends_in_s2d(es):
         return bool(es) and isinstance(es[-1], RouteEntry) and es[-1].slot < 0
@@ -658,12 +753,39 @@ def _lower_fork(g, x, heads, nslots):
     return entries, join, nslots
 
 
+def _emit_add_block(g, join, lowered, nslots):
+    """The entries of a fork joined by the Add `join` (its inputs' chains lowered in `lowered`):
+    Stash(x), f..., Shortcut(x), Release(x) with one empty branch, else Stash(x), first..., Stash(a),
+    Restore(x), second..., Shortcut(a), Release(x), Release(a).  The slots are the lowest free
+    numbers and are all released, so at most two are live on top of the Concat forks' ones."""
+    last_node, leaky = join, False
+    succ = list(g.G.successors(join))
+    if not g.is_out_node(join) and len(succ) == 1 and isinstance(succ[0], LeakyReLU) \
+            and len(list(g.G.predecessors(succ[0]))) == 1:
+        last_node, leaky = succ[0], True  # a single LeakyReLU directly after the Add: the shortcut's activation
+    nodes = [join] + ([last_node] if leaky else [])
+    x_slot = nslots
+    if not lowered[0] or not lowered[1]:
+        if x_slot + 1 > MAX_SLOTS or not (lowered[0] or lowered[1]):
+            return None
+        entries = [StashEntry(x_slot)] + (lowered[0] or lowered[1])
+        entries += [ShortcutEntry(x_slot, leaky, nodes), ReleaseEntry(x_slot)]
+        return entries, last_node, nslots
+    a_slot = nslots + 1
+    if a_slot + 1 > MAX_SLOTS:
+        return None
+    entries = [StashEntry(x_slot)] + lowered[0] + [StashEntry(a_slot), RestoreEntry(x_slot)] + lowered[1]
+    entries += [ShortcutEntry(a_slot, leaky, nodes), ReleaseEntry(x_slot), ReleaseEntry(a_slot)]
+    return entries, last_node, nslots
+
+
 def lower_graph(g):
     """Lower a builder graph to fused plan entries, or None if the plan cannot express it (then
     the node-by-node path runs).  Expressible: a chain of Conv2D (with its BiasAdd / BatchNorm /
-    LeakyReLU), MaxPool2D and SpaceToDepth, and forks of two such chains (either may be empty)
-    joined by one Concat, any number of them in sequence within the plan's slots; nested forks
-    are not."""
+    LeakyReLU), MaxPool2D, SpaceToDepth and Upsample, and forks of two such chains (either may be
+    empty) joined by one Concat or one Add (with a LeakyReLU directly after it), any number of
+    them in sequence within the plan's slots (an Add block gives its slots back); nested forks are
+    not."""
     if g.in_node is None or g.out_node is None:
         return None
     entries = []
@@ -725,8 +847,9 @@ def _pad_code(padding):
     return 1 if padding == 'SAME' else 0
 
 
-def _add_structural(lib, h, e):
-    """Emit a StashEntry / RestoreEntry / RouteEntry; False if `e` is none of them."""
+def _add_structural(lib, h, e, leaky_variant=1):
+    """Emit a StashEntry / RestoreEntry / RouteEntry / ShortcutEntry / ReleaseEntry /
+    UpsampleEntry; False if `e` is none of them."""
     if isinstance(e, StashEntry):
         slot = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_stash(h, ctypes.byref(slot)), "dnn_plan_add_stash", lib)
@@ -736,6 +859,12 @@ def _add_structural(lib, h, e):
         _check(lib.dnn_plan_add_restore(h, e.slot), "dnn_plan_add_restore", lib)
     elif isinstance(e, RouteEntry):
         _check(lib.dnn_plan_add_route(h, e.block, e.slot, 1 if e.slot_first else 0), "dnn_plan_add_route", lib)
+    elif isinstance(e, ShortcutEntry):
+        _check(lib.dnn_plan_add_shortcut(h, e.slot, leaky_variant if e.leaky else 0), "dnn_plan_add_shortcut", lib)
+    elif isinstance(e, ReleaseEntry):
+        _check(lib.dnn_plan_add_release(h, e.slot), "dnn_plan_add_release", lib)
+    elif isinstance(e, UpsampleEntry):
+        _check(lib.dnn_plan_add_upsample(h, e.factor), "dnn_plan_add_upsample", lib)
     else:
         return False
     return True
@@ -760,7 +889,7 @@ class Plan(object):
             _check(self.lib.dnn_plan_set_latency_mode(self.h, 1), "dnn_plan_set_latency_mode", self.lib)
         self.entries = entries
         for e in entries:
-            if _add_structural(self.lib, self.h, e):
+            if _add_structural(self.lib, self.h, e, leaky_variant):
                 continue
             if isinstance(e, ConvEntry):
                 c = e.conv
@@ -796,7 +925,7 @@ class Plan(object):
     def from_graph(cls, g, device=0, **kw):
         entries = lower_graph(g)
         if entries is None:
-            raise DnnHipError("graph is not a conv/pool chain (with Concat-joined forks) the fused plan can express")
+            raise DnnHipError("graph is not a conv/pool chain (with Concat- or Add-joined forks) the fused plan can express")
         return cls(g.in_node.in_shape[0], tuple(g.in_node.in_shape[1:]), entries, device=device, **kw)
 
     @staticmethod

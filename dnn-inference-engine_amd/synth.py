@@ -131,6 +131,45 @@ def yolov2_weights(seed=WEIGHT_SEED, width_div=1, n_out=YOLOV2_N_OUT, in_c=IN_SH
     return ws
 
 
+# Darknet-53 + YOLOv3's stride-32 branch (darknet53.py): the stem, then per stage (width, residual
+# blocks): a 3x3 stride-2 conv to `width`, then blocks of 1x1 x width/2, 3x3 x width and a shortcut;
+# then the branch's (width, kernel) convs and a linear 1x1 head
+DARKNET53_STEM = 32
+DARKNET53_STAGES = ((64, 1), (128, 2), (256, 8), (512, 8), (1024, 4))
+DARKNET53_BRANCH = ((512, 1), (1024, 3), (512, 1), (1024, 3), (512, 1), (1024, 3))
+DARKNET53_RESIDUAL_GAIN = 0.25  # gamma of each block's second conv: x + f(x) grows by 1 + gain^2 in variance
+
+
+def darknet53_weights(seed=WEIGHT_SEED, width_div=1, n_out=YOLOV2_N_OUT, in_c=IN_SHAPE[2]):
+    """The 59-entry weight list darknet53.DARKNET53 consumes (52 trunk convs, the stride-32
+    branch's 6 convs and its linear head), from the same counter-based generators as
+    yolov2_weights (layer i draws from streams 10 i + j) with the same width_div.  He-scaled
+    kernels keep a conv chain at O(1); a residual sum x + f(x) would double the variance per
+    block, so the gamma of each block's second conv is scaled by DARKNET53_RESIDUAL_GAIN (23 blocks
+    then grow the variance by 1.0625^23, about 4).  n_out defaults to a YOLOv2-format head (5
+    anchors x 85), which yolo_post decodes; YOLOv3's own layer 81 has 255 outputs."""
+    def wd(c):
+        if c % width_div:
+            raise ValueError(f"width_div {width_div} does not divide {c}")
+        return c // width_div
+
+    ws = [layer_weights(0, in_c, wd(DARKNET53_STEM), k=3, seed=seed)]
+    ic = wd(DARKNET53_STEM)
+    for width, blocks in DARKNET53_STAGES:
+        ws.append(layer_weights(len(ws), ic, wd(width), k=3, seed=seed))
+        ic = wd(width)
+        for _ in range(blocks):
+            ws.append(layer_weights(len(ws), ic, wd(width // 2), k=1, seed=seed))
+            w = layer_weights(len(ws), wd(width // 2), ic, k=3, seed=seed)
+            w["gamma"] = (w["gamma"] * np.float32(DARKNET53_RESIDUAL_GAIN)).astype(np.float32)
+            ws.append(w)
+    for width, k in DARKNET53_BRANCH:
+        ws.append(layer_weights(len(ws), ic, wd(width), k=k, seed=seed))
+        ic = wd(width)
+    ws.append(layer_weights(len(ws), ic, n_out, k=1, seed=seed, bn=False))
+    return ws
+
+
 def yolo_zero_weights(channels=CHANNELS, in_c=IN_SHAPE[2]):
     """yolo_weights' shapes with zero values, without running the generator: what a
     non-root rank lays its plan out with before the weight broadcast fills it."""

@@ -71,8 +71,8 @@ int dnn_plan_add_max_pool(dnn_plan* plan, int kh, int kw, int stride_h, int stri
 /* Fork / join entries (fp32 plans, batch and latency mode; on an fp16 plan each of the three
  * fails).  The reference has no such nodes: they extend its chain to YOLOv2's passthrough.
  *
- * dnn_plan_add_stash: the current tensor becomes slot *slot (0, 1, ... in stash order, at most 4
- * slots) and execution continues on it.  No kernel: the layer that produces the tensor writes it
+ * dnn_plan_add_stash: the current tensor becomes slot *slot (the lowest free number: 0, 1, ... in
+ * stash order unless a slot was released, at most 4 live slots) and execution continues on it.  No kernel: the layer that produces the tensor writes it
  * into the slot's region of the workspace (batch x H x W x C floats) instead of an activation
  * buffer; a stash as the first entry names the caller's input.  A slot is written once per run.
  * dnn_plan_add_restore: the current tensor and shape become the slot's.  No kernel.
@@ -94,6 +94,36 @@ int dnn_plan_add_route(dnn_plan* plan, int block, int slot, int slot_first);
 int dnn_route_host(const float* a, const float* b, float* out, int n, int h, int w, int ca, int block, int cb,
                    int b_first);
 
+/* Residual and top-down entries (fp32 plans, batch and latency mode; on an fp16 plan each of the
+ * three fails).  The reference has no such nodes: they extend its chain to the residual block
+ * y = x + f(x) of Darknet-53 and to the upsample + concat merge of detection necks.
+ *
+ * dnn_plan_add_shortcut: current = act(current + slot's tensor), element by element.  The slot
+ *   must be live and of the current tensor's shape.  One fp32 add, rounded once; leaky as in
+ *   dnn_plan_add_conv (0 none, 1, 2).  One kernel ("shortcut%d" in dnn_plan_kernel_info, one flop
+ *   per output element, three tensors of bytes).
+ * dnn_plan_add_upsample: nearest neighbour, [H, W, C] -> [H*factor, W*factor, C],
+ *   out[h, w, c] = in[h / factor, w / factor, c], factor in 1..8.  One kernel ("upsample%d", 0 flops).
+ * dnn_plan_add_release: the slot stops being live.  No kernel.  The next dnn_plan_add_stash
+ *   returns the lowest free slot number, so a plan may stash any number of tensors as long as at
+ *   most 4 are live at once.  A restore, route, shortcut or second release of a released slot
+ *   fails and changes nothing.  The slot's workspace region is handed back too: once no live slot
+ *   names a region and the current tensor has left it, a producer added AFTER that point may be
+ *   given it (the smallest free region that fits, else the largest, which grows), so no layer
+ *   writes a region that it or an earlier layer reads; dnn_plan_memory sizes each region by the
+ *   largest tensor it ever holds.  A chain of residual blocks alternates between two regions.
+ * The inputs and outputs of all three are plain NHWC fp32 (they stop the conv / pool fusions like
+ * the fork / join entries); a failed call leaves the plan unchanged. */
+int dnn_plan_add_shortcut(dnn_plan* plan, int slot, int leaky);
+int dnn_plan_add_upsample(dnn_plan* plan, int factor);
+int dnn_plan_add_release(dnn_plan* plan, int slot);
+
+/* The shortcut and upsample kernels on host tensors (H2D copies, launch, D2H copy, synchronise):
+ * out = act(a + b) over [n, h, w, c]; out [n, h*factor, w*factor, c] from a [n, h, w, c].  Each
+ * tensor must be below 2 GiB (refused from the arguments, before any allocation). */
+int dnn_shortcut_host(const float* a, const float* b, float* out, int n, int h, int w, int c, int leaky);
+int dnn_upsample_host(const float* a, float* out, int n, int h, int w, int c, int factor);
+
 /* Output shape of the plan so far (per image, plus the planned batch). */
 int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int* c);
 
@@ -102,7 +132,9 @@ int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int*
  * direct = direct conv, patch = LDS-patch MFMA conv), GEMM config, whether a 2x2/s2 max
  * pool is fused and whether the GEMM is split along K (splitK=3: partials + an ordered
  * reduce/epilogue kernel); a stash or restore line gives the tensor's shape and its slot, a
- * route line both shapes, the block and the slot with its shape.  A 2x2/s2 MaxPool2D directly
+ * route line both shapes, the block and the slot with its shape, a shortcut line the shape, the
+ * slot and the activation, an upsample line both shapes and the factor, a release line the
+ * slot and its tensor's shape.  A 2x2/s2 MaxPool2D directly
  * after an implicit, patch or direct conv is folded into it; set DNN_HIP_FUSE=0 in the
  * environment before dnn_plan_create to keep every conv explicit and every pool separate
  * (DNN_HIP_PATCH=0: no patch mode). */
