@@ -128,6 +128,7 @@ struct ImplicitConv {
   int sh_ow = 0, sh_oh = 0, sh_pw = 0, sh_ph = 0;
 };
 bool implicit_conv_supported(int C, int kh, int kw);
+bool buf_pads_ok(const ImplicitConv& ic);  // front pads the buffer-addressed input fetch covers
 void implicit_conv_magic(ImplicitConv* ic);
 void magic_u32(int d, unsigned* mag, int* sh);  // n / d == (umulhi(n, mag) + n) >> sh, 0 <= n < 2^31
 enum GemmMode : int { GEMM_DENSE = 0, GEMM_IMPLICIT = 1, GEMM_IMPLICIT_POOL = 2 };

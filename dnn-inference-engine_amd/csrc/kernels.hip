@@ -442,6 +442,9 @@ static int launch_glds(int cfg, const float* A, int lda, const float* Bt, int ld
 static bool fits_buf(long long bytes) { return bytes > 0 && bytes < 0x80000000LL; }
 // DNN_HIP_GEMM_BUF=0: flat 64-bit DMA addresses (experiments and the equivalence tests)
 static bool abuf_enabled() { return !getenv_flag_off("DNN_HIP_GEMM_BUF"); }
+// front pads the implicit GEMMs' shifted descriptor base (one row + one pixel before the input)
+// covers: the first window's top-left pixel (-pt, -pl) must not lie before it
+bool buf_pads_ok(const ImplicitConv& ic) { return (1LL - ic.pt) * ic.W + 1 - ic.pl >= 0; }
 
 // N-major tile order (round 1 experiment, measured without gain): off
 int nmajor_order(int N, int tilesN) {
@@ -560,14 +563,19 @@ int launch_gemm_implicit(int cfg, int mode, const float* in, const ImplicitConv&
   if (int rc = split_setup(cfg, M, N, Kpad, splits, slab, tickets, C, ldc, epi.flags, &sk, &g, &tilesN)) return rc;
   float* out = sk.steps ? slab : C;
   const int ldo = sk.steps ? N : ldc;
-  // buffer-addressed DMA when each K-step is one tap (C % 32 == 0) and the descriptors fit
+  // buffer-addressed DMA when each K-step is one tap (C % 32 == 0) and the descriptors fit.
+  // The descriptor base sits one row and one pixel before the input, which keeps a lane's
+  // unsigned offset (its window's top-left pixel) non-negative for a top pad of at most 1; a
+  // larger one (a 5x5 or 5x1 SAME conv) would wrap it into the range that reads as padding for
+  // image 0's first output row, so those layers take the flat addresses (buf_pads_ok)
   const long long per_img = mode == GEMM_IMPLICIT_POOL ? 4LL * ic.PH * ic.PW : (long long)ic.OH * ic.OW;
   const long long nimg = per_img > 0 ? M / per_img : 0;
   const long long a_bytes = ((nimg * ic.H * ic.W + ic.W + 1) * (long long)ic.C) * 4;
   const long long b_bytes = (long long)tilesN * ci.bn * ldb * 4;
   BufDesc bd{in - (size_t)(ic.W + 1) * ic.C, (unsigned)a_bytes, (unsigned)b_bytes};
-  const BufDesc* pbd =
-      (abuf_enabled() && ic.C % 32 == 0 && fits_buf(a_bytes) && fits_buf(b_bytes)) ? &bd : nullptr;
+  const BufDesc* pbd = (abuf_enabled() && ic.C % 32 == 0 && buf_pads_ok(ic) && fits_buf(a_bytes) && fits_buf(b_bytes))
+                           ? &bd
+                           : nullptr;
   if (mode == GEMM_IMPLICIT)
     return launch_glds<GEMM_IMPLICIT>(cfg, in, 0, Bt, ldb, out, ldo, (int)M, N, Kpad, epi, tilesN, ic, sk, pbd,
                                       dim3(g), stream);
@@ -627,6 +635,7 @@ int launch_gemm_persist(int cfg, int mode, const float* in, const ImplicitConv& 
                         float* C, int ldc, long long M, int N, int Kpad, const EpiParams& epi, hipStream_t stream) {
   if (M == 0 || N == 0) return 0;
   if (!persist_enabled() || (mode != GEMM_IMPLICIT && mode != GEMM_IMPLICIT_POOL) || ic_in.C % 32 != 0 ||
+      !buf_pads_ok(ic_in) ||  // (buffer addresses only: see launch_gemm_implicit)
       M > 0x7fffffffLL || Kpad % 32 != 0 || !implicit_conv_supported(ic_in.C, ic_in.kh, ic_in.kw) ||
       (mode == GEMM_IMPLICIT_POOL && M % 4 != 0) || (epi.flags & EPI_OUT_X3))  // (split-plane output: tile kernel)
     return -3;

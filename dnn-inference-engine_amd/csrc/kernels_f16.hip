@@ -127,7 +127,8 @@ int launch_gemm16(int cfg, int mode, const half_t* A, int lda, const ImplicitCon
     abase = A - (size_t)(ic.W + 1) * ic.C;
   }
   const long long b_bytes = (long long)((N + 511) / 512) * 512 * ldb * 2;
-  const bool shape_ok = mode == GEMM_DENSE || ic.C % 64 == 0 || ic.C == 32;
+  // (a top pad above 1 would take a lane's offset below the shifted base: flat addresses)
+  const bool shape_ok = mode == GEMM_DENSE || ((ic.C % 64 == 0 || ic.C == 32) && buf_pads_ok(ic));
   const bool abuf = !getenv_flag_off("DNN_HIP_GEMM_BUF") && shape_ok && a_bytes > 0 && a_bytes < 0x80000000LL &&
                     b_bytes > 0 && b_bytes < 0x80000000LL;
   if (cfg == GEMM16_128x512_W16 && !abuf) cfg = GEMM16_128x128;  // same MFMA family and K order

@@ -472,6 +472,14 @@ static void set_cfg(dnn_plan* p, PlanLayer& L) {
   L.Kpad = (int)align_up(L.K, gemm_cfg_bk(L.cfg));
   L.Npad = (int)align_up(L.OC, gemm_cfg_bn(L.cfg));
   L.splits = (L.cfg >= GEMM_128x128_K32 && L.Kpad == L.K) ? choose_splitk(L.OC, L.K, fused_splitk(p)) : 1;
+  // one fp32 chain of K / 2 MFMAs misses the 2e-6 per-layer bar from K of about 4608 on (measured
+  // 2.1e-6 .. 4.6e-6 at K = 4608 .. 9216, 2.7e-6 at 6125: DESIGN.md §2).  Long-K layers the
+  // (N, K) rule leaves whole (N < 512; the explicit GEMM's zero-padded K too) are summed in three
+  // or two parts like conv5-conv7: still a function of (N, K) and the config alone
+  if (L.splits == 1 && L.cfg >= GEMM_128x128_K32 && L.K >= 4608 && (fused_splitk(p) || L.OC % 4 == 0)) {
+    const int nk = L.Kpad / 32;
+    L.splits = nk % 3 == 0 ? 3 : nk % 2 == 0 ? 2 : 1;
+  }
   if (p->latency && fused_splitk(p) && L.Kpad == L.K) {
     // a tile config and split for this M when the batch rule leaves the chip idle
     int cfg = L.cfg, sp = L.splits;
