@@ -35,6 +35,11 @@
 // once no live slot names it and the current tensor has left it, but only to a producer added
 // after that point (region_free_from): a layer never writes a region that it, or a layer before
 // it, still reads.  Plans without a release are laid out exactly as before.
+//
+// Taps: a tap entry makes the current tensor an extra output of the plan.  It is a stash without a
+// slot number: the producer writes the tensor into a region (to_region), the tap holds a reference
+// to that region that is never dropped, so no later producer is given it, and the caller reads the
+// region's device address (dnn_plan_tap_buffer) after a run.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -118,7 +123,7 @@ static const char* kModeName[] = {"gemm", "direct_a", "implicit", "direct", "pat
 enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, LOC_IN = 2, LOC_REGION = 3 };
 
 struct PlanLayer {
-  int type = 0;  // 0 conv, 1 pool, 2 stash, 3 restore, 4 route, 5 shortcut, 6 upsample, 7 release (LAYER_*)
+  int type = 0;  // 0 conv, 1 pool, 2 stash, 3 restore, 4 route, 5 shortcut, 6 upsample, 7 release, 8 tap (LAYER_*)
   // shapes (per image): input H,W,C -> conv/pool output OH,OW,OC (-> fused pool PH,PW)
   int H = 0, W = 0, C = 0, OH = 0, OW = 0, OC = 0;
   int kh = 0, kw = 0, sh = 1, sw = 1, pt = 0, pl = 0;
@@ -153,8 +158,13 @@ struct PlanLayer {
 };
 
 enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
-                       LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7 };
+                       LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8 };
 constexpr int kMaxSlots = 4;
+
+struct PlanTap {
+  int h, w, c;  // per image
+  int region;   // the region that holds it, for good
+};
 
 struct PlanSlot {
   int h, w, c;  // per image
@@ -185,6 +195,7 @@ struct dnn_plan {
   // one) as per-image floats (the largest tensor a region ever holds), their float offsets inside
   // the slot area
   std::vector<PlanSlot> slots;
+  std::vector<PlanTap> taps;  // extra outputs (at most DNN_PLAN_MAX_TAPS): each holds its region for good
   std::vector<size_t> region_elems, region_off;
   // while adding: live slots naming each region, and the first layer index that may write it again
   // (a region with no live slot whose tensor is no longer current; INT_MAX while it is still read)
@@ -320,7 +331,7 @@ static void layout(dnn_plan* p) {
     } else if (L.type == LAYER_UPSAMPLE) {
       snprintf(nm, sizeof(nm), "upsample%d", nup++);
       p->kernels.push_back({nm, (int)i, 7, 0.0, in_b + out_b});
-    }  // (a stash, a restore or a release launches nothing)
+    }  // (a stash, a restore, a release or a tap launches nothing)
   }
   // where each layer writes.  Chains keep the ping-pong by layer parity; with fork / join entries
   // a layer followed by a stash writes that slot's region, and any other one the activation
@@ -333,7 +344,7 @@ static void layout(dnn_plan* p) {
     while (last > 0 && p->layers[last - 1].type == LAYER_RELEASE) --last;
     for (size_t i = 0; i < p->layers.size(); ++i) {
       PlanLayer& L = p->layers[i];
-      if (L.type == LAYER_STASH || L.type == LAYER_RELEASE) {
+      if (L.type == LAYER_STASH || L.type == LAYER_RELEASE || L.type == LAYER_TAP) {
         L.dst_loc = cur;
       } else if (L.type == LAYER_RESTORE) {
         L.dst_loc = cur = L.slot_loc;
@@ -795,6 +806,8 @@ static void shape_only_layer(const dnn_plan* p, PlanLayer* L, int type) {
   L->C = L->OC = p->cur_c;
 }
 
+static void current_into_region(dnn_plan* p);
+
 int dnn_plan_add_stash(dnn_plan* p, int* slot) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_stash: plan is NULL or finalized");
   DNN_REQUIRE(slot != nullptr, "dnn_plan_add_stash: slot is NULL");
@@ -802,6 +815,82 @@ int dnn_plan_add_stash(dnn_plan* p, int* slot) {
   int number = 0;  // the lowest free slot number
   while (number < (int)p->slots.size() && p->slots[number].live) ++number;
   DNN_REQUIRE(number < kMaxSlots, "dnn_plan_add_stash: all %d slots are in use", kMaxSlots);
+  current_into_region(p);
+  if (p->cur_src >= LOC_REGION) p->region_refs[p->cur_src - LOC_REGION]++;
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_STASH);
+  L.slot = number;
+  L.slot_loc = p->cur_src;
+  const PlanSlot S{p->cur_h, p->cur_w, p->cur_c, p->cur_src, true};
+  if (number == (int)p->slots.size())
+    p->slots.push_back(S);
+  else
+    p->slots[number] = S;
+  p->layers.push_back(std::move(L));
+  *slot = number;
+  return 0;
+}
+
+int dnn_plan_add_tap(dnn_plan* p, int* index) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_tap: plan is NULL or finalized");
+  DNN_REQUIRE(index != nullptr, "dnn_plan_add_tap: index is NULL");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_tap: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(p->cur_src != LOC_IN, "dnn_plan_add_tap: no layer has run yet (the current tensor is the plan's input)");
+  DNN_REQUIRE((int)p->taps.size() < DNN_PLAN_MAX_TAPS, "dnn_plan_add_tap: all %d taps are in use",
+              DNN_PLAN_MAX_TAPS);
+  current_into_region(p);
+  const int r = p->cur_src - LOC_REGION;
+  p->region_refs[r]++;  // never dropped: the region is no later producer's
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_TAP);
+  L.slot = (int)p->taps.size();  // (the tap's index)
+  L.slot_loc = p->cur_src;
+  p->taps.push_back(PlanTap{p->cur_h, p->cur_w, p->cur_c, r});
+  p->layers.push_back(std::move(L));
+  *index = (int)p->taps.size() - 1;
+  return 0;
+}
+
+int dnn_plan_num_taps(const dnn_plan* p) { return p ? (int)p->taps.size() : -2; }
+
+int dnn_plan_tap_shape(const dnn_plan* p, int index, int* h, int* w, int* c) {
+  DNN_REQUIRE(p, "dnn_plan_tap_shape: plan is NULL");
+  DNN_REQUIRE(index >= 0 && index < (int)p->taps.size(), "dnn_plan_tap_shape: tap %d of %d", index,
+              (int)p->taps.size());
+  const PlanTap& T = p->taps[index];
+  if (h) *h = T.h;
+  if (w) *w = T.w;
+  if (c) *c = T.c;
+  return 0;
+}
+
+int dnn_plan_tap_buffer(const dnn_plan* p, int index, void** ptr, size_t* bytes) {
+  DNN_REQUIRE(p && p->finalized, "dnn_plan_tap_buffer: plan not finalized");
+  DNN_REQUIRE(index >= 0 && index < (int)p->taps.size(), "dnn_plan_tap_buffer: tap %d of %d", index,
+              (int)p->taps.size());
+  const PlanTap& T = p->taps[index];
+  float* regions = p->ws + 2 * p->act_floats + p->col_floats + p->slab_floats + p->ticket_floats + p->pad_floats;
+  if (ptr) *ptr = regions + p->region_off[T.region];
+  if (bytes) *bytes = (size_t)p->batch * T.h * T.w * T.c * sizeof(float);
+  return 0;
+}
+
+int dnn_plan_tap_read_host(const dnn_plan* p, int index, int n, float* h_out) {
+  void* ptr = nullptr;
+  int rc = dnn_plan_tap_buffer(p, index, &ptr, nullptr);
+  if (rc) return rc;
+  DNN_REQUIRE(n >= 0 && n <= p->batch && (n == 0 || h_out), "dnn_plan_tap_read_host: n=%d outside [0, %d] or NULL output",
+              n, p->batch);
+  if (n == 0) return 0;
+  const PlanTap& T = p->taps[index];
+  DNN_HIP_TRY(hipSetDevice(p->device));
+  DNN_HIP_TRY(hipMemcpy(h_out, ptr, (size_t)n * T.h * T.w * T.c * sizeof(float), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// While adding: the current tensor is about to be named by a slot or a tap.  If it is the last
+// computing layer's output, that layer is made to write a region, and the tensor then sits there.
+static void current_into_region(dnn_plan* p) {
   if (p->cur_src < 0) {  // the last computing layer's output: that layer writes a slot region
     int producer = (int)p->layers.size() - 1;  // (only release entries can follow it)
     while (p->layers[producer].type == LAYER_RELEASE) --producer;
@@ -831,19 +920,6 @@ int dnn_plan_add_stash(dnn_plan* p, int* slot) {
     p->layers[producer].to_region = r;
     p->cur_src = LOC_REGION + r;
   }  // (else the plan's input, or a tensor that already sits in a region)
-  if (p->cur_src >= LOC_REGION) p->region_refs[p->cur_src - LOC_REGION]++;
-  PlanLayer L;
-  shape_only_layer(p, &L, LAYER_STASH);
-  L.slot = number;
-  L.slot_loc = p->cur_src;
-  const PlanSlot S{p->cur_h, p->cur_w, p->cur_c, p->cur_src, true};
-  if (number == (int)p->slots.size())
-    p->slots.push_back(S);
-  else
-    p->slots[number] = S;
-  p->layers.push_back(std::move(L));
-  *slot = number;
-  return 0;
 }
 
 int dnn_plan_add_release(dnn_plan* p, int slot) {
@@ -1125,9 +1201,9 @@ int dnn_plan_finalize(dnn_plan* p, int device, void* weights, void* workspace) {
     while (last > 0 && p->layers[last - 1].type == LAYER_RELEASE) --last;
     DNN_REQUIRE(last > 0, "dnn_plan_finalize: plan has no layer that computes");
     const int t = p->layers[last - 1].type;
-    DNN_REQUIRE(t != LAYER_STASH && t != LAYER_RESTORE,
+    DNN_REQUIRE(t != LAYER_STASH && t != LAYER_RESTORE && t != LAYER_TAP,
                 "dnn_plan_finalize: the plan ends in a %s: its output would not be written (end with a layer that "
-                "computes)", t == LAYER_STASH ? "stash" : "restore");
+                "computes)", t == LAYER_STASH ? "stash" : t == LAYER_TAP ? "tap" : "restore");
   }
   if (p->fp16)
     for (auto& L : p->layers) {
@@ -1333,8 +1409,8 @@ int dnn_plan_run(dnn_plan* p, int n, const float* d_in, float* d_out, void* stre
   };
   for (int i = 0; i < nl; ++i) {
     PlanLayer& L = p->layers[i];
-    // a stash: its producer wrote the slot's region (or it is d_in); a release: nothing to do
-    if (L.type == LAYER_STASH || L.type == LAYER_RELEASE) continue;
+    // a stash or a tap: its producer wrote the region (or it is d_in); a release: nothing to do
+    if (L.type == LAYER_STASH || L.type == LAYER_RELEASE || L.type == LAYER_TAP) continue;
     if (L.type == LAYER_RESTORE) {
       cur = at(L.dst_loc);
       continue;
@@ -1572,6 +1648,8 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
                L.factor);
     } else if (L.type == LAYER_RELEASE) {
       snprintf(line, sizeof(line), "release %dx%dx%d slot=%d\n", L.H, L.W, L.C, L.slot);
+    } else if (L.type == LAYER_TAP) {
+      snprintf(line, sizeof(line), "tap %dx%dx%d index=%d\n", L.H, L.W, L.C, L.slot);
     } else
       snprintf(line, sizeof(line), "pool %dx%dx%d -> %dx%dx%d k%dx%d s%d%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.kh,
                L.kw, L.sh, p->fp16 ? " fp16" : "");

@@ -1,4 +1,5 @@
-// Arithmetic of the YOLOv2 postprocessing kernels (postprocess.hip, postprocess_head.hip):
+// Arithmetic of the YOLO postprocessing kernels (postprocess.hip, postprocess_head.hip,
+// postprocess_multi.hip):
 // the reference's fp32 decode and integer IoU (cs492-projects/proj3/yolov2tiny.py:113-140,
 // :179-195, :229-234) as numpy 2.x evaluates them, shared so both kernels round alike.
 #pragma once
@@ -38,6 +39,29 @@ __device__ __forceinline__ float sigmoid_ref(float x) {
   const double log2_e32 = 0x1.715475968cddcp+0;  // log2((double)float32(np.e)) = 1.4426949970774023
   const float pw = (float)exp2((double)(-x) * log2_e32);
   return 1.0f / (1.0f + pw);
+}
+
+// the float32 add.reduce of numpy over e[c] = exp(q[c] - m), c < C <= 128 (unblocked pairwise
+// sum): sequential below 8 elements, else 8 accumulators over whole groups of 8, combined
+// pairwise, then the tail in order
+__device__ __forceinline__ float softmax_sum(const float* __restrict__ q, int C, float m) {
+  if (C < 8) {
+    float s = np_expf(q[0] - m);  // 0 + e[0] = e[0] exactly
+    for (int c = 1; c < C; ++c) s = s + np_expf(q[c] - m);
+    return s;
+  }
+  float r[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) r[j] = np_expf(q[j] - m);
+  const int full = C - (C % 8);
+  int i = 8;
+  for (; i < full; i += 8) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r[j] = r[j] + np_expf(q[i + j] - m);
+  }
+  float s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+  for (; i < C; ++i) s = s + np_expf(q[i] - m);
+  return s;
 }
 
 // int(float32) with the reference's failure cases flagged: truncation toward zero

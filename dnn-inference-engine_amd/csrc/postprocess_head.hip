@@ -32,29 +32,6 @@ constexpr int PH_WAVES = PH_THREADS / 64;
 constexpr int PH_LDS_BOXES = 2048;  // 16 K keys + 8 K kept + 80 K boxes = 104 KiB of LDS
 constexpr int PH_BOX_BYTES = 40;    // 4 x int64 corners + fp32 score + int class
 
-// the float32 add.reduce of numpy over e[c] = exp(q[c] - m), c < C <= 128 (unblocked pairwise
-// sum): sequential below 8 elements, else 8 accumulators over whole groups of 8, combined
-// pairwise, then the tail in order
-__device__ __forceinline__ float softmax_sum(const float* __restrict__ q, int C, float m) {
-  if (C < 8) {
-    float s = np_expf(q[0] - m);  // 0 + e[0] = e[0] exactly
-    for (int c = 1; c < C; ++c) s = s + np_expf(q[c] - m);
-    return s;
-  }
-  float r[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) r[j] = np_expf(q[j] - m);
-  const int full = C - (C % 8);
-  int i = 8;
-  for (; i < full; i += 8) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = r[j] + np_expf(q[i + j] - m);
-  }
-  float s = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-  for (; i < C; ++i) s = s + np_expf(q[i] - m);
-  return s;
-}
-
 // CAP: capacity of the key and kept arrays (>= boxes, power of two).  WS: the box store is the
 // workspace (true) or LDS (false, boxes <= CAP).
 template <int CAP, bool WS>
@@ -230,13 +207,13 @@ yolo_head_kernel(const dnn_yolo_head head, const float* __restrict__ pred, dnn_d
   if (tid == 0) counts[img] = nk;
 }
 
-// < 0 with the error set, else grid_h * grid_w * n_anchors
-static int head_boxes(const dnn_yolo_head* h, const char* who) {
+// < 0 with the error set, else grid_h * grid_w * n_anchors (at most max_boxes: postprocess_multi.hip has its own cap)
+int yolo_head_boxes(const dnn_yolo_head* h, const char* who, long long max_boxes) {
   if (!h) {
     set_error("%s: NULL head", who);
     return -2;
   }
-  if (h->grid_h < 1 || h->grid_w < 1 || h->grid_h > DNN_YOLO_MAX_BOXES || h->grid_w > DNN_YOLO_MAX_BOXES ||
+  if (h->grid_h < 1 || h->grid_w < 1 || h->grid_h > max_boxes || h->grid_w > max_boxes ||
       h->n_anchors < 1 || h->n_anchors > DNN_YOLO_MAX_ANCHORS || h->n_classes < 1 ||
       h->n_classes > DNN_YOLO_MAX_CLASSES) {
     set_error("%s: head %d x %d cells, %d anchors, %d classes: need >= 1 cell, 1..%d anchors, 1..%d classes", who,
@@ -244,9 +221,9 @@ static int head_boxes(const dnn_yolo_head* h, const char* who) {
     return -2;
   }
   const long long nb = (long long)h->grid_h * h->grid_w * h->n_anchors;
-  if (nb > DNN_YOLO_MAX_BOXES) {
-    set_error("%s: %d x %d cells x %d anchors = %lld boxes > %d", who, h->grid_h, h->grid_w, h->n_anchors, nb,
-              DNN_YOLO_MAX_BOXES);
+  if (nb > max_boxes) {
+    set_error("%s: %d x %d cells x %d anchors = %lld boxes > %lld", who, h->grid_h, h->grid_w, h->n_anchors, nb,
+              max_boxes);
     return -2;
   }
   if (!(h->score_thr >= 0.0f) || h->iou_thr != h->iou_thr || !(h->cell > 0.0f) || h->cell > 3.0e38f) {
@@ -262,6 +239,8 @@ static int head_boxes(const dnn_yolo_head* h, const char* who) {
   }
   return (int)nb;
 }
+
+static int head_boxes(const dnn_yolo_head* h, const char* who) { return yolo_head_boxes(h, who, DNN_YOLO_MAX_BOXES); }
 
 static unsigned long long head_workspace(int nb, int n_images) {
   return nb > PH_LDS_BOXES ? (unsigned long long)n_images * nb * PH_BOX_BYTES : 0ull;

@@ -56,14 +56,14 @@ def structure():
     return s
 
 
-def validate(weights, n_out=None):
-    """Check the 59-layer structure (keys, kernel sizes, channels chaining through the residual
-    sums) and return it as fp32 contiguous arrays."""
-    if not isinstance(weights, (list, tuple)) or len(weights) != N_LAYERS:
-        raise yolo_weights.WeightFileError(f"expected a list of {N_LAYERS} layer dicts")
-    out = []
-    ic, width = 3, None
-    for i, (w, (ksize, _, role)) in enumerate(zip(weights, structure())):
+def validate_chain(weights, struct, ic, first=0, width=None):
+    """Check the layer dicts `weights` against `struct` (entries as structure()'s) as one chain
+    that starts with `ic` input channels: keys, kernel sizes, channels chaining through the
+    residual sums.  `first` is the first layer's number in messages.  Returns (the layers as fp32
+    contiguous arrays, the last layer's output channels, the output channels of each "down"
+    conv)."""
+    out, downs = [], []
+    for i, (w, (ksize, _, role)) in enumerate(zip(weights, struct), start=first):
         keys = ("kernel", "biases") + (yolo_weights.BN_KEYS if role != "head" else ())
         if not isinstance(w, dict) or any(k not in w for k in keys):
             raise yolo_weights.WeightFileError(f"layer {i}: expected a dict with {keys}")
@@ -79,11 +79,21 @@ def validate(weights, n_out=None):
             raise yolo_weights.WeightFileError(f"layer {i}: {k.shape[2]} input channels, expected {ic}")
         if role == "down":
             width = k.shape[3]
+            downs.append(width)
         elif role == "expand" and k.shape[3] != width:  # the sum needs the block's input shape
             raise yolo_weights.WeightFileError(f"layer {i}: a residual block's second conv has {k.shape[3]} "
                                                f"outputs, its input {width} channels")
         ic = k.shape[3]
         out.append(d)
+    return out, ic, downs
+
+
+def validate(weights, n_out=None):
+    """Check the 59-layer structure (keys, kernel sizes, channels chaining through the residual
+    sums) and return it as fp32 contiguous arrays."""
+    if not isinstance(weights, (list, tuple)) or len(weights) != N_LAYERS:
+        raise yolo_weights.WeightFileError(f"expected a list of {N_LAYERS} layer dicts")
+    out, ic, _ = validate_chain(weights, structure(), 3)
     if n_out is not None and ic != n_out:
         raise yolo_weights.WeightFileError(f"last layer has {ic} outputs; this head needs {n_out}")
     return out

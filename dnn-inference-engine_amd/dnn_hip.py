@@ -19,7 +19,10 @@ YOLOv2's passthrough: a fork joined by a Concat lowers to stash / restore / rout
 (the route kernel does the fold and the concat in one pass).  Two more, `Add` and `Upsample`
 (`create_add`, `create_upsample`), express the residual block y = x + f(x) and the top-down
 merge: a fork joined by an Add lowers to stash / shortcut / release entries (a release hands the
-slot and its workspace region back, so any number of blocks fit in one plan).  With
+slot and its workspace region back, so any number of blocks fit in one plan).  A graph may have
+extra outputs (`DnnGraphBuilder.add_out_node`, `DnnInferenceEngine.run_all`): each becomes a tap
+entry of the plan, and a branch that ends in one, or a tensor concatenated many layers later, lowers
+too (lower_graph; YOLOv3's three heads and two merges, yolov3.py).  With
 `debug=True` (or a graph the plan cannot express) it instead runs node by node through
 the per-op C-ABI (`conv2d_mul`, `bias_add`, ... in libdnn_hip.so, include/dnn_hip.h),
 exactly like the reference, and saves every layer to ./intermediate/layer_{k}.npy
@@ -69,6 +72,11 @@ def _bind_plan_api(lib):
         "dnn_plan_add_shortcut": (i, [vp, i, i]),
         "dnn_plan_add_upsample": (i, [vp, i]),
         "dnn_plan_add_release": (i, [vp, i]),
+        "dnn_plan_add_tap": (i, [vp, P(i)]),
+        "dnn_plan_num_taps": (i, [vp]),
+        "dnn_plan_tap_shape": (i, [vp, i, P(i), P(i), P(i)]),
+        "dnn_plan_tap_buffer": (i, [vp, i, P(vp), P(sz)]),
+        "dnn_plan_tap_read_host": (i, [vp, i, i, vp]),
         "dnn_shortcut_host": (i, [vp, vp, vp, i, i, i, i, i]),
         "dnn_upsample_host": (i, [vp, vp, i, i, i, i, i]),
         "dnn_plan_output_shape": (i, [vp, P(i), P(i), P(i), P(i)]),
@@ -197,6 +205,23 @@ class DnnInferenceEngine(object):
             return out
         return self._run_nodes()
 
+    def run_all(self, tin):
+        """Every output of a graph with extra outputs (DnnGraphBuilder.add_out_node): the extra
+        ones in declaration order, then the primary one.  Same two paths as run()."""
+        self.g.in_node.set_input(tin)
+        extras = list(self.g.extra_out_nodes)
+        if not self.debug and lower_graph(self.g) is not None:
+            x = np.ascontiguousarray(tin, dtype=np.float32)
+            plan = self.plan()
+            outs = plan.run_host_all(x)  # taps in plan order, then the primary output
+            by_node = {id(e.node): t for e, t in zip(plan.tap_entries, outs[:-1])}
+            for n in extras:
+                n.result = by_node[id(n)]
+            self.g.out_node.result = outs[-1]
+            return [by_node[id(n)] for n in extras] + [outs[-1]]
+        primary = self._run_nodes()
+        return [n.result for n in extras] + [primary]
+
     # -- node-by-node path through the per-op ABI (the reference's traversal) --------
     def _run_nodes(self):
         out = {}
@@ -258,12 +283,21 @@ class DnnGraphBuilder(object):
                          "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0}
         self.in_node = None
         self.out_node = None
+        self.extra_out_nodes = []
 
     def set_in_node(self, node):
         self.in_node = node
 
     def set_out_node(self, node):
         self.out_node = node
+
+    def add_out_node(self, node):
+        """Declare an extra output (not in the reference: its graphs have one).  Extra outputs
+        are returned by DnnInferenceEngine.run_all in the order declared, before the primary
+        output of set_out_node, which must be the last tensor the graph computes."""
+        if any(n is node for n in self.extra_out_nodes):
+            raise ValueError("node is already an extra output")
+        self.extra_out_nodes.append(node)
 
     def is_out_node(self, node):
         return self.out_node is node
@@ -476,6 +510,7 @@ class LeakyReLU(DnnNode):
 
 MAX_ROUTE_BLOCK = 8  # dnn_plan_add_route / dnn_route_host: block in 1..8
 MAX_SLOTS = 4        # dnn_plan_add_stash: slots per plan
+MAX_TAPS = 4         # DNN_PLAN_MAX_TAPS: extra outputs per plan
 
 
 def _route_host(name, a, b, out, block, b_first=False):
@@ -656,6 +691,30 @@ class UpsampleEntry(object):
         self.nodes = list(nodes)
 
 
+class TapEntry(object):
+    """dnn_plan_add_tap: the current tensor becomes the plan's extra output `index` (no kernel);
+    `node` is the graph node it is the result of (None in plans assembled by hand)."""
+
+    def __init__(self, index, node=None):
+        self.index = int(index)
+        self.node = node
+        self.nodes = []
+
+
+def _is_output(g, node):
+    return g.is_out_node(node) or any(n is node for n in getattr(g, "extra_out_nodes", ()))
+
+
+def _free_slots(live, count):
+    """The `count` lowest slot numbers not in `live` (dnn_plan_add_stash hands them out so)."""
+    out, k = [], 0
+    while len(out) < count:
+        if k not in live:
+            out.append(k)
+        k += 1
+    return out
+
+
 def _lower_one(g, nxt):
     """The plan entry that starts at node `nxt`, and the last node it covers; None if `nxt` is
     not the start of one."""
@@ -664,7 +723,7 @@ def _lower_one(g, nxt):
         cur = nxt
         for kind in (BiasAdd, BatchNorm, LeakyReLU):
             nn = list(g.G.successors(cur))
-            if g.is_out_node(cur) or len(nn) != 1 or not isinstance(nn[0], kind):
+            if _is_output(g, cur) or len(nn) != 1 or not isinstance(nn[0], kind):
                 continue
             cur = nn[0]
             if kind is BiasAdd:
@@ -684,10 +743,23 @@ def _lower_one(g, nxt):
     return None  # a standalone element-wise op: not expressible as a fused entry
 
 
-def _lower_fork(g, x, heads, nslots):
+def _lower_chain(g, chain):
+    """The entries of a plain chain of nodes, or None."""
+    es, i = [], 0
+    while i < len(chain):
+        r = _lower_one(g, chain[i])
+        if r is None:
+            return None
+        es.append(r[0])
+        i += len(r[0].nodes)
+    return es
+
+
+def _lower_fork(g, x, heads, live):
     """Node `x` has the two successors `heads`: lower the two chains up to the Concat or Add that
-    joins them.  Returns (entries, the last node covered, slots used so far), or None for anything
-    but two plain chains (either may be empty) meeting in one Concat or one Add.  A Concat keeps its
+    joins them.  Returns (entries, the last node covered, live slots afterwards), or None for
+    anything but two plain chains (either may be empty) meeting in one Concat or one Add.  `live`
+    is the set of slot numbers in use; new slots are the lowest free numbers.  A Concat keeps its
     slots to the end of the plan; an Add block releases every slot it opens, so any number of them
     fit in sequence."""
     chains, joins = [], []
@@ -695,8 +767,8 @@ def _lower_fork(g, x, heads, nslots):
         chain = []
         while not (isinstance(cur, (Concat, Add)) and len(list(g.G.predecessors(cur))) == 2):
             succ = list(g.G.successors(cur))
-            if len(list(g.G.predecessors(cur))) != 1 or len(succ) != 1 or g.is_out_node(cur):
-                return None  # a nested fork, a join of another kind, or the output inside a branch
+            if len(list(g.G.predecessors(cur))) != 1 or len(succ) != 1 or _is_output(g, cur):
+                return None  # a nested fork, a join of another kind, or an output inside a branch
             chain.append(cur)
             cur = succ[0]
         chains.append(chain)
@@ -711,16 +783,12 @@ def _lower_fork(g, x, heads, nslots):
         return None
     lowered = []  # the join's inputs in order
     for chain in chains:
-        es, i = [], 0
-        while i < len(chain):
-            r = _lower_one(g, chain[i])
-            if r is None:
-                return None
-            es.append(r[0])
-            i += len(r[0].nodes)
+        es = _lower_chain(g, chain)
+        if es is None:
+            return None
         lowered.append(es)
     if isinstance(join, Add):
-        return _emit_add_block(g, join, lowered, nslots)
+        return _emit_add_block(g, join, lowered, live)
 
     def ends_in_s2d(es):
         return bool(es) and isinstance(es[-1], RouteEntry) and es[-1].slot < 0
@@ -734,15 +802,15 @@ def _lower_fork(g, x, heads, nslots):
     else:
         last = 0 if ends_in_s2d(lowered[0]) and not ends_in_s2d(lowered[1]) else 1
     first = 1 - last
-    x_slot = nslots
+    x_slot, b_new = _free_slots(live, 2)
     entries = [StashEntry(x_slot)]
-    nslots += 1
+    used = {x_slot}
     b_slot = x_slot
     if lowered[first]:
-        b_slot = nslots
-        nslots += 1
+        b_slot = b_new
+        used.add(b_slot)
         entries += lowered[first] + [StashEntry(b_slot), RestoreEntry(x_slot)]
-    if nslots > MAX_SLOTS:
+    if max(used) >= MAX_SLOTS:
         return None
     tail = list(lowered[last])
     block, nodes = 1, [join]
@@ -750,33 +818,47 @@ def _lower_fork(g, x, heads, nslots):
         s2d = tail.pop()
         block, nodes = s2d.block, s2d.nodes + [join]
     entries += tail + [RouteEntry(block, b_slot, slot_first=(first == 0), nodes=nodes)]
-    return entries, join, nslots
+    return entries, join, live | used
 
 
-def _emit_add_block(g, join, lowered, nslots):
+def _emit_add_block(g, join, lowered, live):
     """The entries of a fork joined by the Add `join` (its inputs' chains lowered in `lowered`):
     Stash(x), f..., Shortcut(x), Release(x) with one empty branch, else Stash(x), first..., Stash(a),
     Restore(x), second..., Shortcut(a), Release(x), Release(a).  The slots are the lowest free
-    numbers and are all released, so at most two are live on top of the Concat forks' ones."""
+    numbers and are all released, so at most two are live on top of the ones already in use."""
     last_node, leaky = join, False
     succ = list(g.G.successors(join))
-    if not g.is_out_node(join) and len(succ) == 1 and isinstance(succ[0], LeakyReLU) \
+    if not _is_output(g, join) and len(succ) == 1 and isinstance(succ[0], LeakyReLU) \
             and len(list(g.G.predecessors(succ[0]))) == 1:
         last_node, leaky = succ[0], True  # a single LeakyReLU directly after the Add: the shortcut's activation
     nodes = [join] + ([last_node] if leaky else [])
-    x_slot = nslots
+    x_slot, a_slot = _free_slots(live, 2)
     if not lowered[0] or not lowered[1]:
         if x_slot + 1 > MAX_SLOTS or not (lowered[0] or lowered[1]):
             return None
         entries = [StashEntry(x_slot)] + (lowered[0] or lowered[1])
         entries += [ShortcutEntry(x_slot, leaky, nodes), ReleaseEntry(x_slot)]
-        return entries, last_node, nslots
-    a_slot = nslots + 1
+        return entries, last_node, live
     if a_slot + 1 > MAX_SLOTS:
         return None
     entries = [StashEntry(x_slot)] + lowered[0] + [StashEntry(a_slot), RestoreEntry(x_slot)] + lowered[1]
     entries += [ShortcutEntry(a_slot, leaky, nodes), ReleaseEntry(x_slot), ReleaseEntry(a_slot)]
-    return entries, last_node, nslots
+    return entries, last_node, live
+
+
+def _output_branch(g, head):
+    """The nodes of a plain chain from `head` to an extra output without successors, or None."""
+    chain, cur = [], head
+    while True:
+        if len(list(g.G.predecessors(cur))) != 1:
+            return None
+        chain.append(cur)
+        succ = list(g.G.successors(cur))
+        if not succ:
+            return chain if _is_output(g, cur) and not g.is_out_node(cur) else None
+        if len(succ) != 1 or _is_output(g, cur):
+            return None
+        cur = succ[0]
 
 
 def lower_graph(g):
@@ -785,31 +867,102 @@ def lower_graph(g):
     LeakyReLU), MaxPool2D, SpaceToDepth and Upsample, and forks of two such chains (either may be
     empty) joined by one Concat or one Add (with a LeakyReLU directly after it), any number of
     them in sequence within the plan's slots (an Add block gives its slots back); nested forks are
-    not."""
+    not.  Graphs with extra outputs (add_out_node) add two patterns at a node x with two
+    successors:
+
+      output branch  one successor starts a plain chain that ends in an extra output without
+                     successors: Stash(x), the chain, Tap, Restore(x), Release(x), and the
+                     lowering goes on from x's other successor;
+      long skip      one successor is a Concat that takes x directly and whose other input the
+                     main line produces later, whatever complete blocks lie in between:
+                     Stash(x), the main line, Route(1, slot, slot_first = x is the Concat's first
+                     input), Release(slot).  A long skip into an Add is not expressible.
+
+    An extra output on the main line is a Tap after the entry that computes it.  Slots are the
+    lowest free numbers; more than MAX_SLOTS live at once gives None."""
     if g.in_node is None or g.out_node is None:
         return None
+    extras = list(getattr(g, "extra_out_nodes", ()))
+    if any(g.is_out_node(n) for n in extras) or len(extras) > MAX_TAPS:
+        return None
     entries = []
-    nslots = 0
+    live = set()      # slot numbers in use
+    pending = {}      # Concat of a long skip -> (slot, x)
+    handled = set()   # (x, successor) edges already dealt with: output-branch heads, long-skip Concats
+    tapped = []
+
+    def tap(node):
+        if any(n is node for n in extras):
+            entries.append(TapEntry(len(tapped), node))
+            tapped.append(node)
+
+    def long_skip(succ):
+        """Stash `node` for the one Concat among `succ` that takes it directly; False if there is
+        not exactly one, or no slot."""
+        skips = [h for h in succ if isinstance(h, Concat) and len(list(g.G.predecessors(h))) == 2
+                 and (h.in_nodes[0] is node) != (h.in_nodes[1] is node)]
+        slot = _free_slots(live, 1)[0]
+        if len(skips) != 1 or slot >= MAX_SLOTS:
+            return False
+        entries.append(StashEntry(slot))
+        live.add(slot)
+        pending[skips[0]] = (slot, node)
+        handled.add((node, skips[0]))
+        return True
+
     node = g.in_node
     while not g.is_out_node(node):
-        succ = list(g.G.successors(node))
+        succ = [s for s in g.G.successors(node) if (node, s) not in handled]
         if len(succ) == 1:
-            if len(list(g.G.predecessors(succ[0]))) != 1:
+            nxt = succ[0]
+            if nxt in pending:  # the main line arrives at a long skip's Concat
+                slot, x = pending.pop(nxt)
+                other = nxt.in_nodes[1] if nxt.in_nodes[0] is x else nxt.in_nodes[0]
+                if other is not node or len(list(g.G.predecessors(nxt))) != 2:
+                    return None
+                entries += [RouteEntry(1, slot, slot_first=nxt.in_nodes[0] is x, nodes=[nxt]), ReleaseEntry(slot)]
+                live.discard(slot)
+                node = nxt
+                tap(node)
+                continue
+            if len(list(g.G.predecessors(nxt))) != 1:
                 return None
-            r = _lower_one(g, succ[0])
+            r = _lower_one(g, nxt)
             if r is None:
                 return None
             entries.append(r[0])
             node = r[1]
+            tap(node)
         elif len(succ) == 2:
-            r = _lower_fork(g, node, succ, nslots)
-            if r is None:
+            r = _lower_fork(g, node, succ, live)
+            if r is not None:
+                entries += r[0]
+                node, live = r[1], set(r[2])
+                tap(node)
+                continue
+            slot = _free_slots(live, 1)[0]
+            if slot >= MAX_SLOTS:
                 return None
-            entries += r[0]
-            node, nslots = r[1], r[2]
+            branches = [(h, _output_branch(g, h)) for h in succ]
+            branches = [(h, c) for h, c in branches if c is not None]
+            if branches:
+                head, chain = branches[0]
+                es = _lower_chain(g, chain)
+                if es is None:
+                    return None
+                entries += [StashEntry(slot)] + es
+                tap(chain[-1])
+                entries += [RestoreEntry(slot), ReleaseEntry(slot)]
+                handled.add((node, head))
+                continue
+            if not long_skip(succ):
+                return None
+        elif len(succ) == 3:  # a long skip from a node that also opens a fork (a residual block's input)
+            if not long_skip(succ):
+                return None
         else:
             return None
-    if not entries:
+    if not entries or pending or len(tapped) != len(extras) or isinstance(entries[-1], TapEntry):
         return None
     return entries
 
@@ -849,7 +1002,7 @@ def _pad_code(padding):
 
 def _add_structural(lib, h, e, leaky_variant=1):
     """Emit a StashEntry / RestoreEntry / RouteEntry / ShortcutEntry / ReleaseEntry /
-    UpsampleEntry; False if `e` is none of them."""
+    UpsampleEntry / TapEntry; False if `e` is none of them."""
     if isinstance(e, StashEntry):
         slot = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_stash(h, ctypes.byref(slot)), "dnn_plan_add_stash", lib)
@@ -865,6 +1018,11 @@ def _add_structural(lib, h, e, leaky_variant=1):
         _check(lib.dnn_plan_add_release(h, e.slot), "dnn_plan_add_release", lib)
     elif isinstance(e, UpsampleEntry):
         _check(lib.dnn_plan_add_upsample(h, e.factor), "dnn_plan_add_upsample", lib)
+    elif isinstance(e, TapEntry):
+        index = ctypes.c_int(-1)
+        _check(lib.dnn_plan_add_tap(h, ctypes.byref(index)), "dnn_plan_add_tap", lib)
+        if index.value != e.index:
+            raise DnnHipError(f"dnn_plan_add_tap gave index {index.value}, the lowering expected {e.index}")
     else:
         return False
     return True
@@ -917,6 +1075,13 @@ class Plan(object):
         _check(self.lib.dnn_plan_output_shape(self.h, ctypes.byref(b), ctypes.byref(oh), ctypes.byref(ow),
                                               ctypes.byref(oc)), "dnn_plan_output_shape", self.lib)
         self.out_shape = (oh.value, ow.value, oc.value)
+        self.tap_entries = [e for e in entries if isinstance(e, TapEntry)]
+        self.tap_shapes = []  # per tap (h, w, c), in tap order
+        for k in range(self.lib.dnn_plan_num_taps(self.h)):
+            th, tw, tc = (ctypes.c_int() for _ in range(3))
+            _check(self.lib.dnn_plan_tap_shape(self.h, k, ctypes.byref(th), ctypes.byref(tw), ctypes.byref(tc)),
+                   "dnn_plan_tap_shape", self.lib)
+            self.tap_shapes.append((th.value, tw.value, tc.value))
         self.device = device
         _check(self.lib.dnn_plan_finalize(self.h, device, weights_ptr, workspace_ptr), "dnn_plan_finalize",
                self.lib)
@@ -958,8 +1123,8 @@ class Plan(object):
             lib.dnn_plan_destroy(h)
 
     def describe(self):
-        buf = ctypes.create_string_buffer(8192)
-        _check(self.lib.dnn_plan_describe(self.h, buf, 8192), "dnn_plan_describe", self.lib)
+        buf = ctypes.create_string_buffer(65536)
+        _check(self.lib.dnn_plan_describe(self.h, buf, 65536), "dnn_plan_describe", self.lib)
         return buf.value.decode()
 
     def weight_buffer(self):
@@ -975,6 +1140,25 @@ class Plan(object):
         out = np.empty((n,) + self.out_shape, dtype=np.float32)
         _check(self.lib.dnn_plan_run_host(self.h, n, _vp(x), _vp(out)), "dnn_plan_run_host", self.lib)
         return out
+
+    def tap_buffer(self, k):
+        """(device address, bytes for the planned batch) of tap `k` (dnn_plan_tap_buffer): after a
+        run of n images the first n x h x w x c floats there are the tap's tensor."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        _check(self.lib.dnn_plan_tap_buffer(self.h, int(k), ctypes.byref(p), ctypes.byref(n)), "dnn_plan_tap_buffer",
+               self.lib)
+        return p.value, n.value
+
+    def run_host_all(self, x):
+        """run_host plus the taps: [tap 0, tap 1, ..., the plan's output] as host arrays."""
+        out = self.run_host(x)
+        n = out.shape[0]
+        taps = []
+        for k, shape in enumerate(self.tap_shapes):
+            t = np.empty((n,) + shape, dtype=np.float32)
+            _check(self.lib.dnn_plan_tap_read_host(self.h, k, n, _vp(t)), "dnn_plan_tap_read_host", self.lib)
+            taps.append(t)
+        return taps + [out]
 
     def run_device(self, n, in_ptr, out_ptr, stream_ptr=None):
         _check(self.lib.dnn_plan_run(self.h, int(n), ctypes.c_void_p(in_ptr), ctypes.c_void_p(out_ptr),

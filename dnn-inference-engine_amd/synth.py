@@ -170,6 +170,44 @@ def darknet53_weights(seed=WEIGHT_SEED, width_div=1, n_out=YOLOV2_N_OUT, in_c=IN
     return ws
 
 
+# YOLOv3's three detection branches (yolov3.py), per scale (stride 32, 16, 8): the branch width w;
+# five alternating 1x1 x w / 3x3 x 2w convs, a 3x3 x 2w conv and the linear 1x1 head.  Between two
+# scales a 1x1 x w/2 reduce conv, an upsample and the concat with the trunk's stage output
+YOLOV3_BRANCH_WIDTHS = (512, 256, 128)
+YOLOV3_N_OUT = 255            # 3 anchors x (5 + 80 COCO classes)
+
+
+def yolov3_weights(seed=WEIGHT_SEED, width_div=1, n_out=YOLOV3_N_OUT, in_c=IN_SHAPE[2]):
+    """The 75-entry weight list yolov3.YOLO_V3 consumes, in Darknet layer order: darknet53's 52
+    trunk convs (the same values as darknet53_weights gives them), then per scale the branch's five
+    alternating 1x1 / 3x3 convs, its 3x3 conv and its linear 1x1 head with n_out outputs, with the
+    1x1 reduce conv in front of each of the two upsamples after the first and the second scale's
+    head.  Same counter-based generators (layer i draws from streams 10 i + j) and width_div as
+    darknet53_weights.  The SAME-padding caveat of darknet53.py applies unchanged: the stride-2
+    convs pad as TensorFlow does, so weights converted from a Darknet checkpoint would compute
+    something else at those five layers."""
+    def wd(c):
+        if c % width_div:
+            raise ValueError(f"width_div {width_div} does not divide {c}")
+        return c // width_div
+
+    n_trunk = 1 + sum(1 + 2 * b for _, b in DARKNET53_STAGES)
+    ws = darknet53_weights(seed=seed, width_div=width_div, n_out=n_out, in_c=in_c)[:n_trunk]
+    ic = wd(DARKNET53_STAGES[-1][0])
+    skips = [wd(DARKNET53_STAGES[-2][0]), wd(DARKNET53_STAGES[-3][0])]  # the stage outputs the concats take
+    for s, width in enumerate(YOLOV3_BRANCH_WIDTHS):
+        for j in range(5):
+            od, k = (wd(width), 1) if j % 2 == 0 else (wd(2 * width), 3)
+            ws.append(layer_weights(len(ws), ic, od, k=k, seed=seed))
+            ic = od
+        ws.append(layer_weights(len(ws), ic, wd(2 * width), k=3, seed=seed))
+        ws.append(layer_weights(len(ws), wd(2 * width), n_out, k=1, seed=seed, bn=False))
+        if s < 2:
+            ws.append(layer_weights(len(ws), ic, wd(width // 2), k=1, seed=seed))
+            ic = wd(width // 2) + skips[s]
+    return ws
+
+
 def yolo_zero_weights(channels=CHANNELS, in_c=IN_SHAPE[2]):
     """yolo_weights' shapes with zero values, without running the generator: what a
     non-root rank lays its plan out with before the weight broadcast fills it."""

@@ -17,6 +17,7 @@ a `YoloHead` and passed as `head=` to the same functions; they then run
     head = YoloHead.for_input(608, 608)              # 19 x 19 cells, VOC anchors and classes
     rows = detect_batch(pred, head=head)             # pred [B,19,19,125]
 """
+import collections
 import ctypes
 
 import math
@@ -64,6 +65,15 @@ class HeadStruct(ctypes.Structure):
                 ("iou_thr", ctypes.c_double), ("anchors", ctypes.c_float * 32)]
 
 
+MAX_SCALES, MULTI_MAX_BOXES = 4, 16384  # DNN_YOLO_MAX_SCALES, DNN_YOLO_MULTI_MAX_BOXES
+CLASS_MODES = {"softmax": 0, "logistic": 1}
+
+
+class MultiStruct(ctypes.Structure):
+    """dnn_yolo_multi (include/dnn_hip_post.h)."""
+    _fields_ = [("n_scales", ctypes.c_int), ("class_mode", ctypes.c_int), ("scale", HeadStruct * MAX_SCALES)]
+
+
 def _bind(lib):
     vp, i = ctypes.c_void_p, ctypes.c_int
     hp, u64 = ctypes.POINTER(HeadStruct), ctypes.c_ulonglong
@@ -83,6 +93,15 @@ def _bind(lib):
     lib.dnn_yolo_postprocess_host.argtypes = [vp, i, vp, i, vp]
     lib.dnn_yolo_pack_detections.restype = i
     lib.dnn_yolo_pack_detections.argtypes = [vp, vp, i, i, vp, vp, vp]
+    mp, pp = ctypes.POINTER(MultiStruct), ctypes.POINTER(vp)
+    lib.dnn_yolo_multi_boxes.restype = i
+    lib.dnn_yolo_multi_boxes.argtypes = [mp]
+    lib.dnn_yolo_multi_workspace.restype = i
+    lib.dnn_yolo_multi_workspace.argtypes = [mp, i, ctypes.POINTER(u64)]
+    lib.dnn_yolo_postprocess_multi.restype = i
+    lib.dnn_yolo_postprocess_multi.argtypes = [mp, pp, i, vp, i, vp, vp, u64, vp]
+    lib.dnn_yolo_postprocess_multi_host.restype = i
+    lib.dnn_yolo_postprocess_multi_host.argtypes = [mp, pp, i, vp, i, vp]
     return lib
 
 
@@ -155,6 +174,114 @@ class YoloHead(object):
     def __repr__(self):
         return (f"YoloHead({self.grid_h}x{self.grid_w} cells, {self.n_anchors} anchors, {self.n_classes} classes, "
                 f"cell {self.cell:g}, score > {self.score_thr:g}, IoU > {self.iou_thr:g})")
+
+
+Scale = collections.namedtuple("Scale", "grid_h grid_w n_anchors n_classes anchors cell score_thr iou_thr")
+Scale.__doc__ = """One scale of a MultiHead: a YoloHead's fields without its own 8192-box limit."""
+
+# the public YOLOv3 anchor table: stride -> (w, h) pairs in pixels
+YOLOV3_ANCHORS = ((32, (116, 90, 156, 198, 373, 326)), (16, (30, 61, 62, 45, 59, 119)), (8, (10, 13, 16, 30, 33, 23)))
+
+
+class MultiHead(object):
+    """Several heads whose boxes compete in one sort and one NMS (dnn_yolo_multi): `scales` is a
+    sequence of 1..4 heads (YoloHead, Scale, or anything with their fields), scale 0's boxes
+    first; class_mode "logistic" (YOLOv3: one sigmoid per class) or "softmax" (YOLOv2).  All
+    scales must agree on classes and thresholds and have at most 16384 boxes together.  Validates
+    like the C side (dnn_yolo_multi_boxes) and raises ValueError."""
+
+    def __init__(self, scales, class_mode="logistic"):
+        scales = list(scales)
+        if not 1 <= len(scales) <= MAX_SCALES:
+            raise ValueError(f"{len(scales)} scales: need 1..{MAX_SCALES}")
+        if class_mode not in CLASS_MODES:
+            raise ValueError(f"class_mode {class_mode!r}: need one of {sorted(CLASS_MODES)}")
+        self.class_mode = class_mode
+        self.scales = []
+        for s in scales:
+            anchors = tuple(float(a) for a in s.anchors)
+            if len(anchors) % 2 or not 1 <= len(anchors) // 2 <= MAX_ANCHORS or len(anchors) != 2 * s.n_anchors:
+                raise ValueError(f"{len(anchors)} anchor values: need (w, h) pairs for {s.n_anchors} of 1.."
+                                 f"{MAX_ANCHORS} anchors")
+            if int(s.grid_h) != s.grid_h or int(s.grid_w) != s.grid_w or s.grid_h < 1 or s.grid_w < 1:
+                raise ValueError(f"grid {s.grid_h} x {s.grid_w}: whole numbers of cells >= 1 expected")
+            if not 1 <= s.n_classes <= MAX_CLASSES:
+                raise ValueError(f"{s.n_classes} classes: need 1..{MAX_CLASSES}")
+            if not (np.float32(s.score_thr) >= 0) or math.isnan(s.iou_thr):
+                raise ValueError(f"score_thr {s.score_thr!r} must be >= 0 and iou_thr {s.iou_thr!r} a number")
+            if not (np.float32(s.cell) > 0 and np.isfinite(np.float32(s.cell))):
+                raise ValueError(f"cell {s.cell!r} must be a finite number of pixels > 0")
+            if not np.all(np.isfinite(np.asarray(anchors, np.float32))):
+                raise ValueError("anchors must be finite")
+            self.scales.append(Scale(int(s.grid_h), int(s.grid_w), int(s.n_anchors), int(s.n_classes), anchors,
+                                     float(s.cell), float(s.score_thr), float(s.iou_thr)))
+        s0 = self.scales[0]
+        for k, s in enumerate(self.scales):
+            if (s.n_classes, np.float32(s.score_thr), s.iou_thr) != (s0.n_classes, np.float32(s0.score_thr), s0.iou_thr):
+                raise ValueError(f"scale {k}: classes and thresholds must be those of scale 0")
+        self.names = getattr(scales[0], "names", None)
+        self.n_classes, self.score_thr, self.iou_thr = s0.n_classes, s0.score_thr, s0.iou_thr
+        self.scale_boxes = [s.grid_h * s.grid_w * s.n_anchors for s in self.scales]
+        self.boxes = sum(self.scale_boxes)
+        if self.boxes > MULTI_MAX_BOXES:
+            raise ValueError(f"{self.boxes} boxes over {len(self.scales)} scales: need <= {MULTI_MAX_BOXES}")
+        self.n_out = [s.n_anchors * (5 + s.n_classes) for s in self.scales]
+        self.pred_shapes = [(s.grid_h, s.grid_w, n) for s, n in zip(self.scales, self.n_out)]
+        self.pred_floats = [h * w * c for h, w, c in self.pred_shapes]
+        self.c = MultiStruct()
+        self.c.n_scales, self.c.class_mode = len(self.scales), CLASS_MODES[class_mode]
+        for k, s in enumerate(self.scales):
+            self.c.scale[k] = HeadStruct(s.grid_h, s.grid_w, s.n_anchors, s.n_classes, s.cell, s.score_thr, s.iou_thr,
+                                         (ctypes.c_float * 32)(*s.anchors))
+        n = _lib.dnn_yolo_multi_boxes(ctypes.byref(self.c))
+        if n != self.boxes:
+            raise ValueError(f"dnn_yolo_multi_boxes: {n}: {dnn_hip.last_error()}")
+
+    @classmethod
+    def yolov3(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3):
+        """YOLOv3's three heads for an in_h x in_w input (multiples of 32): strides 32, 16, 8 with
+        the public anchor table, the pixel anchors divided by the stride (exact in fp32: every
+        stride is a power of two), logistic class scores."""
+        if in_h < 32 or in_w < 32 or in_h % 32 or in_w % 32:
+            raise ValueError(f"input {in_h} x {in_w}: height and width must be multiples of 32")
+        n_classes = classes if isinstance(classes, (int, np.integer)) else len(classes)
+        scales = [Scale(in_h // st, in_w // st, 3, int(n_classes), tuple(a / st for a in px), float(st), score_thr,
+                        iou_thr) for st, px in YOLOV3_ANCHORS]
+        head = cls(scales, "logistic")
+        head.names = None if isinstance(classes, (int, np.integer)) else tuple(classes)
+        return head
+
+    def workspace_bytes(self, n_images):
+        b = ctypes.c_ulonglong(0)
+        dnn_hip._check(_lib.dnn_yolo_multi_workspace(ctypes.byref(self.c), n_images, ctypes.byref(b)),
+                       "dnn_yolo_multi_workspace")
+        return int(b.value)
+
+    def __repr__(self):
+        grids = ", ".join(f"{s.grid_h}x{s.grid_w}x{s.n_anchors}" for s in self.scales)
+        return (f"MultiHead({grids}; {self.n_classes} classes, {self.class_mode}, score > {self.score_thr:g}, "
+                f"IoU > {self.iou_thr:g})")
+
+
+def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
+    """preds: one fp32 host array per scale of `head` (a MultiHead), [B, *head.pred_shapes[s]] ->
+    per image the rows detect_batch returns, from one sort and one NMS over all scales."""
+    if len(preds) != len(head.scales):
+        raise ValueError(f"{len(preds)} prediction tensors for {len(head.scales)} scales")
+    ps = [np.ascontiguousarray(p, dtype=np.float32) for p in preds]
+    if any(p.size % f for p, f in zip(ps, head.pred_floats)):
+        raise ValueError(f"predictions of shapes {[p.shape for p in ps]} are not [B, ...] of {head.pred_shapes}")
+    ns = {p.size // f for p, f in zip(ps, head.pred_floats)}
+    if len(ns) != 1:
+        raise ValueError(f"the scales hold different numbers of images: {sorted(ns)}")
+    n = ns.pop()
+    max_det = head.boxes if max_det is None else max_det
+    dets = np.zeros((n, max_det), DETECTION_DTYPE)
+    counts = np.zeros(n, np.int32)
+    ptrs = (ctypes.c_void_p * len(ps))(*[p.ctypes.data for p in ps])
+    dnn_hip._check(_lib.dnn_yolo_postprocess_multi_host(ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det,
+                                                        counts.ctypes.data), "dnn_yolo_postprocess_multi_host")
+    return _rows(dets, counts, max_det, raise_errors)
 
 
 def _rows(dets, counts, max_det, raise_errors=True):
@@ -270,3 +397,30 @@ class DetectionBuffers(object):
             max_det = N_BOXES if head is None else head.boxes
         d = np.ascontiguousarray(dets_u8).view(DETECTION_DTYPE).reshape(len(counts), max_det)
         return _rows(d, np.asarray(counts), max_det, raise_errors)
+
+
+class MultiDetectionBuffers(DetectionBuffers):
+    """DetectionBuffers for a MultiHead: `run(pred_ptrs, n, stream)` takes one device pointer per
+    scale and goes through dnn_yolo_postprocess_multi; dets, counts, `pack` and `to_rows` are the
+    base class's (max_det defaults to head.boxes), so dnn_yolo_pack_detections and
+    dist.gather_detections apply unchanged."""
+
+    def __init__(self, n, device, head, max_det=None):
+        import torch
+        max_det = head.boxes if max_det is None else max_det
+        self.n, self.max_det, self.head = n, max_det, head
+        self.workspace = torch.zeros(head.workspace_bytes(n), dtype=torch.uint8, device=device)
+        self.dets = torch.zeros((n, max_det, DETECTION_DTYPE.itemsize), dtype=torch.uint8, device=device)
+        self.counts = torch.zeros(n, dtype=torch.int32, device=device)
+        self.packed = torch.zeros((n * max_det, DETECTION_DTYPE.itemsize), dtype=torch.uint8, device=device)
+        self.total = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def run(self, pred_ptrs, n, stream):
+        if n > self.n:
+            raise ValueError(f"{n} images > the {self.n} these buffers were sized for")
+        if len(pred_ptrs) != len(self.head.scales):
+            raise ValueError(f"{len(pred_ptrs)} prediction pointers for {len(self.head.scales)} scales")
+        ptrs = (ctypes.c_void_p * len(pred_ptrs))(*[int(p) for p in pred_ptrs])
+        dnn_hip._check(_lib.dnn_yolo_postprocess_multi(
+            ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
+            self.workspace.data_ptr(), self.workspace.numel(), stream), "dnn_yolo_postprocess_multi")

@@ -118,6 +118,33 @@ int dnn_plan_add_shortcut(dnn_plan* plan, int slot, int leaky);
 int dnn_plan_add_upsample(dnn_plan* plan, int factor);
 int dnn_plan_add_release(dnn_plan* plan, int slot);
 
+/* Taps: extra outputs of a plan (fp32 plans, batch and latency mode).  The reference's graphs have
+ * one output; YOLOv3 has three.
+ *
+ * dnn_plan_add_tap: the current tensor becomes extra output *index (0, 1, ... in call order, at
+ *   most DNN_PLAN_MAX_TAPS) and execution continues on it.  No kernel.  A tap is a stash that is
+ *   never released and takes no slot number: the layer that produces the tensor writes it into a
+ *   workspace region owned by the tap (plain NHWC fp32; the conv / pool fusions stop as for a
+ *   stash) and later consumers read it from there; a tensor that already sits in a region (just
+ *   stashed or restored) is tapped in place.  From the tap entry on no later producer is given
+ *   that region.  Fails, leaving the plan unchanged, on an fp16 plan, on a finalized plan, when no
+ *   layer has run yet (the current tensor is the plan's input) and for a fifth tap.  A plan cannot
+ *   end in a tap (dnn_plan_finalize fails, as for a stash): the last tensor goes to d_out.
+ * dnn_plan_num_taps / dnn_plan_tap_shape: the taps so far and each one's per-image shape.
+ * dnn_plan_tap_buffer (after finalize): the tap's device address and its size for the planned
+ *   batch.  After a run of n images has completed on its stream the first n*h*w*c floats there
+ *   are the tap's tensor, valid until the next run; the rest is not written.  The address is the
+ *   same for every run (dnn_plan_run, dnn_plan_run_host, dnn_plan_run_graph) and lies inside a
+ *   caller-supplied workspace.
+ * dnn_plan_tap_read_host: host-pointer convenience for use after dnn_plan_run_host: a synchronous
+ *   device-to-host copy of the first n images of the tap into h_out [n, h, w, c]. */
+#define DNN_PLAN_MAX_TAPS 4
+int dnn_plan_add_tap(dnn_plan* plan, int* index);
+int dnn_plan_num_taps(const dnn_plan* plan);
+int dnn_plan_tap_shape(const dnn_plan* plan, int index, int* h, int* w, int* c);
+int dnn_plan_tap_buffer(const dnn_plan* plan, int index, void** ptr, size_t* bytes);
+int dnn_plan_tap_read_host(const dnn_plan* plan, int index, int n, float* h_out);
+
 /* The shortcut and upsample kernels on host tensors (H2D copies, launch, D2H copy, synchronise):
  * out = act(a + b) over [n, h, w, c]; out [n, h*factor, w*factor, c] from a [n, h, w, c].  Each
  * tensor must be below 2 GiB (refused from the arguments, before any allocation). */
@@ -134,15 +161,16 @@ int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int*
  * reduce/epilogue kernel); a stash or restore line gives the tensor's shape and its slot, a
  * route line both shapes, the block and the slot with its shape, a shortcut line the shape, the
  * slot and the activation, an upsample line both shapes and the factor, a release line the
- * slot and its tensor's shape.  A 2x2/s2 MaxPool2D directly
+ * slot and its tensor's shape, a tap line ("tap HxWxC index=k") the shape and the tap's index.
+ * A 2x2/s2 MaxPool2D directly
  * after an implicit, patch or direct conv is folded into it; set DNN_HIP_FUSE=0 in the
  * environment before dnn_plan_create to keep every conv explicit and every pool separate
  * (DNN_HIP_PATCH=0: no patch mode). */
 int dnn_plan_describe(const dnn_plan* plan, char* buf, int buf_len);
 
 /* Device bytes the plan needs: packed weights + epilogue params, and workspace
- * (two activation buffers + the im2col buffer + one region per stashed tensor) for the planned
- * batch. */
+ * (two activation buffers + the im2col buffer + one region per stashed or tapped tensor) for the
+ * planned batch. */
 int dnn_plan_memory(const dnn_plan* plan, size_t* weight_bytes, size_t* workspace_bytes);
 
 /* Bind device memory and upload weights.  weights / workspace may be NULL, in which case

@@ -101,6 +101,61 @@ int dnn_yolo_postprocess_head(const dnn_yolo_head* head, const float* pred, int 
 int dnn_yolo_postprocess_head_host(const dnn_yolo_head* head, const float* pred, int n_images, dnn_detection* dets,
                                    int max_det, int* counts);
 
+/* ---- several heads, one NMS: YOLOv3's three scales --------------------------------------
+ * The reference has one head.  YOLOv3 predicts at strides 32, 16 and 8, each with its own grid,
+ * cell size and anchors, and logistic class scores; all boxes of an image then compete in one
+ * sort and one NMS.  A dnn_yolo_multi lists the heads ("scales").
+ *
+ * Box order: the image's boxes are the scales' boxes concatenated, scale 0 first, each scale in
+ * (row, col, anchor) order; the global box index is the position in that list.  Geometry and
+ * objectness of a box are the single-head rules above with its scale's grid, cell and anchors
+ * (anchors in cells: YOLOv3's pixel anchors divided by the stride, exact in fp32).  Class
+ * scores: class_mode 0 is the single-head softmax; class_mode 1 gives every class
+ * p[c] = 1 / (1 + e ** -logit[c]) in fp32 (the objectness formula), the class is the first index
+ * of the largest computed p (the rounded values are compared, not the logits) and the score is
+ * conf * p[class], one fp32 multiply.  Candidates (score > score_thr) of all scales go through
+ * one sort (score descending, ties: lower global index) and one greedy NMS with the integer-area
+ * IoU, as above.  This is the reference's NMS, which is class-agnostic: a box suppresses an
+ * overlapping box of any class.  Darknet's own YOLOv3 NMS runs per class, so it keeps
+ * overlapping boxes of different classes that this one drops.
+ * counts[i]: as above, -1 when any box of any scale (candidate or not) has a corner that is not
+ * finite or out of range, -2 when an evaluated IoU denominator is zero; such an image does not
+ * touch the other images' results.
+ *
+ * Every scale must be a valid dnn_yolo_head, except that its own boxes may exceed
+ * DNN_YOLO_MAX_BOXES: only the sum over scales is bounded, by DNN_YOLO_MULTI_MAX_BOXES.  All
+ * scales must agree on n_classes, score_thr and iou_thr. */
+#define DNN_YOLO_MAX_SCALES 4
+#define DNN_YOLO_MULTI_MAX_BOXES 16384 /* 416 x 416 YOLOv3: 10,647; 512 x 512: 16,128 */
+
+typedef struct dnn_yolo_multi {
+  int n_scales;   /* 1..4 */
+  int class_mode; /* 0 softmax (YOLOv2), 1 logistic (YOLOv3) */
+  dnn_yolo_head scale[DNN_YOLO_MAX_SCALES];
+} dnn_yolo_multi;
+
+/* Boxes of one image, summed over the scales, or < 0 (message in dnn_last_error()) for an
+ * invalid description.  Host only: no device is touched. */
+int dnn_yolo_multi_boxes(const dnn_yolo_multi* multi);
+
+/* Bytes of device scratch dnn_yolo_postprocess_multi needs for n_images images: 40 bytes per
+ * decoded box (the sort keys fill the LDS, so the box store is always here). */
+int dnn_yolo_multi_workspace(const dnn_yolo_multi* multi, int n_images, unsigned long long* bytes);
+
+/* Device pointers, asynchronous on `stream`.  pred: a HOST array of n_scales device pointers,
+ * pred[s] = [n_images][grid_h][grid_w][n_anchors * (5 + n_classes)] fp32 of scale s;
+ * dets: [n_images][max_det]; counts: [n_images]; workspace: 8-byte aligned, at least
+ * dnn_yolo_multi_workspace() bytes.  dets / counts have the layout of the single-head entries,
+ * so dnn_yolo_pack_detections applies unchanged. */
+int dnn_yolo_postprocess_multi(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
+                               dnn_detection* dets, int max_det, int* counts, void* workspace,
+                               unsigned long long workspace_bytes, void* stream);
+
+/* Host pointers (pred: n_scales host tensors), synchronous: allocates its scratch, copies in,
+ * runs, copies out. */
+int dnn_yolo_postprocess_multi_host(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
+                                    dnn_detection* dets, int max_det, int* counts);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus

@@ -1,0 +1,104 @@
+"""Times the full YOLOv3 at 416 x 416 on one GPU: the plan (75 convs, 23 shortcuts, 2 upsamples,
+2 routes, 2 taps), darknet53.py's plan beside it (what the trunk and the stride-32 branch cost
+alone), and the three-scale decode of the 10,647 boxes on typical inputs (a few hundred
+candidates per image) and on inputs where every box is a candidate.
+
+  python tools/yolov3_time.py [--batch 1] [--reps 20] [--rounds 5] [--decode-only]
+
+Each figure is the median over `rounds` of the device time of one run: HIP events around `reps`
+back-to-back runs on one stream, after a warm-up.  Prints one JSON line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(R, "dnn-inference-engine_amd"))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import darknet53  # noqa: E402
+import dnn_hip  # noqa: E402
+import synth  # noqa: E402
+import yolo_post  # noqa: E402
+import yolov3  # noqa: E402
+
+
+def device_ms(fn, reps, rounds):
+    """Median over rounds of (HIP-event time of reps calls) / reps, after one warm-up round."""
+    out = []
+    for r in range(rounds + 1):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize()
+        if r:
+            out.append(a.elapsed_time(b) / reps)
+    return statistics.median(out)
+
+
+def time_plan(g, batch, reps, rounds):
+    plan = dnn_hip.Plan.from_graph(g, device=0)
+    x = torch.from_numpy(synth.frames(range(batch))).cuda()
+    y = torch.empty((batch,) + plan.out_shape, dtype=torch.float32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    ms = device_ms(lambda: plan.run_device(batch, x.data_ptr(), y.data_ptr(), stream), reps, rounds)
+    nk = len(plan.kernels())
+    wb = plan.weight_buffer()[1]
+    plan.close()
+    return {"ms": round(ms, 3), "kernels": nk, "weight_MiB": round(wb / 2 ** 20, 1)}
+
+
+def predictions(head, batch, saturate, seed=0):
+    """Random head tensors: normal logits; typical: objectness N(-6, 2) (about 1 box in 400 above
+    0.3 before the class score); saturate: objectness 8 and one class logit of 12 on every box."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for s in head.scales:
+        p = rng.standard_normal((batch, s.grid_h, s.grid_w, s.n_anchors, 5 + s.n_classes)).astype(np.float32)
+        p[..., 4] = 8.0 if saturate else (rng.standard_normal(p.shape[:-1]) * 2.0 - 6.0)
+        hot = rng.integers(0, s.n_classes, size=p.shape[:-1])
+        np.put_along_axis(p[..., 5:], hot[..., None], np.float32(12.0 if saturate else 6.0), -1)
+        out.append(torch.from_numpy(p.reshape(batch, s.grid_h, s.grid_w, -1)).cuda())
+    return out
+
+
+def time_decode(batch, reps, rounds):
+    head = yolo_post.MultiHead.yolov3(416, 416)
+    buf = yolo_post.MultiDetectionBuffers(batch, torch.device("cuda", 0), head)
+    stream = torch.cuda.current_stream().cuda_stream
+    out = {"boxes": head.boxes}
+    for name, sat in (("typical", False), ("saturated", True)):
+        preds = predictions(head, batch, sat)
+        ptrs = [p.data_ptr() for p in preds]
+        ms = device_ms(lambda: buf.run(ptrs, batch, stream), reps, rounds)
+        counts = buf.counts.cpu().numpy()
+        out[name] = {"ms": round(ms, 3), "counts": [int(c) for c in counts]}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--decode-only", action="store_true")
+    a = ap.parse_args()
+    res = {"batch": a.batch, "decode": time_decode(a.batch, a.reps, a.rounds)}
+    if not a.decode_only:
+        shape = (a.batch, 416, 416, 3)
+        w3 = yolov3.validate(synth.yolov3_weights())
+        res["yolov3_plan"] = time_plan(yolov3.build_graph(dnn_hip.DnnGraphBuilder, w3, in_shape=shape)[0], a.batch,
+                                       a.reps, a.rounds)
+        wd = darknet53.validate(synth.darknet53_weights(n_out=255))
+        res["darknet53_plan"] = time_plan(darknet53.build_graph(dnn_hip.DnnGraphBuilder, wd, in_shape=shape)[0],
+                                          a.batch, a.reps, a.rounds)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
