@@ -329,6 +329,16 @@ int launch_shortcut(const float* a, const float* b, float* out, long long count,
 // 1..8; 16-byte accesses when C % 4 == 0.  Every tensor < 2 GiB
 int launch_upsample(const float* in, float* out, int n, int H, int W, int C, int factor, hipStream_t stream);
 
+// spp.hip: spatial pyramid pooling in one pass.  out [n, H, W, (n_sizes + 1) * C]: channel block j
+// is the sizes[j] x sizes[j] / stride-1 / SAME max pool of a [n, H, W, C] (maxpool_nhwc_kernel's
+// bits: -FLT_MAX padding, row-major scan, m >= v ? m : v), and a itself is the last block, or the
+// first with x_first.  n_sizes in 1..SPP_MAX_SIZES, each size odd in 3..SPP_MAX_K; 16-byte
+// accesses when C % 4 == 0.  Every tensor < 2 GiB
+constexpr int SPP_MAX_SIZES = 3;
+constexpr int SPP_MAX_K = 13;
+int launch_spp(const float* a, float* out, int n, int H, int W, int C, int n_sizes, const int* sizes, int x_first,
+               hipStream_t stream);
+
 // element-wise ops of the per-op ABI
 int launch_bias_add(const float* in, const float* b, float* out, long long n, int C, hipStream_t s);
 int launch_bn_mvg(const float* in, const float* mean, const float* sq, const float* gamma, float* out,

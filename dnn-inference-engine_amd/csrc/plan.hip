@@ -40,6 +40,10 @@
 // slot number: the producer writes the tensor into a region (to_region), the tap holds a reference
 // to that region that is never dropped, so no later producer is given it, and the caller reads the
 // region's device address (dnn_plan_tap_buffer) after a run.
+//
+// Spatial pyramid pooling: an spp entry (spp.hip) writes up to three stride-1 SAME max pools of the
+// current tensor and the tensor itself as channel blocks of one output, in one kernel.  Like the
+// other join entries it reads and writes plain NHWC fp32 and stops the conv / pool peepholes.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -123,7 +127,7 @@ static const char* kModeName[] = {"gemm", "direct_a", "implicit", "direct", "pat
 enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, LOC_IN = 2, LOC_REGION = 3 };
 
 struct PlanLayer {
-  int type = 0;  // 0 conv, 1 pool, 2 stash, 3 restore, 4 route, 5 shortcut, 6 upsample, 7 release, 8 tap (LAYER_*)
+  int type = 0;  // 0 conv, 1 pool, 2 stash, 3 restore, 4 route, 5 shortcut, 6 upsample, 7 release, 8 tap, 9 spp (LAYER_*)
   // shapes (per image): input H,W,C -> conv/pool output OH,OW,OC (-> fused pool PH,PW)
   int H = 0, W = 0, C = 0, OH = 0, OW = 0, OC = 0;
   int kh = 0, kw = 0, sh = 1, sw = 1, pt = 0, pl = 0;
@@ -152,13 +156,15 @@ struct PlanLayer {
   int slot_loc = LOC_NONE;  // where the slot's tensor lives when this entry is added (slot numbers are reused)
   int factor = 1;           // upsample
   int leaky = 0;            // shortcut: 0 none, 1 / 2 the conv epilogue's variants
+  int n_sizes = 0, sizes[DNN_SPP_MAX_SIZES] = {0, 0, 0};  // spp: the pools' window sizes, in block order
+  bool x_first = false;     // spp: the input's copy is the first channel block
   int dst_loc = 0;          // where this layer writes (LOC_*; layout())
   int out_h() const { return pool ? PH : OH; }
   int out_w() const { return pool ? PW : OW; }
 };
 
 enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
-                       LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8 };
+                       LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9 };
 constexpr int kMaxSlots = 4;
 
 struct PlanTap {
@@ -175,7 +181,7 @@ struct PlanSlot {
 struct KernelDesc {
   std::string name;
   int layer;
-  int kind;             // 0 im2col, 1 gemm / conv, 2 pool, 3 reduce / combine, 4 convert, 5 route, 6 shortcut, 7 upsample
+  int kind;             // 0 im2col, 1 gemm / conv, 2 pool, 3 reduce / combine, 4 convert, 5 route, 6 shortcut, 7 upsample, 8 spp
   double flops, bytes;  // algorithmic, full planned batch
 };
 
@@ -259,7 +265,7 @@ static bool fp16_direct_out(const dnn_plan* p) {
 static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
-  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0;  // kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7
+  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0;  // kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7
   p->kernels.clear();
   const double B = p->batch;
   for (size_t i = 0; i < p->layers.size(); ++i) {
@@ -331,6 +337,9 @@ static void layout(dnn_plan* p) {
     } else if (L.type == LAYER_UPSAMPLE) {
       snprintf(nm, sizeof(nm), "upsample%d", nup++);
       p->kernels.push_back({nm, (int)i, 7, 0.0, in_b + out_b});
+    } else if (L.type == LAYER_SPP) {  // reads the input once, writes n_sizes + 1 blocks of its size
+      snprintf(nm, sizeof(nm), "spp%d", nspp++);
+      p->kernels.push_back({nm, (int)i, 8, 0.0, in_b + out_b});
     }  // (a stash, a restore, a release or a tap launches nothing)
   }
   // where each layer writes.  Chains keep the ping-pong by layer parity; with fork / join entries
@@ -1039,6 +1048,58 @@ int dnn_plan_add_upsample(dnn_plan* p, int factor) {
   return 0;
 }
 
+static int spp_sizes_ok(const char* who, int n_sizes, const int* sizes) {
+  DNN_REQUIRE(sizes != nullptr, "%s: sizes is NULL", who);
+  DNN_REQUIRE(n_sizes >= 1 && n_sizes <= DNN_SPP_MAX_SIZES, "%s: n_sizes %d outside 1..%d", who, n_sizes,
+              DNN_SPP_MAX_SIZES);
+  for (int j = 0; j < n_sizes; ++j)
+    DNN_REQUIRE(sizes[j] >= 3 && sizes[j] <= DNN_SPP_MAX_K && sizes[j] % 2 == 1,
+                "%s: size %d (entry %d) is not odd and in 3..%d", who, sizes[j], j, DNN_SPP_MAX_K);
+  return 0;
+}
+
+int dnn_plan_add_spp(dnn_plan* p, int n_sizes, const int* sizes, int x_first) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_spp: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_spp: fp32 plans only (this is an fp16 plan)");
+  if (int rc = spp_sizes_ok("dnn_plan_add_spp", n_sizes, sizes)) return rc;
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_SPP);
+  L.OC = (n_sizes + 1) * L.C;
+  L.n_sizes = n_sizes;
+  for (int j = 0; j < n_sizes; ++j) L.sizes[j] = sizes[j];
+  L.x_first = x_first != 0;
+  current_leaves(p);
+  p->layers.push_back(std::move(L));
+  p->cur_c = p->layers.back().OC;
+  p->cur_src = -1;
+  return 0;
+}
+
+int dnn_spp_host(const float* a, float* out, int n, int h, int w, int c, int n_sizes, const int* sizes, int x_first) {
+  DNN_REQUIRE(a && out, "dnn_spp_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_spp_host: bad shape n=%d %dx%dx%d", n, h, w, c);
+  if (int rc = spp_sizes_ok("dnn_spp_host", n_sizes, sizes)) return rc;
+  if (n == 0) return 0;
+  const size_t af = (size_t)n * h * w * c, of = af * (n_sizes + 1);
+  DNN_REQUIRE(of * 4 < 0x80000000ULL, "dnn_spp_host: the output of n=%d %dx%dx%d with %d sizes is >= 2 GiB; split the batch",
+              n, h, w, c, n_sizes);
+  const size_t o_off = align_up(af, 64);
+  float* d = nullptr;
+  DNN_HIP_TRY(hipMalloc(&d, (o_off + of) * sizeof(float)));
+  int rc = 0;
+  if (hipMemcpy(d, a, af * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("dnn_spp_host: host to device copy failed");
+    rc = -1;
+  }
+  if (!rc) rc = launch_spp(d, d + o_off, n, h, w, c, n_sizes, sizes, x_first, nullptr);
+  if (!rc && hipMemcpy(out, d + o_off, of * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("dnn_spp_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
+    rc = -1;
+  }
+  (void)hipFree(d);
+  return rc;
+}
+
 int dnn_route_host(const float* a, const float* b, float* out, int n, int h, int w, int ca, int block, int cb,
                    int b_first) {
   DNN_REQUIRE(a && out, "dnn_route_host: NULL tensor");
@@ -1527,6 +1588,9 @@ int dnn_plan_run(dnn_plan* p, int n, const float* d_in, float* d_out, void* stre
     } else if (L.type == LAYER_UPSAMPLE) {
       if ((rc = record(p, k, s))) return rc;
       if ((rc = launch_upsample(cur, dst, n, L.H, L.W, L.C, L.factor, s))) return rc;
+    } else if (L.type == LAYER_SPP) {
+      if ((rc = record(p, k, s))) return rc;
+      if ((rc = launch_spp(cur, dst, n, L.H, L.W, L.C, L.n_sizes, L.sizes, L.x_first ? 1 : 0, s))) return rc;
     } else {
       PoolGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, 0};
       if ((rc = record(p, k, s))) return rc;
@@ -1650,6 +1714,12 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
       snprintf(line, sizeof(line), "release %dx%dx%d slot=%d\n", L.H, L.W, L.C, L.slot);
     } else if (L.type == LAYER_TAP) {
       snprintf(line, sizeof(line), "tap %dx%dx%d index=%d\n", L.H, L.W, L.C, L.slot);
+    } else if (L.type == LAYER_SPP) {
+      char sz[32] = "";
+      for (int j = 0; j < L.n_sizes; ++j)
+        snprintf(sz + strlen(sz), sizeof(sz) - strlen(sz), j ? ",%d" : "%d", L.sizes[j]);
+      snprintf(line, sizeof(line), "spp %dx%dx%d -> %dx%dx%d sizes=%s x=%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, sz,
+               L.x_first ? "first" : "last");
     } else
       snprintf(line, sizeof(line), "pool %dx%dx%d -> %dx%dx%d k%dx%d s%d%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.kh,
                L.kw, L.sh, p->fp16 ? " fp16" : "");

@@ -22,7 +22,9 @@ merge: a fork joined by an Add lowers to stash / shortcut / release entries (a r
 slot and its workspace region back, so any number of blocks fit in one plan).  A graph may have
 extra outputs (`DnnGraphBuilder.add_out_node`, `DnnInferenceEngine.run_all`): each becomes a tap
 entry of the plan, and a branch that ends in one, or a tensor concatenated many layers later, lowers
-too (lower_graph; YOLOv3's three heads and two merges, yolov3.py).  With
+too (lower_graph; YOLOv3's three heads and two merges, yolov3.py).  `Spp` (`create_spp`) is
+YOLOv3-SPP's pyramid pooling block, [maxpool13(x), maxpool9(x), maxpool5(x), x] on channels: one
+node, one spp plan entry, one kernel (yolov3_spp.py).  With
 `debug=True` (or a graph the plan cannot express) it instead runs node by node through
 the per-op C-ABI (`conv2d_mul`, `bias_add`, ... in libdnn_hip.so, include/dnn_hip.h),
 exactly like the reference, and saves every layer to ./intermediate/layer_{k}.npy
@@ -79,6 +81,8 @@ def _bind_plan_api(lib):
         "dnn_plan_tap_read_host": (i, [vp, i, i, vp]),
         "dnn_shortcut_host": (i, [vp, vp, vp, i, i, i, i, i]),
         "dnn_upsample_host": (i, [vp, vp, i, i, i, i, i]),
+        "dnn_plan_add_spp": (i, [vp, i, P(i), i]),
+        "dnn_spp_host": (i, [vp, vp, i, i, i, i, i, P(i), i]),
         "dnn_plan_output_shape": (i, [vp, P(i), P(i), P(i), P(i)]),
         "dnn_plan_describe": (i, [vp, ctypes.c_char_p, i]),
         "dnn_plan_memory": (i, [vp, P(sz), P(sz)]),
@@ -280,7 +284,7 @@ class DnnGraphBuilder(object):
     def __init__(self):
         self.G = nx.DiGraph() if nx is not None else _DiGraph()
         self.name_num = {"conv2d": 0, "bias_add": 0, "max_pool2d": 0, "batch_norm": 0, "leaky_relu": 0,
-                         "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0}
+                         "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0, "spp": 0}
         self.in_node = None
         self.out_node = None
         self.extra_out_nodes = []
@@ -357,6 +361,11 @@ class DnnGraphBuilder(object):
 
     def create_upsample(self, in_node, factor):
         out_node = Upsample(self.get_name("upsample"), in_node, factor)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_spp(self, in_node, ksizes, x_first=False):
+        out_node = Spp(self.get_name("spp"), in_node, ksizes, x_first)
         self.G.add_edge(in_node, out_node)
         return out_node
 
@@ -608,6 +617,50 @@ class Upsample(DnnNode):
         _check(rc, self.name)
 
 
+MAX_SPP_SIZES = 3  # DNN_SPP_MAX_SIZES: pools per spp entry
+MAX_SPP_K = 13     # DNN_SPP_MAX_K: the largest pool window (sizes are odd, 3..13)
+
+
+def _spp_sizes(ksizes):
+    """The window sizes of an Spp as a tuple of ints; ValueError unless 1..MAX_SPP_SIZES odd sizes
+    in 3..MAX_SPP_K."""
+    try:
+        ks = list(ksizes)
+    except TypeError:
+        raise ValueError
+    if not 1 <= len(ks) <= MAX_SPP_SIZES:
+        raise ValueError
+    for k in ks:
+        if isinstance(k, bool) or int(k) != k or not 3 <= k <= MAX_SPP_K or int(k) % 2 == 0:
+            raise ValueError
+    return tuple(int(k) for k in ks)
+
+
+class Spp(DnnNode):
+    """Not in the reference (YOLOv3-SPP's neck needs it): spatial pyramid pooling,
+    [n, H, W, C] -> [n, H, W, (len(ksizes) + 1) * C].  Channel block j is MaxPool2D(ksize
+    ksizes[j], stride 1, SAME) of the input, bit for bit, in the order given; the input itself is
+    the last block, or the first with x_first.  (13, 9, 5) is Darknet's order, (5, 9, 13) with
+    x_first YOLOv5's.  run() -> dnn_spp_host."""
+
+    def __init__(self, name, in_node, ksizes, x_first=False):
+        if len(in_node.result.shape) != 4:
+            raise ValueError
+        self.ksizes = _spp_sizes(ksizes)
+        batch, h, w, c = in_node.result.shape
+        self.in_node = in_node
+        self.x_first = bool(x_first)
+        self.result = np.zeros((batch, h, w, (len(self.ksizes) + 1) * c), dtype='float32')
+        self.name = name
+
+    def run(self):
+        a = np.ascontiguousarray(self.in_node.result, dtype=np.float32)
+        sizes = (ctypes.c_int * len(self.ksizes))(*self.ksizes)
+        rc = mylib.dnn_spp_host(_vp(a), _vp(self.result), *map(int, a.shape), len(self.ksizes), sizes,
+                                1 if self.x_first else 0)
+        _check(rc, self.name)
+
+
 class Input(DnnNode):
     """proj3/dnn_openblas.py:287-300 (unchanged contract)."""
 
@@ -691,6 +744,15 @@ class UpsampleEntry(object):
         self.nodes = list(nodes)
 
 
+class SppEntry(object):
+    """dnn_plan_add_spp: the stride-1 SAME max pools `ksizes` of the current tensor and the tensor
+    itself (first with x_first, else last) as channel blocks of one output."""
+
+    def __init__(self, ksizes, x_first=False, nodes=()):
+        self.ksizes, self.x_first = _spp_sizes(ksizes), bool(x_first)
+        self.nodes = list(nodes)
+
+
 class TapEntry(object):
     """dnn_plan_add_tap: the current tensor becomes the plan's extra output `index` (no kernel);
     `node` is the graph node it is the result of (None in plans assembled by hand)."""
@@ -740,6 +802,8 @@ def _lower_one(g, nxt):
         return RouteEntry(nxt.block, nodes=[nxt]), nxt
     if isinstance(nxt, Upsample):
         return UpsampleEntry(nxt.factor, nodes=[nxt]), nxt
+    if isinstance(nxt, Spp):
+        return SppEntry(nxt.ksizes, nxt.x_first, nodes=[nxt]), nxt
     return None  # a standalone element-wise op: not expressible as a fused entry
 
 
@@ -864,7 +928,7 @@ def _output_branch(g, head):
 def lower_graph(g):
     """Lower a builder graph to fused plan entries, or None if the plan cannot express it (then
     the node-by-node path runs).  Expressible: a chain of Conv2D (with its BiasAdd / BatchNorm /
-    LeakyReLU), MaxPool2D, SpaceToDepth and Upsample, and forks of two such chains (either may be
+    LeakyReLU), MaxPool2D, SpaceToDepth, Upsample and Spp, and forks of two such chains (either may be
     empty) joined by one Concat or one Add (with a LeakyReLU directly after it), any number of
     them in sequence within the plan's slots (an Add block gives its slots back); nested forks are
     not.  Graphs with extra outputs (add_out_node) add two patterns at a node x with two
@@ -1002,7 +1066,7 @@ def _pad_code(padding):
 
 def _add_structural(lib, h, e, leaky_variant=1):
     """Emit a StashEntry / RestoreEntry / RouteEntry / ShortcutEntry / ReleaseEntry /
-    UpsampleEntry / TapEntry; False if `e` is none of them."""
+    UpsampleEntry / SppEntry / TapEntry; False if `e` is none of them."""
     if isinstance(e, StashEntry):
         slot = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_stash(h, ctypes.byref(slot)), "dnn_plan_add_stash", lib)
@@ -1018,6 +1082,9 @@ def _add_structural(lib, h, e, leaky_variant=1):
         _check(lib.dnn_plan_add_release(h, e.slot), "dnn_plan_add_release", lib)
     elif isinstance(e, UpsampleEntry):
         _check(lib.dnn_plan_add_upsample(h, e.factor), "dnn_plan_add_upsample", lib)
+    elif isinstance(e, SppEntry):
+        sizes = (ctypes.c_int * len(e.ksizes))(*e.ksizes)
+        _check(lib.dnn_plan_add_spp(h, len(e.ksizes), sizes, 1 if e.x_first else 0), "dnn_plan_add_spp", lib)
     elif isinstance(e, TapEntry):
         index = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_tap(h, ctypes.byref(index)), "dnn_plan_add_tap", lib)

@@ -208,6 +208,81 @@ def yolov3_weights(seed=WEIGHT_SEED, width_div=1, n_out=YOLOV3_N_OUT, in_c=IN_SH
     return ws
 
 
+# YOLOv3-SPP (yolov3_spp.py): YOLOv3 with a pyramid pooling block in the stride-32 branch, whose
+# neck becomes 1x1, 3x3, 1x1, SPP (x4 channels), 1x1, 3x3, 1x1: one conv more than YOLOv3's
+YOLOV3_SPP_POOLS = (13, 9, 5)
+
+
+def yolov3_spp_weights(seed=WEIGHT_SEED, width_div=1, n_out=YOLOV3_N_OUT, in_c=IN_SHAPE[2]):
+    """The 76-entry weight list yolov3_spp.YOLO_V3_SPP consumes, in Darknet layer order: as
+    yolov3_weights, but the stride-32 branch has six neck convs (1x1, 3x3, 1x1, then after the SPP
+    block a 1x1 on 4 x the width, 3x3, 1x1) before its 3x3 conv and head.  Same generators (layer
+    i draws from streams 10 i + j), width_div and padding caveat as yolov3_weights; the 52 trunk
+    layers have yolov3_weights' values."""
+    def wd(c):
+        if c % width_div:
+            raise ValueError(f"width_div {width_div} does not divide {c}")
+        return c // width_div
+
+    n_trunk = 1 + sum(1 + 2 * b for _, b in DARKNET53_STAGES)
+    ws = darknet53_weights(seed=seed, width_div=width_div, n_out=n_out, in_c=in_c)[:n_trunk]
+    ic = wd(DARKNET53_STAGES[-1][0])
+    skips = [wd(DARKNET53_STAGES[-2][0]), wd(DARKNET53_STAGES[-3][0])]
+    for s, width in enumerate(YOLOV3_BRANCH_WIDTHS):
+        neck = [(wd(width), 1), (wd(2 * width), 3)] * 2 + [(wd(width), 1)]
+        if s == 0:  # the SPP block after the third conv: the next one reads (pools + 1) x width channels
+            neck = neck[:3] + [None] + neck[2:]
+        for item in neck:
+            if item is None:
+                ic *= len(YOLOV3_SPP_POOLS) + 1
+                continue
+            od, k = item
+            ws.append(layer_weights(len(ws), ic, od, k=k, seed=seed))
+            ic = od
+        ws.append(layer_weights(len(ws), ic, wd(2 * width), k=3, seed=seed))
+        ws.append(layer_weights(len(ws), wd(2 * width), n_out, k=1, seed=seed, bn=False))
+        if s < 2:
+            ws.append(layer_weights(len(ws), ic, wd(width // 2), k=1, seed=seed))
+            ic = wd(width // 2) + skips[s]
+    return ws
+
+
+# YOLOv3-tiny (yolov3_tiny.py): (output channels, kernel size) of the 13 convs in Darknet order:
+# the six 3x3 convs of the pooled stack, 3x3 x 1024, 1x1 x 256 (= y), head 0's 3x3 x 512 and linear
+# head, the merge's 1x1 x 128, head 1's 3x3 x 256 and linear head (None: n_out)
+YOLOV3_TINY_CONVS = ((16, 3), (32, 3), (64, 3), (128, 3), (256, 3), (512, 3), (1024, 3), (256, 1), (512, 3),
+                     (None, 1), (128, 1), (256, 3), (None, 1))
+YOLOV3_TINY_SKIP_FROM = 4  # the concat takes conv 4's output (26 x 26 x 256 at 416)
+
+
+def yolov3_tiny_weights(seed=WEIGHT_SEED, width_div=1, n_out=YOLOV3_N_OUT, in_c=IN_SHAPE[2]):
+    """The 13-entry weight list yolov3_tiny.YOLO_V3_TINY consumes, in Darknet layer order, from
+    the same counter-based generators (layer i draws from streams 10 i + j).  width_div divides
+    every channel count except the input's and the heads' n_out."""
+    def wd(c):
+        if c % width_div:
+            raise ValueError(f"width_div {width_div} does not divide {c}")
+        return c // width_div
+
+    ws = []
+    ic = in_c
+    y_c = skip_c = None
+    for i, (od, k) in enumerate(YOLOV3_TINY_CONVS):
+        head = od is None
+        if i == 10:  # the merge's reduce conv reads y
+            ic = y_c
+        elif i == 11:  # the first conv after the concat
+            ic += skip_c
+        od = n_out if head else wd(od)
+        ws.append(layer_weights(i, ic, od, k=k, seed=seed, bn=not head))
+        ic = od
+        if i == YOLOV3_TINY_SKIP_FROM:
+            skip_c = od
+        if i == 7:
+            y_c = od
+    return ws
+
+
 def yolo_zero_weights(channels=CHANNELS, in_c=IN_SHAPE[2]):
     """yolo_weights' shapes with zero values, without running the generator: what a
     non-root rank lays its plan out with before the weight broadcast fills it."""

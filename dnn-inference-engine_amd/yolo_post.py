@@ -183,6 +183,10 @@ Scale.__doc__ = """One scale of a MultiHead: a YoloHead's fields without its own
 YOLOV3_ANCHORS = ((32, (116, 90, 156, 198, 373, 326)), (16, (30, 61, 62, 45, 59, 119)), (8, (10, 13, 16, 30, 33, 23)))
 
 
+# the public YOLOv3-tiny anchor table, two scales
+YOLOV3_TINY_ANCHORS = ((32, (81, 82, 135, 169, 344, 319)), (16, (10, 14, 23, 27, 37, 58)))
+
+
 class MultiHead(object):
     """Several heads whose boxes compete in one sort and one NMS (dnn_yolo_multi): `scales` is a
     sequence of 1..4 heads (YoloHead, Scale, or anything with their fields), scale 0's boxes
@@ -247,6 +251,21 @@ class MultiHead(object):
         n_classes = classes if isinstance(classes, (int, np.integer)) else len(classes)
         scales = [Scale(in_h // st, in_w // st, 3, int(n_classes), tuple(a / st for a in px), float(st), score_thr,
                         iou_thr) for st, px in YOLOV3_ANCHORS]
+        head = cls(scales, "logistic")
+        head.names = None if isinstance(classes, (int, np.integer)) else tuple(classes)
+        return head
+
+    @classmethod
+    def yolov3_tiny(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3):
+        """YOLOv3-tiny's two heads for an in_h x in_w input (multiples of 32): strides 32 and 16
+        with the public anchor table (the stride-16 head takes the three smallest anchors, the
+        official cfg's mask 0,1,2), the pixel anchors divided by the stride (exact in fp32),
+        logistic class scores."""
+        if in_h < 32 or in_w < 32 or in_h % 32 or in_w % 32:
+            raise ValueError(f"input {in_h} x {in_w}: height and width must be multiples of 32")
+        n_classes = classes if isinstance(classes, (int, np.integer)) else len(classes)
+        scales = [Scale(in_h // st, in_w // st, 3, int(n_classes), tuple(a / st for a in px), float(st), score_thr,
+                        iou_thr) for st, px in YOLOV3_TINY_ANCHORS]
         head = cls(scales, "logistic")
         head.names = None if isinstance(classes, (int, np.integer)) else tuple(classes)
         return head

@@ -197,7 +197,7 @@ class YOLO_V3(object):
             raise ValueError(f"frames {x.shape} do not fit plan [{plan.batch}, {plan.in_shape}]")
         device = torch.device("cuda", plan.device)
         if self._dev is None:
-            order = [[id(e.node) for e in plan.tap_entries].index(id(o)) for o in self.outs[:2]]
+            order = [[id(e.node) for e in plan.tap_entries].index(id(o)) for o in self.outs[:-1]]
             self._dev = {
                 "in": torch.empty((plan.batch,) + plan.in_shape, dtype=torch.float32, device=device),
                 "out": torch.empty((plan.batch,) + plan.out_shape, dtype=torch.float32, device=device),

@@ -9,7 +9,9 @@
  * operation order), each MaxPool2D one pool entry, and activations never leave HBM.
  * It is what `dnn_hip.DnnInferenceEngine.run` (the Python mirror of dnn_openblas.py)
  * lowers the graph to.  Beyond the reference's chains, stash / restore / route entries let a
- * plan fork and join (YOLOv2's passthrough: space-to-depth + channel concat).
+ * plan fork and join (YOLOv2's passthrough: space-to-depth + channel concat), shortcut /
+ * upsample / release entries express residual and top-down networks, taps give a plan extra
+ * outputs (YOLOv3's three heads), and an spp entry is YOLOv3-SPP's pyramid pooling block.
  *
  * Conventions: plain C ABI, cdecl, no torch types.  All tensors NHWC fp32 contiguous,
  * conv kernels HWIO (the pickle layout of proj3/yolov2tiny.py:30-77).  Functions return
@@ -151,6 +153,32 @@ int dnn_plan_tap_read_host(const dnn_plan* plan, int index, int n, float* h_out)
 int dnn_shortcut_host(const float* a, const float* b, float* out, int n, int h, int w, int c, int leaky);
 int dnn_upsample_host(const float* a, float* out, int n, int h, int w, int c, int factor);
 
+/* Spatial pyramid pooling (fp32 plans, batch and latency mode; on an fp16 plan it fails).  The
+ * reference has no such node: it is the SPP block of YOLOv3-SPP's stride-32 neck,
+ *   x -> [maxpool13(x), maxpool9(x), maxpool5(x), x]   concatenated on channels.
+ *
+ * dnn_plan_add_spp: current [H, W, C] -> [H, W, (n_sizes + 1) * C].  Channel block j is
+ *   MaxPool2D(ksize = sizes[j], stride 1, SAME) of the current tensor, bit for bit what
+ *   dnn_plan_add_max_pool computes (-FLT_MAX padding, the window scanned in row-major order with
+ *   m = m >= v ? m : v, so the first maximal element wins, the sign of a zero included; finite
+ *   inputs), in the order given; the tensor itself is the last block, or the first with x_first
+ *   (13, 9, 5 with x last is Darknet's order, x first with 5, 9, 13 YOLOv5's).  n_sizes in
+ *   1..DNN_SPP_MAX_SIZES, each size odd and in 3..DNN_SPP_MAX_K; sizes may repeat.  One kernel
+ *   ("spp%d" in dnn_plan_kernel_info, 0 flops, n_sizes + 2 tensors of bytes: the input once, the
+ *   output once), whatever n_sizes.  Input and output are plain NHWC fp32 (the entry stops the
+ *   conv / pool fusions like the fork / join entries); the input may be the caller's d_in, the
+ *   output goes to a slot or tap region when a stash or tap follows and to d_out when the entry is
+ *   the plan's last.  Fails, leaving the plan unchanged, on an fp16 plan, on a finalized plan, for
+ *   a NULL sizes, a bad n_sizes and an even or out-of-range size.
+ * dnn_spp_host: the kernel on host tensors (H2D copy, launch, D2H copy, synchronise):
+ *   a [n, h, w, c] -> out [n, h, w, (n_sizes + 1) * c].  Each tensor must be below 2 GiB (refused
+ *   from the arguments, before any allocation). */
+#define DNN_SPP_MAX_SIZES 3
+#define DNN_SPP_MAX_K 13
+int dnn_plan_add_spp(dnn_plan* plan, int n_sizes, const int* sizes, int x_first);
+int dnn_spp_host(const float* a, float* out, int n, int h, int w, int c, int n_sizes, const int* sizes,
+                 int x_first);
+
 /* Output shape of the plan so far (per image, plus the planned batch). */
 int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int* c);
 
@@ -161,7 +189,8 @@ int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int*
  * reduce/epilogue kernel); a stash or restore line gives the tensor's shape and its slot, a
  * route line both shapes, the block and the slot with its shape, a shortcut line the shape, the
  * slot and the activation, an upsample line both shapes and the factor, a release line the
- * slot and its tensor's shape, a tap line ("tap HxWxC index=k") the shape and the tap's index.
+ * slot and its tensor's shape, a tap line ("tap HxWxC index=k") the shape and the tap's index,
+ * an spp line ("spp HxWxC -> HxWx(k+1)C sizes=13,9,5 x=last") both shapes, the sizes and x's place.
  * A 2x2/s2 MaxPool2D directly
  * after an implicit, patch or direct conv is folded into it; set DNN_HIP_FUSE=0 in the
  * environment before dnn_plan_create to keep every conv explicit and every pool separate

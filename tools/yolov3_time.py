@@ -1,9 +1,11 @@
 """Times the full YOLOv3 at 416 x 416 on one GPU: the plan (75 convs, 23 shortcuts, 2 upsamples,
 2 routes, 2 taps), darknet53.py's plan beside it (what the trunk and the stride-32 branch cost
 alone), and the three-scale decode of the 10,647 boxes on typical inputs (a few hundred
-candidates per image) and on inputs where every box is a candidate.
+candidates per image) and on inputs where every box is a candidate.  --model picks the network:
+yolov3 (the default, as above), yolov3_spp (76 convs and the spp entry; the decode is YOLOv3's),
+yolov3_tiny (13 convs, two scales, 2,535 boxes) or all.
 
-  python tools/yolov3_time.py [--batch 1] [--reps 20] [--rounds 5] [--decode-only]
+  python tools/yolov3_time.py [--model yolov3] [--batch 1] [--reps 20] [--rounds 5] [--decode-only]
 
 Each figure is the median over `rounds` of the device time of one run: HIP events around `reps`
 back-to-back runs on one stream, after a warm-up.  Prints one JSON line."""
@@ -24,6 +26,8 @@ import dnn_hip  # noqa: E402
 import synth  # noqa: E402
 import yolo_post  # noqa: E402
 import yolov3  # noqa: E402
+import yolov3_spp  # noqa: E402
+import yolov3_tiny  # noqa: E402
 
 
 def device_ms(fn, reps, rounds):
@@ -67,8 +71,8 @@ def predictions(head, batch, saturate, seed=0):
     return out
 
 
-def time_decode(batch, reps, rounds):
-    head = yolo_post.MultiHead.yolov3(416, 416)
+def time_decode(batch, reps, rounds, head=None):
+    head = head or yolo_post.MultiHead.yolov3(416, 416)
     buf = yolo_post.MultiDetectionBuffers(batch, torch.device("cuda", 0), head)
     stream = torch.cuda.current_stream().cuda_stream
     out = {"boxes": head.boxes}
@@ -87,10 +91,23 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--decode-only", action="store_true")
+    ap.add_argument("--model", choices=("yolov3", "yolov3_spp", "yolov3_tiny", "all"), default="yolov3")
     a = ap.parse_args()
-    res = {"batch": a.batch, "decode": time_decode(a.batch, a.reps, a.rounds)}
-    if not a.decode_only:
-        shape = (a.batch, 416, 416, 3)
+    shape = (a.batch, 416, 416, 3)
+    res = {"batch": a.batch}
+    if a.model in ("yolov3", "yolov3_spp", "all"):
+        res["decode"] = time_decode(a.batch, a.reps, a.rounds)
+    if a.model in ("yolov3_tiny", "all"):
+        res["decode_tiny"] = time_decode(a.batch, a.reps, a.rounds, yolo_post.MultiHead.yolov3_tiny(416, 416))
+    if not a.decode_only and a.model in ("yolov3_spp", "all"):
+        ws = yolov3_spp.validate(synth.yolov3_spp_weights())
+        res["yolov3_spp_plan"] = time_plan(yolov3_spp.build_graph(dnn_hip.DnnGraphBuilder, ws, in_shape=shape)[0],
+                                           a.batch, a.reps, a.rounds)
+    if not a.decode_only and a.model in ("yolov3_tiny", "all"):
+        wt = yolov3_tiny.validate(synth.yolov3_tiny_weights())
+        res["yolov3_tiny_plan"] = time_plan(yolov3_tiny.build_graph(dnn_hip.DnnGraphBuilder, wt, in_shape=shape)[0],
+                                            a.batch, a.reps, a.rounds)
+    if not a.decode_only and a.model in ("yolov3", "all"):
         w3 = yolov3.validate(synth.yolov3_weights())
         res["yolov3_plan"] = time_plan(yolov3.build_graph(dnn_hip.DnnGraphBuilder, w3, in_shape=shape)[0], a.batch,
                                        a.reps, a.rounds)
