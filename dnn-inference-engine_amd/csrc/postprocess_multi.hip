@@ -39,6 +39,126 @@ struct MultiPred {
   const float* p[DNN_YOLO_MAX_SCALES];
 };
 
+// One box of one scale (q: its 5 + C values; b, col, row: its anchor and cell): corners truncated to
+// int64 in out[0..3] (false when one is not finite or out of range), the score conf * p(class) and
+// the class.  Shared by both kernels below so that they round alike.
+__device__ __forceinline__ bool decode_box(const float* q, int C, bool logistic, int b, int col, int row,
+                                           const float* anchors_s, float cell_px, long long* out, float* score,
+                                           int* cls) {
+  const float cx = ((float)col + sigmoid_ref(q[0])) * cell_px;
+  const float cy = ((float)row + sigmoid_ref(q[1])) * cell_px;
+  const float rw = (np_expf(q[2]) * anchors_s[2 * b]) * cell_px;
+  const float rh = (np_expf(q[3]) * anchors_s[2 * b + 1]) * cell_px;
+  const float conf = sigmoid_ref(q[4]);
+  const float* lg = q + 5;
+  int best = 0;
+  float bp;
+  if (logistic) {
+    bp = sigmoid_ref(lg[0]);
+    for (int c = 1; c < C; ++c) {
+      const float pc = sigmoid_ref(lg[c]);
+      if (pc > bp) {  // first index of the largest rounded value
+        bp = pc;
+        best = c;
+      }
+    }
+  } else {
+    float m = lg[0];
+    for (int c = 1; c < C; ++c) m = lg[c] > m ? lg[c] : m;
+    const float sum = softmax_sum(lg, C, m);
+    bp = np_expf(lg[0] - m) / sum;
+    for (int c = 1; c < C; ++c) {
+      const float pc = np_expf(lg[c] - m) / sum;
+      if (pc > bp) {  // first index of the max quotient
+        bp = pc;
+        best = c;
+      }
+    }
+  }
+  const float hw = rw / 2.0f, hh = rh / 2.0f;
+  long long l = 0, t = 0, r = 0, bt = 0;
+  const bool ok = trunc_i64(cx - hw, &l) && trunc_i64(cx + hw, &r) && trunc_i64(cy - hh, &t) &&
+                  trunc_i64(cy + hh, &bt);
+  out[0] = l;
+  out[1] = t;
+  out[2] = r;
+  out[3] = bt;
+  *score = conf * bp;
+  *cls = best;
+  return ok;
+}
+
+// Bitonic sort of keys[0 .. ns) (ns a power of two) by the whole workgroup, ascending.
+__device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int ns, int tid) {
+  for (int kk = 2; kk <= ns; kk <<= 1) {
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < ns; i += PM_THREADS) {
+        const int ij = i ^ j;
+        if (ij > i) {
+          const unsigned long long a = keys[i], c = keys[ij];
+          if (((i & kk) == 0) == (a > c)) {
+            keys[i] = c;
+            keys[ij] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// Blocked greedy NMS of the n sorted candidates seg[0 .. n) by the whole workgroup (every thread
+// calls it; *n_kept == 0 on entry, published by a barrier).  The box index is the key's low
+// IDX_BITS bits.  The kept list (int box indices) is written in place over seg (see the top of the
+// file); *n_kept is its length after the closing barrier.
+template <int IDX_BITS>
+__device__ __forceinline__ void nms_workgroup(unsigned long long* seg, int n, const long long (*box)[4],
+                                              double iou_thr, unsigned long long* hitw, int* n_kept, int* zero_den,
+                                              int lane, int wid) {
+  int* kept = reinterpret_cast<int*>(seg);
+  for (int base = 0; base < n; base += 64) {
+    const int m = n - base < 64 ? n - base : 64;
+    const int nk = *n_kept;  // kept from earlier blocks: final
+    const bool live = lane < m;
+    const int mine = live ? (int)(seg[base + lane] & ((1ull << IDX_BITS) - 1ull)) : 0;
+    long long bi[4] = {0, 0, 0, 0};
+    if (live) {
+      bi[0] = box[mine][0];
+      bi[1] = box[mine][1];
+      bi[2] = box[mine][2];
+      bi[3] = box[mine][3];
+    }
+    bool hit = false, zd = false;
+    for (int j = wid; j < nk; j += PM_WAVES) {
+      const int kj = kept[j];  // wave-uniform
+      const long long bj[4] = {box[kj][0], box[kj][1], box[kj][2], box[kj][3]};
+      if (live && iou_gt(bi, bj, iou_thr, &zd)) hit = true;
+    }
+    const unsigned long long hw_ = __ballot(hit);
+    if (lane == 0) hitw[wid] = hw_;
+    if (__any(zd) && lane == 0) *zero_den = 1;
+    __syncthreads();  // every wave has read its keys of this block and the kept list
+    if (wid == 0) {
+      unsigned long long dropped = m < 64 ? ~((1ull << m) - 1ull) : 0ull;
+#pragma unroll
+      for (int wv = 0; wv < PM_WAVES; ++wv) dropped |= hitw[wv];
+      bool zt = false;
+      for (int i = 0; i < m; ++i) {
+        if ((dropped >> i) & 1ull) continue;  // wave-uniform: candidate i is kept
+        const int ki = __shfl(mine, i);       // (no key is read here: the list below overwrites them)
+        const long long bk[4] = {box[ki][0], box[ki][1], box[ki][2], box[ki][3]};
+        const bool h = live && lane > i && iou_gt(bi, bk, iou_thr, &zt);
+        dropped |= __ballot(h);
+      }
+      const unsigned long long keep = ~dropped;
+      if ((keep >> lane) & 1ull) kept[nk + __popcll(keep & ((1ull << lane) - 1ull))] = mine;
+      if (__any(zt) && lane == 0) *zero_den = 1;
+      if (lane == 0) *n_kept = nk + __popcll(keep);
+    }
+    __syncthreads();
+  }
+}
+
 __global__ void __launch_bounds__(PM_THREADS)
 yolo_multi_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* __restrict__ dets, int max_det,
                   int* __restrict__ counts, char* workspace, int nb) {
@@ -98,46 +218,14 @@ yolo_multi_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* 
     const float cell_px = s_cell[s];
     const float* q = s_pred[s] + (size_t)kk * stride;
     const int b = kk % A, cell = kk / A, col = cell % gw, row = cell / gw;
-    const float cx = ((float)col + sigmoid_ref(q[0])) * cell_px;
-    const float cy = ((float)row + sigmoid_ref(q[1])) * cell_px;
-    const float rw = (np_expf(q[2]) * anchors[s][2 * b]) * cell_px;
-    const float rh = (np_expf(q[3]) * anchors[s][2 * b + 1]) * cell_px;
-    const float conf = sigmoid_ref(q[4]);
-    const float* lg = q + 5;
-    int best = 0;
-    float bp;
-    if (logistic) {
-      bp = sigmoid_ref(lg[0]);
-      for (int c = 1; c < C; ++c) {
-        const float pc = sigmoid_ref(lg[c]);
-        if (pc > bp) {  // first index of the largest rounded value
-          bp = pc;
-          best = c;
-        }
-      }
-    } else {
-      float m = lg[0];
-      for (int c = 1; c < C; ++c) m = lg[c] > m ? lg[c] : m;
-      const float sum = softmax_sum(lg, C, m);
-      bp = np_expf(lg[0] - m) / sum;
-      for (int c = 1; c < C; ++c) {
-        const float pc = np_expf(lg[c] - m) / sum;
-        if (pc > bp) {  // first index of the max quotient
-          bp = pc;
-          best = c;
-        }
-      }
-    }
-    const float hw = rw / 2.0f, hh = rh / 2.0f;
-    long long l = 0, t = 0, r = 0, bt = 0;
-    const bool ok = trunc_i64(cx - hw, &l) && trunc_i64(cx + hw, &r) && trunc_i64(cy - hh, &t) &&
-                    trunc_i64(cy + hh, &bt);
-    if (!ok) bad = 1;
-    box[k][0] = l;
-    box[k][1] = t;
-    box[k][2] = r;
-    box[k][3] = bt;
-    const float sc = conf * bp;
+    long long c4[4];
+    float sc;
+    int best;
+    if (!decode_box(q, C, logistic, b, col, row, anchors[s], cell_px, c4, &sc, &best)) bad = 1;
+    box[k][0] = c4[0];
+    box[k][1] = c4[1];
+    box[k][2] = c4[2];
+    box[k][3] = c4[3];
     score_of[k] = sc;
     cls_of[k] = best;
     if (sc > score_thr) {  // score_thr >= 0: sc is positive, larger float bits = larger score
@@ -155,64 +243,10 @@ yolo_multi_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* 
   // ---- phase 2: bitonic sort of the first pow2 >= n keys
   int ns = 1;
   while (ns < n) ns <<= 1;
-  for (int kk = 2; kk <= ns; kk <<= 1) {
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < ns; i += PM_THREADS) {
-        const int ij = i ^ j;
-        if (ij > i) {
-          const unsigned long long a = keys[i], c = keys[ij];
-          if (((i & kk) == 0) == (a > c)) {
-            keys[i] = c;
-            keys[ij] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  bitonic_sort(keys, ns, tid);
 
   // ---- phase 3: blocked greedy NMS, the kept list in place over keys[0 .. base)
-  for (int base = 0; base < n; base += 64) {
-    const int m = n - base < 64 ? n - base : 64;
-    const int nk = n_kept;  // kept from earlier blocks: final
-    const bool live = lane < m;
-    const int mine = live ? (int)(keys[base + lane] & 0xffffffffu) : 0;
-    long long bi[4] = {0, 0, 0, 0};
-    if (live) {
-      bi[0] = box[mine][0];
-      bi[1] = box[mine][1];
-      bi[2] = box[mine][2];
-      bi[3] = box[mine][3];
-    }
-    bool hit = false, zd = false;
-    for (int j = wid; j < nk; j += PM_WAVES) {
-      const int kj = kept[j];  // wave-uniform
-      const long long bj[4] = {box[kj][0], box[kj][1], box[kj][2], box[kj][3]};
-      if (live && iou_gt(bi, bj, iou_thr, &zd)) hit = true;
-    }
-    const unsigned long long hw_ = __ballot(hit);
-    if (lane == 0) hitw[wid] = hw_;
-    if (__any(zd) && lane == 0) zero_den = 1;
-    __syncthreads();  // every wave has read its keys of this block and the kept list
-    if (wid == 0) {
-      unsigned long long dropped = m < 64 ? ~((1ull << m) - 1ull) : 0ull;
-#pragma unroll
-      for (int wv = 0; wv < PM_WAVES; ++wv) dropped |= hitw[wv];
-      bool zt = false;
-      for (int i = 0; i < m; ++i) {
-        if ((dropped >> i) & 1ull) continue;  // wave-uniform: candidate i is kept
-        const int ki = __shfl(mine, i);       // (no key is read here: the list below overwrites them)
-        const long long bk[4] = {box[ki][0], box[ki][1], box[ki][2], box[ki][3]};
-        const bool h = live && lane > i && iou_gt(bi, bk, iou_thr, &zt);
-        dropped |= __ballot(h);
-      }
-      const unsigned long long keep = ~dropped;
-      if ((keep >> lane) & 1ull) kept[nk + __popcll(keep & ((1ull << lane) - 1ull))] = mine;
-      if (__any(zt) && lane == 0) zero_den = 1;
-      if (lane == 0) n_kept = nk + __popcll(keep);
-    }
-    __syncthreads();
-  }
+  nms_workgroup<32>(keys, n, box, iou_thr, hitw, &n_kept, &zero_den, lane, wid);
 
   if (zero_den) {
     if (tid == 0) counts[img] = -2;
@@ -221,6 +255,289 @@ yolo_multi_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* 
   const int nk = n_kept, nw = nk < max_det ? nk : max_det;
   for (int r = tid; r < nw; r += PM_THREADS) {
     const int k = kept[r];
+    dnn_detection d;
+    d.cls = cls_of[k];
+    d.score = score_of[k];
+    d.left = box[k][0];
+    d.top = box[k][1];
+    d.right = box[k][2];
+    d.bottom = box[k][3];
+    dets[(size_t)img * max_det + r] = d;
+  }
+  if (tid == 0) counts[img] = nk;
+}
+
+// ---- per-class NMS (DNN_YOLO_NMS_PER_CLASS) ----------------------------------------------------
+// The per-class result is the class-agnostic algorithm run on each class's candidates alone,
+// merged by (score descending, global index).  So the candidates are sorted class-major, every
+// class is a contiguous segment of the sorted keys, and the segments are independent:
+//
+//   phase 1  the decode above; a candidate's key is class (7 bits) | ~score (32) | global index
+//            (14), and an LDS counter per class is bumped.  A prefix sum over the counters gives
+//            every class's segment [seg_start[c], seg_start[c + 1]) before the sort.
+//   phase 2  the same bitonic sort: class-major, score descending inside a class.
+//   phase 3  waves draw classes from an LDS ticket and run the blocked greedy NMS on a segment
+//            ALONE, with wave-level operations only: no barrier inside, nobody waits for anybody.
+//            The kept list of a segment goes in place over the segment's own consumed keys (the
+//            invariant at the top of the file with "segment start" for "array start").  Segments
+//            longer than PC_BIG candidates are left to a second pass in which the whole workgroup
+//            runs nms_workgroup on each of them in turn (16 waves share the scan of the kept list).
+//   phase 4  the kept lists are gathered into registers (position p of the concatenated lists,
+//            found by a search in the prefix sum of the list lengths), then written back as dense
+//            ~score | index keys, sorted over pow2 >= kept, and emitted as above.
+constexpr int PC_CLS_BITS = 7, PC_IDX_BITS = 14;
+// Candidates of one class above which the whole workgroup takes the segment.  A wave alone pays for
+// every kept box of its segment itself, so long chains are cheaper split over 16 waves even with
+// two barriers per block: measured at 256, 1024 and 4096, 256 was never slower.
+constexpr int PC_BIG = 256;
+static_assert(DNN_YOLO_MAX_CLASSES <= (1 << PC_CLS_BITS), "the class does not fit its key field");
+static_assert(DNN_YOLO_MULTI_MAX_BOXES <= (1 << PC_IDX_BITS), "the global box index does not fit its key field");
+static_assert(PC_CLS_BITS + 32 + PC_IDX_BITS < 64, "a candidate's key must stay below ~0ull");
+static_assert(PM_CAP <= 16 * PM_THREADS, "phase 4 holds 16 kept entries per thread in registers");
+
+__device__ __forceinline__ long long readlane_i64(long long v, int l) {  // l: wave-uniform
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(unsigned long long)v, l);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)v >> 32), l);
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// Orders this wave's own LDS reads and writes (the hardware executes one wave's LDS operations
+// in order; this keeps the compiler from moving them across).
+__device__ __forceinline__ void wave_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// start[c] = in[0] + .. + in[c - 1] for c <= 128 (in[c] counts as 0 for c >= C); one whole wave.
+__device__ __forceinline__ void wave_scan_128(const int* in, int C, int* start, int lane) {
+  const int a = 2 * lane < C ? in[2 * lane] : 0, b = 2 * lane + 1 < C ? in[2 * lane + 1] : 0;
+  int incl = a + b;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int v = __shfl_up(incl, d);
+    if (lane >= d) incl += v;
+  }
+  start[2 * lane] = incl - a - b;
+  start[2 * lane + 1] = incl - b;
+  if (lane == 63) start[128] = incl;
+}
+
+// Blocked greedy NMS of the len sorted candidates seg[0 .. len) of one class by ONE wave (all 64
+// lanes call it).  Returns the length of the kept list, written in place over seg; *zd is set when
+// an evaluated IoU had a zero denominator.
+__device__ __forceinline__ int nms_wave(unsigned long long* seg, int len, const long long (*box)[4], double iou_thr,
+                                        int lane, bool* zd) {
+  int* kept = reinterpret_cast<int*>(seg);
+  int nk = 0;
+  for (int base = 0; base < len; base += 64) {
+    const int m = len - base < 64 ? len - base : 64;
+    const bool live = lane < m;
+    const int mine = live ? (int)(seg[base + lane] & ((1ull << PC_IDX_BITS) - 1ull)) : 0;
+    wave_lds_fence();  // the block's keys are in registers before the list grows over them
+    long long bi[4] = {0, 0, 0, 0};
+    if (live) {
+      bi[0] = box[mine][0];
+      bi[1] = box[mine][1];
+      bi[2] = box[mine][2];
+      bi[3] = box[mine][3];
+    }
+    bool hit = false;
+    // kept boxes of earlier blocks, 64 at a time: one gather, then lane t's box against every lane
+    for (int j0 = 0; j0 < nk; j0 += 64) {
+      const int cnt = nk - j0 < 64 ? nk - j0 : 64;
+      const int kj = lane < cnt ? kept[j0 + lane] : 0;  // (box 0 always exists)
+      const long long g0 = box[kj][0], g1 = box[kj][1], g2 = box[kj][2], g3 = box[kj][3];
+      for (int t = 0; t < cnt; ++t) {
+        const long long bj[4] = {readlane_i64(g0, t), readlane_i64(g1, t), readlane_i64(g2, t), readlane_i64(g3, t)};
+        if (live && iou_gt(bi, bj, iou_thr, zd)) hit = true;
+      }
+    }
+    unsigned long long dropped = (m < 64 ? ~((1ull << m) - 1ull) : 0ull) | __ballot(hit);
+    for (int i = 0; i < m; ++i) {
+      if ((dropped >> i) & 1ull) continue;  // wave-uniform: candidate i is kept
+      const long long bk[4] = {readlane_i64(bi[0], i), readlane_i64(bi[1], i), readlane_i64(bi[2], i),
+                               readlane_i64(bi[3], i)};
+      const bool h = live && lane > i && iou_gt(bi, bk, iou_thr, zd);
+      dropped |= __ballot(h);
+    }
+    const unsigned long long keep = ~dropped;
+    // at most base + m entries after this: below byte 4 (base + 64) <= 8 (base + 64), the next key
+    if ((keep >> lane) & 1ull) kept[nk + __popcll(keep & ((1ull << lane) - 1ull))] = mine;
+    nk += __popcll(keep);
+    wave_lds_fence();  // the list is written before the next block scans it
+  }
+  return nk;
+}
+
+__global__ void __launch_bounds__(PM_THREADS)
+yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* __restrict__ dets,
+                            int max_det, int* __restrict__ counts, char* workspace, int nb) {
+  __shared__ unsigned long long keys[PM_CAP];
+  __shared__ float anchors[DNN_YOLO_MAX_SCALES][2 * DNN_YOLO_MAX_ANCHORS];
+  __shared__ const float* s_pred[DNN_YOLO_MAX_SCALES];
+  __shared__ int s_off[DNN_YOLO_MAX_SCALES + 1], s_gw[DNN_YOLO_MAX_SCALES], s_na[DNN_YOLO_MAX_SCALES];
+  __shared__ float s_cell[DNN_YOLO_MAX_SCALES];
+  __shared__ unsigned long long hitw[PM_WAVES];
+  __shared__ int cls_cnt[DNN_YOLO_MAX_CLASSES];        // candidates per class
+  __shared__ int seg_start[DNN_YOLO_MAX_CLASSES + 1];  // their prefix sum: class c is keys[seg_start[c] .. seg_start[c+1])
+  __shared__ int seg_kept[DNN_YOLO_MAX_CLASSES];       // kept per class
+  __shared__ int out_off[DNN_YOLO_MAX_CLASSES + 1];    // their prefix sum
+  __shared__ int n_cand, bad, n_kept, zero_den, ticket;
+
+  const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int S = mh.n_scales, C = mh.scale[0].n_classes, stride = 5 + C;
+  const bool logistic = mh.class_mode == 1;
+  const float score_thr = mh.scale[0].score_thr;
+  const double iou_thr = mh.scale[0].iou_thr;
+
+  char* w = workspace + (size_t)img * nb * PM_BOX_BYTES;
+  long long (*box)[4] = reinterpret_cast<long long (*)[4]>(w);
+  float* score_of = reinterpret_cast<float*>(w + (size_t)nb * 32);
+  int* cls_of = reinterpret_cast<int*>(w + (size_t)nb * 36);
+
+  int nsort = 1;  // keys that the first sort can touch: pow2 >= nb, <= PM_CAP
+  while (nsort < nb) nsort <<= 1;
+  if (tid == 0) {
+    n_cand = 0;
+    bad = 0;
+    n_kept = 0;
+    zero_den = 0;
+    ticket = 0;
+    int off = 0;
+#pragma unroll
+    for (int s = 0; s < DNN_YOLO_MAX_SCALES; ++s) {
+      const bool on = s < S;
+      const int b = on ? mh.scale[s].grid_h * mh.scale[s].grid_w * mh.scale[s].n_anchors : 0;
+      s_off[s] = off;
+      s_gw[s] = on ? mh.scale[s].grid_w : 1;
+      s_na[s] = on ? mh.scale[s].n_anchors : 1;
+      s_cell[s] = on ? mh.scale[s].cell : 1.0f;
+      s_pred[s] = on ? pred.p[s] + (size_t)img * b * stride : nullptr;
+      off += b;
+    }
+    s_off[DNN_YOLO_MAX_SCALES] = off;
+  }
+  if (tid < 2 * DNN_YOLO_MAX_ANCHORS) {
+#pragma unroll
+    for (int s = 0; s < DNN_YOLO_MAX_SCALES; ++s) anchors[s][tid] = mh.scale[s].anchors[tid];
+  }
+  if (tid < DNN_YOLO_MAX_CLASSES) {
+    cls_cnt[tid] = 0;
+    seg_kept[tid] = 0;
+  }
+  for (int i = tid; i < nsort; i += PM_THREADS) keys[i] = ~0ull;
+  __syncthreads();
+
+  // ---- phase 1: decode
+  for (int k = tid; k < nb; k += PM_THREADS) {
+    int s = 0;
+    while (s + 1 < S && k >= s_off[s + 1]) ++s;
+    const int kk = k - s_off[s], A = s_na[s], gw = s_gw[s];
+    const float cell_px = s_cell[s];
+    const float* q = s_pred[s] + (size_t)kk * stride;
+    const int b = kk % A, cell = kk / A, col = cell % gw, row = cell / gw;
+    long long c4[4];
+    float sc;
+    int best;
+    if (!decode_box(q, C, logistic, b, col, row, anchors[s], cell_px, c4, &sc, &best)) bad = 1;
+    box[k][0] = c4[0];
+    box[k][1] = c4[1];
+    box[k][2] = c4[2];
+    box[k][3] = c4[3];
+    score_of[k] = sc;
+    cls_of[k] = best;
+    if (sc > score_thr) {  // score_thr >= 0: sc is positive, larger float bits = larger score
+      const int pos = atomicAdd(&n_cand, 1);
+      atomicAdd(&cls_cnt[best], 1);
+      keys[pos] = ((unsigned long long)best << (32 + PC_IDX_BITS)) |
+                  ((unsigned long long)(~__float_as_uint(sc)) << PC_IDX_BITS) | (unsigned)k;
+    }
+  }
+  __syncthreads();
+  const int n = n_cand;
+  if (bad) {
+    if (tid == 0) counts[img] = -1;
+    return;
+  }
+  if (wid == 0) wave_scan_128(cls_cnt, C, seg_start, lane);
+
+  // ---- phase 2: bitonic sort of the first pow2 >= n keys: class-major
+  int ns = 1;
+  while (ns < n) ns <<= 1;
+  bitonic_sort(keys, ns, tid);
+  __syncthreads();  // seg_start too (the sort has no barrier when n <= 1)
+
+  // ---- phase 3a: one wave per class segment, no barrier, nobody waits
+  {
+    bool zd = false;
+    for (;;) {
+      int c = 0;
+      if (lane == 0) c = atomicAdd(&ticket, 1);
+      c = __builtin_amdgcn_readfirstlane(c);  // lane 0's ticket, in a scalar register
+      if (c >= C) break;
+      const int s0 = __builtin_amdgcn_readfirstlane(seg_start[c]);
+      const int len = __builtin_amdgcn_readfirstlane(seg_start[c + 1]) - s0;
+      if (len == 0 || len > PC_BIG) continue;
+      const int nk = nms_wave(keys + s0, len, box, iou_thr, lane, &zd);
+      if (lane == 0) seg_kept[c] = nk;
+    }
+    if (__any(zd) && lane == 0) zero_den = 1;
+  }
+  __syncthreads();
+
+  // ---- phase 3b: the long segments, each by the whole workgroup (n_kept is 0 here)
+  for (int c = 0; c < C; ++c) {
+    const int s0 = __builtin_amdgcn_readfirstlane(seg_start[c]);
+    const int len = __builtin_amdgcn_readfirstlane(seg_start[c + 1]) - s0;
+    if (len <= PC_BIG) continue;  // workgroup-uniform
+    nms_workgroup<PC_IDX_BITS>(keys + s0, len, box, iou_thr, hitw, &n_kept, &zero_den, lane, wid);
+    if (tid == 0) {
+      seg_kept[c] = n_kept;
+      n_kept = 0;
+    }
+    __syncthreads();
+  }
+
+  // ---- phase 4: merge the kept lists by (score, global index)
+  if (wid == 0) wave_scan_128(seg_kept, C, out_off, lane);
+  __syncthreads();
+  if (zero_den) {
+    if (tid == 0) counts[img] = -2;
+    return;
+  }
+  const int nk = out_off[DNN_YOLO_MAX_CLASSES];
+  int mine[16];  // entries tid, tid + 1024, ... of the concatenated kept lists
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int p = tid + i * PM_THREADS;
+    mine[i] = 0;
+    if (p < nk) {
+      int lo = 0, hi = C;  // the class with out_off[lo] <= p < out_off[lo + 1]
+      while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (out_off[mid] <= p) lo = mid;
+        else hi = mid;
+      }
+      mine[i] = reinterpret_cast<const int*>(keys + seg_start[lo])[p - out_off[lo]];
+    }
+  }
+  __syncthreads();  // every list entry is in a register: the keys may be overwritten
+  int ns2 = 1;
+  while (ns2 < nk) ns2 <<= 1;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int p = tid + i * PM_THREADS;
+    if (p < nk)
+      keys[p] = ((unsigned long long)(~__float_as_uint(score_of[mine[i]])) << 32) | (unsigned)mine[i];
+    else if (p < ns2)
+      keys[p] = ~0ull;
+  }
+  __syncthreads();
+  bitonic_sort(keys, ns2, tid);
+
+  const int nw = nk < max_det ? nk : max_det;
+  for (int r = tid; r < nw; r += PM_THREADS) {
+    const int k = (int)(keys[r] & 0xffffffffu);
     dnn_detection d;
     d.cls = cls_of[k];
     d.score = score_of[k];
@@ -272,12 +589,19 @@ static unsigned long long multi_workspace(int nb, int n_images) {
   return (unsigned long long)n_images * nb * PM_BOX_BYTES;
 }
 
-static int launch_yolo_multi(const dnn_yolo_multi* m, const float* const* pred, int n_images, dnn_detection* dets,
-                             int max_det, int* counts, void* workspace, unsigned long long workspace_bytes,
-                             hipStream_t stream) {
-  const char* who = "dnn_yolo_postprocess_multi";
+static bool nms_mode_ok(int nms_mode, const char* who) {
+  if (nms_mode == DNN_YOLO_NMS_ANY_CLASS || nms_mode == DNN_YOLO_NMS_PER_CLASS) return true;
+  set_error("%s: nms_mode %d: need %d (any class) or %d (per class)", who, nms_mode, DNN_YOLO_NMS_ANY_CLASS,
+            DNN_YOLO_NMS_PER_CLASS);
+  return false;
+}
+
+static int launch_yolo_multi(const char* who, const dnn_yolo_multi* m, const float* const* pred, int n_images,
+                             dnn_detection* dets, int max_det, int* counts, void* workspace,
+                             unsigned long long workspace_bytes, int nms_mode, hipStream_t stream) {
   const int nb = multi_boxes(m, who);
   if (nb < 0) return nb;
+  if (!nms_mode_ok(nms_mode, who)) return -2;
   if (n_images < 0 || max_det < 0 || (n_images > 0 && (!pred || !counts || (max_det > 0 && !dets)))) {
     set_error("%s: bad arguments (n_images=%d max_det=%d)", who, n_images, max_det);
     return -2;
@@ -297,14 +621,64 @@ static int launch_yolo_multi(const dnn_yolo_multi* m, const float* const* pred, 
               workspace, workspace_bytes, n_images, nb, need);
     return -2;
   }
-  hipLaunchKernelGGL(yolo_multi_kernel, dim3(n_images), dim3(PM_THREADS), 0, stream, *m, mp, dets, max_det, counts,
-                     static_cast<char*>(workspace), nb);
+  // with one class the two rules are the same function: the class-agnostic kernel serves both
+  if (nms_mode == DNN_YOLO_NMS_PER_CLASS && m->scale[0].n_classes > 1)
+    hipLaunchKernelGGL(yolo_multi_classwise_kernel, dim3(n_images), dim3(PM_THREADS), 0, stream, *m, mp, dets,
+                       max_det, counts, static_cast<char*>(workspace), nb);
+  else
+    hipLaunchKernelGGL(yolo_multi_kernel, dim3(n_images), dim3(PM_THREADS), 0, stream, *m, mp, dets, max_det, counts,
+                       static_cast<char*>(workspace), nb);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("launch yolo_multi: %s", hipGetErrorString(e));
     return -1;
   }
   return 0;
+}
+
+// Host pointers, synchronous: allocates the scratch, copies in, runs, copies out.
+static int yolo_multi_host(const char* who, const dnn_yolo_multi* m, const float* const* pred, int n_images,
+                           dnn_detection* dets, int max_det, int* counts, int nms_mode) {
+  const int nb = multi_boxes(m, who);
+  if (nb < 0) return nb;
+  if (!nms_mode_ok(nms_mode, who)) return -2;
+  DNN_REQUIRE(n_images >= 0 && max_det >= 0, "%s: bad arguments", who);
+  if (n_images == 0) return 0;
+  DNN_REQUIRE(pred && counts && (max_det == 0 || dets), "%s: NULL pointer", who);
+  const int stride = 5 + m->scale[0].n_classes;
+  size_t pf[DNN_YOLO_MAX_SCALES] = {0}, poff[DNN_YOLO_MAX_SCALES] = {0}, pb = 0;
+  for (int s = 0; s < m->n_scales; ++s) {
+    DNN_REQUIRE(pred[s], "%s: pred[%d] is NULL", who, s);
+    const dnn_yolo_head& h = m->scale[s];
+    pf[s] = (size_t)n_images * h.grid_h * h.grid_w * h.n_anchors * stride * sizeof(float);
+    poff[s] = pb;
+    pb += (pf[s] + 7) & ~(size_t)7;  // keeps every tensor, dets and the workspace 8-byte aligned
+  }
+  const size_t db = (size_t)n_images * max_det * sizeof(dnn_detection);
+  const size_t cb = ((size_t)n_images * sizeof(int) + 7) & ~(size_t)7;
+  const size_t wb = (size_t)multi_workspace(nb, n_images);
+  char* buf = nullptr;
+  DNN_HIP_TRY(hipMalloc(&buf, pb + db + cb + wb));
+  const float* d_pred[DNN_YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
+  dnn_detection* d_dets = reinterpret_cast<dnn_detection*>(buf + pb);
+  int* d_counts = reinterpret_cast<int*>(buf + pb + db);
+  int rc = 0;
+  for (int s = 0; s < m->n_scales && !rc; ++s) {
+    d_pred[s] = reinterpret_cast<const float*>(buf + poff[s]);
+    if (hipMemcpy(buf + poff[s], pred[s], pf[s], hipMemcpyHostToDevice) != hipSuccess) {
+      set_error("%s: copy in failed", who);
+      rc = -1;
+    }
+  }
+  if (!rc) rc = launch_yolo_multi(who, m, d_pred, n_images, d_dets, max_det, d_counts, buf + pb + db + cb, wb, nms_mode,
+                                    nullptr);
+  if (!rc && (hipMemcpy(counts, d_counts, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+              (db && hipMemcpy(dets, d_dets, db, hipMemcpyDeviceToHost) != hipSuccess))) {
+    set_error("%s: copy out failed", who);
+    rc = -1;
+  }
+  (void)hipFree(buf);
+  return rc;
 }
 
 }  // namespace dnnhip
@@ -324,51 +698,37 @@ int dnn_yolo_multi_workspace(const dnn_yolo_multi* m, int n_images, unsigned lon
 int dnn_yolo_postprocess_multi(const dnn_yolo_multi* m, const float* const* pred, int n_images, dnn_detection* dets,
                                int max_det, int* counts, void* workspace, unsigned long long workspace_bytes,
                                void* stream) {
-  return dnnhip::launch_yolo_multi(m, pred, n_images, dets, max_det, counts, workspace, workspace_bytes,
-                                   static_cast<hipStream_t>(stream));
+  return dnnhip::launch_yolo_multi("dnn_yolo_postprocess_multi", m, pred, n_images, dets, max_det, counts, workspace,
+                                   workspace_bytes, DNN_YOLO_NMS_ANY_CLASS, static_cast<hipStream_t>(stream));
 }
 
 int dnn_yolo_postprocess_multi_host(const dnn_yolo_multi* m, const float* const* pred, int n_images,
                                     dnn_detection* dets, int max_det, int* counts) {
-  const char* who = "dnn_yolo_postprocess_multi_host";
+  return dnnhip::yolo_multi_host("dnn_yolo_postprocess_multi_host", m, pred, n_images, dets, max_det, counts,
+                                 DNN_YOLO_NMS_ANY_CLASS);
+}
+
+int dnn_yolo_multi_nms_workspace(const dnn_yolo_multi* m, int n_images, int nms_mode, unsigned long long* bytes) {
+  const char* who = "dnn_yolo_multi_nms_workspace";
   const int nb = dnnhip::multi_boxes(m, who);
   if (nb < 0) return nb;
-  DNN_REQUIRE(n_images >= 0 && max_det >= 0, "dnn_yolo_postprocess_multi_host: bad arguments");
-  if (n_images == 0) return 0;
-  DNN_REQUIRE(pred && counts && (max_det == 0 || dets), "dnn_yolo_postprocess_multi_host: NULL pointer");
-  const int stride = 5 + m->scale[0].n_classes;
-  size_t pf[DNN_YOLO_MAX_SCALES] = {0}, poff[DNN_YOLO_MAX_SCALES] = {0}, pb = 0;
-  for (int s = 0; s < m->n_scales; ++s) {
-    DNN_REQUIRE(pred[s], "dnn_yolo_postprocess_multi_host: pred[%d] is NULL", s);
-    const dnn_yolo_head& h = m->scale[s];
-    pf[s] = (size_t)n_images * h.grid_h * h.grid_w * h.n_anchors * stride * sizeof(float);
-    poff[s] = pb;
-    pb += (pf[s] + 7) & ~(size_t)7;  // keeps every tensor, dets and the workspace 8-byte aligned
-  }
-  const size_t db = (size_t)n_images * max_det * sizeof(dnn_detection);
-  const size_t cb = ((size_t)n_images * sizeof(int) + 7) & ~(size_t)7;
-  const size_t wb = (size_t)dnnhip::multi_workspace(nb, n_images);
-  char* buf = nullptr;
-  DNN_HIP_TRY(hipMalloc(&buf, pb + db + cb + wb));
-  const float* d_pred[DNN_YOLO_MAX_SCALES] = {nullptr, nullptr, nullptr, nullptr};
-  dnn_detection* d_dets = reinterpret_cast<dnn_detection*>(buf + pb);
-  int* d_counts = reinterpret_cast<int*>(buf + pb + db);
-  int rc = 0;
-  for (int s = 0; s < m->n_scales && !rc; ++s) {
-    d_pred[s] = reinterpret_cast<const float*>(buf + poff[s]);
-    if (hipMemcpy(buf + poff[s], pred[s], pf[s], hipMemcpyHostToDevice) != hipSuccess) {
-      dnnhip::set_error("dnn_yolo_postprocess_multi_host: copy in failed");
-      rc = -1;
-    }
-  }
-  if (!rc) rc = dnnhip::launch_yolo_multi(m, d_pred, n_images, d_dets, max_det, d_counts, buf + pb + db + cb, wb, nullptr);
-  if (!rc && (hipMemcpy(counts, d_counts, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
-              (db && hipMemcpy(dets, d_dets, db, hipMemcpyDeviceToHost) != hipSuccess))) {
-    dnnhip::set_error("dnn_yolo_postprocess_multi_host: copy out failed");
-    rc = -1;
-  }
-  (void)hipFree(buf);
-  return rc;
+  if (!dnnhip::nms_mode_ok(nms_mode, who)) return -2;
+  DNN_REQUIRE(n_images >= 0 && bytes, "dnn_yolo_multi_nms_workspace: bad arguments (n_images=%d)", n_images);
+  *bytes = dnnhip::multi_workspace(nb, n_images);  // both kernels: 40 bytes per box
+  return 0;
+}
+
+int dnn_yolo_postprocess_multi_nms(const dnn_yolo_multi* m, const float* const* pred, int n_images,
+                                   dnn_detection* dets, int max_det, int* counts, void* workspace,
+                                   unsigned long long workspace_bytes, int nms_mode, void* stream) {
+  return dnnhip::launch_yolo_multi("dnn_yolo_postprocess_multi_nms", m, pred, n_images, dets, max_det, counts,
+                                   workspace, workspace_bytes, nms_mode, static_cast<hipStream_t>(stream));
+}
+
+int dnn_yolo_postprocess_multi_nms_host(const dnn_yolo_multi* m, const float* const* pred, int n_images,
+                                        dnn_detection* dets, int max_det, int* counts, int nms_mode) {
+  return dnnhip::yolo_multi_host("dnn_yolo_postprocess_multi_nms_host", m, pred, n_images, dets, max_det, counts,
+                                 nms_mode);
 }
 
 }  // extern "C"

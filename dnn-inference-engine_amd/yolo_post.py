@@ -67,6 +67,7 @@ class HeadStruct(ctypes.Structure):
 
 MAX_SCALES, MULTI_MAX_BOXES = 4, 16384  # DNN_YOLO_MAX_SCALES, DNN_YOLO_MULTI_MAX_BOXES
 CLASS_MODES = {"softmax": 0, "logistic": 1}
+NMS_MODES = {"any": 0, "per_class": 1}  # DNN_YOLO_NMS_ANY_CLASS, DNN_YOLO_NMS_PER_CLASS
 
 
 class MultiStruct(ctypes.Structure):
@@ -102,6 +103,12 @@ def _bind(lib):
     lib.dnn_yolo_postprocess_multi.argtypes = [mp, pp, i, vp, i, vp, vp, u64, vp]
     lib.dnn_yolo_postprocess_multi_host.restype = i
     lib.dnn_yolo_postprocess_multi_host.argtypes = [mp, pp, i, vp, i, vp]
+    lib.dnn_yolo_multi_nms_workspace.restype = i
+    lib.dnn_yolo_multi_nms_workspace.argtypes = [mp, i, i, ctypes.POINTER(u64)]
+    lib.dnn_yolo_postprocess_multi_nms.restype = i
+    lib.dnn_yolo_postprocess_multi_nms.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, vp]
+    lib.dnn_yolo_postprocess_multi_nms_host.restype = i
+    lib.dnn_yolo_postprocess_multi_nms_host.argtypes = [mp, pp, i, vp, i, vp, i]
     return lib
 
 
@@ -191,16 +198,21 @@ class MultiHead(object):
     """Several heads whose boxes compete in one sort and one NMS (dnn_yolo_multi): `scales` is a
     sequence of 1..4 heads (YoloHead, Scale, or anything with their fields), scale 0's boxes
     first; class_mode "logistic" (YOLOv3: one sigmoid per class) or "softmax" (YOLOv2).  All
-    scales must agree on classes and thresholds and have at most 16384 boxes together.  Validates
-    like the C side (dnn_yolo_multi_boxes) and raises ValueError."""
+    scales must agree on classes and thresholds and have at most 16384 boxes together.  nms "any"
+    is the reference's class-agnostic greedy NMS; "per_class" is Darknet's / torchvision
+    batched_nms's rule, where a box is suppressed only by a kept box of its own class (one class
+    per box, the arg-max: Darknet's multi-label output is not built).  Validates like the C side
+    (dnn_yolo_multi_boxes) and raises ValueError."""
 
-    def __init__(self, scales, class_mode="logistic"):
+    def __init__(self, scales, class_mode="logistic", nms="any"):
         scales = list(scales)
         if not 1 <= len(scales) <= MAX_SCALES:
             raise ValueError(f"{len(scales)} scales: need 1..{MAX_SCALES}")
         if class_mode not in CLASS_MODES:
             raise ValueError(f"class_mode {class_mode!r}: need one of {sorted(CLASS_MODES)}")
-        self.class_mode = class_mode
+        if nms not in NMS_MODES:
+            raise ValueError(f"nms {nms!r}: need one of {sorted(NMS_MODES)}")
+        self.class_mode, self.nms = class_mode, nms
         self.scales = []
         for s in scales:
             anchors = tuple(float(a) for a in s.anchors)
@@ -242,7 +254,7 @@ class MultiHead(object):
             raise ValueError(f"dnn_yolo_multi_boxes: {n}: {dnn_hip.last_error()}")
 
     @classmethod
-    def yolov3(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3):
+    def yolov3(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3, nms="any"):
         """YOLOv3's three heads for an in_h x in_w input (multiples of 32): strides 32, 16, 8 with
         the public anchor table, the pixel anchors divided by the stride (exact in fp32: every
         stride is a power of two), logistic class scores."""
@@ -251,12 +263,12 @@ class MultiHead(object):
         n_classes = classes if isinstance(classes, (int, np.integer)) else len(classes)
         scales = [Scale(in_h // st, in_w // st, 3, int(n_classes), tuple(a / st for a in px), float(st), score_thr,
                         iou_thr) for st, px in YOLOV3_ANCHORS]
-        head = cls(scales, "logistic")
+        head = cls(scales, "logistic", nms)
         head.names = None if isinstance(classes, (int, np.integer)) else tuple(classes)
         return head
 
     @classmethod
-    def yolov3_tiny(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3):
+    def yolov3_tiny(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3, nms="any"):
         """YOLOv3-tiny's two heads for an in_h x in_w input (multiples of 32): strides 32 and 16
         with the public anchor table (the stride-16 head takes the three smallest anchors, the
         official cfg's mask 0,1,2), the pixel anchors divided by the stride (exact in fp32),
@@ -266,25 +278,27 @@ class MultiHead(object):
         n_classes = classes if isinstance(classes, (int, np.integer)) else len(classes)
         scales = [Scale(in_h // st, in_w // st, 3, int(n_classes), tuple(a / st for a in px), float(st), score_thr,
                         iou_thr) for st, px in YOLOV3_TINY_ANCHORS]
-        head = cls(scales, "logistic")
+        head = cls(scales, "logistic", nms)
         head.names = None if isinstance(classes, (int, np.integer)) else tuple(classes)
         return head
 
     def workspace_bytes(self, n_images):
         b = ctypes.c_ulonglong(0)
-        dnn_hip._check(_lib.dnn_yolo_multi_workspace(ctypes.byref(self.c), n_images, ctypes.byref(b)),
-                       "dnn_yolo_multi_workspace")
+        dnn_hip._check(_lib.dnn_yolo_multi_nms_workspace(ctypes.byref(self.c), n_images, NMS_MODES[self.nms],
+                                                         ctypes.byref(b)), "dnn_yolo_multi_nms_workspace")
         return int(b.value)
 
     def __repr__(self):
         grids = ", ".join(f"{s.grid_h}x{s.grid_w}x{s.n_anchors}" for s in self.scales)
+        nms = "" if self.nms == "any" else f", NMS {self.nms}"
         return (f"MultiHead({grids}; {self.n_classes} classes, {self.class_mode}, score > {self.score_thr:g}, "
-                f"IoU > {self.iou_thr:g})")
+                f"IoU > {self.iou_thr:g}{nms})")
 
 
 def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
     """preds: one fp32 host array per scale of `head` (a MultiHead), [B, *head.pred_shapes[s]] ->
-    per image the rows detect_batch returns, from one sort and one NMS over all scales."""
+    per image the rows detect_batch returns, from one sort and one NMS over all scales (the NMS
+    rule is head.nms)."""
     if len(preds) != len(head.scales):
         raise ValueError(f"{len(preds)} prediction tensors for {len(head.scales)} scales")
     ps = [np.ascontiguousarray(p, dtype=np.float32) for p in preds]
@@ -298,8 +312,9 @@ def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
     dets = np.zeros((n, max_det), DETECTION_DTYPE)
     counts = np.zeros(n, np.int32)
     ptrs = (ctypes.c_void_p * len(ps))(*[p.ctypes.data for p in ps])
-    dnn_hip._check(_lib.dnn_yolo_postprocess_multi_host(ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det,
-                                                        counts.ctypes.data), "dnn_yolo_postprocess_multi_host")
+    dnn_hip._check(_lib.dnn_yolo_postprocess_multi_nms_host(ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det,
+                                                            counts.ctypes.data, NMS_MODES[head.nms]),
+                   "dnn_yolo_postprocess_multi_nms_host")
     return _rows(dets, counts, max_det, raise_errors)
 
 
@@ -420,9 +435,9 @@ class DetectionBuffers(object):
 
 class MultiDetectionBuffers(DetectionBuffers):
     """DetectionBuffers for a MultiHead: `run(pred_ptrs, n, stream)` takes one device pointer per
-    scale and goes through dnn_yolo_postprocess_multi; dets, counts, `pack` and `to_rows` are the
-    base class's (max_det defaults to head.boxes), so dnn_yolo_pack_detections and
-    dist.gather_detections apply unchanged."""
+    scale and goes through dnn_yolo_postprocess_multi_nms with head.nms; dets, counts, `pack` and
+    `to_rows` are the base class's (max_det defaults to head.boxes), so dnn_yolo_pack_detections
+    and dist.gather_detections apply unchanged."""
 
     def __init__(self, n, device, head, max_det=None):
         import torch
@@ -440,6 +455,7 @@ class MultiDetectionBuffers(DetectionBuffers):
         if len(pred_ptrs) != len(self.head.scales):
             raise ValueError(f"{len(pred_ptrs)} prediction pointers for {len(self.head.scales)} scales")
         ptrs = (ctypes.c_void_p * len(pred_ptrs))(*[int(p) for p in pred_ptrs])
-        dnn_hip._check(_lib.dnn_yolo_postprocess_multi(
+        dnn_hip._check(_lib.dnn_yolo_postprocess_multi_nms(
             ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
-            self.workspace.data_ptr(), self.workspace.numel(), stream), "dnn_yolo_postprocess_multi")
+            self.workspace.data_ptr(), self.workspace.numel(), NMS_MODES[self.head.nms], stream),
+            "dnn_yolo_postprocess_multi_nms")

@@ -33,8 +33,11 @@ Two differences from the Darknet original:
   * the stride-2 convs use the engine's SAME padding (TensorFlow's: on an even input one row and
     one column of zeros at the bottom / right only), Darknet pads 1 on every side, so weights
     converted from a Darknet checkpoint compute something else at those five layers;
-  * the NMS is the reference's class-agnostic one over all scales (include/dnn_hip_post.h);
-    Darknet's runs per class.
+  * the default NMS is the reference's class-agnostic one over all scales
+    (include/dnn_hip_post.h).  Darknet's per-class rule is
+    `head=yolo_post.MultiHead.yolov3(h, w, classes, nms="per_class")`; a box still carries one
+    class, the arg-max, where Darknet also emits one detection per class above the threshold
+    (multi-label), which is not built.
 """
 import numpy as np
 

@@ -115,9 +115,20 @@ int dnn_yolo_postprocess_head_host(const dnn_yolo_head* head, const float* pred,
  * of the largest computed p (the rounded values are compared, not the logits) and the score is
  * conf * p[class], one fp32 multiply.  Candidates (score > score_thr) of all scales go through
  * one sort (score descending, ties: lower global index) and one greedy NMS with the integer-area
- * IoU, as above.  This is the reference's NMS, which is class-agnostic: a box suppresses an
- * overlapping box of any class.  Darknet's own YOLOv3 NMS runs per class, so it keeps
- * overlapping boxes of different classes that this one drops.
+ * IoU, as above.
+ *
+ * NMS rule (nms_mode of the *_nms entries; the entries without it use DNN_YOLO_NMS_ANY_CLASS):
+ *   DNN_YOLO_NMS_ANY_CLASS  the reference's: a candidate is kept unless an earlier kept box of ANY
+ *     class has IoU > iou_thr with it.  A person box suppresses the bicycle box it overlaps.
+ *   DNN_YOLO_NMS_PER_CLASS  Darknet's do_nms_sort / torchvision's batched_nms rule: candidates are
+ *     visited in the same order, and a candidate is kept unless an earlier kept box OF ITS OWN
+ *     CLASS has IoU > iou_thr with it.  The evaluated IoUs are those of a candidate against every
+ *     kept box of its class (all of them, no early exit), so an image can carry -2 under one rule
+ *     and be clean under the other, in either direction.  The rows are the kept boxes in the
+ *     global sorted order (score descending, ties: lower global index), which is not class-major.
+ *     With n_classes == 1 the two rules are the same function.
+ *   A box still has ONE class, the arg-max.  Darknet additionally emits one detection per class
+ *   above the threshold for each box (multi-label); that is not built.
  * counts[i]: as above, -1 when any box of any scale (candidate or not) has a corner that is not
  * finite or out of range, -2 when an evaluated IoU denominator is zero; such an image does not
  * touch the other images' results.
@@ -155,6 +166,23 @@ int dnn_yolo_postprocess_multi(const dnn_yolo_multi* multi, const float* const* 
  * runs, copies out. */
 int dnn_yolo_postprocess_multi_host(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
                                     dnn_detection* dets, int max_det, int* counts);
+
+/* The same three entries with the NMS rule as an argument (see "NMS rule" above).  nms_mode 0 goes
+ * through dnn_yolo_postprocess_multi's launcher: the same dets, counts and workspace contents, byte
+ * for byte, and the same workspace size.  Any other value than these two returns -2 ("nms_mode" in
+ * dnn_last_error()) before anything is launched; all other checks are those of the entries above.
+ * Both rules need the same workspace, 40 bytes per box. */
+#define DNN_YOLO_NMS_ANY_CLASS 0 /* the reference's */
+#define DNN_YOLO_NMS_PER_CLASS 1
+
+int dnn_yolo_multi_nms_workspace(const dnn_yolo_multi* multi, int n_images, int nms_mode, unsigned long long* bytes);
+
+int dnn_yolo_postprocess_multi_nms(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
+                                   dnn_detection* dets, int max_det, int* counts, void* workspace,
+                                   unsigned long long workspace_bytes, int nms_mode, void* stream);
+
+int dnn_yolo_postprocess_multi_nms_host(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
+                                        dnn_detection* dets, int max_det, int* counts, int nms_mode);
 
 #pragma GCC visibility pop
 
