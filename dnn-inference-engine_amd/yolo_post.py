@@ -68,6 +68,8 @@ class HeadStruct(ctypes.Structure):
 MAX_SCALES, MULTI_MAX_BOXES = 4, 16384  # DNN_YOLO_MAX_SCALES, DNN_YOLO_MULTI_MAX_BOXES
 CLASS_MODES = {"softmax": 0, "logistic": 1}
 NMS_MODES = {"any": 0, "per_class": 1}  # DNN_YOLO_NMS_ANY_CLASS, DNN_YOLO_NMS_PER_CLASS
+LABEL_MODES = {"argmax": 0, "multi": 1}  # DNN_YOLO_LABELS_ARGMAX, DNN_YOLO_LABELS_MULTI
+MULTI_MAX_CANDIDATES = 16384  # DNN_YOLO_MULTI_MAX_CANDIDATES: (box, class) pairs above the threshold
 
 
 class MultiStruct(ctypes.Structure):
@@ -109,6 +111,12 @@ def _bind(lib):
     lib.dnn_yolo_postprocess_multi_nms.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, vp]
     lib.dnn_yolo_postprocess_multi_nms_host.restype = i
     lib.dnn_yolo_postprocess_multi_nms_host.argtypes = [mp, pp, i, vp, i, vp, i]
+    lib.dnn_yolo_multi_labels_workspace.restype = i
+    lib.dnn_yolo_multi_labels_workspace.argtypes = [mp, i, i, ctypes.POINTER(u64)]
+    lib.dnn_yolo_postprocess_multi_labels.restype = i
+    lib.dnn_yolo_postprocess_multi_labels.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, vp]
+    lib.dnn_yolo_postprocess_multi_labels_host.restype = i
+    lib.dnn_yolo_postprocess_multi_labels_host.argtypes = [mp, pp, i, vp, i, vp, i]
     return lib
 
 
@@ -116,7 +124,8 @@ _lib = _bind(dnn_hip.mylib)
 
 
 ERRORS = {-1: "a box corner is not finite or out of int64 range (the reference's int() raises there)",
-          -2: "an IoU denominator is zero (the reference raises ZeroDivisionError)"}
+          -2: "an IoU denominator is zero (the reference raises ZeroDivisionError)",
+          -3: f"more than {MULTI_MAX_CANDIDATES} multi-label candidates (box, class) above the score threshold"}
 
 
 class YoloHead(object):
@@ -200,11 +209,14 @@ class MultiHead(object):
     first; class_mode "logistic" (YOLOv3: one sigmoid per class) or "softmax" (YOLOv2).  All
     scales must agree on classes and thresholds and have at most 16384 boxes together.  nms "any"
     is the reference's class-agnostic greedy NMS; "per_class" is Darknet's / torchvision
-    batched_nms's rule, where a box is suppressed only by a kept box of its own class (one class
-    per box, the arg-max: Darknet's multi-label output is not built).  Validates like the C side
-    (dnn_yolo_multi_boxes) and raises ValueError."""
+    batched_nms's rule, where a box is suppressed only by a kept box of its own class.  labels
+    "argmax" gives a box one class, the arg-max; "multi" is Darknet's multi-label output, one
+    detection per class whose score conf * p[class] is above the threshold, so an image can have
+    more rows than boxes (`max_det`; at most 16384 candidates, else the image's code is -3).  It
+    needs nms="per_class": under the class-agnostic rule a box's second label is always suppressed
+    by its first.  Validates like the C side (dnn_yolo_multi_boxes) and raises ValueError."""
 
-    def __init__(self, scales, class_mode="logistic", nms="any"):
+    def __init__(self, scales, class_mode="logistic", nms="any", labels="argmax"):
         scales = list(scales)
         if not 1 <= len(scales) <= MAX_SCALES:
             raise ValueError(f"{len(scales)} scales: need 1..{MAX_SCALES}")
@@ -212,7 +224,12 @@ class MultiHead(object):
             raise ValueError(f"class_mode {class_mode!r}: need one of {sorted(CLASS_MODES)}")
         if nms not in NMS_MODES:
             raise ValueError(f"nms {nms!r}: need one of {sorted(NMS_MODES)}")
-        self.class_mode, self.nms = class_mode, nms
+        if not isinstance(labels, str) or labels not in LABEL_MODES:
+            raise ValueError(f"labels {labels!r}: need one of {sorted(LABEL_MODES)}")
+        if labels == "multi" and nms != "per_class":
+            raise ValueError('labels "multi" needs nms "per_class": under the class-agnostic rule a box\'s second '
+                             "label is always suppressed by its first")
+        self.class_mode, self.nms, self.labels = class_mode, nms, labels
         self.scales = []
         for s in scales:
             anchors = tuple(float(a) for a in s.anchors)
@@ -241,6 +258,8 @@ class MultiHead(object):
         self.boxes = sum(self.scale_boxes)
         if self.boxes > MULTI_MAX_BOXES:
             raise ValueError(f"{self.boxes} boxes over {len(self.scales)} scales: need <= {MULTI_MAX_BOXES}")
+        # the most rows an image can have: the default row capacity of detect_batch_multi and the buffers
+        self.max_det = self.boxes if labels == "argmax" else min(self.boxes * self.n_classes, MULTI_MAX_CANDIDATES)
         self.n_out = [s.n_anchors * (5 + s.n_classes) for s in self.scales]
         self.pred_shapes = [(s.grid_h, s.grid_w, n) for s, n in zip(self.scales, self.n_out)]
         self.pred_floats = [h * w * c for h, w, c in self.pred_shapes]
@@ -254,7 +273,7 @@ class MultiHead(object):
             raise ValueError(f"dnn_yolo_multi_boxes: {n}: {dnn_hip.last_error()}")
 
     @classmethod
-    def yolov3(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3, nms="any"):
+    def yolov3(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3, nms="any", labels="argmax"):
         """YOLOv3's three heads for an in_h x in_w input (multiples of 32): strides 32, 16, 8 with
         the public anchor table, the pixel anchors divided by the stride (exact in fp32: every
         stride is a power of two), logistic class scores."""
@@ -263,12 +282,12 @@ class MultiHead(object):
         n_classes = classes if isinstance(classes, (int, np.integer)) else len(classes)
         scales = [Scale(in_h // st, in_w // st, 3, int(n_classes), tuple(a / st for a in px), float(st), score_thr,
                         iou_thr) for st, px in YOLOV3_ANCHORS]
-        head = cls(scales, "logistic", nms)
+        head = cls(scales, "logistic", nms, labels)
         head.names = None if isinstance(classes, (int, np.integer)) else tuple(classes)
         return head
 
     @classmethod
-    def yolov3_tiny(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3, nms="any"):
+    def yolov3_tiny(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3, nms="any", labels="argmax"):
         """YOLOv3-tiny's two heads for an in_h x in_w input (multiples of 32): strides 32 and 16
         with the public anchor table (the stride-16 head takes the three smallest anchors, the
         official cfg's mask 0,1,2), the pixel anchors divided by the stride (exact in fp32),
@@ -278,12 +297,17 @@ class MultiHead(object):
         n_classes = classes if isinstance(classes, (int, np.integer)) else len(classes)
         scales = [Scale(in_h // st, in_w // st, 3, int(n_classes), tuple(a / st for a in px), float(st), score_thr,
                         iou_thr) for st, px in YOLOV3_TINY_ANCHORS]
-        head = cls(scales, "logistic", nms)
+        head = cls(scales, "logistic", nms, labels)
         head.names = None if isinstance(classes, (int, np.integer)) else tuple(classes)
         return head
 
     def workspace_bytes(self, n_images):
         b = ctypes.c_ulonglong(0)
+        if self.labels == "multi":
+            dnn_hip._check(_lib.dnn_yolo_multi_labels_workspace(ctypes.byref(self.c), n_images,
+                                                                LABEL_MODES[self.labels], ctypes.byref(b)),
+                           "dnn_yolo_multi_labels_workspace")
+            return int(b.value)
         dnn_hip._check(_lib.dnn_yolo_multi_nms_workspace(ctypes.byref(self.c), n_images, NMS_MODES[self.nms],
                                                          ctypes.byref(b)), "dnn_yolo_multi_nms_workspace")
         return int(b.value)
@@ -291,14 +315,15 @@ class MultiHead(object):
     def __repr__(self):
         grids = ", ".join(f"{s.grid_h}x{s.grid_w}x{s.n_anchors}" for s in self.scales)
         nms = "" if self.nms == "any" else f", NMS {self.nms}"
+        labels = "" if self.labels == "argmax" else f", labels {self.labels}"
         return (f"MultiHead({grids}; {self.n_classes} classes, {self.class_mode}, score > {self.score_thr:g}, "
-                f"IoU > {self.iou_thr:g}{nms})")
+                f"IoU > {self.iou_thr:g}{nms}{labels})")
 
 
 def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
     """preds: one fp32 host array per scale of `head` (a MultiHead), [B, *head.pred_shapes[s]] ->
     per image the rows detect_batch returns, from one sort and one NMS over all scales (the NMS
-    rule is head.nms)."""
+    rule is head.nms, the labels of a box head.labels; max_det defaults to head.max_det)."""
     if len(preds) != len(head.scales):
         raise ValueError(f"{len(preds)} prediction tensors for {len(head.scales)} scales")
     ps = [np.ascontiguousarray(p, dtype=np.float32) for p in preds]
@@ -308,10 +333,15 @@ def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
     if len(ns) != 1:
         raise ValueError(f"the scales hold different numbers of images: {sorted(ns)}")
     n = ns.pop()
-    max_det = head.boxes if max_det is None else max_det
+    max_det = head.max_det if max_det is None else max_det
     dets = np.zeros((n, max_det), DETECTION_DTYPE)
     counts = np.zeros(n, np.int32)
     ptrs = (ctypes.c_void_p * len(ps))(*[p.ctypes.data for p in ps])
+    if head.labels == "multi":
+        dnn_hip._check(_lib.dnn_yolo_postprocess_multi_labels_host(
+            ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det, counts.ctypes.data, LABEL_MODES[head.labels]),
+            "dnn_yolo_postprocess_multi_labels_host")
+        return _rows(dets, counts, max_det, raise_errors)
     dnn_hip._check(_lib.dnn_yolo_postprocess_multi_nms_host(ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det,
                                                             counts.ctypes.data, NMS_MODES[head.nms]),
                    "dnn_yolo_postprocess_multi_nms_host")
@@ -435,13 +465,15 @@ class DetectionBuffers(object):
 
 class MultiDetectionBuffers(DetectionBuffers):
     """DetectionBuffers for a MultiHead: `run(pred_ptrs, n, stream)` takes one device pointer per
-    scale and goes through dnn_yolo_postprocess_multi_nms with head.nms; dets, counts, `pack` and
-    `to_rows` are the base class's (max_det defaults to head.boxes), so dnn_yolo_pack_detections
-    and dist.gather_detections apply unchanged."""
+    scale and goes through dnn_yolo_postprocess_multi_nms with head.nms, or with head.labels
+    "multi" through dnn_yolo_postprocess_multi_labels; dets, counts, `pack` and `to_rows` are the
+    base class's (max_det defaults to head.max_det: head.boxes, or with "multi" the most
+    candidates an image can have), so dnn_yolo_pack_detections and dist.gather_detections apply
+    unchanged."""
 
     def __init__(self, n, device, head, max_det=None):
         import torch
-        max_det = head.boxes if max_det is None else max_det
+        max_det = head.max_det if max_det is None else max_det
         self.n, self.max_det, self.head = n, max_det, head
         self.workspace = torch.zeros(head.workspace_bytes(n), dtype=torch.uint8, device=device)
         self.dets = torch.zeros((n, max_det, DETECTION_DTYPE.itemsize), dtype=torch.uint8, device=device)
@@ -455,6 +487,12 @@ class MultiDetectionBuffers(DetectionBuffers):
         if len(pred_ptrs) != len(self.head.scales):
             raise ValueError(f"{len(pred_ptrs)} prediction pointers for {len(self.head.scales)} scales")
         ptrs = (ctypes.c_void_p * len(pred_ptrs))(*[int(p) for p in pred_ptrs])
+        if self.head.labels == "multi":
+            dnn_hip._check(_lib.dnn_yolo_postprocess_multi_labels(
+                ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
+                self.workspace.data_ptr(), self.workspace.numel(), LABEL_MODES[self.head.labels], stream),
+                "dnn_yolo_postprocess_multi_labels")
+            return
         dnn_hip._check(_lib.dnn_yolo_postprocess_multi_nms(
             ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
             self.workspace.data_ptr(), self.workspace.numel(), NMS_MODES[self.head.nms], stream),

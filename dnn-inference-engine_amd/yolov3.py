@@ -35,9 +35,10 @@ Two differences from the Darknet original:
     converted from a Darknet checkpoint compute something else at those five layers;
   * the default NMS is the reference's class-agnostic one over all scales
     (include/dnn_hip_post.h).  Darknet's per-class rule is
-    `head=yolo_post.MultiHead.yolov3(h, w, classes, nms="per_class")`; a box still carries one
-    class, the arg-max, where Darknet also emits one detection per class above the threshold
-    (multi-label), which is not built.
+    `head=yolo_post.MultiHead.yolov3(h, w, classes, nms="per_class")`, and with
+    `labels="multi"` beside it a box gives one detection per class above the threshold, as
+    Darknet's does (the default is one class per box, the arg-max).  The detection buffers are
+    sized by `head.max_det`, which with "multi" is more than the boxes.
 """
 import numpy as np
 

@@ -23,9 +23,9 @@ and detect are yolov3.YOLO_V3's; the decode is yolo_post.MultiHead.yolov3.
 Out of scope, as for yolov3.py:
 
   * Darknet .cfg / .weights import: weights arrive as yolo_weights layer dicts;
-  * Darknet's multi-label output: a box carries one class, the arg-max.  The default NMS is the
-    reference's class-agnostic one over all scales; Darknet's per-class rule is
-    `head=yolo_post.MultiHead.yolov3(h, w, classes, nms="per_class")`;
+  * the defaults are not Darknet's: the NMS is the reference's class-agnostic one over all scales
+    and a box carries one class, the arg-max.  Darknet's per-class rule with its multi-label
+    output is `head=yolo_post.MultiHead.yolov3(h, w, classes, nms="per_class", labels="multi")`;
   * the stride-2 convs use the engine's SAME padding (bottom / right on an even input), Darknet
     pads 1 on every side, so a converted Darknet checkpoint computes something else at those five
     layers.  The SPP pools themselves are Darknet's: stride 1 with size // 2 on every side.

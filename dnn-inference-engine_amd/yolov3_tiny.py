@@ -27,10 +27,11 @@ a multiple of 32, and the stride-1 pool pads bottom / right only, as Darknet's d
 Out of scope:
 
   * Darknet .cfg / .weights import: weights arrive as yolo_weights layer dicts;
-  * Darknet's multi-label output (one detection per class above the threshold for each box): a
-    box carries one class, the arg-max.  The default NMS is the reference's class-agnostic one
-    over both scales (include/dnn_hip_post.h); Darknet's per-class rule is
-    `head=yolo_post.MultiHead.yolov3_tiny(h, w, classes, nms="per_class")`.
+  * the defaults are not Darknet's: the NMS is the reference's class-agnostic one over both
+    scales (include/dnn_hip_post.h) and a box carries one class, the arg-max.  Darknet's
+    per-class rule with its multi-label output (one detection per class above the threshold for
+    each box) is `head=yolo_post.MultiHead.yolov3_tiny(h, w, classes, nms="per_class",
+    labels="multi")`.
 """
 import darknet53
 import dnn_hip

@@ -127,11 +127,28 @@ int dnn_yolo_postprocess_head_host(const dnn_yolo_head* head, const float* pred,
  *     and be clean under the other, in either direction.  The rows are the kept boxes in the
  *     global sorted order (score descending, ties: lower global index), which is not class-major.
  *     With n_classes == 1 the two rules are the same function.
- *   A box still has ONE class, the arg-max.  Darknet additionally emits one detection per class
- *   above the threshold for each box (multi-label); that is not built.
+ *   In these entries a box has ONE class, the arg-max.
+ *
+ * Labels (labels_mode of the *_labels entries, whose NMS rule is DNN_YOLO_NMS_PER_CLASS; defined for
+ * class_mode 0 and 1):
+ *   DNN_YOLO_LABELS_ARGMAX  one class per box, as above.
+ *   DNN_YOLO_LABELS_MULTI   Darknet's multi-label output: every class c of a box has the score
+ *     s[c] = conf * p[c], one fp32 multiply, with p[c] the per-class value above (the sigmoid of
+ *     logit[c], or the softmax quotient with its sum order), and (box, c) is a candidate iff
+ *     s[c] > score_thr.  Darknet's extra gate objectness > thresh is implied: p[c] <= 1 and fp32
+ *     multiplication is monotone, so s[c] <= conf.  Boxes, conf and the global box index are those
+ *     above.  Candidates are ordered by (score descending, global box index ascending, class
+ *     ascending) and go through the per-class NMS: a candidate is kept unless an earlier kept
+ *     candidate of its own class has IoU > iou_thr with it, every kept box of that class evaluated.
+ *     The rows are the kept candidates in that order: cls the candidate's class, score its s[c], the
+ *     corners the box's.  One box gives up to n_classes rows, so an image can have more rows than
+ *     boxes, but at most DNN_YOLO_MULTI_MAX_CANDIDATES candidates (their sort keys live in LDS):
+ *     an image with more gets counts[i] = -3 and no rows.  With n_classes == 1 the two label modes
+ *     are the same function.
  * counts[i]: as above, -1 when any box of any scale (candidate or not) has a corner that is not
- * finite or out of range, -2 when an evaluated IoU denominator is zero; such an image does not
- * touch the other images' results.
+ * finite or out of range, else -3 when the image has too many multi-label candidates (no NMS runs),
+ * else -2 when an evaluated IoU denominator is zero; such an image does not touch the other images'
+ * results.
  *
  * Every scale must be a valid dnn_yolo_head, except that its own boxes may exceed
  * DNN_YOLO_MAX_BOXES: only the sum over scales is bounded, by DNN_YOLO_MULTI_MAX_BOXES.  All
@@ -183,6 +200,27 @@ int dnn_yolo_postprocess_multi_nms(const dnn_yolo_multi* multi, const float* con
 
 int dnn_yolo_postprocess_multi_nms_host(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
                                         dnn_detection* dets, int max_det, int* counts, int nms_mode);
+
+/* The same three entries for the per-class NMS rule with the label mode as an argument (see
+ * "Labels" above).  labels_mode 0 goes through the *_nms launcher with DNN_YOLO_NMS_PER_CLASS: the
+ * same dets, counts and workspace contents, byte for byte, and the same workspace size.  Any other
+ * value than these two returns -2 ("labels_mode" in dnn_last_error()) before anything is launched;
+ * all other checks are those of the entries above.  Both modes need the same workspace, 40 bytes
+ * per box; a multi-label image can have up to min(boxes * n_classes,
+ * DNN_YOLO_MULTI_MAX_CANDIDATES) rows, which is what max_det should allow for. */
+#define DNN_YOLO_LABELS_ARGMAX 0
+#define DNN_YOLO_LABELS_MULTI 1
+#define DNN_YOLO_MULTI_MAX_CANDIDATES 16384 /* (box, class) pairs above the threshold, per image */
+
+int dnn_yolo_multi_labels_workspace(const dnn_yolo_multi* multi, int n_images, int labels_mode,
+                                    unsigned long long* bytes);
+
+int dnn_yolo_postprocess_multi_labels(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
+                                      dnn_detection* dets, int max_det, int* counts, void* workspace,
+                                      unsigned long long workspace_bytes, int labels_mode, void* stream);
+
+int dnn_yolo_postprocess_multi_labels_host(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
+                                           dnn_detection* dets, int max_det, int* counts, int labels_mode);
 
 #pragma GCC visibility pop
 
