@@ -136,6 +136,7 @@ struct PlanLayer {
   int K = 0, Kpad = 0, Npad = 0, cfg = 0, epi_flags = 0;
   int splits = 1;  // split-K partial count (> 1: GEMM writes partials, a reduce kernel finishes)
   bool pool = false;  // a 2x2/stride-2 max pool fused into this conv
+  bool xpad = false;  // explicit pads (dnn_plan_add_conv_padded): shown by dnn_plan_describe
   bool x3lat = false;  // MODE_X3 on the small-M kernel (latency plans: launch_conv_x3_lat)
   bool x3k = false;    // MODE_X3 with the K split inside the workgroup (latency plans: launch_conv_x3_ktile)
   bool pool1 = false;  // x3k / x3img: a 2x2/stride-1 SAME pool fused (same output frame)
@@ -534,14 +535,25 @@ int dnn_plan_set_latency_mode(dnn_plan* p, int on) {
   return 0;
 }
 
-int dnn_plan_add_conv(dnn_plan* p, int kh, int kw, int od, int stride_h, int stride_w, int padding,
-                      const float* kernel, const float* biases, const float* mean, const float* var,
-                      const float* gamma, float eps, int leaky) {
-  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_conv: plan is NULL or finalized");
-  DNN_REQUIRE(kh > 0 && kw > 0 && od > 0 && stride_h > 0 && stride_w > 0, "dnn_plan_add_conv: bad args");
-  DNN_REQUIRE((mean == nullptr) == (var == nullptr) && (var == nullptr) == (gamma == nullptr),
-              "dnn_plan_add_conv: mean/var/gamma must be all set or all NULL");
-  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_plan_add_conv: leaky must be 0, 1 or 2");
+}  // extern "C"
+
+// What a conv entry's epilogue is made of: dnn_plan_add_conv's BiasAdd / BatchNorm, or
+// dnn_plan_add_conv_padded's per-channel scale / shift (EPI_BN_AB with alpha = scale, beta = -shift)
+struct ConvEpilogueSpec {
+  const float *biases = nullptr, *mean = nullptr, *var = nullptr, *gamma = nullptr;
+  float eps = 0.f;
+  const float *scale = nullptr, *shift = nullptr;
+  int leaky = 0;
+};
+
+// The body both conv entries share: mode selection, config, epilogue parameters.  The caller has
+// checked its arguments and worked out the geometry (OH, OW and the front pads pt, pl);
+// `xpad`: the pads were given explicitly (dnn_plan_add_conv_padded), for dnn_plan_describe.
+static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int stride_w, int OH, int pt, int OW,
+                          int pl, bool xpad, const float* kernel, const ConvEpilogueSpec& ep) {
+  const float *biases = ep.biases, *mean = ep.mean, *var = ep.var, *gamma = ep.gamma;
+  const float eps = ep.eps;
+  const int leaky = ep.leaky;
   PlanLayer L;
   L.type = 0;
   L.H = p->cur_h;
@@ -551,10 +563,11 @@ int dnn_plan_add_conv(dnn_plan* p, int kh, int kw, int od, int stride_h, int str
   L.kw = kw;
   L.sh = stride_h;
   L.sw = stride_w;
-  out_pads(L.H, kh, stride_h, padding, &L.OH, &L.pt);
-  out_pads(L.W, kw, stride_w, padding, &L.OW, &L.pl);
-  DNN_REQUIRE(L.OH > 0 && L.OW > 0, "dnn_plan_add_conv: empty output (%dx%d input, %dx%d kernel)", L.H, L.W, kh,
-              kw);
+  L.OH = OH;
+  L.OW = OW;
+  L.pt = pt;
+  L.pl = pl;
+  L.xpad = xpad;
   L.OC = od;
   L.K = kh * kw * L.C;
   const bool one_by_one = kh == 1 && kw == 1 && stride_h == 1 && stride_w == 1 && L.pt == 0 && L.pl == 0 &&
@@ -653,6 +666,9 @@ int dnn_plan_add_conv(dnn_plan* p, int kh, int kw, int od, int stride_h, int str
   const bool fold16 = p->fp16 && mean;
   if (fold16)
     L.epi_flags = EPI_BN_AB | ((L.epi_flags & (EPI_LEAKY_F64 | EPI_LEAKY_F32)) ? EPI_LEAKY_F32 : 0);
+  // the affine entry (fp32 plans): v * scale + shift as EPI_BN_AB's v * alpha - beta with
+  // beta = -shift (the negation is exact, so both round alike)
+  if (ep.scale) L.epi_flags |= EPI_BN_AB;
   if (kernel) {
     L.have_host = true;
     L.w.assign(kernel, kernel + (size_t)L.K * od);
@@ -678,6 +694,10 @@ int dnn_plan_add_conv(dnn_plan* p, int kh, int kw, int od, int stride_h, int str
         L.bias[d] = 0.f;
         L.gamma[d] = 1.f;
       }
+      if (ep.scale) {  // EPI_BN_AB: mean slot = alpha, sq slot = beta
+        L.mean[d] = ep.scale[d];
+        L.sq[d] = -ep.shift[d];
+      }
     }
   }
   current_leaves(p);
@@ -687,6 +707,52 @@ int dnn_plan_add_conv(dnn_plan* p, int kh, int kw, int od, int stride_h, int str
   p->cur_c = od;
   p->cur_src = -1;
   return 0;
+}
+
+extern "C" {
+
+int dnn_plan_add_conv(dnn_plan* p, int kh, int kw, int od, int stride_h, int stride_w, int padding,
+                      const float* kernel, const float* biases, const float* mean, const float* var,
+                      const float* gamma, float eps, int leaky) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_conv: plan is NULL or finalized");
+  DNN_REQUIRE(kh > 0 && kw > 0 && od > 0 && stride_h > 0 && stride_w > 0, "dnn_plan_add_conv: bad args");
+  DNN_REQUIRE((mean == nullptr) == (var == nullptr) && (var == nullptr) == (gamma == nullptr),
+              "dnn_plan_add_conv: mean/var/gamma must be all set or all NULL");
+  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_plan_add_conv: leaky must be 0, 1 or 2");
+  int OH, OW, pt, pl;
+  out_pads(p->cur_h, kh, stride_h, padding, &OH, &pt);
+  out_pads(p->cur_w, kw, stride_w, padding, &OW, &pl);
+  DNN_REQUIRE(OH > 0 && OW > 0, "dnn_plan_add_conv: empty output (%dx%d input, %dx%d kernel)", p->cur_h, p->cur_w, kh,
+              kw);
+  ConvEpilogueSpec ep;
+  ep.biases = biases;
+  ep.mean = mean;
+  ep.var = var;
+  ep.gamma = gamma;
+  ep.eps = eps;
+  ep.leaky = leaky;
+  return add_conv_layer(p, kh, kw, od, stride_h, stride_w, OH, pt, OW, pl, false, kernel, ep);
+}
+
+int dnn_plan_add_conv_padded(dnn_plan* p, int kh, int kw, int od, int stride_h, int stride_w, int pad_h, int pad_w,
+                             const float* kernel, const float* scale, const float* shift, int leaky) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_conv_padded: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_conv_padded: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(kh > 0 && kw > 0 && od > 0 && stride_h > 0 && stride_w > 0, "dnn_plan_add_conv_padded: bad args");
+  DNN_REQUIRE(pad_h >= 0 && pad_h < kh && pad_w >= 0 && pad_w < kw,
+              "dnn_plan_add_conv_padded: pads %d,%d outside [0, kernel) for a %dx%d kernel", pad_h, pad_w, kh, kw);
+  DNN_REQUIRE((scale == nullptr) == (shift == nullptr),
+              "dnn_plan_add_conv_padded: scale and shift must be both set or both NULL");
+  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_plan_add_conv_padded: leaky must be 0, 1 or 2");
+  const int span_h = p->cur_h + 2 * pad_h - kh, span_w = p->cur_w + 2 * pad_w - kw;
+  DNN_REQUIRE(span_h >= 0 && span_w >= 0, "dnn_plan_add_conv_padded: empty output (%dx%d input, %dx%d kernel, pads %d,%d)",
+              p->cur_h, p->cur_w, kh, kw, pad_h, pad_w);
+  ConvEpilogueSpec ep;
+  ep.scale = scale;
+  ep.shift = shift;
+  ep.leaky = leaky;
+  return add_conv_layer(p, kh, kw, od, stride_h, stride_w, span_h / stride_h + 1, pad_h, span_w / stride_w + 1, pad_w,
+                        true, kernel, ep);
 }
 
 int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_w, int padding) {
@@ -742,8 +808,9 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
                                        prev.sw, prev.pt, prev.pl)) {
         prev.mode = MODE_TILE16;  // (its producer already writes the zero-bordered input) the pool fused
         ok = true;
-      } else if (prev.mode == MODE_GEMM && direct_conv_pool_supported(prev.C, prev.OC, prev.kh, prev.kw, prev.sh,
-                                                                      prev.sw)) {
+      } else if (prev.mode == MODE_GEMM && prev.pt == prev.pl && prev.pt <= 1 &&  // (VALID's or SAME's pads: the
+                 // direct kernels are checked with no others; other explicit pads keep the GEMM)
+                 direct_conv_pool_supported(prev.C, prev.OC, prev.kh, prev.kw, prev.sh, prev.sw)) {
         prev.mode = MODE_DIRECT;
         ok = true;
       } else if (prev.mode == MODE_X3 && !p->fp16 &&
@@ -1153,6 +1220,48 @@ int dnn_shortcut_host(const float* a, const float* b, float* out, int n, int h, 
   if (!rc) rc = launch_shortcut(d, d + step, d + 2 * step, (long long)f, leaky, nullptr);
   if (!rc && hipMemcpy(out, d + 2 * step, f * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
     set_error("dnn_shortcut_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
+    rc = -1;
+  }
+  (void)hipFree(d);
+  return rc;
+}
+
+int dnn_scale_shift_host(const float* a, const float* scale, const float* shift, float* out, int n, int h, int w,
+                         int c, int leaky) {
+  DNN_REQUIRE(a && out, "dnn_scale_shift_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_scale_shift_host: bad shape n=%d %dx%dx%d", n, h, w, c);
+  DNN_REQUIRE((scale == nullptr) == (shift == nullptr), "dnn_scale_shift_host: scale and shift must be both set or both NULL");
+  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_scale_shift_host: leaky must be 0, 1 or 2");
+  DNN_REQUIRE(scale || leaky, "dnn_scale_shift_host: nothing to do (no scale / shift and no leaky)");
+  if (n == 0) return 0;
+  const size_t f = (size_t)n * h * w * c;
+  DNN_REQUIRE(f * 4 < 0x80000000ULL, "dnn_scale_shift_host: a tensor of n=%d %dx%dx%d is >= 2 GiB; split the batch", n,
+              h, w, c);
+  const size_t step = align_up(f, 64), cstep = align_up((size_t)c, 64);
+  std::vector<float> beta(c);
+  for (int k = 0; k < c; ++k) beta[k] = scale ? -shift[k] : 0.f;  // v * alpha - beta, beta = -shift (exact)
+  float* d = nullptr;
+  DNN_HIP_TRY(hipMalloc(&d, (2 * step + 2 * cstep) * sizeof(float)));
+  float *d_t = d + step, *d_al = d + 2 * step, *d_be = d_al + cstep;
+  int rc = 0;
+  if (hipMemcpy(d, a, f * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+      (scale && (hipMemcpy(d_al, scale, c * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+                 hipMemcpy(d_be, beta.data(), c * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))) {
+    set_error("dnn_scale_shift_host: host to device copy failed");
+    rc = -1;
+  }
+  const float* res = d;
+  if (!rc && scale) {
+    rc = launch_bn_ab(d, d_al, d_be, d_t, (long long)f, c, nullptr);
+    res = d_t;
+  }
+  if (!rc && leaky) {
+    float* dst = res == d ? d_t : d;
+    rc = launch_leaky(res, dst, (long long)f, leaky == 2 ? 1 : 0, nullptr);
+    res = dst;
+  }
+  if (!rc && hipMemcpy(out, res, f * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
+    set_error("dnn_scale_shift_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
     rc = -1;
   }
   (void)hipFree(d);
@@ -1688,13 +1797,15 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
   for (size_t i = 0; i < p->layers.size(); ++i) {
     const PlanLayer& L = p->layers[i];
     if (L.type == 0) {
-      char sk[32] = "";
+      char sk[32] = "", xp[48] = "";
       if (L.splits > 1) snprintf(sk, sizeof(sk), " splitK=%d", L.splits);
-      snprintf(line, sizeof(line), "conv %dx%dx%d -> %dx%dx%d k%dx%d s%d mode=%s cfg=%d K=%d Kpad=%d%s%s%s%s%s\n", L.H,
+      if (L.xpad)  // dnn_plan_add_conv_padded: the pads on every side, and its scale / shift epilogue
+        snprintf(xp, sizeof(xp), " pad=%d,%d%s", L.pt, L.pl, (L.epi_flags & EPI_BN_AB) ? " affine" : "");
+      snprintf(line, sizeof(line), "conv %dx%dx%d -> %dx%dx%d k%dx%d s%d mode=%s cfg=%d K=%d Kpad=%d%s%s%s%s%s%s\n", L.H,
                L.W, L.C, L.out_h(), L.out_w(), L.OC, L.kh, L.kw, L.sh, L.x3lat ? "x3_lat" : L.x3k ? "x3_ktile" : L.x3img ? "x3_img" : kModeName[L.mode], L.cfg, L.K, L.Kpad,
                L.pool ? " +pool2x2s2" : L.pool1 ? " +pool2x2s1" : "", sk,
                L.splits > 1 ? (L.mode == MODE_X3 ? " x3-combine" : fused_splitk(p) ? " combine" : "") : "",
-               p->fp16 ? " fp16" : "", p->latency ? " latency" : "");
+               p->fp16 ? " fp16" : "", p->latency ? " latency" : "", xp);
     } else if (L.type == LAYER_STASH || L.type == LAYER_RESTORE) {
       snprintf(line, sizeof(line), "%s %dx%dx%d slot=%d\n", L.type == LAYER_STASH ? "stash" : "restore", L.H, L.W, L.C,
                L.slot);

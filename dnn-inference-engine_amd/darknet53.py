@@ -24,7 +24,9 @@ Two differences from the Darknet original:
 
   * the stride-2 convs use the engine's SAME padding (TensorFlow's: on an even input one row and
     one column of zeros at the bottom / right only), Darknet pads 1 on every side, so weights
-    converted from a Darknet checkpoint compute something else at those five layers;
+    converted from a Darknet checkpoint compute something else at those five layers
+    (darknet_import.DarknetModel builds the network from a .cfg with Darknet's padding and reads
+    .weights files; this hand-written model keeps SAME);
   * the output is the raw [n, in / 32, in / 32, n_out] tensor.  YOLOv3's own decode (logistic
     class scores, three scales) is not part of this model; an n_out in YOLOv2's format
     (anchors x (5 + classes)) decodes with yolo_post.YoloHead as before.

@@ -24,7 +24,11 @@ extra outputs (`DnnGraphBuilder.add_out_node`, `DnnInferenceEngine.run_all`): ea
 entry of the plan, and a branch that ends in one, or a tensor concatenated many layers later, lowers
 too (lower_graph; YOLOv3's three heads and two merges, yolov3.py).  `Spp` (`create_spp`) is
 YOLOv3-SPP's pyramid pooling block, [maxpool13(x), maxpool9(x), maxpool5(x), x] on channels: one
-node, one spp plan entry, one kernel (yolov3_spp.py).  With
+node, one spp plan entry, one kernel (yolov3_spp.py).  `Conv2DPadded` (`create_conv2d_padded`) is
+a conv with the same zero padding on both sides of each axis (Darknet's), `ScaleShift`
+(`create_scale_shift`) a per-channel y = x * scale + shift (a BatchNorm folded on the host) and
+`LeakyReLUF32` (`create_leaky_relu_f32`) the fp32 leaky max(x, 0.1f x); a conv followed by a
+ScaleShift and either leaky lowers to one dnn_plan_add_conv_padded entry (darknet_import.py).  With
 `debug=True` (or a graph the plan cannot express) it instead runs node by node through
 the per-op C-ABI (`conv2d_mul`, `bias_add`, ... in libdnn_hip.so, include/dnn_hip.h),
 exactly like the reference, and saves every layer to ./intermediate/layer_{k}.npy
@@ -66,6 +70,8 @@ def _bind_plan_api(lib):
         "dnn_plan_create": (i, [i, i, i, i, P(vp)]),
         "dnn_plan_destroy": (None, [vp]),
         "dnn_plan_add_conv": (i, [vp, i, i, i, i, i, i, vp, vp, vp, vp, vp, f, i]),
+        "dnn_plan_add_conv_padded": (i, [vp, i, i, i, i, i, i, i, vp, vp, vp, i]),
+        "dnn_scale_shift_host": (i, [vp, vp, vp, vp, i, i, i, i, i]),
         "dnn_plan_add_max_pool": (i, [vp, i, i, i, i, i]),
         "dnn_plan_add_stash": (i, [vp, P(i)]),
         "dnn_plan_add_restore": (i, [vp, i]),
@@ -284,7 +290,8 @@ class DnnGraphBuilder(object):
     def __init__(self):
         self.G = nx.DiGraph() if nx is not None else _DiGraph()
         self.name_num = {"conv2d": 0, "bias_add": 0, "max_pool2d": 0, "batch_norm": 0, "leaky_relu": 0,
-                         "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0, "spp": 0}
+                         "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0, "spp": 0,
+                         "conv2d_padded": 0, "scale_shift": 0, "leaky_relu_f32": 0}
         self.in_node = None
         self.out_node = None
         self.extra_out_nodes = []
@@ -366,6 +373,25 @@ class DnnGraphBuilder(object):
 
     def create_spp(self, in_node, ksizes, x_first=False):
         out_node = Spp(self.get_name("spp"), in_node, ksizes, x_first)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_conv2d_padded(self, in_node, kernel, strides, pads):
+        """A conv with explicit zero padding: `pads` = (pad_h, pad_w), each applied on both sides
+        (Darknet's rule; create_conv2d's SAME is TensorFlow's)."""
+        out_node = Conv2DPadded(self.get_name("conv2d_padded"), in_node, kernel, strides, pads)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_scale_shift(self, in_node, scale, shift):
+        out_node = ScaleShift(self.get_name("scale_shift"), in_node, scale, shift)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_leaky_relu_f32(self, in_node):
+        """The fp32 leaky max(x, 0.1f * x) (dnn_avx.c's; the plan's leaky 2), which is Darknet's
+        x > 0 ? x : .1f * x for every non-NaN x.  create_leaky_relu rounds 0.1 * x in double."""
+        out_node = LeakyReLUF32(self.get_name("leaky_relu_f32"), in_node)
         self.G.add_edge(in_node, out_node)
         return out_node
 
@@ -515,6 +541,90 @@ class LeakyReLU(DnnNode):
         x = np.ascontiguousarray(self.in_node.result, dtype=np.float32)
         mylib.leaky_relu(_fp(x), _fp(self.result), *map(ctypes.c_int, self.result.shape))
         _check_legacy(self.name)
+
+
+class Conv2DPadded(DnnNode):
+    """Not in the reference (Darknet's convs need it): Conv2D with `pads` = (pad_h, pad_w) zeros on
+    BOTH sides of each axis, out = (in + 2 * pad - k) // stride + 1, 0 <= pad < k.  run() ->
+    conv2d_mul on the np.pad'ed input, like Conv2D."""
+
+    def __init__(self, name, in_node, kernel, strides, pads):
+        batch, ih, iw, ic = in_node.result.shape
+        kh, kw, kernel_ic, od = kernel.shape
+        if kernel_ic != ic:
+            raise ValueError
+        try:
+            ph, pw = (int(v) for v in pads)
+        except (TypeError, ValueError):
+            raise ValueError
+        if (ph, pw) != tuple(pads) or not (0 <= ph < kh and 0 <= pw < kw):
+            raise ValueError
+        if len(strides) != 4 or strides[1] < 1 or strides[2] < 1:
+            raise ValueError
+        if ih + 2 * ph < kh or iw + 2 * pw < kw:
+            raise ValueError
+        oh = (ih + 2 * ph - kh) // strides[1] + 1
+        ow = (iw + 2 * pw - kw) // strides[2] + 1
+        self.in_node = in_node
+        self.kernel = np.ascontiguousarray(kernel).astype(np.float32)
+        self.strides = strides
+        self.pads = (ph, pw)
+        self.result = np.zeros((batch, oh, ow, od), dtype='float32')
+        self.kernel_r = np.ascontiguousarray(self.kernel.transpose(2, 0, 1, 3).reshape(-1, od))
+        self.col = np.zeros((0,), dtype=np.float32)
+        self.name = name
+
+    def run(self):
+        ph, pw = self.pads
+        in_layer = np.ascontiguousarray(np.pad(self.in_node.result, [(0, 0), (ph, ph), (pw, pw), (0, 0)], 'constant'),
+                                        dtype=np.float32)
+        mylib.conv2d_mul(
+            _fp(in_layer), _fp(self.col), _fp(self.kernel_r), _fp(self.result),
+            *map(ctypes.c_int, self.result.shape),
+            *map(ctypes.c_int, in_layer.shape[1:]),
+            *map(ctypes.c_int, self.kernel.shape[:2]),
+            *map(ctypes.c_int, self.strides[1:3]))
+        _check_legacy(self.name)
+
+
+def _scale_shift_host(name, x, scale, shift, out, leaky):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    rc = mylib.dnn_scale_shift_host(_vp(x), _vp(scale), _vp(shift), _vp(out), *map(int, x.shape), int(leaky))
+    _check(rc, name)
+
+
+class ScaleShift(DnnNode):
+    """Not in the reference (a BatchNorm folded on the host needs it): y = x * scale[c] +
+    shift[c], one fp32 multiply and one fp32 add per element.  In a plan it exists only as the
+    epilogue of the conv before it.  run() -> dnn_scale_shift_host."""
+
+    def __init__(self, name, in_node, scale, shift):
+        scale, shift = np.asarray(scale), np.asarray(shift)
+        if len(in_node.result.shape) != 4:
+            raise ValueError
+        if not all(a.ndim == 1 and a.shape[0] == in_node.result.shape[-1] for a in (scale, shift)):
+            raise ValueError
+        self.in_node = in_node
+        self.scale = np.ascontiguousarray(scale, dtype=np.float32)
+        self.shift = np.ascontiguousarray(shift, dtype=np.float32)
+        self.result = np.zeros(in_node.result.shape, dtype='float32')
+        self.name = name
+
+    def run(self):
+        _scale_shift_host(self.name, self.in_node.result, self.scale, self.shift, self.result, 0)
+
+
+class LeakyReLUF32(DnnNode):
+    """Not in the reference's OpenBLAS engine: the fp32 leaky max(x, 0.1f * x) (dnn_avx.c's form,
+    the plan's leaky 2; Darknet's for every non-NaN x).  run() -> dnn_scale_shift_host."""
+
+    def __init__(self, name, in_node):
+        self.in_node = in_node
+        self.result = np.zeros(in_node.result.shape, dtype='float32')
+        self.name = name
+
+    def run(self):
+        _scale_shift_host(self.name, self.in_node.result, None, None, self.result, 2)
 
 
 MAX_ROUTE_BLOCK = 8  # dnn_plan_add_route / dnn_route_host: block in 1..8
@@ -688,6 +798,17 @@ class ConvEntry(object):
         self.nodes = [conv]
 
 
+class PaddedConvEntry(object):
+    """dnn_plan_add_conv_padded: Conv2DPadded (or a Conv2D whose pads are the same on both sides)
+    [-> ScaleShift] [-> LeakyReLU | LeakyReLUF32]; `pads` = (pad_h, pad_w), `affine` the ScaleShift
+    node or None, `leaky` 0, or 2 for LeakyReLUF32, or None for a LeakyReLU (the plan's
+    leaky_variant)."""
+
+    def __init__(self, conv, pads):
+        self.conv, self.pads, self.affine, self.leaky = conv, tuple(pads), None, 0
+        self.nodes = [conv]
+
+
 class PoolEntry(object):
     def __init__(self, pool):
         self.pool = pool
@@ -780,7 +901,36 @@ def _free_slots(live, count):
 def _lower_one(g, nxt):
     """The plan entry that starts at node `nxt`, and the last node it covers; None if `nxt` is
     not the start of one."""
-    if isinstance(nxt, Conv2D):
+    if isinstance(nxt, ScaleShift):
+        raise DnnHipError(f"{nxt.name}: a ScaleShift exists in a plan only as the epilogue of the conv directly "
+                          "before it (Conv2DPadded, or a Conv2D padded alike on both sides, with no BiasAdd / "
+                          "BatchNorm and no other consumer in between); run the graph with debug=True otherwise")
+    if isinstance(nxt, (Conv2D, Conv2DPadded)):
+        nn = list(g.G.successors(nxt))
+        follows = not _is_output(g, nxt) and len(nn) == 1 and isinstance(nn[0], (ScaleShift, LeakyReLUF32))
+        if isinstance(nxt, Conv2DPadded):
+            pads = nxt.pads
+        elif follows and nxt.pad_top == nxt.pad_bottom and nxt.pad_left == nxt.pad_right:
+            pads = (nxt.pad_top, nxt.pad_left)  # VALID, or a SAME that pads alike on both sides
+        else:
+            pads = None
+        if pads is not None:
+            e = PaddedConvEntry(nxt, pads)
+            cur = nxt
+            for kinds in ((ScaleShift,), (LeakyReLU, LeakyReLUF32)):
+                nn = list(g.G.successors(cur))
+                if _is_output(g, cur) or len(nn) != 1 or not isinstance(nn[0], kinds):
+                    continue
+                cur = nn[0]
+                if isinstance(cur, ScaleShift):
+                    e.affine = cur
+                else:
+                    e.leaky = 2 if isinstance(cur, LeakyReLUF32) else None
+                e.nodes.append(cur)
+            nn = list(g.G.successors(cur))
+            if cur is nxt and not _is_output(g, cur) and len(nn) == 1 and isinstance(nn[0], (BiasAdd, BatchNorm)):
+                return None  # BiasAdd / BatchNorm are dnn_plan_add_conv's epilogue: use ScaleShift
+            return e, cur
         e = ConvEntry(nxt)
         cur = nxt
         for kind in (BiasAdd, BatchNorm, LeakyReLU):
@@ -943,7 +1093,12 @@ def lower_graph(g):
                      input), Release(slot).  A long skip into an Add is not expressible.
 
     An extra output on the main line is a Tap after the entry that computes it.  Slots are the
-    lowest free numbers; more than MAX_SLOTS live at once gives None."""
+    lowest free numbers; more than MAX_SLOTS live at once gives None.
+
+    A Conv2DPadded [-> ScaleShift] [-> LeakyReLU | LeakyReLUF32] is one PaddedConvEntry
+    (dnn_plan_add_conv_padded), and so is a Conv2D directly followed by a ScaleShift or a
+    LeakyReLUF32 when its SAME / VALID pads are the same on both sides.  A ScaleShift anywhere else
+    has no plan form: DnnHipError (the node-by-node path, debug=True, runs any graph)."""
     if g.in_node is None or g.out_node is None:
         return None
     extras = list(getattr(g, "extra_out_nodes", ()))
@@ -1116,7 +1271,18 @@ class Plan(object):
         for e in entries:
             if _add_structural(self.lib, self.h, e, leaky_variant):
                 continue
-            if isinstance(e, ConvEntry):
+            if isinstance(e, PaddedConvEntry):
+                c = e.conv
+                kh, kw, _, od = c.kernel.shape
+                scale = e.affine.scale if e.affine is not None else None
+                shift = e.affine.shift if e.affine is not None else None
+                keep = (c.kernel, scale, shift)  # noqa: F841 (alive across the call)
+                rc = self.lib.dnn_plan_add_conv_padded(
+                    self.h, kh, kw, od, int(c.strides[1]), int(c.strides[2]), e.pads[0], e.pads[1],
+                    _vp(c.kernel) if upload else None, _vp(scale), _vp(shift),
+                    leaky_variant if e.leaky is None else e.leaky)
+                _check(rc, "dnn_plan_add_conv_padded", self.lib)
+            elif isinstance(e, ConvEntry):
                 c = e.conv
                 kh, kw, _, od = c.kernel.shape
                 bias = e.bias.biases if e.bias is not None else None
@@ -1161,9 +1327,8 @@ class Plan(object):
         return cls(g.in_node.in_shape[0], tuple(g.in_node.in_shape[1:]), entries, device=device, **kw)
 
     @staticmethod
-    def memory(batch, in_shape, entries, lib=None, precision="fp32", latency=False):
-        """(weight_bytes, workspace_bytes) a plan of this shape needs, without finalizing."""
-        lib = lib or mylib
+    def _declared(batch, in_shape, entries, lib, precision, latency):
+        """A plan handle with the entries' shapes declared (no weights, not finalized: no device)."""
         h = ctypes.c_void_p()
         _check(lib.dnn_plan_create(int(batch), *in_shape, ctypes.byref(h)), "dnn_plan_create", lib)
         try:
@@ -1173,7 +1338,14 @@ class Plan(object):
             for e in entries:
                 if _add_structural(lib, h, e):
                     continue
-                if isinstance(e, ConvEntry):
+                if isinstance(e, PaddedConvEntry):
+                    kh, kw, _, od = e.conv.kernel.shape
+                    sc = _vp(e.affine.scale) if e.affine is not None else None  # (only says: affine or not)
+                    _check(lib.dnn_plan_add_conv_padded(h, kh, kw, od, int(e.conv.strides[1]), int(e.conv.strides[2]),
+                                                        e.pads[0], e.pads[1], None, sc, sc,
+                                                        1 if e.leaky is None else e.leaky),
+                           "dnn_plan_add_conv_padded", lib)
+                elif isinstance(e, ConvEntry):
                     kh, kw, _, od = e.conv.kernel.shape
                     _check(lib.dnn_plan_add_conv(h, kh, kw, od, int(e.conv.strides[1]), int(e.conv.strides[2]),
                                                  _pad_code(e.conv.padding), None, None, None, None, None, 0.0,
@@ -1183,9 +1355,32 @@ class Plan(object):
                     _check(lib.dnn_plan_add_max_pool(h, int(p.ksize[1]), int(p.ksize[2]), int(p.strides[1]),
                                                      int(p.strides[2]), _pad_code(p.padding)),
                            "dnn_plan_add_max_pool", lib)
+        except Exception:
+            lib.dnn_plan_destroy(h)
+            raise
+        return h
+
+    @staticmethod
+    def memory(batch, in_shape, entries, lib=None, precision="fp32", latency=False):
+        """(weight_bytes, workspace_bytes) a plan of this shape needs, without finalizing."""
+        lib = lib or mylib
+        h = Plan._declared(batch, in_shape, entries, lib, precision, latency)
+        try:
             wb, sb = ctypes.c_size_t(), ctypes.c_size_t()
             _check(lib.dnn_plan_memory(h, ctypes.byref(wb), ctypes.byref(sb)), "dnn_plan_memory", lib)
             return wb.value, sb.value
+        finally:
+            lib.dnn_plan_destroy(h)
+
+    @staticmethod
+    def lowering(batch, in_shape, entries, lib=None, precision="fp32", latency=False):
+        """dnn_plan_describe's text for a plan of this shape, without finalizing (needs no device)."""
+        lib = lib or mylib
+        h = Plan._declared(batch, in_shape, entries, lib, precision, latency)
+        try:
+            buf = ctypes.create_string_buffer(65536)
+            _check(lib.dnn_plan_describe(h, buf, 65536), "dnn_plan_describe", lib)
+            return buf.value.decode()
         finally:
             lib.dnn_plan_destroy(h)
 

@@ -185,7 +185,8 @@ def yolov3_weights(seed=WEIGHT_SEED, width_div=1, n_out=YOLOV3_N_OUT, in_c=IN_SH
     head.  Same counter-based generators (layer i draws from streams 10 i + j) and width_div as
     darknet53_weights.  The SAME-padding caveat of darknet53.py applies unchanged: the stride-2
     convs pad as TensorFlow does, so weights converted from a Darknet checkpoint would compute
-    something else at those five layers."""
+    something else at those five layers (darknet_import.DarknetModel pads as Darknet does; its
+    tests turn these generators' draws into Darknet-order weight files)."""
     def wd(c):
         if c % width_div:
             raise ValueError(f"width_div {width_div} does not divide {c}")

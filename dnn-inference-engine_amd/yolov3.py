@@ -32,7 +32,9 @@ Two differences from the Darknet original:
 
   * the stride-2 convs use the engine's SAME padding (TensorFlow's: on an even input one row and
     one column of zeros at the bottom / right only), Darknet pads 1 on every side, so weights
-    converted from a Darknet checkpoint compute something else at those five layers;
+    converted from a Darknet checkpoint compute something else at those five layers
+    (darknet_import.DarknetModel builds the network from a .cfg with Darknet's padding and reads
+    .weights files; this hand-written model keeps SAME);
   * the default NMS is the reference's class-agnostic one over all scales
     (include/dnn_hip_post.h).  Darknet's per-class rule is
     `head=yolo_post.MultiHead.yolov3(h, w, classes, nms="per_class")`, and with

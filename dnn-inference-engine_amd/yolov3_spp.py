@@ -22,13 +22,16 @@ and detect are yolov3.YOLO_V3's; the decode is yolo_post.MultiHead.yolov3.
 
 Out of scope, as for yolov3.py:
 
-  * Darknet .cfg / .weights import: weights arrive as yolo_weights layer dicts;
+  * Darknet .cfg / .weights files: this model takes yolo_weights layer dicts
+    (darknet_import.DarknetModel reads the files, finds the SPP pattern in the cfg and lowers it to
+    the same spp entry);
   * the defaults are not Darknet's: the NMS is the reference's class-agnostic one over all scales
     and a box carries one class, the arg-max.  Darknet's per-class rule with its multi-label
     output is `head=yolo_post.MultiHead.yolov3(h, w, classes, nms="per_class", labels="multi")`;
   * the stride-2 convs use the engine's SAME padding (bottom / right on an even input), Darknet
     pads 1 on every side, so a converted Darknet checkpoint computes something else at those five
-    layers.  The SPP pools themselves are Darknet's: stride 1 with size // 2 on every side.
+    layers (darknet_import's convs pad as Darknet does).  The SPP pools themselves are Darknet's:
+    stride 1 with size // 2 on every side.
 """
 import darknet53
 import dnn_hip

@@ -26,7 +26,8 @@ a multiple of 32, and the stride-1 pool pads bottom / right only, as Darknet's d
 
 Out of scope:
 
-  * Darknet .cfg / .weights import: weights arrive as yolo_weights layer dicts;
+  * Darknet .cfg / .weights files: this model takes yolo_weights layer dicts
+    (darknet_import.DarknetModel reads the files and lowers to the same plan entries);
   * the defaults are not Darknet's: the NMS is the reference's class-agnostic one over both
     scales (include/dnn_hip_post.h) and a box carries one class, the arg-max.  Darknet's
     per-class rule with its multi-label output (one detection per class above the threshold for

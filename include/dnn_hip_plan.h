@@ -11,7 +11,9 @@
  * lowers the graph to.  Beyond the reference's chains, stash / restore / route entries let a
  * plan fork and join (YOLOv2's passthrough: space-to-depth + channel concat), shortcut /
  * upsample / release entries express residual and top-down networks, taps give a plan extra
- * outputs (YOLOv3's three heads), and an spp entry is YOLOv3-SPP's pyramid pooling block.
+ * outputs (YOLOv3's three heads), an spp entry is YOLOv3-SPP's pyramid pooling block, and
+ * dnn_plan_add_conv_padded is Darknet's conv: explicit padding on every side and a folded
+ * BatchNorm as a per-channel scale / shift (darknet_import.py builds whole networks from it).
  *
  * Conventions: plain C ABI, cdecl, no torch types.  All tensors NHWC fp32 contiguous,
  * conv kernels HWIO (the pickle layout of proj3/yolov2tiny.py:30-77).  Functions return
@@ -66,6 +68,36 @@ int dnn_plan_set_latency_mode(dnn_plan* plan, int on);
 int dnn_plan_add_conv(dnn_plan* plan, int kh, int kw, int od, int stride_h, int stride_w, int padding,
                       const float* kernel, const float* biases, const float* mean, const float* var,
                       const float* gamma, float eps, int leaky);
+
+/* Append a conv with explicit zero padding and a per-channel affine epilogue (fp32 plans, batch
+ * and latency mode; on an fp16 plan it fails).  The reference has no such node: it is Darknet's
+ * convolutional layer with its BatchNorm folded on the host.
+ *
+ * Geometry: pad_h rows of zeros above AND below, pad_w columns left AND right,
+ *   OH = (H + 2*pad_h - kh) / stride_h + 1 (likewise OW), 0 <= pad < k.  Unlike SAME, a 3x3 /
+ *   stride-2 conv with pad 1 on an even map reads one row and column before the frame and none
+ *   after it (Darknet's sampling).  An empty output fails.
+ * Epilogue: y = leaky(v * scale[oc] + shift[oc]); scale and shift are both set or both NULL (no
+ *   affine step).  It runs as the kernels' v * alpha - beta with alpha = scale and beta = -shift,
+ *   which rounds as v * scale + shift does (one multiply, one add, never contracted).  leaky: 0
+ *   none, 1, 2 as dnn_plan_add_conv; max(v, 0.1f * v) (2) equals Darknet's x > 0 ? x : .1f * x
+ *   for every non-NaN x.
+ * kernel: [kh][kw][in_c][od] HWIO, copied; NULL declares the shape only, as for dnn_plan_add_conv
+ *   (scale / shift then only say whether the layer has the affine step).
+ * The execution mode is chosen exactly as dnn_plan_add_conv chooses it for the same geometry, so
+ * a 3x3 / stride-1 / pad-1 entry runs what a SAME one runs; the conv0 direct kernels take front
+ * pads 0,0 and 1,1 only (other pads before a 2x2/s2 pool stay on the im2col GEMM).
+ * dnn_plan_describe appends " pad=<pad_h>,<pad_w>" and, with scale / shift, " affine" to the
+ * layer's line.  A failed call leaves the plan unchanged. */
+int dnn_plan_add_conv_padded(dnn_plan* plan, int kh, int kw, int od, int stride_h, int stride_w, int pad_h,
+                             int pad_w, const float* kernel, const float* scale, const float* shift, int leaky);
+
+/* The affine epilogue on a host tensor (H2D copies, launches, D2H copy, synchronise):
+ * out = leaky(a * scale[c] + shift[c]) over [n, h, w, c], the element-wise kernels of the per-op
+ * ABI with beta = -shift; scale / shift both NULL: the activation alone (leaky 1 or 2).  The tensor
+ * must be below 2 GiB (refused from the arguments, before any allocation). */
+int dnn_scale_shift_host(const float* a, const float* scale, const float* shift, float* out, int n, int h, int w,
+                         int c, int leaky);
 
 /* Append a MaxPool2D (proj3/dnn_openblas.py:213-242). */
 int dnn_plan_add_max_pool(dnn_plan* plan, int kh, int kw, int stride_h, int stride_w, int padding);
