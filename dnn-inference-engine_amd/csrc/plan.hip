@@ -4,22 +4,36 @@
 // host numpy arrays (proj3/dnn_openblas.py:29-57; each CUDA/cuBLAS call even mallocs and
 // copies per image, dnn_cuda.cu:193-210).  Here the same node chain is lowered once to a
 // list of device steps.  Each conv entry (Conv2D + its BiasAdd / BatchNorm / LeakyReLU as
-// the GEMM epilogue) runs in one of four modes:
-//   GEMM      explicit im2col into a col buffer + LDS-tiled fp32-MFMA GEMM (the reference's
-//             im2col + sgemm structure, dnn_openblas.c:160-194; generic fallback)
-//   DIRECT_A  1x1 / stride 1 / unpadded: the NHWC input IS the col matrix, GEMM only
-//   IMPLICIT  implicit GEMM: the LDS-DMA loader gathers the im2col rows straight from the
-//             input (per-lane source addresses), no col buffer
-//   DIRECT    3x3 conv with <= 4 input channels (conv0): direct FMA conv, weights in LDS
-//   PATCH     3x3 SAME conv with 16/32 input channels + 2x2 pool (conv1): input patch and
-//             weights DMA'd to LDS once per tile, taps are constant LDS offsets (conv_patch.hip)
-// and a following 2x2/stride-2 MaxPool2D is fused into the IMPLICIT / DIRECT epilogue
-// (pool-window-major rows), otherwise it is its own pool entry.  Weights are packed once
-// into a device arena as Bt[Npad][Kpad] (K order kh,kw,ic; HWIO as-is for DIRECT) plus four
+// the GEMM epilogue) runs as one kernel variant (ConvVariant):
+//   gemm       explicit im2col into a col buffer + LDS-tiled fp32-MFMA GEMM (the reference's
+//              im2col + sgemm structure, dnn_openblas.c:160-194; generic fallback)
+//   direct_a   1x1 / stride 1 / unpadded: the NHWC input IS the col matrix, GEMM only
+//   implicit   implicit GEMM: the LDS-DMA loader gathers the im2col rows straight from the
+//              input (per-lane source addresses), no col buffer
+//   direct     3x3 conv with <= 4 input channels (conv0): direct FMA conv, weights in LDS
+//   patch      3x3 SAME conv with 16/32 input channels + 2x2 pool (conv1): input patch and
+//              weights DMA'd to LDS once per tile, taps are constant LDS offsets (conv_patch.hip)
+//   patch16, tile16, img16   fp16 3x3 convs on a zero-bordered input: whole rows, 2-D tiles with
+//              the 2x2/s2 pool, one frame per tile with a 2x2/s1 pool (conv6/conv7, conv2-conv4, conv5)
+//   x3, x3_lat, x3_ktile, x3_img   fp32 3x3 convs on the bf16 MFMA with exact 3-way splits, reading
+//              split zero-bordered planes: the batch tiles, the small-M K slices, the K split
+//              inside the workgroup (latency plans), whole-image tiles with a 2x2/s1 pool
+//   x3_1x1, x3_1x1_ktile   fp32 1x1 conv with the same arithmetic on its producer's split planes
+// and a following 2x2 MaxPool2D is fused into the conv where the variant can take it (PoolFuse:
+// stride 2 with pool-window-major rows, or stride 1 on the same frame), otherwise it is its own
+// pool entry.  Weights are packed once
+// into a device arena as Bt[Npad][Kpad] (K order kh,kw,ic; HWIO as-is for direct) plus four
 // Npad-long epilogue vectors (bias, mean, sqrt(var+eps), gamma).  Activations ping-pong
 // between two workspace buffers.  DNN_HIP_FUSE=0 in the environment at plan creation
 // forces the explicit GEMM path with separate pools (for A/B checks); DNN_HIP_PATCH=0 keeps
-// PATCH-eligible layers on the implicit GEMM.
+// patch-eligible layers on the implicit GEMM.
+//
+// Layers, steps, walker: the dnn_plan_add_* entries only record layers (and rewrite the last ones:
+// a pool fuses into its conv, a conv asks its producer for a zero-bordered output).  layout()
+// lowers the layers to steps, one per kernel launch in launch order, each with its name, flops,
+// bytes and the resolved locations it reads and writes, and fills the workspace map (WsMap).
+// dnn_plan_run walks the steps: record(i), launch step i; the per-kernel timings, marks and clock
+// stamps index the same list, so they cannot drift from what runs.
 //
 // Fork / join (fp32 plans): a stash entry names the current tensor as a slot, and the layer that
 // produces it writes it into the slot's own workspace region instead of an activation buffer, so
@@ -55,6 +69,7 @@
 #include <string>
 #include <vector>
 #include "dnn_common.h"
+#include "plan_internal.h"
 #include "../../include/dnn_hip_plan.h"
 
 namespace dnnhip {
@@ -104,51 +119,74 @@ void out_pads(int in, int k, int s, int same, int* out, int* pad_front) {
   }
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+int spp_sizes_ok(const char* who, int n_sizes, const int* sizes) {
+  DNN_REQUIRE(sizes != nullptr, "%s: sizes is NULL", who);
+  DNN_REQUIRE(n_sizes >= 1 && n_sizes <= DNN_SPP_MAX_SIZES, "%s: n_sizes %d outside 1..%d", who, n_sizes,
+              DNN_SPP_MAX_SIZES);
+  for (int j = 0; j < n_sizes; ++j)
+    DNN_REQUIRE(sizes[j] >= 3 && sizes[j] <= DNN_SPP_MAX_K && sizes[j] % 2 == 1,
+                "%s: size %d (entry %d) is not odd and in 3..%d", who, sizes[j], j, DNN_SPP_MAX_K);
+  return 0;
+}
 
 }  // namespace dnnhip
 
 using namespace dnnhip;
 
-// MODE_PATCH16: fp16 3x3 conv on a zero-bordered input (conv3x3_f16_acc_kernel; conv6/conv7)
-// MODE_TILE16: fp16 3x3 conv + 2x2/s2 pool on 2-D tiles of a zero-bordered input
-//   (conv3x3_f16_tile_kernel; conv2-conv4)
-// MODE_X3: fp32 3x3 conv on the bf16 MFMA with exact 3-way splits, split zero-bordered input
-// (conv3x3_x3_patch_kernel; conv6/conv7 of the fp32 path)
-// MODE_X3_1X1: fp32 1x1 conv with the same arithmetic on its producer's split planes
-// (conv1x1_x3_kernel; conv8 of the fp32 path)
-enum ConvMode : int { MODE_GEMM = 0, MODE_DIRECT_A = 1, MODE_IMPLICIT = 2, MODE_DIRECT = 3, MODE_PATCH = 4,
-                      MODE_PATCH16 = 5, MODE_X3 = 6, MODE_X3_1X1 = 7, MODE_TILE16 = 8 };
-static const char* kModeName[] = {"gemm", "direct_a", "implicit", "direct", "patch", "patch16", "patch_x3", "x3_1x1",
-                                  "tile16"};
+// The launcher form a conv entry runs as, each named once (the header comment describes them;
+// kVariantName is what dnn_plan_describe prints as mode=).
+enum ConvVariant : int {
+  CONV_GEMM, CONV_DIRECT_A, CONV_IMPLICIT, CONV_DIRECT, CONV_PATCH,  // both precisions
+  CONV_PATCH16, CONV_TILE16, CONV_IMG16,                             // fp16, zero-bordered input
+  CONV_X3, CONV_X3_LAT, CONV_X3_KTILE, CONV_X3_IMG,                  // fp32 3x3 on split planes
+  CONV_X3_1X1, CONV_X3_1X1_KTILE                                     // fp32 1x1 on split planes
+};
+static const char* const kVariantName[] = {"gemm", "direct_a", "implicit", "direct", "patch", "patch16", "tile16",
+                                           "tile16", "patch_x3", "x3_lat", "x3_ktile", "x3_img", "x3_1x1",
+                                           "x3_ktile"};
+// a 2x2 max pool fused into a conv, as the launchers take it: stride 2 (pool-window-major rows, the
+// output frame is PH x PW) or stride 1 SAME (the same output frame)
+enum PoolFuse : int { POOL_NONE = 0, POOL_S2 = 1, POOL_S1 = 2 };
+
+static bool is_x3(int v) { return v >= CONV_X3 && v <= CONV_X3_IMG; }  // the 3x3 x3 convs
+static bool is_x3_1x1(int v) { return v == CONV_X3_1X1 || v == CONV_X3_1X1_KTILE; }
+static bool is_tile16(int v) { return v == CONV_TILE16 || v == CONV_IMG16; }
+// the x3 arithmetic: the input is the producer's split planes (the 16-channel x3 conv alone reads
+// fp32, add_conv_layer) and the weights are three bf16 pieces each
+static bool reads_split_planes(int v) { return is_x3(v) || is_x3_1x1(v); }
+// how upload_weights packs Bt: three bf16 pieces per weight, or launch_pack_weights' order
+enum WeightPack : int { PACK_HWIO, PACK_BT, PACK_BT_TILE16, PACK_BT_PATCH16, PACK_X3 };
+static WeightPack weight_pack(int v) {
+  return v == CONV_DIRECT ? PACK_HWIO : reads_split_planes(v) ? PACK_X3 : is_tile16(v) ? PACK_BT_TILE16
+         : v == CONV_PATCH16 ? PACK_BT_PATCH16 : PACK_BT;
+}
 
 // where a tensor of a run lives: the caller's output / input, one of the two ping-pong activation
-// buffers, or slot region r (LOC_REGION + r)
-enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, LOC_IN = 2, LOC_REGION = 3 };
+// buffers, slot region r (LOC_REGION + r), or layer j's zero-bordered / split-plane area (LOC_PAD + j)
+enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, LOC_IN = 2, LOC_REGION = 3,
+                       LOC_PAD = 1 << 24 };
+
+enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
+                       LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9 };
 
 struct PlanLayer {
-  int type = 0;  // 0 conv, 1 pool, 2 stash, 3 restore, 4 route, 5 shortcut, 6 upsample, 7 release, 8 tap, 9 spp (LAYER_*)
+  int type = LAYER_CONV;
   // shapes (per image): input H,W,C -> conv/pool output OH,OW,OC (-> fused pool PH,PW)
   int H = 0, W = 0, C = 0, OH = 0, OW = 0, OC = 0;
   int kh = 0, kw = 0, sh = 1, sw = 1, pt = 0, pl = 0;
   // conv
-  int mode = MODE_GEMM;
+  int variant = CONV_GEMM;
   int K = 0, Kpad = 0, Npad = 0, cfg = 0, epi_flags = 0;
   int splits = 1;  // split-K partial count (> 1: GEMM writes partials, a reduce kernel finishes)
-  bool pool = false;  // a 2x2/stride-2 max pool fused into this conv
+  int pool = POOL_NONE;  // a 2x2 max pool fused into this conv
   bool xpad = false;  // explicit pads (dnn_plan_add_conv_padded): shown by dnn_plan_describe
-  bool x3lat = false;  // MODE_X3 on the small-M kernel (latency plans: launch_conv_x3_lat)
-  bool x3k = false;    // MODE_X3 with the K split inside the workgroup (latency plans: launch_conv_x3_ktile)
-  bool pool1 = false;  // x3k / x3img: a 2x2/stride-1 SAME pool fused (same output frame)
-  bool x3img = false;  // MODE_X3 on whole-image tiles over all of K (launch_conv_x3_img), pool1 fused
-  bool out_padded = false;  // output written zero-bordered (the next layer is MODE_PATCH16 / MODE_X3;
-                            // fp32 plans: as x3 split planes)
+  bool out_padded = false;  // output written zero-bordered (the next layer reads_split_planes / is
+                            // patch16 / tile16; fp32 plans: as x3 split planes)
   size_t pad_off = 0;       // its zero-bordered output region: float offset inside the pad area
   int PH = 0, PW = 0;
   size_t w_off = 0, epi_off = 0;  // float offsets in the weight arena
   bool have_host = false;
   std::vector<float> w, bias, mean, sq, gamma;
-  int kernel_idx = 0;  // index of this layer's first kernel in the kernel list
   // fork / join: the slot a stash defines, a restore switches to or a route reads as b (-1: none)
   int slot = -1;
   int block = 1, Cb = 0;    // route: space-to-depth block, channels of b
@@ -159,13 +197,15 @@ struct PlanLayer {
   int leaky = 0;            // shortcut: 0 none, 1 / 2 the conv epilogue's variants
   int n_sizes = 0, sizes[DNN_SPP_MAX_SIZES] = {0, 0, 0};  // spp: the pools' window sizes, in block order
   bool x_first = false;     // spp: the input's copy is the first channel block
-  int dst_loc = 0;          // where this layer writes (LOC_*; layout())
-  int out_h() const { return pool ? PH : OH; }
-  int out_w() const { return pool ? PW : OW; }
+  int dst_loc = 0;          // where this layer writes when its output is plain NHWC (LOC_*; layout())
+  bool is_conv() const { return type == LAYER_CONV; }
+  bool is(int v) const { return type == LAYER_CONV && variant == v; }
+  int out_h() const { return pool == POOL_S2 ? PH : OH; }
+  int out_w() const { return pool == POOL_S2 ? PW : OW; }
+  // the GEMM's rows for n images (pool-window-major rows with a fused stride-2 pool)
+  long long rows(long long n) const { return pool == POOL_S2 ? 4 * n * PH * PW : n * OH * OW; }
 };
 
-enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
-                       LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9 };
 constexpr int kMaxSlots = 4;
 
 struct PlanTap {
@@ -179,11 +219,32 @@ struct PlanSlot {
   bool live = true;  // false once released: its number is free for the next stash
 };
 
-struct KernelDesc {
+// One kernel launch of a run.  The step list is in launch order: a step's index is its kernel index
+// in the ABI (dnn_plan_kernel_info, the timing / mark / clock calls).  Nothing here depends on a
+// run's n or pointers.
+enum StepKind : int {
+  STEP_CVT_IN,           // fp16 plans: the fp32 frames to fp16
+  STEP_IM2COL,           // src -> the col buffer
+  STEP_CONV,             // the layer's conv (gemm: on the col buffer); split layers leave partials in the slab
+  STEP_REDUCE,           // slab partials + epilogue -> dst (split-K without the in-GEMM combine)
+  STEP_X3_COMBINE,       // an x3 conv's slab partials + its epilogue -> dst
+  STEP_POOL,
+  STEP_X3_COMBINE_POOL,  // a pool layer's step that also combines the partials of x3 conv `layer - 1`
+  STEP_ROUTE, STEP_SHORTCUT, STEP_UPSAMPLE, STEP_SPP,
+  STEP_CVT_OUT           // fp16 plans: the last activation to the fp32 output
+};
+
+struct Step {
   std::string name;
-  int layer;
-  int kind;             // 0 im2col, 1 gemm / conv, 2 pool, 3 reduce / combine, 4 convert, 5 route, 6 shortcut, 7 upsample, 8 spp
+  int layer;            // the layer it belongs to (-1: the plan's edge conversions)
+  StepKind kind;
   double flops, bytes;  // algorithmic, full planned batch
+  int src, dst;         // where it reads the current tensor and writes its output (TensorLoc)
+};
+
+// float offsets of the workspace's areas, in this order (layout())
+struct WsMap {
+  size_t act0 = 0, act1 = 0, col = 0, slab = 0, tickets = 0, pad = 0, regions = 0, zero = 0;
 };
 
 struct dnn_plan {
@@ -196,7 +257,7 @@ struct dnn_plan {
   bool direct_out = false;  // fp16: the last layer writes the fp32 output itself (fp16_direct_out)
   bool latency = false;  // split K by M too (dnn_plan_set_latency_mode): batch-1 latency plans
   std::vector<PlanLayer> layers;
-  std::vector<KernelDesc> kernels;
+  std::vector<Step> steps;  // what a run launches, in order (layout())
   // fork / join: slots by number (at most kMaxSlots, a released number is reused); regions (one
   // per stashed layer output unless a free one fits; slots of a restored or re-stashed tensor share
   // one) as per-image floats (the largest tensor a region ever holds), their float offsets inside
@@ -218,6 +279,7 @@ struct dnn_plan {
   size_t ws_floats = 0;
   bool own_ws = false;
   size_t act_floats = 0, col_floats = 0, slab_floats = 0, ticket_floats = 0, pad_floats = 0;
+  WsMap at;  // where those areas start
   static constexpr size_t kZeroFloats = 64;  // zero page: source of padding taps (implicit GEMM)
   // staging for dnn_plan_run_host
   float* h_in_dev = nullptr;
@@ -260,60 +322,106 @@ static bool fused_splitk(const dnn_plan* p) { return p->splitk_fused; }
 static bool fp16_direct_out(const dnn_plan* p) {
   if (!p->fp16 || p->layers.empty() || getenv_flag_off("DNN_HIP_F16_DIRECT_OUT")) return false;
   const PlanLayer& L = p->layers.back();
-  return L.type == 0 && L.mode == MODE_DIRECT_A && gemm16_f32out_supported(L.splits, L.Npad) && !L.out_padded;
+  return L.is(CONV_DIRECT_A) && gemm16_f32out_supported(L.splits, L.Npad) && !L.out_padded;
 }
 
+// Where each layer writes its plain NHWC output.  Chains keep the ping-pong by layer parity; with
+// fork / join entries a layer followed by a stash writes that slot's region, and any other one the
+// activation buffer that does not hold its input (the only other live tensors are in slot regions).
+// fp16 plans convert their last activation to the output, unless the last layer writes it (direct_out)
+static void place_outputs(dnn_plan* p) {
+  bool fork = false;
+  for (auto& L : p->layers) fork = fork || L.type >= LAYER_STASH;
+  int cur = LOC_IN;
+  size_t last = p->layers.size();  // the last layer that is not a release writes the output
+  while (last > 0 && p->layers[last - 1].type == LAYER_RELEASE) --last;
+  if (p->fp16 && !p->direct_out) last = 0;
+  for (size_t i = 0; i < p->layers.size(); ++i) {
+    PlanLayer& L = p->layers[i];
+    if (L.type == LAYER_STASH || L.type == LAYER_RELEASE || L.type == LAYER_TAP) {
+      L.dst_loc = cur;
+    } else if (L.type == LAYER_RESTORE) {
+      L.dst_loc = cur = L.slot_loc;
+    } else {
+      L.dst_loc = i + 1 == last ? LOC_OUT
+                  : !fork                   ? (int)(i & 1)
+                  : L.to_region >= 0        ? LOC_REGION + L.to_region
+                  : cur == LOC_ACT0         ? LOC_ACT1
+                                            : LOC_ACT0;
+      cur = L.dst_loc;
+    }
+  }
+}
+
+// Lowers the layers to the step list and sizes the weight arena and the workspace.  The peepholes
+// rewrite layers until finalize and dnn_plan_memory / dnn_plan_num_kernels ask before it, so this
+// derives everything from the layers each time it is called.
 static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
+  place_outputs(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
   int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0;  // kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7
-  p->kernels.clear();
+  p->steps.clear();
   const double B = p->batch;
-  for (size_t i = 0; i < p->layers.size(); ++i) {
+  const int nl = (int)p->layers.size();
+  int cur = LOC_IN;  // where the current tensor lies
+  char nm[64];
+  auto step = [&](int layer, StepKind kind, double flops, double bytes, int src, int dst) {
+    p->steps.push_back(Step{nm, layer, kind, flops, bytes, src, dst});
+  };
+  // fp16 plans convert at the edges: fp32 frames in (unless conv0 is direct: it reads them), fp32 out
+  if (p->fp16 && !(nl && p->layers[0].is(CONV_DIRECT))) {
+    snprintf(nm, sizeof(nm), "input.cvt");
+    step(-1, STEP_CVT_IN, 0.0, 6.0 * B * p->in_h * p->in_w * p->in_c, LOC_IN, LOC_ACT1);  // (layer 0 writes act0)
+    cur = LOC_ACT1;
+  }
+  for (int i = 0; i < nl; ++i) {
     PlanLayer& L = p->layers[i];
     act = std::max(act, (size_t)L.out_h() * L.out_w() * L.OC);
     const double M = B * L.OH * L.OW;
     const double in_b = 4.0 * B * L.H * L.W * L.C, out_b = 4.0 * B * L.out_h() * L.out_w() * L.OC;
-    L.kernel_idx = (int)p->kernels.size();
-    char nm[64];
-    if (L.type == 0) {
+    const int out = L.out_padded ? LOC_PAD + i : L.dst_loc;
+    // a stash, a tap (its producer wrote the region, or it is the input), a release and a restore launch nothing
+    if (L.type == LAYER_STASH || L.type == LAYER_RELEASE || L.type == LAYER_TAP) continue;
+    if (L.type == LAYER_RESTORE) {
+      cur = L.dst_loc;
+      continue;
+    }
+    if (L.type == LAYER_CONV) {
       L.w_off = off;
       // fp16 GEMM layers hold Bt in halves (2 per float slot); conv0's direct kernel reads fp32
-      const bool half_w = p->fp16 && L.mode != MODE_DIRECT;
-      if (L.mode == MODE_X3 || L.mode == MODE_X3_1X1)  // three bf16 pieces per weight
+      const bool half_w = p->fp16 && L.variant != CONV_DIRECT;
+      if (weight_pack(L.variant) == PACK_X3)  // three bf16 pieces per weight
         off = align_up(off + (size_t)L.Npad * L.Kpad * 3 / 2, 64);
       else
         off = align_up(off + ((size_t)L.Npad * L.Kpad + (half_w ? 1 : 0)) / (half_w ? 2 : 1), 64);
       L.epi_off = off;
       off = align_up(off + 4 * (size_t)L.Npad, 64);
       const double flops = 2.0 * M * L.OC * L.K, w_b = 4.0 * L.K * L.OC;
-      if (L.mode == MODE_GEMM) {
+      const int src = p->fp16 && L.variant == CONV_DIRECT ? LOC_IN : cur;  // (conv0's direct kernel reads the fp32 frames)
+      if (L.variant == CONV_GEMM) {
         col = std::max(col, (size_t)L.OH * L.OW * L.Kpad);
         snprintf(nm, sizeof(nm), "conv%d.im2col", nconv);
         // algorithmic bytes: col written once + input read once
-        p->kernels.push_back({nm, (int)i, 0, 0.0, 4.0 * M * L.K + in_b});
-        snprintf(nm, sizeof(nm), "conv%d.gemm", nconv++);
-        p->kernels.push_back({nm, (int)i, 1, flops, 4.0 * M * L.K + w_b + out_b});
-      } else if (L.mode == MODE_DIRECT || L.mode == MODE_PATCH) {
-        snprintf(nm, sizeof(nm), L.mode == MODE_DIRECT ? "conv%d.direct" : "conv%d.patch", nconv++);
-        p->kernels.push_back({nm, (int)i, 1, flops, in_b + w_b + out_b});
-      } else {  // DIRECT_A reads the input as A; IMPLICIT reads it once per tap in the ideal
+        step(i, STEP_IM2COL, 0.0, 4.0 * M * L.K + in_b, src, LOC_NONE);
         snprintf(nm, sizeof(nm), "conv%d.gemm", nconv);
-        p->kernels.push_back({nm, (int)i, 1, flops, in_b + w_b + out_b});
-        ++nconv;
+        step(i, STEP_CONV, flops, 4.0 * M * L.K + w_b + out_b, LOC_NONE, out);
+      } else {  // direct_a reads the input as A; the implicit forms read it once per tap in the ideal
+        snprintf(nm, sizeof(nm), L.variant == CONV_DIRECT ? "conv%d.direct" : L.variant == CONV_PATCH ? "conv%d.patch"
+                                                                                                     : "conv%d.gemm", nconv);
+        step(i, STEP_CONV, flops, in_b + w_b + out_b, src, out);
       }
-      if (L.mode == MODE_X3 && L.splits > 1) {  // raw partials; combined by the next pool, or:
-        slab = std::max(slab, (size_t)L.splits * L.OH * L.OW * L.OC);
-        const bool pool_next = i + 1 < p->layers.size() && p->layers[i + 1].type == LAYER_POOL;
-        if (!pool_next) {
-          snprintf(nm, sizeof(nm), "conv%d.combine", nconv - 1);
-          p->kernels.push_back({nm, (int)i, 3, (L.splits - 1) * M * L.OC, 4.0 * (L.splits + 1) * M * L.OC});
+      const double sum_flops = (L.splits - 1) * M * L.OC, sum_bytes = 4.0 * (L.splits + 1) * M * L.OC;
+      if (is_x3(L.variant)) {
+        if (L.splits > 1) {  // raw partials; combined by the next pool's step, or by a step of its own
+          slab = std::max(slab, (size_t)L.splits * L.OH * L.OW * L.OC);
+          if (!(i + 1 < nl && p->layers[i + 1].type == LAYER_POOL)) {
+            snprintf(nm, sizeof(nm), "conv%d.combine", nconv);
+            step(i, STEP_X3_COMBINE, sum_flops, sum_bytes, LOC_NONE, out);
+          }
         }
-      }
-      if (L.mode == MODE_X3) {
-        // (split-K partials: below)
       } else if (L.splits > 1 && fused_splitk(p)) {  // partials combined by the GEMM's last-arriving split
-        const long long Mg = L.pool ? 4LL * p->batch * L.PH * L.PW : (long long)M;  // the GEMM's rows
+        const long long Mg = L.rows(p->batch);
         slab_fused = std::max(slab_fused, (size_t)(p->fp16 ? splitk16_fused_slab_floats(L.cfg, Mg, L.OC, L.splits)
                                                            : splitk_fused_slab_floats(L.cfg, Mg, L.OC, L.splits)));
         tickets = std::max(tickets, (size_t)(p->fp16 ? splitk16_tiles(L.cfg, Mg, L.OC)
@@ -322,58 +430,35 @@ static void layout(dnn_plan* p) {
           tickets = std::max(tickets, (size_t)splitk16_tiles(GEMM16_128x128, (long long)M, L.OC));
       } else if (L.splits > 1) {  // partials written by the GEMM, summed + epilogue by the reduce kernel
         slab = std::max(slab, (size_t)L.splits * L.OH * L.OW * L.OC);
-        snprintf(nm, sizeof(nm), "conv%d.reduce", nconv - 1);
-        p->kernels.push_back({nm, (int)i, 3, (L.splits - 1) * M * L.OC, 4.0 * (L.splits + 1) * M * L.OC});
+        snprintf(nm, sizeof(nm), "conv%d.reduce", nconv);
+        step(i, STEP_REDUCE, sum_flops, sum_bytes, LOC_NONE, out);
       }
-      if (L.pool) npool++;
+      ++nconv;
+      if (L.pool == POOL_S2) npool++;
     } else if (L.type == LAYER_POOL) {
+      // behind a split x3 conv the pool's kernel sums that conv's partials and applies its epilogue first
+      const bool combines = i > 0 && p->layers[i - 1].is_conv() && is_x3(p->layers[i - 1].variant) &&
+                            p->layers[i - 1].splits > 1;
       snprintf(nm, sizeof(nm), "pool%d", npool++);
-      p->kernels.push_back({nm, (int)i, 2, 0.0, in_b + out_b});
+      step(i, combines ? STEP_X3_COMBINE_POOL : STEP_POOL, 0.0, in_b + out_b, cur, out);
     } else if (L.type == LAYER_ROUTE) {  // reads a and b, writes out: input bytes == output bytes
       snprintf(nm, sizeof(nm), "route%d", nroute++);
-      p->kernels.push_back({nm, (int)i, 5, 0.0, 2.0 * out_b});
+      step(i, STEP_ROUTE, 0.0, 2.0 * out_b, cur, out);
     } else if (L.type == LAYER_SHORTCUT) {  // one add per output element; reads a and b, writes out
       snprintf(nm, sizeof(nm), "shortcut%d", nshort++);
-      p->kernels.push_back({nm, (int)i, 6, out_b / 4.0, 3.0 * out_b});
+      step(i, STEP_SHORTCUT, out_b / 4.0, 3.0 * out_b, cur, out);
     } else if (L.type == LAYER_UPSAMPLE) {
       snprintf(nm, sizeof(nm), "upsample%d", nup++);
-      p->kernels.push_back({nm, (int)i, 7, 0.0, in_b + out_b});
+      step(i, STEP_UPSAMPLE, 0.0, in_b + out_b, cur, out);
     } else if (L.type == LAYER_SPP) {  // reads the input once, writes n_sizes + 1 blocks of its size
       snprintf(nm, sizeof(nm), "spp%d", nspp++);
-      p->kernels.push_back({nm, (int)i, 8, 0.0, in_b + out_b});
-    }  // (a stash, a restore, a release or a tap launches nothing)
-  }
-  // where each layer writes.  Chains keep the ping-pong by layer parity; with fork / join entries
-  // a layer followed by a stash writes that slot's region, and any other one the activation
-  // buffer that does not hold its input (the only other live tensors are in slot regions)
-  {
-    bool fork = false;
-    for (auto& L : p->layers) fork = fork || L.type >= LAYER_STASH;
-    int cur = LOC_IN;
-    size_t last = p->layers.size();  // the last layer that is not a release writes the output
-    while (last > 0 && p->layers[last - 1].type == LAYER_RELEASE) --last;
-    for (size_t i = 0; i < p->layers.size(); ++i) {
-      PlanLayer& L = p->layers[i];
-      if (L.type == LAYER_STASH || L.type == LAYER_RELEASE || L.type == LAYER_TAP) {
-        L.dst_loc = cur;
-      } else if (L.type == LAYER_RESTORE) {
-        L.dst_loc = cur = L.slot_loc;
-      } else {
-        L.dst_loc = i + 1 == last ? LOC_OUT
-                    : !fork                   ? (int)(i & 1)
-                    : L.to_region >= 0        ? LOC_REGION + L.to_region
-                    : cur == LOC_ACT0         ? LOC_ACT1
-                                              : LOC_ACT0;
-        cur = L.dst_loc;
-      }
+      step(i, STEP_SPP, 0.0, in_b + out_b, cur, out);
     }
+    cur = out;
   }
-  if (p->fp16) {  // fp16 plans convert at the edges: fp32 frames in (unless conv0 is direct), fp32 out
-    if (p->layers.empty() || p->layers[0].mode != MODE_DIRECT)
-      p->kernels.insert(p->kernels.begin(), {"input.cvt", -1, 4, 0.0, 6.0 * B * p->in_h * p->in_w * p->in_c});
-    if (!p->direct_out)
-      p->kernels.push_back({"output.cvt", -1, 4, 0.0, 6.0 * B * p->cur_h * p->cur_w * p->cur_c});
-    for (auto& L : p->layers) L.kernel_idx += (p->layers.empty() || p->layers[0].mode != MODE_DIRECT) ? 1 : 0;
+  if (p->fp16 && !p->direct_out) {
+    snprintf(nm, sizeof(nm), "output.cvt");
+    step(-1, STEP_CVT_OUT, 0.0, 6.0 * B * p->cur_h * p->cur_w * p->cur_c, cur, LOC_OUT);
   }
   p->weight_floats = align_up(off, 64);
   // activation buffers hold fp16 elements on the fp16 path
@@ -381,7 +466,7 @@ static void layout(dnn_plan* p) {
   p->col_floats = align_up(col * (size_t)p->batch, 64);
   p->slab_floats = align_up(std::max(slab * (size_t)p->batch, slab_fused), 64);
   p->ticket_floats = align_up(tickets, 64);  // unsigned tickets of the fused split-K layers
-  // zero-bordered activations feeding MODE_PATCH16 (fp16, 2 B per element) / MODE_X3 (3 bf16
+  // zero-bordered activations feeding patch16 / tile16 (fp16, 2 B per element) / x3 (3 bf16
   // pieces, 6 B) layers: one region per producer (zeroed once at finalize; each producer
   // rewrites only its own interior, so its borders stay zero whatever the layers' shapes)
   size_t pad_total = 0;
@@ -400,8 +485,18 @@ static void layout(dnn_plan* p) {
     slot_total += align_up(p->region_elems[r] * (size_t)p->batch, 64);
   }
   p->slot_floats = slot_total;
-  p->ws_floats = 2 * p->act_floats + p->col_floats + p->slab_floats + p->ticket_floats + p->pad_floats +
-                 p->slot_floats + dnn_plan::kZeroFloats;
+  // the workspace: two activation buffers, im2col's col, the split-K slab and tickets, the
+  // zero-bordered areas, the slot regions, the zero page (source of the implicit GEMM's padding taps)
+  WsMap& m = p->at;
+  m.act0 = 0;
+  m.act1 = m.act0 + p->act_floats;
+  m.col = m.act1 + p->act_floats;
+  m.slab = m.col + p->col_floats;
+  m.tickets = m.slab + p->slab_floats;
+  m.pad = m.tickets + p->ticket_floats;
+  m.regions = m.pad + p->pad_floats;
+  m.zero = m.regions + p->slot_floats;
+  p->ws_floats = m.zero + dnn_plan::kZeroFloats;
 }
 
 // While adding: the layer about to be pushed (index layers.size()) consumes or replaces the current
@@ -414,6 +509,16 @@ static void current_leaves(dnn_plan* p) {
 
 static bool slot_is_live(const dnn_plan* p, int slot) {
   return slot >= 0 && slot < (int)p->slots.size() && p->slots[slot].live;
+}
+
+// While adding: a layer that computes replaces the current tensor with its output
+static void push_computing(dnn_plan* p, PlanLayer&& L) {
+  current_leaves(p);
+  p->cur_h = L.out_h();
+  p->cur_w = L.out_w();
+  p->cur_c = L.OC;
+  p->cur_src = -1;
+  p->layers.push_back(std::move(L));
 }
 
 extern "C" {
@@ -452,21 +557,21 @@ void dnn_plan_destroy(dnn_plan* p) {
 
 static void set_cfg(dnn_plan* p, PlanLayer& L) {
   const long long M = (long long)p->batch * L.OH * L.OW;
-  if (!p->fp16 && L.mode == MODE_X3_1X1) {  // one config: 32 x 128 tiles over all of K
+  if (!p->fp16 && is_x3_1x1(L.variant)) {  // one config: 32 x 128 tiles over all of K
     L.cfg = 0;
     L.Kpad = L.K;
     L.Npad = (int)align_up(L.OC, 128);
     L.splits = 1;
     return;
   }
-  if (!p->fp16 && L.mode == MODE_X3) {  // one config per width (kernels_x3.hip); split-K by (N, K) only
+  if (!p->fp16 && is_x3(L.variant)) {  // one config per width (kernels_x3.hip); split-K by (N, K) only
     L.cfg = 0;
     L.Kpad = L.C == 16 ? 160 : L.K;  // (16 channels: 5 steps of two taps)
     L.Npad = L.OC;  // (a multiple of 256, or of 32 / 64 / 128 for the tile kernels)
-    L.splits = L.x3k ? 1 : L.x3lat ? x3_lat_splits(L.OC, L.K) : x3_splits(L.OC, L.K);
+    L.splits = L.variant == CONV_X3_KTILE ? 1 : L.variant == CONV_X3_LAT ? x3_lat_splits(L.OC, L.K) : x3_splits(L.OC, L.K);
     return;
   }
-  if (p->fp16 && L.mode == MODE_PATCH16) {  // one config: 192x256 tiles, no split
+  if (p->fp16 && L.variant == CONV_PATCH16) {  // one config: 192x256 tiles, no split
     L.cfg = 0;
     L.Kpad = L.K;
     L.Npad = (int)align_up(L.OC, 256);
@@ -480,7 +585,7 @@ static void set_cfg(dnn_plan* p, PlanLayer& L) {
     L.splits = (L.Kpad == L.K) ? choose_splitk16(L.OC, L.K) : 1;
     return;
   }
-  L.cfg = L.mode == MODE_IMPLICIT ? choose_gemm_cfg_implicit(M, L.OC, L.K) : choose_gemm_cfg(M, L.OC, L.K);
+  L.cfg = L.variant == CONV_IMPLICIT ? choose_gemm_cfg_implicit(M, L.OC, L.K) : choose_gemm_cfg(M, L.OC, L.K);
   if (const char* e = getenv("DNN_HIP_CFG")) {  // tuning experiments: "K:cfg,K:cfg,..."
     for (const char* q = e; *q;) {
       int k = 0, c = 0, n = 0;
@@ -546,7 +651,22 @@ struct ConvEpilogueSpec {
   int leaky = 0;
 };
 
-// The body both conv entries share: mode selection, config, epilogue parameters.  The caller has
+// fp16 plans: producers that can write their output zero-bordered (what patch16 / tile16 / img16
+// read): a separate pool, a patch16 or tile16 conv, or the pooled conv1 patch kernel
+static bool can_write_zero_bordered16(const PlanLayer& q) {
+  return q.type == LAYER_POOL || q.is(CONV_PATCH16) || (q.is_conv() && is_tile16(q.variant)) ||
+         (q.is(CONV_PATCH) && q.pool == POOL_S2);
+}
+
+// fp32 plans: producers that can write the x3 convs' split planes: a separate pool, another x3
+// conv, a pool-fused implicit GEMM without split-K (its epilogue splits, EPI_OUT_X3) or the
+// pool-fused patch conv (conv1)
+static bool can_write_split_planes(const PlanLayer& q) {
+  return q.type == LAYER_POOL || (q.is_conv() && is_x3(q.variant)) ||
+         (q.is(CONV_IMPLICIT) && q.pool == POOL_S2 && q.splits == 1) || (q.is(CONV_PATCH) && q.pool == POOL_S2);
+}
+
+// The body both conv entries share: variant selection, config, epilogue parameters.  The caller has
 // checked its arguments and worked out the geometry (OH, OW and the front pads pt, pl);
 // `xpad`: the pads were given explicitly (dnn_plan_add_conv_padded), for dnn_plan_describe.
 static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int stride_w, int OH, int pt, int OW,
@@ -555,7 +675,7 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
   const float eps = ep.eps;
   const int leaky = ep.leaky;
   PlanLayer L;
-  L.type = 0;
+  L.type = LAYER_CONV;
   L.H = p->cur_h;
   L.W = p->cur_w;
   L.C = p->cur_c;
@@ -575,24 +695,24 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
   if (p->fp16) {
     // fp16 path: 1x1 on the input, implicit GEMM (C % 8 == 0), or conv0's direct kernel (set
     // when its 2x2/s2 pool arrives); anything else is rejected at finalize
-    L.mode = one_by_one ? MODE_DIRECT_A : (L.C % 8 == 0 && kh * kw <= 30) ? MODE_IMPLICIT : MODE_GEMM;
+    L.variant = one_by_one ? CONV_DIRECT_A : (L.C % 8 == 0 && kh * kw <= 30) ? CONV_IMPLICIT : CONV_GEMM;
     // 3x3 wide layers whose producer (a separate pool or another such conv) can write a
     // zero-bordered output: the patch kernel (input staged once per 64-channel chunk)
-    if (L.mode == MODE_IMPLICIT && !p->layers.empty() &&
+    if (L.variant == CONV_IMPLICIT && !p->layers.empty() &&
         conv_patch16_supported(L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt, L.pl)) {
       PlanLayer& prev = p->layers.back();
-      if (prev.type == 1 || (prev.mode == MODE_PATCH16 && !prev.pool) || prev.mode == MODE_TILE16) {
-        L.mode = MODE_PATCH16;
+      if (can_write_zero_bordered16(prev) && !prev.is(CONV_PATCH)) {  // (not behind the conv1 patch kernel)
+        L.variant = CONV_PATCH16;
         prev.out_padded = true;
       }
     }
   } else if (one_by_one)
-    L.mode = MODE_DIRECT_A;
+    L.variant = CONV_DIRECT_A;
   else if (p->fuse && implicit_conv_supported(L.C, kh, kw) &&
            choose_gemm_cfg_implicit((long long)p->batch * L.OH * L.OW, od, L.K) >= 0)
-    L.mode = MODE_IMPLICIT;
+    L.variant = CONV_IMPLICIT;
   else
-    L.mode = MODE_GEMM;  // may become MODE_DIRECT when a 2x2/s2 pool follows (conv0)
+    L.variant = CONV_GEMM;  // may become CONV_DIRECT when a 2x2/s2 pool follows (conv0)
   // fp32 3x3 wide layers fed by a separate pool or another such conv: the x3 conv (its producer
   // writes the split planes).  Batch plans choose it by the layer alone, so a batch-1 plan and a
   // batch-64 plan run the same arithmetic.  Latency plans (with the in-GEMM split-K combine) take
@@ -601,7 +721,7 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
   // columns x one or two chunks per workgroup, 8 waves splitting rows / columns / chunks;
   // conv6 / conv7 of a one-frame plan) when it makes at least two K slices
   bool x3_cand = false, x3_lat = false, x3_k = false;
-  if (!p->fp16 && L.mode == MODE_IMPLICIT && !p->layers.empty()) {
+  if (!p->fp16 && L.variant == CONV_IMPLICIT && !p->layers.empty()) {
     const bool batch_ok = conv_x3_supported(L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt, L.pl);
     // (the narrow kernels take small tiles in latency plans: batch_ok is enough.  conv1 at one
     // frame: the 16-channel kernel's 4 x 26 tiles 10.6 us, its 16 x 26 ones 11.7, the fp32 patch
@@ -633,26 +753,18 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
   // (latency plans whose frame leaves those tiles few: the K-split 1x1 form, 16 x 32 tiles)
   const long long t1x1 = ((long long)p->batch * L.OH * L.OW + 31) / 32 * ((od + 127) / 128);
   const bool lat1x1 = p->latency && fused_splitk(p) && t1x1 < 256;
-  if (!p->fp16 && L.mode == MODE_DIRECT_A && !p->layers.empty() && p->layers.back().type == 0 &&
-      p->layers.back().mode == MODE_X3 &&
+  if (!p->fp16 && L.variant == CONV_DIRECT_A && !p->layers.empty() && p->layers.back().is_conv() &&
+      is_x3(p->layers.back().variant) &&
       (lat1x1 ? conv_x3_1x1_ktile_supported(L.C, od, L.H, L.W) : conv_x3_1x1_supported(L.C, od, L.H, L.W))) {
-    L.mode = MODE_X3_1X1;
-    L.x3k = lat1x1;
+    L.variant = lat1x1 ? CONV_X3_1X1_KTILE : CONV_X3_1X1;
     p->layers.back().out_padded = true;
   }
   if (x3_cand) {
-    // producers that can write the split planes: a separate pool, another x3 conv, a pool-fused
-    // implicit GEMM without split-K (its epilogue splits, EPI_OUT_X3) or the pool-fused patch
-    // conv (conv1)
     PlanLayer& prev = p->layers.back();
     if (L.C == 16) {  // the 16-channel x3 kernel reads the producer's fp32 output (conv1)
-      L.mode = MODE_X3;
-    } else if ((prev.type == 1 && prev.C % 32 == 0) || (prev.type == 0 && prev.mode == MODE_X3) ||
-        (prev.type == 0 && prev.mode == MODE_IMPLICIT && prev.pool && prev.splits == 1) ||
-        (prev.type == 0 && prev.mode == MODE_PATCH && prev.pool)) {
-      L.mode = MODE_X3;
-      L.x3lat = x3_lat;
-      L.x3k = x3_k;
+      L.variant = CONV_X3;
+    } else if (can_write_split_planes(prev) && (prev.type != LAYER_POOL || prev.C % 32 == 0)) {
+      L.variant = x3_k ? CONV_X3_KTILE : x3_lat ? CONV_X3_LAT : CONV_X3;
       prev.out_padded = true;
     }
   }
@@ -700,12 +812,7 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
       }
     }
   }
-  current_leaves(p);
-  p->layers.push_back(std::move(L));
-  p->cur_h = p->layers.back().OH;
-  p->cur_w = p->layers.back().OW;
-  p->cur_c = od;
-  p->cur_src = -1;
+  push_computing(p, std::move(L));
   return 0;
 }
 
@@ -759,7 +866,7 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_max_pool: plan is NULL or finalized");
   DNN_REQUIRE(kh > 0 && kw > 0 && stride_h > 0 && stride_w > 0, "dnn_plan_add_max_pool: bad args");
   PlanLayer L;
-  L.type = 1;
+  L.type = LAYER_POOL;
   L.H = p->cur_h;
   L.W = p->cur_w;
   L.C = L.OC = p->cur_c;
@@ -775,52 +882,51 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
       L.pl == 0) {
     PlanLayer& prev = p->layers.back();
     // (latency plans: a split implicit conv keeps its split, the combine pools)
-    if (prev.type == 0 && !prev.pool &&
+    if (prev.is_conv() && !prev.pool &&
         (prev.splits == 1 ||
-         (prev.mode == MODE_IMPLICIT && !p->fp16 && fused_splitk(p) && generic_combine_cfg(prev.cfg)))) {
+         (prev.variant == CONV_IMPLICIT && !p->fp16 && fused_splitk(p) && generic_combine_cfg(prev.cfg)))) {
       bool ok = false;
-      if (prev.mode == MODE_IMPLICIT) {
+      if (prev.variant == CONV_IMPLICIT) {
         ok = true;
         if (!p->fp16 && p->patch && prev.splits == 1 && patch_conv_pool_supported(prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw,
                                                   prev.sh, prev.sw, prev.pt, prev.pl) &&
             prev.Kpad == patch_conv_kpad(prev.C))
-          prev.mode = MODE_PATCH;  // same packed weights (Bt[Npad][Kpad]) as the implicit GEMM
+          prev.variant = CONV_PATCH;  // same packed weights (Bt[Npad][Kpad]) as the implicit GEMM
         if (p->fp16 && p->patch &&
             conv1_patch_f16_supported(prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw, prev.sh,
                                       prev.sw, prev.pt, prev.pl))
-          prev.mode = MODE_PATCH;  // fp16 patch kernel on the same fp16 Bt
+          prev.variant = CONV_PATCH;  // fp16 patch kernel on the same fp16 Bt
         // fp16 3x3 layers whose producer can write a zero-bordered output (a separate pool, the
         // conv1 patch kernel, another tile or patch16 conv): the 2-D tile kernel (its weights
         // packed in order 5 into the same Npad x Kpad slot)
-        if (p->fp16 && prev.mode == MODE_IMPLICIT && prev.splits == 1 && p->layers.size() >= 2 &&
+        if (p->fp16 && prev.variant == CONV_IMPLICIT && prev.splits == 1 && p->layers.size() >= 2 &&
             conv_tile16_supported(prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw, prev.sh,
                                   prev.sw, prev.pt, prev.pl) &&
             prev.Kpad % 32 == 0) {
           PlanLayer& q = p->layers[p->layers.size() - 2];
-          if (q.type == 1 || (q.type == 0 && (q.mode == MODE_PATCH16 || q.mode == MODE_TILE16 ||
-                                              (q.mode == MODE_PATCH && q.pool)))) {
-            prev.mode = MODE_TILE16;
+          if (can_write_zero_bordered16(q)) {
+            prev.variant = CONV_TILE16;
             q.out_padded = true;
           }
         }
-      } else if (p->fp16 && prev.mode == MODE_PATCH16 &&
+      } else if (p->fp16 && prev.variant == CONV_PATCH16 &&
                  conv_tile16_supported(prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw, prev.sh,
                                        prev.sw, prev.pt, prev.pl)) {
-        prev.mode = MODE_TILE16;  // (its producer already writes the zero-bordered input) the pool fused
+        prev.variant = CONV_TILE16;  // (its producer already writes the zero-bordered input) the pool fused
         ok = true;
-      } else if (prev.mode == MODE_GEMM && prev.pt == prev.pl && prev.pt <= 1 &&  // (VALID's or SAME's pads: the
+      } else if (prev.variant == CONV_GEMM && prev.pt == prev.pl && prev.pt <= 1 &&  // (VALID's or SAME's pads: the
                  // direct kernels are checked with no others; other explicit pads keep the GEMM)
                  direct_conv_pool_supported(prev.C, prev.OC, prev.kh, prev.kw, prev.sh, prev.sw)) {
-        prev.mode = MODE_DIRECT;
+        prev.variant = CONV_DIRECT;
         ok = true;
-      } else if (prev.mode == MODE_X3 && !p->fp16 &&
-                 (prev.x3k ? conv_x3_ktile_supported(p->batch, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW,
+      } else if (is_x3(prev.variant) && !p->fp16 &&
+                 (prev.variant == CONV_X3_KTILE ? conv_x3_ktile_supported(p->batch, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW,
                                                      prev.kh, prev.kw, prev.sh, prev.sw, prev.pt, prev.pl, 1)
                            : conv_x3_pool_supported(prev.OC, prev.C, prev.H, prev.W))) {
         ok = true;  // pool-window-major rows, pooled before the epilogue in the x3 kernel
       }
       if (ok) {
-        prev.pool = true;
+        prev.pool = POOL_S2;
         prev.PH = L.OH;
         prev.PW = L.OW;
         p->cur_h = L.OH;
@@ -829,29 +935,27 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
       }
     }
   }
-  // a 2x2/stride-1 SAME pool (YOLO's pool5) into a single-frame x3k conv before it: the conv
+  // a 2x2/stride-1 SAME pool (YOLO's pool5) into a single-frame x3_ktile conv before it: the conv
   // computes the row below each tile too and pools before its epilogue
   if (p->fuse && !p->layers.empty() && kh == 2 && kw == 2 && stride_h == 1 && stride_w == 1 && L.pt == 0 &&
       L.pl == 0 && L.OH == L.H && L.OW == L.W) {
     PlanLayer& prev = p->layers.back();
-    if (prev.type == 0 && prev.mode == MODE_X3 && prev.x3k && !prev.pool && !prev.pool1 &&
+    if (prev.is(CONV_X3_KTILE) && !prev.pool &&
         conv_x3_ktile_supported(p->batch, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw,
                                 prev.sh, prev.sw, prev.pt, prev.pl, 2)) {
-      prev.pool1 = true;
+      prev.pool = POOL_S1;
       return 0;
     }
     // ... into an fp16 conv of a 13 x 13 frame fed by a zero-bordered producer (conv5 + pool5 of
     // the fp16 path): the tile kernel's whole-frame form, pool taken from its fp16 stage
-    if (p->fp16 && prev.type == 0 && (prev.mode == MODE_IMPLICIT || prev.mode == MODE_PATCH16) && !prev.pool &&
-        !prev.pool1 && p->layers.size() >= 2 &&
+    if (p->fp16 && (prev.is(CONV_IMPLICIT) || prev.is(CONV_PATCH16)) && !prev.pool && p->layers.size() >= 2 &&
         prev.kh == 3 && prev.kw == 3 && prev.sh == 1 && prev.sw == 1 && prev.pt == 1 && prev.pl == 1 &&
         prev.OH == prev.H && prev.OW == prev.W && prev.Kpad % 32 == 0 &&
         conv_img16_supported(prev.C, prev.OC, prev.H, prev.W)) {
       PlanLayer& q = p->layers[p->layers.size() - 2];
-      if (q.type == 1 || (q.type == 0 && (q.mode == MODE_PATCH16 || q.mode == MODE_TILE16 ||
-                                          (q.mode == MODE_PATCH && q.pool)))) {
-        prev.mode = MODE_TILE16;
-        prev.pool1 = true;
+      if (can_write_zero_bordered16(q)) {
+        prev.variant = CONV_IMG16;
+        prev.pool = POOL_S1;
         prev.splits = 1;
         q.out_padded = true;
         return 0;
@@ -859,19 +963,14 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
     }
     // ... into a batch-tile x3 conv of a small frame (conv5 + pool5): whole-image tiles over all
     // of K (gemm_x3_img.h) instead of K slices whose partials the pool combines
-    if (prev.type == 0 && prev.mode == MODE_X3 && !prev.x3k && !prev.x3lat && !prev.pool && !prev.pool1 &&
-        prev.C != 16 && conv_x3_img_supported(prev.C, prev.OC, prev.H, prev.W)) {
-      prev.pool1 = true;
-      prev.x3img = true;
+    if (prev.is(CONV_X3) && !prev.pool && prev.C != 16 && conv_x3_img_supported(prev.C, prev.OC, prev.H, prev.W)) {
+      prev.variant = CONV_X3_IMG;
+      prev.pool = POOL_S1;
       prev.splits = 1;
       return 0;
     }
   }
-  current_leaves(p);
-  p->layers.push_back(std::move(L));
-  p->cur_h = p->layers.back().OH;
-  p->cur_w = p->layers.back().OW;
-  p->cur_src = -1;
+  push_computing(p, std::move(L));
   return 0;
 }
 
@@ -945,8 +1044,7 @@ int dnn_plan_tap_buffer(const dnn_plan* p, int index, void** ptr, size_t* bytes)
   DNN_REQUIRE(index >= 0 && index < (int)p->taps.size(), "dnn_plan_tap_buffer: tap %d of %d", index,
               (int)p->taps.size());
   const PlanTap& T = p->taps[index];
-  float* regions = p->ws + 2 * p->act_floats + p->col_floats + p->slab_floats + p->ticket_floats + p->pad_floats;
-  if (ptr) *ptr = regions + p->region_off[T.region];
+  if (ptr) *ptr = p->ws + p->at.regions + p->region_off[T.region];
   if (bytes) *bytes = (size_t)p->batch * T.h * T.w * T.c * sizeof(float);
   return 0;
 }
@@ -1065,12 +1163,7 @@ int dnn_plan_add_route(dnn_plan* p, int block, int slot, int slot_first) {
     L.slot_loc = S.loc;
   }
   L.OC = block * block * L.C + L.Cb;
-  current_leaves(p);
-  p->layers.push_back(std::move(L));
-  p->cur_h = p->layers.back().OH;
-  p->cur_w = p->layers.back().OW;
-  p->cur_c = p->layers.back().OC;
-  p->cur_src = -1;
+  push_computing(p, std::move(L));
   return 0;
 }
 
@@ -1089,9 +1182,7 @@ int dnn_plan_add_shortcut(dnn_plan* p, int slot, int leaky) {
   L.slot = slot;
   L.slot_loc = S.loc;
   L.leaky = leaky;
-  current_leaves(p);
-  p->layers.push_back(std::move(L));
-  p->cur_src = -1;
+  push_computing(p, std::move(L));
   return 0;
 }
 
@@ -1107,21 +1198,7 @@ int dnn_plan_add_upsample(dnn_plan* p, int factor) {
   L.OH = L.H * factor;
   L.OW = L.W * factor;
   L.factor = factor;
-  current_leaves(p);
-  p->layers.push_back(std::move(L));
-  p->cur_h = p->layers.back().OH;
-  p->cur_w = p->layers.back().OW;
-  p->cur_src = -1;
-  return 0;
-}
-
-static int spp_sizes_ok(const char* who, int n_sizes, const int* sizes) {
-  DNN_REQUIRE(sizes != nullptr, "%s: sizes is NULL", who);
-  DNN_REQUIRE(n_sizes >= 1 && n_sizes <= DNN_SPP_MAX_SIZES, "%s: n_sizes %d outside 1..%d", who, n_sizes,
-              DNN_SPP_MAX_SIZES);
-  for (int j = 0; j < n_sizes; ++j)
-    DNN_REQUIRE(sizes[j] >= 3 && sizes[j] <= DNN_SPP_MAX_K && sizes[j] % 2 == 1,
-                "%s: size %d (entry %d) is not odd and in 3..%d", who, sizes[j], j, DNN_SPP_MAX_K);
+  push_computing(p, std::move(L));
   return 0;
 }
 
@@ -1135,163 +1212,8 @@ int dnn_plan_add_spp(dnn_plan* p, int n_sizes, const int* sizes, int x_first) {
   L.n_sizes = n_sizes;
   for (int j = 0; j < n_sizes; ++j) L.sizes[j] = sizes[j];
   L.x_first = x_first != 0;
-  current_leaves(p);
-  p->layers.push_back(std::move(L));
-  p->cur_c = p->layers.back().OC;
-  p->cur_src = -1;
+  push_computing(p, std::move(L));
   return 0;
-}
-
-int dnn_spp_host(const float* a, float* out, int n, int h, int w, int c, int n_sizes, const int* sizes, int x_first) {
-  DNN_REQUIRE(a && out, "dnn_spp_host: NULL tensor");
-  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_spp_host: bad shape n=%d %dx%dx%d", n, h, w, c);
-  if (int rc = spp_sizes_ok("dnn_spp_host", n_sizes, sizes)) return rc;
-  if (n == 0) return 0;
-  const size_t af = (size_t)n * h * w * c, of = af * (n_sizes + 1);
-  DNN_REQUIRE(of * 4 < 0x80000000ULL, "dnn_spp_host: the output of n=%d %dx%dx%d with %d sizes is >= 2 GiB; split the batch",
-              n, h, w, c, n_sizes);
-  const size_t o_off = align_up(af, 64);
-  float* d = nullptr;
-  DNN_HIP_TRY(hipMalloc(&d, (o_off + of) * sizeof(float)));
-  int rc = 0;
-  if (hipMemcpy(d, a, af * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("dnn_spp_host: host to device copy failed");
-    rc = -1;
-  }
-  if (!rc) rc = launch_spp(d, d + o_off, n, h, w, c, n_sizes, sizes, x_first, nullptr);
-  if (!rc && hipMemcpy(out, d + o_off, of * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-    set_error("dnn_spp_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
-    rc = -1;
-  }
-  (void)hipFree(d);
-  return rc;
-}
-
-int dnn_route_host(const float* a, const float* b, float* out, int n, int h, int w, int ca, int block, int cb,
-                   int b_first) {
-  DNN_REQUIRE(a && out, "dnn_route_host: NULL tensor");
-  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && ca > 0 && cb >= 0, "dnn_route_host: bad shape n=%d %dx%dx%d cb=%d", n, h, w,
-              ca, cb);
-  DNN_REQUIRE(block >= 1 && block <= 8, "dnn_route_host: block %d outside 1..8", block);
-  DNN_REQUIRE(h % block == 0 && w % block == 0, "dnn_route_host: %dx%d input is not a multiple of block %d", h, w,
-              block);
-  DNN_REQUIRE((b != nullptr) == (cb > 0), "dnn_route_host: b must be NULL exactly when cb == 0");
-  if (n == 0) return 0;
-  const size_t pix = (size_t)n * (h / block) * (w / block);
-  const size_t af = (size_t)n * h * w * ca, bf = pix * cb, of = pix * ((size_t)block * block * ca + cb);
-  DNN_REQUIRE(af * 4 < 0x80000000ULL && bf * 4 < 0x80000000ULL && of * 4 < 0x80000000ULL,
-              "dnn_route_host: a tensor of n=%d %dx%dx%d block %d cb=%d is >= 2 GiB; split the batch", n, h, w, ca,
-              block, cb);
-  const size_t a_off = 0, b_off = align_up(af, 64), o_off = b_off + align_up(bf, 64);
-  float* d = nullptr;
-  DNN_HIP_TRY(hipMalloc(&d, (o_off + of) * sizeof(float)));
-  int rc = 0;
-  if (hipMemcpy(d + a_off, a, af * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      (bf && hipMemcpy(d + b_off, b, bf * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) {
-    set_error("dnn_route_host: host to device copy failed");
-    rc = -1;
-  }
-  if (!rc) rc = launch_route(d + a_off, bf ? d + b_off : nullptr, d + o_off, n, h, w, ca, block, cb, b_first, nullptr);
-  if (!rc && hipMemcpy(out, d + o_off, of * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-    set_error("dnn_route_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
-    rc = -1;
-  }
-  (void)hipFree(d);
-  return rc;
-}
-
-int dnn_shortcut_host(const float* a, const float* b, float* out, int n, int h, int w, int c, int leaky) {
-  DNN_REQUIRE(a && b && out, "dnn_shortcut_host: NULL tensor");
-  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_shortcut_host: bad shape n=%d %dx%dx%d", n, h, w, c);
-  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_shortcut_host: leaky must be 0, 1 or 2");
-  if (n == 0) return 0;
-  const size_t f = (size_t)n * h * w * c;
-  DNN_REQUIRE(f * 4 < 0x80000000ULL, "dnn_shortcut_host: a tensor of n=%d %dx%dx%d is >= 2 GiB; split the batch", n, h,
-              w, c);
-  const size_t step = align_up(f, 64);
-  float* d = nullptr;
-  DNN_HIP_TRY(hipMalloc(&d, (2 * step + f) * sizeof(float)));
-  int rc = 0;
-  if (hipMemcpy(d, a, f * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(d + step, b, f * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("dnn_shortcut_host: host to device copy failed");
-    rc = -1;
-  }
-  if (!rc) rc = launch_shortcut(d, d + step, d + 2 * step, (long long)f, leaky, nullptr);
-  if (!rc && hipMemcpy(out, d + 2 * step, f * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-    set_error("dnn_shortcut_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
-    rc = -1;
-  }
-  (void)hipFree(d);
-  return rc;
-}
-
-int dnn_scale_shift_host(const float* a, const float* scale, const float* shift, float* out, int n, int h, int w,
-                         int c, int leaky) {
-  DNN_REQUIRE(a && out, "dnn_scale_shift_host: NULL tensor");
-  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_scale_shift_host: bad shape n=%d %dx%dx%d", n, h, w, c);
-  DNN_REQUIRE((scale == nullptr) == (shift == nullptr), "dnn_scale_shift_host: scale and shift must be both set or both NULL");
-  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_scale_shift_host: leaky must be 0, 1 or 2");
-  DNN_REQUIRE(scale || leaky, "dnn_scale_shift_host: nothing to do (no scale / shift and no leaky)");
-  if (n == 0) return 0;
-  const size_t f = (size_t)n * h * w * c;
-  DNN_REQUIRE(f * 4 < 0x80000000ULL, "dnn_scale_shift_host: a tensor of n=%d %dx%dx%d is >= 2 GiB; split the batch", n,
-              h, w, c);
-  const size_t step = align_up(f, 64), cstep = align_up((size_t)c, 64);
-  std::vector<float> beta(c);
-  for (int k = 0; k < c; ++k) beta[k] = scale ? -shift[k] : 0.f;  // v * alpha - beta, beta = -shift (exact)
-  float* d = nullptr;
-  DNN_HIP_TRY(hipMalloc(&d, (2 * step + 2 * cstep) * sizeof(float)));
-  float *d_t = d + step, *d_al = d + 2 * step, *d_be = d_al + cstep;
-  int rc = 0;
-  if (hipMemcpy(d, a, f * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      (scale && (hipMemcpy(d_al, scale, c * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-                 hipMemcpy(d_be, beta.data(), c * sizeof(float), hipMemcpyHostToDevice) != hipSuccess))) {
-    set_error("dnn_scale_shift_host: host to device copy failed");
-    rc = -1;
-  }
-  const float* res = d;
-  if (!rc && scale) {
-    rc = launch_bn_ab(d, d_al, d_be, d_t, (long long)f, c, nullptr);
-    res = d_t;
-  }
-  if (!rc && leaky) {
-    float* dst = res == d ? d_t : d;
-    rc = launch_leaky(res, dst, (long long)f, leaky == 2 ? 1 : 0, nullptr);
-    res = dst;
-  }
-  if (!rc && hipMemcpy(out, res, f * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-    set_error("dnn_scale_shift_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
-    rc = -1;
-  }
-  (void)hipFree(d);
-  return rc;
-}
-
-int dnn_upsample_host(const float* a, float* out, int n, int h, int w, int c, int factor) {
-  DNN_REQUIRE(a && out, "dnn_upsample_host: NULL tensor");
-  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_upsample_host: bad shape n=%d %dx%dx%d", n, h, w, c);
-  DNN_REQUIRE(factor >= 1 && factor <= 8, "dnn_upsample_host: factor %d outside 1..8", factor);
-  if (n == 0) return 0;
-  const size_t af = (size_t)n * h * w * c;
-  DNN_REQUIRE(af * 4 < 0x80000000ULL && af * factor * factor * 4 < 0x80000000ULL,
-              "dnn_upsample_host: the output of n=%d %dx%dx%d factor %d is >= 2 GiB; split the batch", n, h, w, c,
-              factor);
-  const size_t of = af * factor * factor, o_off = align_up(af, 64);
-  float* d = nullptr;
-  DNN_HIP_TRY(hipMalloc(&d, (o_off + of) * sizeof(float)));
-  int rc = 0;
-  if (hipMemcpy(d, a, af * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-    set_error("dnn_upsample_host: host to device copy failed");
-    rc = -1;
-  }
-  if (!rc) rc = launch_upsample(d, d + o_off, n, h, w, c, factor, nullptr);
-  if (!rc && hipMemcpy(out, d + o_off, of * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) {
-    set_error("dnn_upsample_host: device to host copy failed (%s)", hipGetErrorString(hipGetLastError()));
-    rc = -1;
-  }
-  (void)hipFree(d);
-  return rc;
 }
 
 int dnn_plan_output_shape(const dnn_plan* p, int* batch, int* h, int* w, int* c) {
@@ -1315,7 +1237,7 @@ int dnn_plan_memory(const dnn_plan* pc, size_t* weight_bytes, size_t* workspace_
 static int upload_weights(dnn_plan* p) {
   size_t maxw = 0, maxp = 0;
   for (auto& L : p->layers)
-    if (L.type == 0) {
+    if (L.is_conv()) {
       maxw = std::max(maxw, L.w.size());
       maxp = std::max(maxp, (size_t)L.Npad * L.Kpad);
     }
@@ -1324,20 +1246,22 @@ static int upload_weights(dnn_plan* p) {
   float* packed32 = tmp + std::max<size_t>(maxw, 1);  // fp16 plans: fp32 pack, then convert
   int rc = 0;
   for (auto& L : p->layers) {
-    if (L.type != 0) continue;
+    if (!L.is_conv()) continue;
     const size_t wb = L.w.size() * sizeof(float);
-    if (L.mode == MODE_DIRECT) {  // HWIO [K][N] as is: one 16-float row per (tap, cin)
+    const WeightPack pack = weight_pack(L.variant);
+    if (pack == PACK_HWIO) {  // HWIO [K][N] as is: one 16-float row per (tap, cin)
       if (hipMemcpy(p->weights + L.w_off, L.w.data(), wb, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
     } else {
       if (hipMemcpy(tmp, L.w.data(), wb, hipMemcpyHostToDevice) != hipSuccess) rc = -1;
       if (p->fp16) {
         if (!rc)
-          rc = launch_pack_weights(tmp, packed32, L.K, L.OC, L.Kpad, L.Npad, L.mode == MODE_TILE16 ? 5 : L.mode == MODE_PATCH16 ? patch16_pack_order() : 0, L.kh,
-                                   L.kw, L.C, 0);
+          rc = launch_pack_weights(tmp, packed32, L.K, L.OC, L.Kpad, L.Npad,
+                                   pack == PACK_BT_TILE16 ? 5 : pack == PACK_BT_PATCH16 ? patch16_pack_order() : 0,
+                                   L.kh, L.kw, L.C, 0);
         if (!rc)
           rc = launch_f32_to_f16(packed32, reinterpret_cast<half_t*>(p->weights + L.w_off),
                                  (long long)L.Npad * L.Kpad, 0);
-      } else if (!rc && (L.mode == MODE_X3 || L.mode == MODE_X3_1X1)) {
+      } else if (!rc && pack == PACK_X3) {
         rc = launch_pack_weights_x3(tmp, reinterpret_cast<unsigned short*>(p->weights + L.w_off), L.K, L.OC, L.Npad,
                                     L.C, 0);
       } else if (!rc) {
@@ -1377,10 +1301,10 @@ int dnn_plan_finalize(dnn_plan* p, int device, void* weights, void* workspace) {
   }
   if (p->fp16)
     for (auto& L : p->layers) {
-      DNN_REQUIRE(L.type != 0 || L.mode != MODE_GEMM,
+      DNN_REQUIRE(!L.is(CONV_GEMM),
                   "dnn_plan_finalize: fp16 plan cannot run conv %dx%dx%d k%dx%d (needs C %% 8 == 0, or <= 4 "
                   "input channels with a fused 2x2/s2 pool)", L.H, L.W, L.C, L.kh, L.kw);
-      DNN_REQUIRE(L.type != 1 || L.C % 8 == 0, "dnn_plan_finalize: fp16 pool needs C %% 8 == 0 (C=%d)", L.C);
+      DNN_REQUIRE(L.type != LAYER_POOL || L.C % 8 == 0, "dnn_plan_finalize: fp16 pool needs C %% 8 == 0 (C=%d)", L.C);
     }
   layout(p);
   // the fused kernels' output stores take 32-bit byte offsets from their region's base (the
@@ -1411,16 +1335,14 @@ int dnn_plan_finalize(dnn_plan* p, int device, void* weights, void* workspace) {
     p->own_ws = true;
   }
   // zero page at the end of the workspace (padding taps of the implicit GEMM read it)
-  DNN_HIP_TRY(hipMemset(p->ws + p->ws_floats - dnn_plan::kZeroFloats, 0, dnn_plan::kZeroFloats * sizeof(float)));
+  DNN_HIP_TRY(hipMemset(p->ws + p->at.zero, 0, dnn_plan::kZeroFloats * sizeof(float)));
   if (p->pad_floats)  // zero borders of the padded activations (interiors are rewritten every run)
-    DNN_HIP_TRY(hipMemset(p->ws + 2 * p->act_floats + p->col_floats + p->slab_floats + p->ticket_floats, 0,
-                          p->pad_floats * sizeof(float)));
+    DNN_HIP_TRY(hipMemset(p->ws + p->at.pad, 0, p->pad_floats * sizeof(float)));
   if (p->ticket_floats)  // fused split-K tickets start at zero; every launch leaves them zero
-    DNN_HIP_TRY(hipMemset(p->ws + 2 * p->act_floats + p->col_floats + p->slab_floats, 0,
-                          p->ticket_floats * sizeof(float)));
+    DNN_HIP_TRY(hipMemset(p->ws + p->at.tickets, 0, p->ticket_floats * sizeof(float)));
   bool all_host = true;
   for (auto& L : p->layers)
-    if (L.type == 0 && !L.have_host) all_host = false;
+    if (L.is_conv() && !L.have_host) all_host = false;
   if (all_host) {
     int rc = upload_weights(p);
     if (rc) return rc;
@@ -1473,250 +1395,218 @@ static int record_events(dnn_plan* p, int kernel, hipStream_t s) {
   return 0;
 }
 
-// fp16 path: fp16 activations between layers, fp32 frames in / predictions out
-static int run_fp16(dnn_plan* p, int n, const float* d_in, float* d_out, hipStream_t s) {
-  half_t* act[2] = {reinterpret_cast<half_t*>(p->ws), reinterpret_cast<half_t*>(p->ws + p->act_floats)};
-  float* slab = p->ws + 2 * p->act_floats + p->col_floats;
-  unsigned* tickets = fused_splitk(p) ? reinterpret_cast<unsigned*>(slab + p->slab_floats) : nullptr;
-  const float* zero = p->ws + p->ws_floats - dnn_plan::kZeroFloats;
-  const int nl = (int)p->layers.size();
-  const half_t* cur = nullptr;
-  int rc = 0;
-  if (p->layers[0].mode != MODE_DIRECT) {  // convert the frames once (into act[1]: layer 0 writes act[0])
-    if ((rc = record(p, 0, s))) return rc;
-    if ((rc = launch_f32_to_f16(d_in, act[1], (long long)n * p->in_h * p->in_w * p->in_c, s))) return rc;
-    cur = act[1];
+// What a run gives its steps: the image count (<= batch), the caller's tensors and the stream
+struct RunArgs {
+  int n;
+  const float* d_in;
+  float* d_out;
+  hipStream_t s;
+};
+
+// the address of a location in this run (LOC_IN is only ever read; LOC_NONE: NULL)
+static float* locate(const dnn_plan* p, const RunArgs& r, int loc) {
+  if (loc >= LOC_PAD) return p->ws + p->at.pad + p->layers[loc - LOC_PAD].pad_off;
+  if (loc >= LOC_REGION) return p->ws + p->at.regions + p->region_off[loc - LOC_REGION];
+  switch (loc) {
+    case LOC_OUT: return r.d_out;
+    case LOC_IN: return const_cast<float*>(r.d_in);
+    case LOC_ACT0: return p->ws + p->at.act0;
+    case LOC_ACT1: return p->ws + p->at.act1;
+    default: return nullptr;
   }
-  half_t* padr = reinterpret_cast<half_t*>(p->ws + 2 * p->act_floats + p->col_floats + p->slab_floats +
-                                            p->ticket_floats);
-  for (int i = 0; i < nl; ++i) {
-    PlanLayer& L = p->layers[i];
-    half_t* dst = L.out_padded ? padr + L.pad_off * 2 : act[i & 1];
-    int k = L.kernel_idx;
-    if (L.type == 0) {
-      const float* e = p->weights + L.epi_off;
-      const EpiParams epi{e, e + L.Npad, e + 2 * L.Npad, e + 3 * L.Npad, L.epi_flags};
-      const half_t* wt = reinterpret_cast<const half_t*>(p->weights + L.w_off);
-      if ((rc = record(p, k, s))) return rc;
-      const long long Mc = (long long)n * L.OH * L.OW;
-      switch (L.mode) {
-        case MODE_DIRECT: {
-          DirectGeom g{n, L.H, L.W, L.OH, L.OW, L.PH, L.PW, L.pt, L.pl};
-          rc = conv0_mfma_supported(L.C, L.OC, L.kh, L.kw, L.sh, L.sw)
-                   ? launch_conv0_mfma_f16(d_in, p->weights + L.w_off, dst, g, L.C, epi, s)
-                   : launch_conv3x3_pool2_direct_f16out(d_in, p->weights + L.w_off, dst, g, L.C, L.OC, epi, s);
-          break;
-        }
-        case MODE_PATCH: {
-          DirectGeom g{n, L.H, L.W, L.OH, L.OW, L.PH, L.PW, L.pt, L.pl};
-          rc = launch_conv1_patch_f16(cur, wt, L.Kpad, dst, g, zero, epi, s, L.out_padded ? 1 : 0);
-          break;
-        }
-        case MODE_DIRECT_A:
-          if (i == nl - 1 && p->direct_out) {
-            rc = launch_gemm16_f32out(cur, L.C, wt, L.Kpad, L.Npad, d_out, L.OC, Mc, L.OC, L.Kpad, epi, s);
-            if (rc) return rc;
-            return record(p, -1, s);
-          }
-          rc = launch_gemm16(L.cfg, GEMM_DENSE, cur, L.C, ImplicitConv{}, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad,
-                             epi, s, L.splits, slab, tickets);
-          break;
-        case MODE_PATCH16:
-          rc = launch_conv_patch16(cur, wt, L.Kpad, dst, L.out_padded ? 1 : 0, Mc, L.OC, L.K, L.H, L.W, L.C, epi, s);
-          break;
-        case MODE_TILE16:
-          rc = launch_conv_tile16(cur, wt, L.Kpad, dst, L.out_padded ? 1 : 0, n, L.OC, L.K, L.H, L.W, L.C, epi, s,
-                                  L.pool1 ? 2 : 1);
-          break;
-        case MODE_IMPLICIT: {
-          ImplicitConv ic{zero, L.H, L.W, L.C, L.OH, L.OW, L.PH, L.PW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl,
-                          L.pool ? 1 : 0};
-          const long long M = L.pool ? 4LL * n * L.PH * L.PW : Mc;
-          rc = launch_gemm16(L.cfg, L.pool ? GEMM_IMPLICIT_POOL : GEMM_IMPLICIT, cur, 0, ic, wt, L.Kpad, dst, L.OC,
-                             M, L.OC, L.Kpad, epi, s, L.splits, slab, tickets);
-          break;
-        }
-        default:
-          set_error("dnn_plan_run: fp16 plan has an unsupported conv mode %d", L.mode);
-          return -2;
-      }
-      if (rc) return rc;
-      if (L.splits > 1 && !tickets) {
-        if ((rc = record(p, ++k, s))) return rc;
-        if ((rc = launch_splitk_reduce16(slab, L.splits, Mc, L.OC, dst, L.OC, epi, s))) return rc;
-      }
-    } else {
-      PoolGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, 0};
-      if ((rc = record(p, k, s))) return rc;
-      if ((rc = launch_maxpool16(cur, dst, g, s, L.out_padded ? 1 : 0))) return rc;
-    }
-    cur = dst;
-  }
-  if ((rc = record(p, (int)p->kernels.size() - 1, s))) return rc;
-  if ((rc = launch_f16_to_f32(cur, d_out, (long long)n * p->cur_h * p->cur_w * p->cur_c, s))) return rc;
-  return record(p, -1, s);
 }
 
+static EpiParams epilogue(const dnn_plan* p, const PlanLayer& L) {
+  const float* e = p->weights + L.epi_off;
+  return EpiParams{e, e + L.Npad, e + 2 * L.Npad, e + 3 * L.Npad, L.epi_flags};
+}
+
+static unsigned* ticket_area(const dnn_plan* p) {  // (NULL: split layers leave partials for a reduce step)
+  return fused_splitk(p) ? reinterpret_cast<unsigned*>(p->ws + p->at.tickets) : nullptr;
+}
+
+// fp16 plans: fp16 activations between layers, fp32 frames in / predictions out
+static int launch_step16(dnn_plan* p, const Step& st, const RunArgs& r) {
+  const int n = r.n;
+  hipStream_t s = r.s;
+  float* src32 = locate(p, r, st.src);  // (fp32 at the plan's edges: the frames, the output)
+  float* dst32 = locate(p, r, st.dst);
+  const half_t* cur = reinterpret_cast<const half_t*>(src32);
+  half_t* dst = reinterpret_cast<half_t*>(dst32);
+  if (st.kind == STEP_CVT_IN) return launch_f32_to_f16(src32, dst, (long long)n * p->in_h * p->in_w * p->in_c, s);
+  if (st.kind == STEP_CVT_OUT) return launch_f16_to_f32(cur, dst32, (long long)n * p->cur_h * p->cur_w * p->cur_c, s);
+  const PlanLayer& L = p->layers[st.layer];
+  const int padded = st.dst >= LOC_PAD ? 1 : 0;  // the output is written zero-bordered
+  float* slab = p->ws + p->at.slab;
+  const float* zero = p->ws + p->at.zero;
+  const long long Mc = (long long)n * L.OH * L.OW;
+  switch (st.kind) {
+    case STEP_POOL: {
+      PoolGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, 0};
+      return launch_maxpool16(cur, dst, g, s, padded);
+    }
+    case STEP_REDUCE:
+      return launch_splitk_reduce16(slab, L.splits, Mc, L.OC, dst, L.OC, epilogue(p, L), s);
+    case STEP_CONV:
+      break;  // (below)
+    default:
+      set_error("dnn_plan_run: fp16 plan has an unsupported step kind %d", (int)st.kind);
+      return -2;
+  }
+  const EpiParams epi = epilogue(p, L);
+  const half_t* wt = reinterpret_cast<const half_t*>(p->weights + L.w_off);
+  const DirectGeom dg{n, L.H, L.W, L.OH, L.OW, L.PH, L.PW, L.pt, L.pl};
+  switch (L.variant) {
+    case CONV_DIRECT:  // (conv0: its source is the fp32 frames, its weights stay fp32)
+      return conv0_mfma_supported(L.C, L.OC, L.kh, L.kw, L.sh, L.sw)
+                 ? launch_conv0_mfma_f16(src32, p->weights + L.w_off, dst, dg, L.C, epi, s)
+                 : launch_conv3x3_pool2_direct_f16out(src32, p->weights + L.w_off, dst, dg, L.C, L.OC, epi, s);
+    case CONV_PATCH:
+      return launch_conv1_patch_f16(cur, wt, L.Kpad, dst, dg, zero, epi, s, padded);
+    case CONV_DIRECT_A:
+      if (st.dst == LOC_OUT)  // (direct_out: the last layer writes the fp32 output)
+        return launch_gemm16_f32out(cur, L.C, wt, L.Kpad, L.Npad, dst32, L.OC, Mc, L.OC, L.Kpad, epi, s);
+      return launch_gemm16(L.cfg, GEMM_DENSE, cur, L.C, ImplicitConv{}, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s,
+                           L.splits, slab, ticket_area(p));
+    case CONV_PATCH16:
+      return launch_conv_patch16(cur, wt, L.Kpad, dst, padded, Mc, L.OC, L.K, L.H, L.W, L.C, epi, s);
+    case CONV_TILE16:
+    case CONV_IMG16:
+      return launch_conv_tile16(cur, wt, L.Kpad, dst, padded, n, L.OC, L.K, L.H, L.W, L.C, epi, s, L.pool);
+    case CONV_IMPLICIT: {
+      ImplicitConv ic{zero, L.H, L.W, L.C, L.OH, L.OW, L.PH, L.PW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl,
+                      L.pool == POOL_S2 ? 1 : 0};
+      return launch_gemm16(L.cfg, L.pool == POOL_S2 ? GEMM_IMPLICIT_POOL : GEMM_IMPLICIT, cur, 0, ic, wt, L.Kpad, dst,
+                           L.OC, L.rows(n), L.OC, L.Kpad, epi, s, L.splits, slab, ticket_area(p));
+    }
+    default:
+      set_error("dnn_plan_run: fp16 plan has an unsupported conv mode %d", L.variant);
+      return -2;
+  }
+}
+
+// fp32 plans.  The launchers that can write x3 split planes take both outputs, one of them NULL
+static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
+  const int n = r.n;
+  hipStream_t s = r.s;
+  const PlanLayer& L = p->layers[st.layer];
+  const float* cur = locate(p, r, st.src);
+  // dst: the layer's plain NHWC output; dsplit: its split-plane area, when that is what the step writes
+  float* dst = locate(p, r, L.dst_loc);
+  unsigned short* dsplit = st.dst >= LOC_PAD ? reinterpret_cast<unsigned short*>(locate(p, r, st.dst)) : nullptr;
+  float* slab = p->ws + p->at.slab;
+  const float* zero = p->ws + p->at.zero;
+  const long long Mc = (long long)n * L.OH * L.OW;
+  switch (st.kind) {
+    case STEP_IM2COL: {
+      ConvGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, L.K, L.Kpad};
+      return launch_im2col(cur, p->ws + p->at.col, g, s);
+    }
+    case STEP_CONV:
+      break;  // (below)
+    case STEP_REDUCE:
+      return launch_splitk_reduce(slab, L.splits, Mc, L.OC, dst, L.OC, epilogue(p, L), s);
+    case STEP_X3_COMBINE: {
+      PoolGeom id{n, L.OH, L.OW, L.OC, L.OH, L.OW, 1, 1, 1, 1, 0, 0, 0};
+      return launch_x3_combine(slab, L.splits, Mc * L.OC, epilogue(p, L), id, dsplit ? nullptr : dst, dsplit, s);
+    }
+    case STEP_POOL: {
+      PoolGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, 0};
+      return dsplit ? launch_maxpool_x3(cur, dsplit, g, s) : launch_maxpool(cur, dst, g, s);
+    }
+    case STEP_X3_COMBINE_POOL: {  // the conv before this pool left partials: sum, its epilogue, pool
+      PoolGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, 0};
+      const PlanLayer& conv = p->layers[st.layer - 1];
+      return launch_x3_combine(slab, conv.splits, (long long)n * conv.OH * conv.OW * conv.OC, epilogue(p, conv), g,
+                               dsplit ? nullptr : dst, dsplit, s);
+    }
+    case STEP_ROUTE:
+      return launch_route(cur, L.slot >= 0 ? locate(p, r, L.slot_loc) : nullptr, dst, n, L.H, L.W, L.C, L.block, L.Cb,
+                          L.slot_first ? 1 : 0, s);
+    case STEP_SHORTCUT:
+      return launch_shortcut(cur, locate(p, r, L.slot_loc), dst, (long long)n * L.H * L.W * L.C, L.leaky, s);
+    case STEP_UPSAMPLE:
+      return launch_upsample(cur, dst, n, L.H, L.W, L.C, L.factor, s);
+    case STEP_SPP:
+      return launch_spp(cur, dst, n, L.H, L.W, L.C, L.n_sizes, L.sizes, L.x_first ? 1 : 0, s);
+    default:
+      set_error("dnn_plan_run: fp32 plan has an unsupported step kind %d", (int)st.kind);
+      return -2;
+  }
+  const EpiParams epi = epilogue(p, L);
+  const float* wt = p->weights + L.w_off;
+  const unsigned short* cur3 = reinterpret_cast<const unsigned short*>(cur);  // (x3 convs: split planes in,
+  const unsigned short* wt3 = reinterpret_cast<const unsigned short*>(wt);    //  three bf16 pieces per weight)
+  const DirectGeom dg{n, L.H, L.W, L.OH, L.OW, L.PH, L.PW, L.pt, L.pl};
+  switch (L.variant) {
+    case CONV_GEMM:
+      return launch_gemm(L.cfg, p->ws + p->at.col, L.Kpad, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s, L.splits,
+                         slab, ticket_area(p));
+    case CONV_DIRECT_A:
+      return launch_gemm(L.cfg, cur, L.C, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s, L.splits, slab,
+                         ticket_area(p));
+    case CONV_IMPLICIT: {
+      ImplicitConv ic{zero, L.H, L.W, L.C, L.OH, L.OW, L.PH, L.PW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl,
+                      L.pool == POOL_S2 ? 1 : 0};
+      const long long M = L.rows(n);
+      const int gm = L.pool == POOL_S2 ? GEMM_IMPLICIT_POOL : GEMM_IMPLICIT;
+      // feeding an x3 conv: the pooled epilogue stores the split planes (EPI_OUT_X3)
+      EpiParams ep = epi;
+      float* o = dst;
+      if (dsplit) {
+        ep.flags |= EPI_OUT_X3;
+        o = reinterpret_cast<float*>(dsplit);
+      }
+      // unsplit layers: the persistent kernel (same bits) when it covers the config
+      int rc = L.splits == 1 ? launch_gemm_persist(L.cfg, gm, cur, ic, wt, L.Kpad, o, L.OC, M, L.OC, L.Kpad, ep, s) : -3;
+      if (rc == -3)
+        rc = launch_gemm_implicit(L.cfg, gm, cur, ic, wt, L.Kpad, o, L.OC, M, L.OC, L.Kpad, ep, s, L.splits, slab,
+                                  ticket_area(p));
+      return rc;
+    }
+    case CONV_DIRECT:
+      return conv0_mfma_supported(L.C, L.OC, L.kh, L.kw, L.sh, L.sw)
+                 ? launch_conv0_mfma(cur, wt, dst, dg, L.C, zero, epi, s)
+                 : launch_conv3x3_pool2_direct(cur, wt, dst, dg, L.C, L.OC, epi, s);
+    case CONV_PATCH:
+      return launch_conv3x3_patch_pool(cur, wt, L.Kpad, dst, dg, L.C, L.OC, zero, epi, s, dsplit);
+    case CONV_X3_1X1:
+      return launch_conv_x3_1x1(cur3, wt3, dst, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s);
+    case CONV_X3_1X1_KTILE:
+      return launch_conv_x3_1x1_ktile(cur3, wt3, dst, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s);
+    case CONV_X3_IMG:
+      return launch_conv_x3_img(cur3, wt3, dsplit ? nullptr : dst, dsplit, n, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s);
+    case CONV_X3_KTILE:
+      return launch_conv_x3_ktile(cur3, wt3, dsplit ? nullptr : dst, dsplit, L.rows(n), L.OC, L.Npad, L.K, L.H, L.W,
+                                  L.C, epi, s, L.pool);
+    case CONV_X3_LAT:  // (always split: raw partials into the slab; the next pool's step or a combine step finishes)
+      return launch_conv_x3_lat(cur3, wt3, slab, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, L.splits, s);
+    case CONV_X3:
+      if (L.splits > 1)  // raw partials into the slab, as above
+        return launch_conv_x3(cur3, wt3, slab, nullptr, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s, L.splits);
+      return launch_conv_x3(cur3, wt3, dsplit ? nullptr : dst, dsplit, L.rows(n), L.OC, L.Npad, L.K, L.H, L.W, L.C, epi,
+                            s, 1, L.pool == POOL_S2 ? 1 : 0, p->latency && fused_splitk(p));
+    default:
+      set_error("dnn_plan_run: fp32 plan has an unsupported conv mode %d", L.variant);
+      return -2;
+  }
+}
+
+// The walker: step i is kernel i of the ABI.  Before each step (its index) and after the last one
+// (-1) record() places the timing events, the mark and the clock stamps.
 int dnn_plan_run(dnn_plan* p, int n, const float* d_in, float* d_out, void* stream) {
   DNN_REQUIRE(p && p->finalized, "dnn_plan_run: plan not finalized");
   DNN_REQUIRE(n >= 0 && n <= p->batch, "dnn_plan_run: n=%d outside [0, %d]", n, p->batch);
   if (n == 0) return 0;
   DNN_REQUIRE(d_in && d_out, "dnn_plan_run: NULL tensor");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (p->fp16) return run_fp16(p, n, d_in, d_out, s);
-  float* act[2] = {p->ws, p->ws + p->act_floats};
-  float* col = p->ws + 2 * p->act_floats;
-  float* slab = col + p->col_floats;
-  unsigned* tickets = fused_splitk(p) ? reinterpret_cast<unsigned*>(slab + p->slab_floats) : nullptr;
-  const float* zero = p->ws + p->ws_floats - dnn_plan::kZeroFloats;
-  const float* cur = d_in;
-  const int nl = (int)p->layers.size();
-  unsigned short* padr = reinterpret_cast<unsigned short*>(slab + p->slab_floats + p->ticket_floats);
-  float* regions = slab + p->slab_floats + p->ticket_floats + p->pad_floats;
-  auto at = [&](int loc) -> float* {  // (LOC_IN is only ever read)
-    return loc == LOC_OUT ? d_out : loc == LOC_IN ? const_cast<float*>(d_in) : loc < LOC_IN ? act[loc]
-                                                                      : regions + p->region_off[loc - LOC_REGION];
-  };
-  for (int i = 0; i < nl; ++i) {
-    PlanLayer& L = p->layers[i];
-    // a stash or a tap: its producer wrote the region (or it is d_in); a release: nothing to do
-    if (L.type == LAYER_STASH || L.type == LAYER_RELEASE || L.type == LAYER_TAP) continue;
-    if (L.type == LAYER_RESTORE) {
-      cur = at(L.dst_loc);
-      continue;
-    }
-    float* dst = at(L.dst_loc);  // chains: d_out for the last layer, else act[i & 1]
-    // output in x3 split planes (the next layer is MODE_X3)
-    unsigned short* dsplit = L.out_padded ? padr + L.pad_off * 2 : nullptr;
-    int k = L.kernel_idx;
-    int rc = 0;
-    if (L.type == 0) {
-      const float* e = p->weights + L.epi_off;
-      const EpiParams epi{e, e + L.Npad, e + 2 * L.Npad, e + 3 * L.Npad, L.epi_flags};
-      const float* wt = p->weights + L.w_off;
-      if ((rc = record(p, k, s))) return rc;
-      const long long Mc = (long long)n * L.OH * L.OW;
-      switch (L.mode) {
-        case MODE_GEMM: {
-          ConvGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, L.K, L.Kpad};
-          if ((rc = launch_im2col(cur, col, g, s))) return rc;
-          if ((rc = record(p, ++k, s))) return rc;
-          rc = launch_gemm(L.cfg, col, L.Kpad, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s, L.splits, slab,
-                           tickets);
-          break;
-        }
-        case MODE_DIRECT_A:
-          rc = launch_gemm(L.cfg, cur, L.C, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s, L.splits, slab,
-                           tickets);
-          break;
-        case MODE_IMPLICIT: {
-          ImplicitConv ic{zero, L.H, L.W, L.C, L.OH, L.OW, L.PH, L.PW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl,
-                          L.pool ? 1 : 0};
-          const long long M = L.pool ? 4LL * n * L.PH * L.PW : Mc;
-          const int gm = L.pool ? GEMM_IMPLICIT_POOL : GEMM_IMPLICIT;
-          // feeding an x3 conv: the pooled epilogue stores the split planes (EPI_OUT_X3)
-          EpiParams ep = epi;
-          float* o = dst;
-          if (dsplit) {
-            ep.flags |= EPI_OUT_X3;
-            o = reinterpret_cast<float*>(dsplit);
-          }
-          // unsplit layers: the persistent kernel (same bits) when it covers the config
-          rc = L.splits == 1 ? launch_gemm_persist(L.cfg, gm, cur, ic, wt, L.Kpad, o, L.OC, M, L.OC, L.Kpad, ep, s)
-                             : -3;
-          if (rc == -3)
-            rc = launch_gemm_implicit(L.cfg, gm, cur, ic, wt, L.Kpad, o, L.OC, M, L.OC, L.Kpad, ep, s, L.splits,
-                                      slab, tickets);
-          break;
-        }
-        case MODE_DIRECT: {
-          DirectGeom g{n, L.H, L.W, L.OH, L.OW, L.PH, L.PW, L.pt, L.pl};
-          rc = conv0_mfma_supported(L.C, L.OC, L.kh, L.kw, L.sh, L.sw)
-                   ? launch_conv0_mfma(cur, wt, dst, g, L.C, zero, epi, s)
-                   : launch_conv3x3_pool2_direct(cur, wt, dst, g, L.C, L.OC, epi, s);
-          break;
-        }
-        case MODE_PATCH: {
-          DirectGeom g{n, L.H, L.W, L.OH, L.OW, L.PH, L.PW, L.pt, L.pl};
-          rc = launch_conv3x3_patch_pool(cur, wt, L.Kpad, dst, g, L.C, L.OC, zero, epi, s, dsplit);
-          break;
-        }
-        case MODE_X3_1X1:
-          rc = L.x3k ? launch_conv_x3_1x1_ktile(reinterpret_cast<const unsigned short*>(cur),
-                                                reinterpret_cast<const unsigned short*>(wt), dst, Mc, L.OC, L.Npad,
-                                                L.K, L.H, L.W, L.C, epi, s)
-                     : launch_conv_x3_1x1(reinterpret_cast<const unsigned short*>(cur),
-                                          reinterpret_cast<const unsigned short*>(wt), dst, Mc, L.OC, L.Npad, L.K, L.H,
-                                          L.W, L.C, epi, s);
-          break;
-        case MODE_X3:
-          if (L.x3img) {
-            rc = launch_conv_x3_img(reinterpret_cast<const unsigned short*>(cur),
-                                    reinterpret_cast<const unsigned short*>(wt), dsplit ? nullptr : dst, dsplit, n,
-                                    L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s);
-          } else if (L.x3k) {
-            rc = launch_conv_x3_ktile(reinterpret_cast<const unsigned short*>(cur),
-                                      reinterpret_cast<const unsigned short*>(wt), dsplit ? nullptr : dst, dsplit,
-                                      L.pool ? 4LL * n * L.PH * L.PW : Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s,
-                                      L.pool ? 1 : L.pool1 ? 2 : 0);
-          } else if (L.splits > 1) {  // raw partials into the slab; the next pool or a combine kernel finishes
-            rc = L.x3lat ? launch_conv_x3_lat(reinterpret_cast<const unsigned short*>(cur),
-                                              reinterpret_cast<const unsigned short*>(wt), slab, Mc, L.OC, L.Npad, L.K,
-                                              L.H, L.W, L.C, L.splits, s)
-                         : launch_conv_x3(reinterpret_cast<const unsigned short*>(cur),
-                                          reinterpret_cast<const unsigned short*>(wt), slab, nullptr, Mc, L.OC, L.Npad,
-                                          L.K, L.H, L.W, L.C, epi, s, L.splits);
-            if (!rc && !(i + 1 < nl && p->layers[i + 1].type == LAYER_POOL)) {
-              PoolGeom id{n, L.OH, L.OW, L.OC, L.OH, L.OW, 1, 1, 1, 1, 0, 0, 0};
-              if ((rc = record(p, ++k, s))) return rc;
-              rc = launch_x3_combine(slab, L.splits, Mc * L.OC, epi, id, dsplit ? nullptr : dst, dsplit, s);
-            }
-          } else {
-            rc = launch_conv_x3(reinterpret_cast<const unsigned short*>(cur),
-                                reinterpret_cast<const unsigned short*>(wt), dsplit ? nullptr : dst, dsplit,
-                                L.pool ? 4LL * n * L.PH * L.PW : Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s, 1,
-                                L.pool ? 1 : 0, p->latency && fused_splitk(p));
-          }
-          break;
-        default:
-          set_error("dnn_plan_run: fp32 plan has an unsupported conv mode %d", L.mode);
-          return -2;
-      }
-      if (rc) return rc;
-      if (L.splits > 1 && !tickets && L.mode != MODE_X3) {
-        if ((rc = record(p, ++k, s))) return rc;
-        if ((rc = launch_splitk_reduce(slab, L.splits, Mc, L.OC, dst, L.OC, epi, s))) return rc;
-      }
-    } else if (L.type == LAYER_ROUTE) {
-      if ((rc = record(p, k, s))) return rc;
-      const float* b = L.slot >= 0 ? at(L.slot_loc) : nullptr;
-      if ((rc = launch_route(cur, b, dst, n, L.H, L.W, L.C, L.block, L.Cb, L.slot_first ? 1 : 0, s))) return rc;
-    } else if (L.type == LAYER_SHORTCUT) {
-      if ((rc = record(p, k, s))) return rc;
-      if ((rc = launch_shortcut(cur, at(L.slot_loc), dst, (long long)n * L.H * L.W * L.C, L.leaky, s))) return rc;
-    } else if (L.type == LAYER_UPSAMPLE) {
-      if ((rc = record(p, k, s))) return rc;
-      if ((rc = launch_upsample(cur, dst, n, L.H, L.W, L.C, L.factor, s))) return rc;
-    } else if (L.type == LAYER_SPP) {
-      if ((rc = record(p, k, s))) return rc;
-      if ((rc = launch_spp(cur, dst, n, L.H, L.W, L.C, L.n_sizes, L.sizes, L.x_first ? 1 : 0, s))) return rc;
-    } else {
-      PoolGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, 0};
-      if ((rc = record(p, k, s))) return rc;
-      const PlanLayer* pv = i > 0 ? &p->layers[i - 1] : nullptr;
-      if (pv && pv->type == 0 && pv->mode == MODE_X3 && pv->splits > 1) {  // combine the x3 partials + pool
-        const float* e = p->weights + pv->epi_off;
-        const EpiParams pe{e, e + pv->Npad, e + 2 * pv->Npad, e + 3 * pv->Npad, pv->epi_flags};
-        rc = launch_x3_combine(slab, pv->splits, (long long)n * pv->OH * pv->OW * pv->OC, pe, g, dsplit ? nullptr : dst,
-                               dsplit, s);
-      } else {
-        rc = dsplit ? launch_maxpool_x3(cur, dsplit, g, s) : launch_maxpool(cur, dst, g, s);
-      }
-      if (rc) return rc;
-    }
-    cur = dsplit ? reinterpret_cast<const float*>(dsplit) : dst;
+  const RunArgs r{n, d_in, d_out, static_cast<hipStream_t>(stream)};
+  const int ns = (int)p->steps.size();
+  for (int i = 0; i < ns; ++i) {
+    int rc;
+    if ((rc = record(p, i, r.s))) return rc;
+    if ((rc = p->fp16 ? launch_step16(p, p->steps[i], r) : launch_step32(p, p->steps[i], r))) return rc;
   }
-  return record(p, -1, s);
+  return record(p, -1, r.s);
 }
 
 int dnn_plan_run_host(dnn_plan* p, int n, const float* h_in, float* h_out) {
@@ -1775,15 +1665,15 @@ int dnn_plan_num_kernels(const dnn_plan* pc) {
   if (!pc) return -2;
   dnn_plan* p = const_cast<dnn_plan*>(pc);
   if (!p->finalized) layout(p);
-  return (int)p->kernels.size();
+  return (int)p->steps.size();
 }
 
 int dnn_plan_kernel_info(const dnn_plan* pc, int idx, char* name, int name_len, double* flops, double* bytes) {
   DNN_REQUIRE(pc, "dnn_plan_kernel_info: plan is NULL");
   dnn_plan* p = const_cast<dnn_plan*>(pc);
   if (!p->finalized) layout(p);
-  DNN_REQUIRE(idx >= 0 && idx < (int)p->kernels.size(), "dnn_plan_kernel_info: bad index %d", idx);
-  const KernelDesc& k = p->kernels[idx];
+  DNN_REQUIRE(idx >= 0 && idx < (int)p->steps.size(), "dnn_plan_kernel_info: bad index %d", idx);
+  const Step& k = p->steps[idx];
   if (name && name_len > 0) snprintf(name, name_len, "%s", k.name.c_str());
   if (flops) *flops = k.flops;
   if (bytes) *bytes = k.bytes;
@@ -1796,15 +1686,15 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
   char line[256];
   for (size_t i = 0; i < p->layers.size(); ++i) {
     const PlanLayer& L = p->layers[i];
-    if (L.type == 0) {
+    if (L.type == LAYER_CONV) {
       char sk[32] = "", xp[48] = "";
       if (L.splits > 1) snprintf(sk, sizeof(sk), " splitK=%d", L.splits);
       if (L.xpad)  // dnn_plan_add_conv_padded: the pads on every side, and its scale / shift epilogue
         snprintf(xp, sizeof(xp), " pad=%d,%d%s", L.pt, L.pl, (L.epi_flags & EPI_BN_AB) ? " affine" : "");
       snprintf(line, sizeof(line), "conv %dx%dx%d -> %dx%dx%d k%dx%d s%d mode=%s cfg=%d K=%d Kpad=%d%s%s%s%s%s%s\n", L.H,
-               L.W, L.C, L.out_h(), L.out_w(), L.OC, L.kh, L.kw, L.sh, L.x3lat ? "x3_lat" : L.x3k ? "x3_ktile" : L.x3img ? "x3_img" : kModeName[L.mode], L.cfg, L.K, L.Kpad,
-               L.pool ? " +pool2x2s2" : L.pool1 ? " +pool2x2s1" : "", sk,
-               L.splits > 1 ? (L.mode == MODE_X3 ? " x3-combine" : fused_splitk(p) ? " combine" : "") : "",
+               L.W, L.C, L.out_h(), L.out_w(), L.OC, L.kh, L.kw, L.sh, kVariantName[L.variant], L.cfg, L.K, L.Kpad,
+               L.pool == POOL_S2 ? " +pool2x2s2" : L.pool == POOL_S1 ? " +pool2x2s1" : "", sk,
+               L.splits > 1 ? (is_x3(L.variant) ? " x3-combine" : fused_splitk(p) ? " combine" : "") : "",
                p->fp16 ? " fp16" : "", p->latency ? " latency" : "", xp);
     } else if (L.type == LAYER_STASH || L.type == LAYER_RESTORE) {
       snprintf(line, sizeof(line), "%s %dx%dx%d slot=%d\n", L.type == LAYER_STASH ? "stash" : "restore", L.H, L.W, L.C,
@@ -1844,7 +1734,7 @@ int dnn_plan_timing_begin(dnn_plan* p, int max_runs) {
   DNN_REQUIRE(p && p->finalized, "dnn_plan_timing_begin: plan not finalized");
   DNN_REQUIRE(max_runs > 0, "dnn_plan_timing_begin: max_runs must be > 0");
   DNN_HIP_TRY(hipSetDevice(p->device));
-  int need = max_runs * ((int)p->kernels.size() + 1) + 1;
+  int need = max_runs * ((int)p->steps.size() + 1) + 1;
   while ((int)p->ev.size() < need) {
     hipEvent_t e;
     DNN_HIP_TRY(hipEventCreate(&e));
@@ -1859,7 +1749,7 @@ int dnn_plan_timing_begin(dnn_plan* p, int max_runs) {
 }
 
 int dnn_plan_timing_begin_only(dnn_plan* p, int max_runs, int kernel_idx) {
-  DNN_REQUIRE(p && kernel_idx >= 0 && kernel_idx < (int)p->kernels.size(),
+  DNN_REQUIRE(p && kernel_idx >= 0 && kernel_idx < (int)p->steps.size(),
               "dnn_plan_timing_begin_only: bad kernel index %d", kernel_idx);
   int rc = dnn_plan_timing_begin(p, max_runs);
   if (rc) return rc;
@@ -1869,7 +1759,7 @@ int dnn_plan_timing_begin_only(dnn_plan* p, int max_runs, int kernel_idx) {
 
 int dnn_plan_clock_begin(dnn_plan* p, int kernel_idx, unsigned long long* dev_buf, int max_runs, int nwg) {
   DNN_REQUIRE(p && p->finalized, "dnn_plan_clock_begin: plan not finalized");
-  DNN_REQUIRE(kernel_idx >= 0 && kernel_idx < (int)p->kernels.size(), "dnn_plan_clock_begin: bad kernel index %d",
+  DNN_REQUIRE(kernel_idx >= 0 && kernel_idx < (int)p->steps.size(), "dnn_plan_clock_begin: bad kernel index %d",
               kernel_idx);
   DNN_REQUIRE(dev_buf && max_runs > 0 && nwg > 0 && nwg <= 65536, "dnn_plan_clock_begin: bad buffer / runs / nwg");
   p->clk_kernel = kernel_idx;
@@ -1883,7 +1773,7 @@ int dnn_plan_clock_begin(dnn_plan* p, int kernel_idx, unsigned long long* dev_bu
 
 int dnn_plan_set_mark(dnn_plan* p, int kernel_idx) {
   DNN_REQUIRE(p && p->finalized, "dnn_plan_set_mark: plan not finalized");
-  DNN_REQUIRE(kernel_idx >= -1 && kernel_idx < (int)p->kernels.size(), "dnn_plan_set_mark: bad kernel index %d",
+  DNN_REQUIRE(kernel_idx >= -1 && kernel_idx < (int)p->steps.size(), "dnn_plan_set_mark: bad kernel index %d",
               kernel_idx);
   if (kernel_idx >= 0 && !p->mark_ev) {
     DNN_HIP_TRY(hipSetDevice(p->device));
@@ -1912,7 +1802,7 @@ int dnn_plan_clock_end(dnn_plan* p, int* runs) {
 int dnn_plan_timing_end(dnn_plan* p, double* ms_sum, long long* launches) {
   DNN_REQUIRE(p && p->timing, "dnn_plan_timing_end: timing not active");
   p->timing = false;
-  const int nk = (int)p->kernels.size();
+  const int nk = (int)p->steps.size();
   for (int i = 0; i < nk; ++i) {
     if (ms_sum) ms_sum[i] = 0.0;
     if (launches) launches[i] = 0;
