@@ -4,6 +4,8 @@
     outs = m.inference(frame)             # one tensor per [yolo] section, in cfg order
     boxes = m.postprocessing(outs)        # one image's label boxes
     rows = m.detect(frames)               # plan + decode on the device
+    rows = m.detect_images(images)        # uint8 images of any sizes: letterbox, plan, decode and
+                                          # the boxes back in each image's pixels, on the device
 
 The whole network lowers to ONE device plan (dnn_hip.lower_graph).  Every [convolutional]
 section is one dnn_plan_add_conv_padded entry: Darknet's padding (`pad` zeros on every side, so a
@@ -44,7 +46,10 @@ Out of scope:
   * YOLOv2's [reorg] and [region]: Darknet's reorg channel order is not the route kernel's
     (TensorFlow's space_to_depth), so yolov2.py's weights are not Darknet's either;
   * grouped convs (`groups` > 1);
-  * letterboxing and image I/O: frames arrive as [n, h, w, 3] fp32 arrays, already resized;
+  * image file decoding: detect_images takes H x W x 3 uint8 arrays of any sizes, letterboxes them
+    on the device as Darknet's letterbox_image does and returns boxes in each image's own pixels
+    (ingest.RaggedIngest, yolo_post.DetectionBuffers.correct); reading a JPEG into such an array
+    is the caller's.  inference and detect still take [n, h, w, 3] fp32 arrays, already resized;
   * fp16 plans: dnn_plan_add_conv_padded is an fp32 entry;
   * heads above 16,384 boxes (608 x 608 YOLOv3 has 22,743): the model is built with head=None,
     inference works and detect raises the decode's error.
@@ -510,6 +515,7 @@ class DarknetModel(yolov3.YOLO_V3):
         self.head = head
         self.sess = dnn_hip.DnnInferenceEngine(self.g, debug, device=device, latency=latency)
         self._dev = None
+        self._ingest = {}  # detect_images' RaggedIngest per pixel order
 
     def _need_head(self):
         if self.head is None:
@@ -522,6 +528,43 @@ class DarknetModel(yolov3.YOLO_V3):
     def detect(self, frames, raise_errors=True):
         self._need_head()
         return super().detect(frames, raise_errors)
+
+    def detect_images(self, images, order="bgr", raise_errors=True):
+        """Detections of up to `batch` H x W x 3 uint8 images of any sizes, each in its own
+        image's pixels: per image the (class, left, top, right, bottom, score) rows of `detect`,
+        mapped back.  On the device throughout: the 8-bit pixels are uploaded and letterboxed as
+        Darknet's letterbox_image does (ingest.RaggedIngest) into the plan's input, the plan and
+        the multi-scale decode run as in `detect`, and the rows are corrected in place
+        (yolo_post.DetectionBuffers.correct).  order "bgr" (cv2 frames) or "rgb".  Leaves dets /
+        counts in self.buffers, ready for its pack()."""
+        import torch
+        import ingest
+        self._need_head()
+        images = list(images)
+        batch, net_hw = self.in_shape[0], self.in_shape[1:3]
+        if self.in_shape[3] != 3:
+            raise ValueError(f"detect_images needs a 3-channel network, [net] has channels = {self.in_shape[3]}")
+        if order not in ingest.PIXEL_ORDERS:
+            raise ValueError(f"order {order!r}: need one of {sorted(ingest.PIXEL_ORDERS)}")
+        _, _, sizes, nbytes = ingest.ragged_layout(images, batch, 1 << 62, net_hw)  # (raises before any device work)
+        n = len(images)
+        plan = self.sess.plan()
+        device = torch.device("cuda", plan.device)
+        d = self._device_buffers(plan, device)
+        with torch.cuda.device(device):
+            compute = torch.cuda.current_stream()
+            stream = compute.cuda_stream
+            ing = self._ingest.get(order)
+            if ing is None or ing.max_bytes < nbytes or ing.compute != compute:
+                ing = ingest.RaggedIngest(batch, max(nbytes, 1), net_hw, device, compute, order)
+                self._ingest[order] = ing
+            ing.submit(images, out_ptr=d["in"].data_ptr())
+            plan.run_device(n, d["in"].data_ptr(), d["out"].data_ptr(), stream)
+            self.buffers.run(d["taps"] + [d["out"].data_ptr()], n, stream)
+            self.buffers.correct(sizes, net_hw, n, stream)
+            dets = self.buffers.dets[:n].cpu().numpy()
+            counts = self.buffers.counts[:n].cpu().numpy()
+        return yolo_post.DetectionBuffers.to_rows(dets, counts, self.buffers.max_det, raise_errors)
 
 
 # ----------------------------------------------------------------------------- the public cfgs

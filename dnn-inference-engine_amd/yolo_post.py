@@ -77,6 +77,19 @@ class MultiStruct(ctypes.Structure):
     _fields_ = [("n_scales", ctypes.c_int), ("class_mode", ctypes.c_int), ("scale", HeadStruct * MAX_SCALES)]
 
 
+class ImageSize(ctypes.Structure):
+    """dnn_image_size (include/dnn_hip_post.h)."""
+    _fields_ = [("h", ctypes.c_int), ("w", ctypes.c_int)]
+
+
+def _sizes(sizes):
+    """[(h, w), ...] as a ctypes array of ImageSize (one spare element, so an empty list has an address)."""
+    arr = (ImageSize * (len(sizes) + 1))()
+    for k, (h, w) in enumerate(sizes):
+        arr[k] = ImageSize(int(h), int(w))
+    return arr
+
+
 def _bind(lib):
     vp, i = ctypes.c_void_p, ctypes.c_int
     hp, u64 = ctypes.POINTER(HeadStruct), ctypes.c_ulonglong
@@ -117,6 +130,11 @@ def _bind(lib):
     lib.dnn_yolo_postprocess_multi_labels.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, vp]
     lib.dnn_yolo_postprocess_multi_labels_host.restype = i
     lib.dnn_yolo_postprocess_multi_labels_host.argtypes = [mp, pp, i, vp, i, vp, i]
+    sp = ctypes.POINTER(ImageSize)
+    lib.dnn_yolo_correct_detections.restype = i
+    lib.dnn_yolo_correct_detections.argtypes = [vp, vp, i, i, sp, i, i, vp]
+    lib.dnn_yolo_correct_detections_host.restype = i
+    lib.dnn_yolo_correct_detections_host.argtypes = [vp, vp, i, i, sp, i, i]
     return lib
 
 
@@ -392,6 +410,24 @@ def detect_batch(predictions, max_det=None, raise_errors=True, head=None):
     return _rows(dets, counts, max_det, raise_errors)
 
 
+def correct_rows_host(dets, counts, sizes, net_hw):
+    """dnn_yolo_correct_detections_host: `dets` a writable DETECTION_DTYPE array [n, max_det] and
+    `counts` int32 [n] as the decode entries fill them (host); rows [0, min(counts[i], max_det))
+    of image i are rewritten in place from net_hw network pixels into the pixels of the
+    sizes[i] = (h, w) image that was letterboxed.  Returns dets."""
+    if not isinstance(dets, np.ndarray) or dets.dtype != DETECTION_DTYPE or dets.ndim != 2 or \
+            not dets.flags.c_contiguous or not dets.flags.writeable:
+        raise ValueError("dets: a writable C-contiguous [n, max_det] array of DETECTION_DTYPE expected")
+    c = np.ascontiguousarray(counts, dtype=np.int32)
+    n, max_det = dets.shape
+    if c.shape != (n,) or len(sizes) != n:
+        raise ValueError(f"{c.shape[0] if c.ndim == 1 else c.shape} counts and {len(sizes)} sizes for {n} images")
+    dnn_hip._check(_lib.dnn_yolo_correct_detections_host(dets.ctypes.data, c.ctypes.data, n, max_det, _sizes(sizes),
+                                                         int(net_hw[0]), int(net_hw[1])),
+                   "dnn_yolo_correct_detections_host")
+    return dets
+
+
 def label_boxes(rows, head=None):
     """(class, l, t, r, b, score) rows -> the reference's label_boxes tuples.  A head with
     other classes than the 20 VOC names gives its own name (the class index where it has only
@@ -452,6 +488,16 @@ class DetectionBuffers(object):
                                                      self.packed.data_ptr(), self.total.data_ptr(), stream),
                        "dnn_yolo_pack_detections")
         return self.packed, self.total, self.counts
+
+    def correct(self, sizes, net_hw, n, stream):
+        """After `run` on letterboxed inputs (ingest.RaggedIngest) and before `pack`: rewrite the
+        rows of images 0..n-1 in place from net_hw network pixels into each image's own pixels,
+        sizes[i] = (h, w) of image i (dnn_yolo_correct_detections; asynchronous on `stream`)."""
+        if n > self.n or len(sizes) != n:
+            raise ValueError(f"{len(sizes)} sizes for {n} images in buffers sized for {self.n}")
+        dnn_hip._check(_lib.dnn_yolo_correct_detections(self.dets.data_ptr(), self.counts.data_ptr(), n, self.max_det,
+                                                        _sizes(sizes), int(net_hw[0]), int(net_hw[1]), stream),
+                       "dnn_yolo_correct_detections")
 
     @staticmethod
     def to_rows(dets_u8, counts, max_det=None, raise_errors=True, head=None):

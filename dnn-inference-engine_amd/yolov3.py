@@ -190,6 +190,20 @@ class YOLO_V3(object):
             raise ValueError(f"postprocessing expects one image, got {len(rows)}")
         return yolo_post.label_boxes(rows[0], self.head)
 
+    def _device_buffers(self, plan, device):
+        """detect's device tensors (input, output, the tap pointers in head order) and
+        self.buffers, made on first use."""
+        import torch
+        if self._dev is None:
+            order = [[id(e.node) for e in plan.tap_entries].index(id(o)) for o in self.outs[:-1]]
+            self._dev = {
+                "in": torch.empty((plan.batch,) + plan.in_shape, dtype=torch.float32, device=device),
+                "out": torch.empty((plan.batch,) + plan.out_shape, dtype=torch.float32, device=device),
+                "taps": [plan.tap_buffer(k)[0] for k in order],
+            }
+            self.buffers = yolo_post.MultiDetectionBuffers(plan.batch, device, self.head)
+        return self._dev
+
     def detect(self, frames, raise_errors=True):
         """Plan and decode on the device for [n <= batch, h, w, 3] host frames: per image the rows
         of yolo_post.detect_batch_multi.  The decode reads the plan's two tap buffers and its
@@ -202,15 +216,7 @@ class YOLO_V3(object):
         if tuple(x.shape[1:]) != plan.in_shape or n > plan.batch:
             raise ValueError(f"frames {x.shape} do not fit plan [{plan.batch}, {plan.in_shape}]")
         device = torch.device("cuda", plan.device)
-        if self._dev is None:
-            order = [[id(e.node) for e in plan.tap_entries].index(id(o)) for o in self.outs[:-1]]
-            self._dev = {
-                "in": torch.empty((plan.batch,) + plan.in_shape, dtype=torch.float32, device=device),
-                "out": torch.empty((plan.batch,) + plan.out_shape, dtype=torch.float32, device=device),
-                "taps": [plan.tap_buffer(k)[0] for k in order],
-            }
-            self.buffers = yolo_post.MultiDetectionBuffers(plan.batch, device, self.head)
-        d = self._dev
+        d = self._device_buffers(plan, device)
         with torch.cuda.device(device):
             stream = torch.cuda.current_stream().cuda_stream
             d["in"][:n].copy_(torch.from_numpy(x))

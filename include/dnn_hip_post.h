@@ -222,6 +222,34 @@ int dnn_yolo_postprocess_multi_labels(const dnn_yolo_multi* multi, const float* 
 int dnn_yolo_postprocess_multi_labels_host(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
                                            dnn_detection* dets, int max_det, int* counts, int labels_mode);
 
+/* ---- boxes back to each image's own pixels ----------------------------------------------
+ * The reference's frames are stretched to the network's size and its boxes stay in network
+ * pixels.  After a letterbox ingest (include/dnn_hip_ingest.h: dnn_letterbox_frames) image i of
+ * size sizes[i] occupies [pad_y, pad_y + new_h) x [pad_x, pad_x + new_w) of the network input
+ * (dnn_letterbox_geometry), and Darknet's correct_yolo_boxes / draw_detections map a box back
+ * and clamp it to the image.  Restated on the integer corners, integer arithmetic only:
+ *   xc = min(max(x, pad_x), pad_x + new_w);  x' = min(((xc - pad_x) * src_w) / new_w, src_w - 1)
+ *   yc = min(max(y, pad_y), pad_y + new_h);  y' = min(((yc - pad_y) * src_h) / new_h, src_h - 1)
+ * for left / right and top / bottom (clamping first bounds the product whatever the corner
+ * held).  Rows [0, min(counts[i], max_det)) of image i are rewritten in place, class and score
+ * untouched; an image with a negative count (an error code) and the rows past the count are left
+ * alone; a box wholly in the padding becomes a zero-width row and stays.  Darknet maps before
+ * its NMS, this runs after the decode's NMS on network pixels.
+ * sizes: a HOST array of n_images sizes, fully read before the call returns; dets / counts:
+ * device, the layout of every decode entry above.  Bad arguments (NULL pointers, negative
+ * counts of images or rows, a non-positive size, a letterbox with a side below 2 pixels: the
+ * message names the image) return nonzero before any device call.  Asynchronous on `stream`. */
+typedef struct dnn_image_size {
+  int h, w;
+} dnn_image_size;
+
+int dnn_yolo_correct_detections(dnn_detection* dets, const int* counts, int n_images, int max_det,
+                                const dnn_image_size* sizes, int net_h, int net_w, void* stream);
+
+/* Host pointers, synchronous (copies in, runs, copies out). */
+int dnn_yolo_correct_detections_host(dnn_detection* dets, const int* counts, int n_images, int max_det,
+                                     const dnn_image_size* sizes, int net_h, int net_w);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
