@@ -51,8 +51,10 @@ Out of scope:
     (ingest.RaggedIngest, yolo_post.DetectionBuffers.correct); reading a JPEG into such an array
     is the caller's.  inference and detect still take [n, h, w, 3] fp32 arrays, already resized;
   * fp16 plans: dnn_plan_add_conv_padded is an fp32 entry;
-  * heads above 16,384 boxes (608 x 608 YOLOv3 has 22,743): the model is built with head=None,
-    inference works and detect raises the decode's error.
+  * heads above 16,384 boxes (608 x 608 YOLOv3 has 22,743) BY DEFAULT: the model is built with
+    head=None, inference works and detect raises the decode's error.  DarknetModel(..., wide=True)
+    builds a yolo_post.WideHead instead (up to 65,536 boxes, at most 16,384 candidates per image)
+    and detect, detect_images and postprocessing work; heads above 65,536 boxes stay out.
 """
 import struct
 
@@ -452,9 +454,10 @@ def _spp(g, sec, srcs):
                        "stride-1 max pools of one tensor, then that tensor)")
 
 
-def multi_head(yolos, in_h, in_w, score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per_class", labels="multi"):
+def multi_head(yolos, in_h, in_w, score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per_class", labels="multi", wide=False):
     """The yolo_post.MultiHead of build_graph's `yolos` for an in_h x in_w input: per [yolo] the
-    anchors its mask picks, in pixels, divided by the scale's stride (input / grid)."""
+    anchors its mask picks, in pixels, divided by the scale's stride (input / grid).  With `wide`
+    a yolo_post.WideHead (up to 65,536 boxes, the grid-wide decode), whatever the box count."""
     scales = []
     for y in yolos:
         gh, gw = y["grid"]
@@ -472,7 +475,7 @@ def multi_head(yolos, in_h, in_w, score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per
         px = [a for m in mask for a in anchors[2 * m:2 * m + 2]]
         scales.append(yolo_post.Scale(gh, gw, len(mask), _int(y, "classes", 20), tuple(a / stride for a in px),
                                       float(stride), score_thr, iou_thr))
-    return yolo_post.MultiHead(scales, "logistic", nms, labels)
+    return (yolo_post.WideHead if wide else yolo_post.MultiHead)(scales, "logistic", nms, labels)
 
 
 _AUTO = object()
@@ -484,12 +487,14 @@ class DarknetModel(yolov3.YOLO_V3):
     [net]'s width and height (default [1, height, width, channels]).  `head` is a
     yolo_post.MultiHead; left out, multi_head's (Darknet's detector defaults; score_thr, iou_thr,
     nms and labels override them), or None where the cfg's boxes exceed the decode's 16,384: then
-    inference works and postprocessing / detect raise the decode's error.  `latency` as
+    inference works and postprocessing / detect raise the decode's error.  `wide=True` makes that
+    head a yolo_post.WideHead instead (up to 65,536 boxes, the grid-wide decode), so the stock
+    608 x 608 cfgs give detections.  `latency` as
     dnn_hip.DnnInferenceEngine's.  inference, postprocessing and detect are yolov3.YOLO_V3's, on
     one tensor per [yolo] section in cfg order."""
 
     def __init__(self, cfg_text, weights, in_shape=None, debug=False, device=None, head=_AUTO, latency=None,
-                 score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per_class", labels="multi"):
+                 score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per_class", labels="multi", wide=False):
         self.sections = parse_cfg(cfg_text)
         h, w, c = net_shape(self.sections, in_shape)
         self.in_shape = (int(in_shape[0]) if in_shape is not None else 1, h, w, c)
@@ -499,7 +504,7 @@ class DarknetModel(yolov3.YOLO_V3):
         self._head_error = None
         if head is _AUTO:
             try:
-                head = multi_head(self.yolos, h, w, score_thr, iou_thr, nms, labels)
+                head = multi_head(self.yolos, h, w, score_thr, iou_thr, nms, labels, wide)
             except DarknetError:
                 raise
             except ValueError as e:

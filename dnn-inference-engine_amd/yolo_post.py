@@ -70,6 +70,7 @@ CLASS_MODES = {"softmax": 0, "logistic": 1}
 NMS_MODES = {"any": 0, "per_class": 1}  # DNN_YOLO_NMS_ANY_CLASS, DNN_YOLO_NMS_PER_CLASS
 LABEL_MODES = {"argmax": 0, "multi": 1}  # DNN_YOLO_LABELS_ARGMAX, DNN_YOLO_LABELS_MULTI
 MULTI_MAX_CANDIDATES = 16384  # DNN_YOLO_MULTI_MAX_CANDIDATES: (box, class) pairs above the threshold
+WIDE_MAX_BOXES = 65536  # DNN_YOLO_WIDE_MAX_BOXES: the box limit of a WideHead
 
 
 class MultiStruct(ctypes.Structure):
@@ -130,6 +131,14 @@ def _bind(lib):
     lib.dnn_yolo_postprocess_multi_labels.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, vp]
     lib.dnn_yolo_postprocess_multi_labels_host.restype = i
     lib.dnn_yolo_postprocess_multi_labels_host.argtypes = [mp, pp, i, vp, i, vp, i]
+    lib.dnn_yolo_wide_boxes.restype = i
+    lib.dnn_yolo_wide_boxes.argtypes = [mp]
+    lib.dnn_yolo_wide_workspace.restype = i
+    lib.dnn_yolo_wide_workspace.argtypes = [mp, i, ctypes.POINTER(u64)]
+    lib.dnn_yolo_postprocess_wide.restype = i
+    lib.dnn_yolo_postprocess_wide.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, i, vp]
+    lib.dnn_yolo_postprocess_wide_host.restype = i
+    lib.dnn_yolo_postprocess_wide_host.argtypes = [mp, pp, i, vp, i, vp, i, i]
     sp = ctypes.POINTER(ImageSize)
     lib.dnn_yolo_correct_detections.restype = i
     lib.dnn_yolo_correct_detections.argtypes = [vp, vp, i, i, sp, i, i, vp]
@@ -234,6 +243,9 @@ class MultiHead(object):
     needs nms="per_class": under the class-agnostic rule a box's second label is always suppressed
     by its first.  Validates like the C side (dnn_yolo_multi_boxes) and raises ValueError."""
 
+    MAX_BOXES = MULTI_MAX_BOXES         # the most boxes over all scales (WideHead: WIDE_MAX_BOXES)
+    BOXES_ENTRY = "dnn_yolo_multi_boxes"  # the C function that validates the description and counts them
+
     def __init__(self, scales, class_mode="logistic", nms="any", labels="argmax"):
         scales = list(scales)
         if not 1 <= len(scales) <= MAX_SCALES:
@@ -274,10 +286,11 @@ class MultiHead(object):
         self.n_classes, self.score_thr, self.iou_thr = s0.n_classes, s0.score_thr, s0.iou_thr
         self.scale_boxes = [s.grid_h * s.grid_w * s.n_anchors for s in self.scales]
         self.boxes = sum(self.scale_boxes)
-        if self.boxes > MULTI_MAX_BOXES:
-            raise ValueError(f"{self.boxes} boxes over {len(self.scales)} scales: need <= {MULTI_MAX_BOXES}")
+        if self.boxes > self.MAX_BOXES:
+            raise ValueError(f"{self.boxes} boxes over {len(self.scales)} scales: need <= {self.MAX_BOXES}")
         # the most rows an image can have: the default row capacity of detect_batch_multi and the buffers
-        self.max_det = self.boxes if labels == "argmax" else min(self.boxes * self.n_classes, MULTI_MAX_CANDIDATES)
+        # (a candidate per box, or with "multi" per box and class; a WideHead has more boxes than candidates)
+        self.max_det = min(self.boxes * (1 if labels == "argmax" else self.n_classes), MULTI_MAX_CANDIDATES)
         self.n_out = [s.n_anchors * (5 + s.n_classes) for s in self.scales]
         self.pred_shapes = [(s.grid_h, s.grid_w, n) for s, n in zip(self.scales, self.n_out)]
         self.pred_floats = [h * w * c for h, w, c in self.pred_shapes]
@@ -286,9 +299,9 @@ class MultiHead(object):
         for k, s in enumerate(self.scales):
             self.c.scale[k] = HeadStruct(s.grid_h, s.grid_w, s.n_anchors, s.n_classes, s.cell, s.score_thr, s.iou_thr,
                                          (ctypes.c_float * 32)(*s.anchors))
-        n = _lib.dnn_yolo_multi_boxes(ctypes.byref(self.c))
+        n = getattr(_lib, self.BOXES_ENTRY)(ctypes.byref(self.c))
         if n != self.boxes:
-            raise ValueError(f"dnn_yolo_multi_boxes: {n}: {dnn_hip.last_error()}")
+            raise ValueError(f"{self.BOXES_ENTRY}: {n}: {dnn_hip.last_error()}")
 
     @classmethod
     def yolov3(cls, in_h, in_w, classes=80, score_thr=0.3, iou_thr=0.3, nms="any", labels="argmax"):
@@ -334,8 +347,26 @@ class MultiHead(object):
         grids = ", ".join(f"{s.grid_h}x{s.grid_w}x{s.n_anchors}" for s in self.scales)
         nms = "" if self.nms == "any" else f", NMS {self.nms}"
         labels = "" if self.labels == "argmax" else f", labels {self.labels}"
-        return (f"MultiHead({grids}; {self.n_classes} classes, {self.class_mode}, score > {self.score_thr:g}, "
+        return (f"{type(self).__name__}({grids}; {self.n_classes} classes, {self.class_mode}, score > {self.score_thr:g}, "
                 f"IoU > {self.iou_thr:g}{nms}{labels})")
+
+
+class WideHead(MultiHead):
+    """A MultiHead of up to 65536 boxes (YOLOv3 at 608 x 608 has 22,743, at 1024 x 1024 64,512) for
+    the grid-wide decode (dnn_yolo_postprocess_wide, csrc/postprocess_wide.hip): the boxes are
+    decoded one thread each over the whole GPU, then one workgroup per image sorts the candidates
+    and runs the NMS.  Same constructor, classmethods, modes, rows and codes as MultiHead; an image
+    may have at most 16384 candidates in every mode (else its code is -3), which is also the most
+    rows (`max_det`).  detect_batch_multi and MultiDetectionBuffers take either class."""
+
+    MAX_BOXES = WIDE_MAX_BOXES
+    BOXES_ENTRY = "dnn_yolo_wide_boxes"
+
+    def workspace_bytes(self, n_images):
+        b = ctypes.c_ulonglong(0)
+        dnn_hip._check(_lib.dnn_yolo_wide_workspace(ctypes.byref(self.c), n_images, ctypes.byref(b)),
+                       "dnn_yolo_wide_workspace")
+        return int(b.value)
 
 
 def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
@@ -355,6 +386,11 @@ def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
     dets = np.zeros((n, max_det), DETECTION_DTYPE)
     counts = np.zeros(n, np.int32)
     ptrs = (ctypes.c_void_p * len(ps))(*[p.ctypes.data for p in ps])
+    if isinstance(head, WideHead):
+        dnn_hip._check(_lib.dnn_yolo_postprocess_wide_host(
+            ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det, counts.ctypes.data, NMS_MODES[head.nms],
+            LABEL_MODES[head.labels]), "dnn_yolo_postprocess_wide_host")
+        return _rows(dets, counts, max_det, raise_errors)
     if head.labels == "multi":
         dnn_hip._check(_lib.dnn_yolo_postprocess_multi_labels_host(
             ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det, counts.ctypes.data, LABEL_MODES[head.labels]),
@@ -512,7 +548,8 @@ class DetectionBuffers(object):
 class MultiDetectionBuffers(DetectionBuffers):
     """DetectionBuffers for a MultiHead: `run(pred_ptrs, n, stream)` takes one device pointer per
     scale and goes through dnn_yolo_postprocess_multi_nms with head.nms, or with head.labels
-    "multi" through dnn_yolo_postprocess_multi_labels; dets, counts, `pack` and `to_rows` are the
+    "multi" through dnn_yolo_postprocess_multi_labels, or for a WideHead through
+    dnn_yolo_postprocess_wide; dets, counts, `pack` and `to_rows` are the
     base class's (max_det defaults to head.max_det: head.boxes, or with "multi" the most
     candidates an image can have), so dnn_yolo_pack_detections and dist.gather_detections apply
     unchanged."""
@@ -533,6 +570,12 @@ class MultiDetectionBuffers(DetectionBuffers):
         if len(pred_ptrs) != len(self.head.scales):
             raise ValueError(f"{len(pred_ptrs)} prediction pointers for {len(self.head.scales)} scales")
         ptrs = (ctypes.c_void_p * len(pred_ptrs))(*[int(p) for p in pred_ptrs])
+        if isinstance(self.head, WideHead):
+            dnn_hip._check(_lib.dnn_yolo_postprocess_wide(
+                ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
+                self.workspace.data_ptr(), self.workspace.numel(), NMS_MODES[self.head.nms],
+                LABEL_MODES[self.head.labels], stream), "dnn_yolo_postprocess_wide")
+            return
         if self.head.labels == "multi":
             dnn_hip._check(_lib.dnn_yolo_postprocess_multi_labels(
                 ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),

@@ -222,6 +222,39 @@ int dnn_yolo_postprocess_multi_labels(const dnn_yolo_multi* multi, const float* 
 int dnn_yolo_postprocess_multi_labels_host(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
                                            dnn_detection* dets, int max_det, int* counts, int labels_mode);
 
+/* ---- heads above DNN_YOLO_MULTI_MAX_BOXES: grid-wide decode, one NMS workgroup per image ----
+ * The entries above decode an image in ONE workgroup and keep a sort key per box in LDS, which is
+ * where their 16,384-box limit comes from; a stock 608 x 608 YOLOv3 has 22,743 boxes.  Only
+ * candidates are sorted, so these entries bound the two counts separately: up to
+ * DNN_YOLO_WIDE_MAX_BOXES boxes per image (YOLOv3 at 1024 x 1024: 64,512), decoded one thread per
+ * box over the whole grid, and up to DNN_YOLO_MULTI_MAX_CANDIDATES candidates per image IN EVERY
+ * MODE (for multi-label the (box, class) pairs, else the boxes above the threshold): an image with
+ * more gets counts[i] = -3 and no rows, after -1 and before -2 as above.  Everything else is the
+ * semantics above, bit for bit: the same boxes, scores, order, rows and codes as the *_multi
+ * entries give for a head both accept.  A call clears the per-image counters, then runs the
+ * decode kernel and the NMS kernel, three launches in that order on `stream`; it may be captured
+ * in a HIP graph.
+ *
+ * nms_mode / labels_mode: (ANY_CLASS, ARGMAX), (PER_CLASS, ARGMAX) or (PER_CLASS, MULTI);
+ * (ANY_CLASS, MULTI) returns -2 (a box's second label would always be suppressed by its first).
+ * With n_classes == 1 all three are the same function.
+ * Workspace: per image 40 bytes per box, DNN_YOLO_MULTI_MAX_CANDIDATES 8-byte keys and one
+ * 64-byte counter block; 8-byte aligned.  All other arguments and checks are those of
+ * dnn_yolo_postprocess_multi_labels. */
+#define DNN_YOLO_WIDE_MAX_BOXES 65536
+
+/* As dnn_yolo_multi_boxes with the sum bounded by DNN_YOLO_WIDE_MAX_BOXES. */
+int dnn_yolo_wide_boxes(const dnn_yolo_multi* multi);
+
+int dnn_yolo_wide_workspace(const dnn_yolo_multi* multi, int n_images, unsigned long long* bytes);
+
+int dnn_yolo_postprocess_wide(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
+                              dnn_detection* dets, int max_det, int* counts, void* workspace,
+                              unsigned long long workspace_bytes, int nms_mode, int labels_mode, void* stream);
+
+int dnn_yolo_postprocess_wide_host(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
+                                   dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode);
+
 /* ---- boxes back to each image's own pixels ----------------------------------------------
  * The reference's frames are stretched to the network's size and its boxes stay in network
  * pixels.  After a letterbox ingest (include/dnn_hip_ingest.h: dnn_letterbox_frames) image i of
