@@ -329,6 +329,11 @@ int launch_shortcut(const float* a, const float* b, float* out, long long count,
 // 1..8; 16-byte accesses when C % 4 == 0.  Every tensor < 2 GiB
 int launch_upsample(const float* in, float* out, int n, int H, int W, int C, int factor, hipStream_t stream);
 
+// slice.hip: a channel range, out [n, H, W, channels] = in [n, H, W, first : first + channels];
+// 16-byte accesses when C, first and channels are multiples of 4.  Every tensor < 2 GiB
+int launch_slice(const float* in, float* out, int n, int H, int W, int C, int first, int channels,
+                 hipStream_t stream);
+
 // spp.hip: spatial pyramid pooling in one pass.  out [n, H, W, (n_sizes + 1) * C]: channel block j
 // is the sizes[j] x sizes[j] / stride-1 / SAME max pool of a [n, H, W, C] (maxpool_nhwc_kernel's
 // bits: -FLT_MAX padding, row-major scan, m >= v ? m : v), and a itself is the last block, or the

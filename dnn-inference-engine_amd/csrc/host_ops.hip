@@ -1,5 +1,5 @@
 // The join / element-wise kernels on host tensors (include/dnn_hip_plan.h: dnn_spp_host,
-// dnn_route_host, dnn_shortcut_host, dnn_scale_shift_host, dnn_upsample_host).  Host code only:
+// dnn_route_host, dnn_shortcut_host, dnn_scale_shift_host, dnn_upsample_host, dnn_slice_host).  Host code only:
 // each entry checks its arguments and hands on_device() its inputs and a launch.
 #include <hip/hip_runtime.h>
 #include <initializer_list>
@@ -153,6 +153,20 @@ int dnn_upsample_host(const float* a, float* out, int n, int h, int w, int c, in
   return on_device("dnn_upsample_host", {{a, af}}, of, out, of, [&](float* const* d, const float** res) {
     *res = d[1];
     return launch_upsample(d[0], d[1], n, h, w, c, factor, nullptr);
+  });
+}
+
+int dnn_slice_host(const float* a, float* out, int n, int h, int w, int c, int first, int channels) {
+  DNN_REQUIRE(a && out, "dnn_slice_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_slice_host: bad shape n=%d %dx%dx%d", n, h, w, c);
+  DNN_REQUIRE(first >= 0 && channels >= 1 && (long long)first + channels <= c,
+              "dnn_slice_host: first %d, channels %d outside the tensor's %d channels", first, channels, c);
+  if (n == 0) return 0;
+  const size_t af = (size_t)n * h * w * c, of = (size_t)n * h * w * channels;
+  DNN_REQUIRE(af * 4 < k2GiB, "dnn_slice_host: a tensor of n=%d %dx%dx%d is >= 2 GiB; split the batch", n, h, w, c);
+  return on_device("dnn_slice_host", {{a, af}}, of, out, of, [&](float* const* d, const float** res) {
+    *res = d[1];
+    return launch_slice(d[0], d[1], n, h, w, c, first, channels, nullptr);
   });
 }
 

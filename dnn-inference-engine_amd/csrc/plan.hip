@@ -58,6 +58,9 @@
 // Spatial pyramid pooling: an spp entry (spp.hip) writes up to three stride-1 SAME max pools of the
 // current tensor and the tensor itself as channel blocks of one output, in one kernel.  Like the
 // other join entries it reads and writes plain NHWC fp32 and stops the conv / pool peepholes.
+//
+// Channel slice: a slice entry (slice.hip) copies a channel range of the current tensor (Darknet's
+// [route] with groups / group_id), one kernel, plain NHWC fp32 on both sides like the entries above.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -167,7 +170,8 @@ enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, 
                        LOC_PAD = 1 << 24 };
 
 enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
-                       LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9 };
+                       LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9,
+                       LAYER_SLICE = 10 };
 
 struct PlanLayer {
   int type = LAYER_CONV;
@@ -194,6 +198,7 @@ struct PlanLayer {
   int to_region = -1;       // a writing layer followed by a stash: the slot region it writes
   int slot_loc = LOC_NONE;  // where the slot's tensor lives when this entry is added (slot numbers are reused)
   int factor = 1;           // upsample
+  int first = 0;            // slice: the first channel taken (OC channels from there)
   int leaky = 0;            // shortcut: 0 none, 1 / 2 the conv epilogue's variants
   int n_sizes = 0, sizes[DNN_SPP_MAX_SIZES] = {0, 0, 0};  // spp: the pools' window sizes, in block order
   bool x_first = false;     // spp: the input's copy is the first channel block
@@ -230,7 +235,7 @@ enum StepKind : int {
   STEP_X3_COMBINE,       // an x3 conv's slab partials + its epilogue -> dst
   STEP_POOL,
   STEP_X3_COMBINE_POOL,  // a pool layer's step that also combines the partials of x3 conv `layer - 1`
-  STEP_ROUTE, STEP_SHORTCUT, STEP_UPSAMPLE, STEP_SPP,
+  STEP_ROUTE, STEP_SHORTCUT, STEP_UPSAMPLE, STEP_SPP, STEP_SLICE,
   STEP_CVT_OUT           // fp16 plans: the last activation to the fp32 output
 };
 
@@ -360,7 +365,8 @@ static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
   place_outputs(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
-  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0;  // kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7
+  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0;
+  // (kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7)
   p->steps.clear();
   const double B = p->batch;
   const int nl = (int)p->layers.size();
@@ -453,6 +459,9 @@ static void layout(dnn_plan* p) {
     } else if (L.type == LAYER_SPP) {  // reads the input once, writes n_sizes + 1 blocks of its size
       snprintf(nm, sizeof(nm), "spp%d", nspp++);
       step(i, STEP_SPP, 0.0, in_b + out_b, cur, out);
+    } else if (L.type == LAYER_SLICE) {  // reads the channels it writes: input bytes == output bytes
+      snprintf(nm, sizeof(nm), "slice%d", nslice++);
+      step(i, STEP_SLICE, 0.0, 2.0 * out_b, cur, out);
     }
     cur = out;
   }
@@ -1202,6 +1211,20 @@ int dnn_plan_add_upsample(dnn_plan* p, int factor) {
   return 0;
 }
 
+int dnn_plan_add_slice(dnn_plan* p, int first, int channels) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_slice: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_slice: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(first >= 0 && channels >= 1 && (long long)first + channels <= p->cur_c,
+              "dnn_plan_add_slice: first %d, channels %d outside the current tensor's %d channels", first, channels,
+              p->cur_c);
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_SLICE);
+  L.OC = channels;
+  L.first = first;
+  push_computing(p, std::move(L));
+  return 0;
+}
+
 int dnn_plan_add_spp(dnn_plan* p, int n_sizes, const int* sizes, int x_first) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_spp: plan is NULL or finalized");
   DNN_REQUIRE(!p->fp16, "dnn_plan_add_spp: fp32 plans only (this is an fp16 plan)");
@@ -1527,6 +1550,8 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
       return launch_shortcut(cur, locate(p, r, L.slot_loc), dst, (long long)n * L.H * L.W * L.C, L.leaky, s);
     case STEP_UPSAMPLE:
       return launch_upsample(cur, dst, n, L.H, L.W, L.C, L.factor, s);
+    case STEP_SLICE:
+      return launch_slice(cur, dst, n, L.H, L.W, L.C, L.first, L.OC, s);
     case STEP_SPP:
       return launch_spp(cur, dst, n, L.H, L.W, L.C, L.n_sizes, L.sizes, L.x_first ? 1 : 0, s);
     default:
@@ -1711,6 +1736,8 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
     } else if (L.type == LAYER_UPSAMPLE) {
       snprintf(line, sizeof(line), "upsample %dx%dx%d -> %dx%dx%d factor=%d\n", L.H, L.W, L.C, L.OH, L.OW, L.OC,
                L.factor);
+    } else if (L.type == LAYER_SLICE) {
+      snprintf(line, sizeof(line), "slice %dx%dx%d -> %dx%dx%d first=%d\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.first);
     } else if (L.type == LAYER_RELEASE) {
       snprintf(line, sizeof(line), "release %dx%dx%d slot=%d\n", L.H, L.W, L.C, L.slot);
     } else if (L.type == LAYER_TAP) {

@@ -31,13 +31,25 @@ struct MultiPred {
   const float* p[DNN_YOLO_MAX_SCALES];
 };
 
+// Darknet's scale_x_y per scale: the box centre's logistic becomes sig * s + b, b = -0.5f * (s - 1.0f)
+// computed on the host in fp32.  s == 1 gives b == -0.0f, and sig * 1.0f + -0.0f is sig bit for bit
+// for every non-NaN sig: the entries without a scale_x_y argument run the same kernels with that.
+struct XyScale {
+  float s[DNN_YOLO_MAX_SCALES], b[DNN_YOLO_MAX_SCALES];
+};
+
+// postprocess_multi.hip: fills *out from a host array of n_scales floats (NULL: all 1); false with
+// the error set (it names scale_x_y) when a value is not finite or not > 0
+bool xy_scale_from(const float* scale_x_y, int n_scales, const char* who, XyScale* out);
+
 // Geometry and objectness of one box of one scale (q: its 5 + C values; b, col, row: its anchor and
 // cell): corners truncated to int64 in out[0..3] (false when one is not finite or out of range) and
-// conf = sigmoid(q[4]).  Shared by all kernels below so that they round alike.
+// conf = sigmoid(q[4]).  xs, xb: the scale's XyScale pair, one fp32 multiply then one fp32 add (the
+// file is built without contraction).  Shared by all kernels below so that they round alike.
 __device__ __forceinline__ bool decode_corners(const float* q, int b, int col, int row, const float* anchors_s,
-                                               float cell_px, long long* out, float* conf) {
-  const float cx = ((float)col + sigmoid_ref(q[0])) * cell_px;
-  const float cy = ((float)row + sigmoid_ref(q[1])) * cell_px;
+                                               float cell_px, float xs, float xb, long long* out, float* conf) {
+  const float cx = ((float)col + (sigmoid_ref(q[0]) * xs + xb)) * cell_px;
+  const float cy = ((float)row + (sigmoid_ref(q[1]) * xs + xb)) * cell_px;
   const float rw = (np_expf(q[2]) * anchors_s[2 * b]) * cell_px;
   const float rh = (np_expf(q[3]) * anchors_s[2 * b + 1]) * cell_px;
   *conf = sigmoid_ref(q[4]);
@@ -84,10 +96,10 @@ __device__ __forceinline__ float class_argmax(const float* lg, int C, bool logis
 
 // One box with ONE label: decode_corners, the score conf * p(class) and the class (the arg-max).
 __device__ __forceinline__ bool decode_box(const float* q, int C, bool logistic, int b, int col, int row,
-                                           const float* anchors_s, float cell_px, long long* out, float* score,
-                                           int* cls) {
+                                           const float* anchors_s, float cell_px, float xs, float xb, long long* out,
+                                           float* score, int* cls) {
   float conf;
-  const bool ok = decode_corners(q, b, col, row, anchors_s, cell_px, out, &conf);
+  const bool ok = decode_corners(q, b, col, row, anchors_s, cell_px, xs, xb, out, &conf);
   const float bp = class_argmax(q + 5, C, logistic, cls);
   *score = conf * bp;
   return ok;

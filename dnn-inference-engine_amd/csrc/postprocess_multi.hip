@@ -18,18 +18,19 @@
 // base + 64 entries, 4 (base + 64) bytes from the start of the array, and the first key still
 // to be read sits at byte 8 (base + 64).  Inside a block every key of the block is read into
 // registers (one per lane) before the first barrier and the list grows only after it.
+#include <cfloat>
 #include "post_multi_dev.h"
 
 namespace dnnhip {
 
 __global__ void __launch_bounds__(PM_THREADS)
-yolo_multi_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* __restrict__ dets, int max_det,
-                  int* __restrict__ counts, char* workspace, int nb) {
+yolo_multi_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pred, dnn_detection* __restrict__ dets,
+                  int max_det, int* __restrict__ counts, char* workspace, int nb) {
   __shared__ unsigned long long keys[PM_CAP];
   __shared__ float anchors[DNN_YOLO_MAX_SCALES][2 * DNN_YOLO_MAX_ANCHORS];
   __shared__ const float* s_pred[DNN_YOLO_MAX_SCALES];
   __shared__ int s_off[DNN_YOLO_MAX_SCALES + 1], s_gw[DNN_YOLO_MAX_SCALES], s_na[DNN_YOLO_MAX_SCALES];
-  __shared__ float s_cell[DNN_YOLO_MAX_SCALES];
+  __shared__ float s_cell[DNN_YOLO_MAX_SCALES], s_xs[DNN_YOLO_MAX_SCALES], s_xb[DNN_YOLO_MAX_SCALES];
   __shared__ unsigned long long hitw[PM_WAVES];
   __shared__ int n_cand, bad, n_kept, zero_den;
   int* kept = reinterpret_cast<int*>(keys);  // in place over the consumed keys (see above)
@@ -61,6 +62,8 @@ yolo_multi_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* 
       s_gw[s] = on ? mh.scale[s].grid_w : 1;
       s_na[s] = on ? mh.scale[s].n_anchors : 1;
       s_cell[s] = on ? mh.scale[s].cell : 1.0f;
+      s_xs[s] = xy.s[s];
+      s_xb[s] = xy.b[s];
       s_pred[s] = on ? pred.p[s] + (size_t)img * b * stride : nullptr;
       off += b;
     }
@@ -84,7 +87,7 @@ yolo_multi_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* 
     long long c4[4];
     float sc;
     int best;
-    if (!decode_box(q, C, logistic, b, col, row, anchors[s], cell_px, c4, &sc, &best)) bad = 1;
+    if (!decode_box(q, C, logistic, b, col, row, anchors[s], cell_px, s_xs[s], s_xb[s], c4, &sc, &best)) bad = 1;
     box[k][0] = c4[0];
     box[k][1] = c4[1];
     box[k][2] = c4[2];
@@ -153,13 +156,14 @@ static_assert(DNN_YOLO_MULTI_MAX_BOXES <= (1 << PC_IDX_BITS), "the global box in
 static_assert(PC_CLS_BITS + 32 + PC_IDX_BITS < 64, "a candidate's key must stay below ~0ull");
 
 __global__ void __launch_bounds__(PM_THREADS)
-yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* __restrict__ dets,
-                            int max_det, int* __restrict__ counts, char* workspace, int nb) {
+yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pred,
+                            dnn_detection* __restrict__ dets, int max_det, int* __restrict__ counts, char* workspace,
+                            int nb) {
   __shared__ unsigned long long keys[PM_CAP];
   __shared__ float anchors[DNN_YOLO_MAX_SCALES][2 * DNN_YOLO_MAX_ANCHORS];
   __shared__ const float* s_pred[DNN_YOLO_MAX_SCALES];
   __shared__ int s_off[DNN_YOLO_MAX_SCALES + 1], s_gw[DNN_YOLO_MAX_SCALES], s_na[DNN_YOLO_MAX_SCALES];
-  __shared__ float s_cell[DNN_YOLO_MAX_SCALES];
+  __shared__ float s_cell[DNN_YOLO_MAX_SCALES], s_xs[DNN_YOLO_MAX_SCALES], s_xb[DNN_YOLO_MAX_SCALES];
   __shared__ unsigned long long hitw[PM_WAVES];
   __shared__ int cls_cnt[DNN_YOLO_MAX_CLASSES];        // candidates per class
   __shared__ int seg_start[DNN_YOLO_MAX_CLASSES + 1];  // their prefix sum: class c is keys[seg_start[c] .. seg_start[c+1])
@@ -195,6 +199,8 @@ yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_d
       s_gw[s] = on ? mh.scale[s].grid_w : 1;
       s_na[s] = on ? mh.scale[s].n_anchors : 1;
       s_cell[s] = on ? mh.scale[s].cell : 1.0f;
+      s_xs[s] = xy.s[s];
+      s_xb[s] = xy.b[s];
       s_pred[s] = on ? pred.p[s] + (size_t)img * b * stride : nullptr;
       off += b;
     }
@@ -222,7 +228,7 @@ yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_d
     long long c4[4];
     float sc;
     int best;
-    if (!decode_box(q, C, logistic, b, col, row, anchors[s], cell_px, c4, &sc, &best)) bad = 1;
+    if (!decode_box(q, C, logistic, b, col, row, anchors[s], cell_px, s_xs[s], s_xb[s], c4, &sc, &best)) bad = 1;
     box[k][0] = c4[0];
     box[k][1] = c4[1];
     box[k][2] = c4[2];
@@ -363,13 +369,14 @@ constexpr int ML_KEY_CLS_MASK = (1 << PC_CLS_BITS) - 1, ML_KEY_IDX_MASK = (1 << 
 static_assert(DNN_YOLO_MULTI_MAX_CANDIDATES == PM_CAP, "the candidates of an image are the keys that fit in LDS");
 
 __global__ void __launch_bounds__(PM_THREADS)
-yolo_multi_labels_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* __restrict__ dets,
-                         int max_det, int* __restrict__ counts, char* workspace, int nb) {
+yolo_multi_labels_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pred,
+                         dnn_detection* __restrict__ dets, int max_det, int* __restrict__ counts, char* workspace,
+                         int nb) {
   __shared__ unsigned long long keys[PM_CAP];
   __shared__ float anchors[DNN_YOLO_MAX_SCALES][2 * DNN_YOLO_MAX_ANCHORS];
   __shared__ const float* s_pred[DNN_YOLO_MAX_SCALES];
   __shared__ int s_off[DNN_YOLO_MAX_SCALES + 1], s_gw[DNN_YOLO_MAX_SCALES], s_na[DNN_YOLO_MAX_SCALES];
-  __shared__ float s_cell[DNN_YOLO_MAX_SCALES];
+  __shared__ float s_cell[DNN_YOLO_MAX_SCALES], s_xs[DNN_YOLO_MAX_SCALES], s_xb[DNN_YOLO_MAX_SCALES];
   __shared__ unsigned long long hitw[PM_WAVES];
   __shared__ int cls_cnt[DNN_YOLO_MAX_CLASSES];        // candidates per class
   __shared__ int seg_start[DNN_YOLO_MAX_CLASSES + 1];  // their prefix sum: class c is keys[seg_start[c] .. seg_start[c+1])
@@ -405,6 +412,8 @@ yolo_multi_labels_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_dete
       s_gw[s] = on ? mh.scale[s].grid_w : 1;
       s_na[s] = on ? mh.scale[s].n_anchors : 1;
       s_cell[s] = on ? mh.scale[s].cell : 1.0f;
+      s_xs[s] = xy.s[s];
+      s_xb[s] = xy.b[s];
       s_pred[s] = on ? pred.p[s] + (size_t)img * b * stride : nullptr;
       off += b;
     }
@@ -437,7 +446,7 @@ yolo_multi_labels_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_dete
     const int b = kk % A, cell = kk / A, col = cell % gw, row = cell / gw;
     long long c4[4];
     float conf;
-    if (!decode_corners(q, b, col, row, anchors[s], s_cell[s], c4, &conf)) bad = 1;
+    if (!decode_corners(q, b, col, row, anchors[s], s_cell[s], s_xs[s], s_xb[s], c4, &conf)) bad = 1;
     box[k][0] = c4[0];
     box[k][1] = c4[1];
     box[k][2] = c4[2];
@@ -651,12 +660,28 @@ bool nms_mode_ok(int nms_mode, const char* who) {
   return false;
 }
 
-static int launch_yolo_multi(const char* who, const dnn_yolo_multi* m, const float* const* pred, int n_images,
+bool xy_scale_from(const float* scale_x_y, int n_scales, const char* who, XyScale* out) {
+  for (int s = 0; s < DNN_YOLO_MAX_SCALES; ++s) {
+    const float v = scale_x_y && s < n_scales ? scale_x_y[s] : 1.0f;
+    if (!(v > 0.0f) || !(v <= FLT_MAX)) {
+      set_error("%s: scale_x_y[%d] = %g: each value must be finite and > 0", who, s, (double)v);
+      return false;
+    }
+    out->s[s] = v;
+    out->b[s] = -0.5f * (v - 1.0f);
+  }
+  return true;
+}
+
+static int launch_yolo_multi(const char* who, const dnn_yolo_multi* m, const float* scale_x_y,
+                             const float* const* pred, int n_images,
                              dnn_detection* dets, int max_det, int* counts, void* workspace,
                              unsigned long long workspace_bytes, int nms_mode, int labels_mode, hipStream_t stream) {
   const int nb = multi_boxes(m, who);
   if (nb < 0) return nb;
   if (!nms_mode_ok(nms_mode, who) || !labels_mode_ok(labels_mode, who)) return -2;
+  XyScale xy;
+  if (!xy_scale_from(scale_x_y, m->n_scales, who, &xy)) return -2;
   if (n_images < 0 || max_det < 0 || (n_images > 0 && (!pred || !counts || (max_det > 0 && !dets)))) {
     set_error("%s: bad arguments (n_images=%d max_det=%d)", who, n_images, max_det);
     return -2;
@@ -679,14 +704,14 @@ static int launch_yolo_multi(const char* who, const dnn_yolo_multi* m, const flo
   // with one class the rules and the label modes are the same function: the class-agnostic kernel
   // serves them all
   if (labels_mode == DNN_YOLO_LABELS_MULTI && nms_mode == DNN_YOLO_NMS_PER_CLASS && m->scale[0].n_classes > 1)
-    hipLaunchKernelGGL(yolo_multi_labels_kernel, dim3(n_images), dim3(PM_THREADS), 0, stream, *m, mp, dets, max_det,
+    hipLaunchKernelGGL(yolo_multi_labels_kernel, dim3(n_images), dim3(PM_THREADS), 0, stream, *m, xy, mp, dets, max_det,
                        counts, static_cast<char*>(workspace), nb);
   else if (nms_mode == DNN_YOLO_NMS_PER_CLASS && m->scale[0].n_classes > 1)
-    hipLaunchKernelGGL(yolo_multi_classwise_kernel, dim3(n_images), dim3(PM_THREADS), 0, stream, *m, mp, dets,
+    hipLaunchKernelGGL(yolo_multi_classwise_kernel, dim3(n_images), dim3(PM_THREADS), 0, stream, *m, xy, mp, dets,
                        max_det, counts, static_cast<char*>(workspace), nb);
   else
-    hipLaunchKernelGGL(yolo_multi_kernel, dim3(n_images), dim3(PM_THREADS), 0, stream, *m, mp, dets, max_det, counts,
-                       static_cast<char*>(workspace), nb);
+    hipLaunchKernelGGL(yolo_multi_kernel, dim3(n_images), dim3(PM_THREADS), 0, stream, *m, xy, mp, dets, max_det,
+                       counts, static_cast<char*>(workspace), nb);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("launch yolo_multi: %s", hipGetErrorString(e));
@@ -696,11 +721,16 @@ static int launch_yolo_multi(const char* who, const dnn_yolo_multi* m, const flo
 }
 
 // Host pointers, synchronous: allocates the scratch, copies in, runs, copies out.
-static int yolo_multi_host(const char* who, const dnn_yolo_multi* m, const float* const* pred, int n_images,
+static int yolo_multi_host(const char* who, const dnn_yolo_multi* m, const float* scale_x_y,
+                           const float* const* pred, int n_images,
                            dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode) {
   const int nb = multi_boxes(m, who);
   if (nb < 0) return nb;
   if (!nms_mode_ok(nms_mode, who) || !labels_mode_ok(labels_mode, who)) return -2;
+  {
+    XyScale xy;
+    if (!xy_scale_from(scale_x_y, m->n_scales, who, &xy)) return -2;
+  }
   DNN_REQUIRE(n_images >= 0 && max_det >= 0, "%s: bad arguments", who);
   if (n_images == 0) return 0;
   DNN_REQUIRE(pred && counts && (max_det == 0 || dets), "%s: NULL pointer", who);
@@ -729,8 +759,9 @@ static int yolo_multi_host(const char* who, const dnn_yolo_multi* m, const float
       rc = -1;
     }
   }
-  if (!rc) rc = launch_yolo_multi(who, m, d_pred, n_images, d_dets, max_det, d_counts, buf + pb + db + cb, wb, nms_mode,
-                                    labels_mode, nullptr);
+  if (!rc)
+    rc = launch_yolo_multi(who, m, scale_x_y, d_pred, n_images, d_dets, max_det, d_counts, buf + pb + db + cb, wb,
+                           nms_mode, labels_mode, nullptr);
   if (!rc && (hipMemcpy(counts, d_counts, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
               (db && hipMemcpy(dets, d_dets, db, hipMemcpyDeviceToHost) != hipSuccess))) {
     set_error("%s: copy out failed", who);
@@ -757,14 +788,14 @@ int dnn_yolo_multi_workspace(const dnn_yolo_multi* m, int n_images, unsigned lon
 int dnn_yolo_postprocess_multi(const dnn_yolo_multi* m, const float* const* pred, int n_images, dnn_detection* dets,
                                int max_det, int* counts, void* workspace, unsigned long long workspace_bytes,
                                void* stream) {
-  return dnnhip::launch_yolo_multi("dnn_yolo_postprocess_multi", m, pred, n_images, dets, max_det, counts, workspace,
-                                   workspace_bytes, DNN_YOLO_NMS_ANY_CLASS, DNN_YOLO_LABELS_ARGMAX,
+  return dnnhip::launch_yolo_multi("dnn_yolo_postprocess_multi", m, nullptr, pred, n_images, dets, max_det, counts,
+                                   workspace, workspace_bytes, DNN_YOLO_NMS_ANY_CLASS, DNN_YOLO_LABELS_ARGMAX,
                                    static_cast<hipStream_t>(stream));
 }
 
 int dnn_yolo_postprocess_multi_host(const dnn_yolo_multi* m, const float* const* pred, int n_images,
                                     dnn_detection* dets, int max_det, int* counts) {
-  return dnnhip::yolo_multi_host("dnn_yolo_postprocess_multi_host", m, pred, n_images, dets, max_det, counts,
+  return dnnhip::yolo_multi_host("dnn_yolo_postprocess_multi_host", m, nullptr, pred, n_images, dets, max_det, counts,
                                  DNN_YOLO_NMS_ANY_CLASS, DNN_YOLO_LABELS_ARGMAX);
 }
 
@@ -781,15 +812,15 @@ int dnn_yolo_multi_nms_workspace(const dnn_yolo_multi* m, int n_images, int nms_
 int dnn_yolo_postprocess_multi_nms(const dnn_yolo_multi* m, const float* const* pred, int n_images,
                                    dnn_detection* dets, int max_det, int* counts, void* workspace,
                                    unsigned long long workspace_bytes, int nms_mode, void* stream) {
-  return dnnhip::launch_yolo_multi("dnn_yolo_postprocess_multi_nms", m, pred, n_images, dets, max_det, counts,
+  return dnnhip::launch_yolo_multi("dnn_yolo_postprocess_multi_nms", m, nullptr, pred, n_images, dets, max_det, counts,
                                    workspace, workspace_bytes, nms_mode, DNN_YOLO_LABELS_ARGMAX,
                                    static_cast<hipStream_t>(stream));
 }
 
 int dnn_yolo_postprocess_multi_nms_host(const dnn_yolo_multi* m, const float* const* pred, int n_images,
                                         dnn_detection* dets, int max_det, int* counts, int nms_mode) {
-  return dnnhip::yolo_multi_host("dnn_yolo_postprocess_multi_nms_host", m, pred, n_images, dets, max_det, counts,
-                                 nms_mode, DNN_YOLO_LABELS_ARGMAX);
+  return dnnhip::yolo_multi_host("dnn_yolo_postprocess_multi_nms_host", m, nullptr, pred, n_images, dets, max_det,
+                                 counts, nms_mode, DNN_YOLO_LABELS_ARGMAX);
 }
 
 int dnn_yolo_multi_labels_workspace(const dnn_yolo_multi* m, int n_images, int labels_mode,
@@ -806,15 +837,42 @@ int dnn_yolo_multi_labels_workspace(const dnn_yolo_multi* m, int n_images, int l
 int dnn_yolo_postprocess_multi_labels(const dnn_yolo_multi* m, const float* const* pred, int n_images,
                                       dnn_detection* dets, int max_det, int* counts, void* workspace,
                                       unsigned long long workspace_bytes, int labels_mode, void* stream) {
-  return dnnhip::launch_yolo_multi("dnn_yolo_postprocess_multi_labels", m, pred, n_images, dets, max_det, counts,
-                                   workspace, workspace_bytes, DNN_YOLO_NMS_PER_CLASS, labels_mode,
+  return dnnhip::launch_yolo_multi("dnn_yolo_postprocess_multi_labels", m, nullptr, pred, n_images, dets, max_det,
+                                   counts, workspace, workspace_bytes, DNN_YOLO_NMS_PER_CLASS, labels_mode,
                                    static_cast<hipStream_t>(stream));
 }
 
 int dnn_yolo_postprocess_multi_labels_host(const dnn_yolo_multi* m, const float* const* pred, int n_images,
                                            dnn_detection* dets, int max_det, int* counts, int labels_mode) {
-  return dnnhip::yolo_multi_host("dnn_yolo_postprocess_multi_labels_host", m, pred, n_images, dets, max_det, counts,
-                                 DNN_YOLO_NMS_PER_CLASS, labels_mode);
+  return dnnhip::yolo_multi_host("dnn_yolo_postprocess_multi_labels_host", m, nullptr, pred, n_images, dets, max_det,
+                                 counts, DNN_YOLO_NMS_PER_CLASS, labels_mode);
+}
+
+// the _xy entries take the wide entry's mode pairs: (any class, multi-label) is no rule of either
+static bool xy_modes_ok(int nms_mode, int labels_mode, const char* who) {
+  if (!dnnhip::nms_mode_ok(nms_mode, who) || !dnnhip::labels_mode_ok(labels_mode, who)) return false;
+  if (labels_mode == DNN_YOLO_LABELS_MULTI && nms_mode != DNN_YOLO_NMS_PER_CLASS) {
+    dnnhip::set_error("%s: multi-label detections need per-class NMS (nms_mode %d)", who, DNN_YOLO_NMS_PER_CLASS);
+    return false;
+  }
+  return true;
+}
+
+int dnn_yolo_postprocess_multi_xy(const dnn_yolo_multi* m, const float* scale_x_y, const float* const* pred,
+                                  int n_images, dnn_detection* dets, int max_det, int* counts, void* workspace,
+                                  unsigned long long workspace_bytes, int nms_mode, int labels_mode, void* stream) {
+  const char* who = "dnn_yolo_postprocess_multi_xy";
+  if (!xy_modes_ok(nms_mode, labels_mode, who)) return -2;
+  return dnnhip::launch_yolo_multi(who, m, scale_x_y, pred, n_images, dets, max_det, counts, workspace,
+                                   workspace_bytes, nms_mode, labels_mode, static_cast<hipStream_t>(stream));
+}
+
+int dnn_yolo_postprocess_multi_xy_host(const dnn_yolo_multi* m, const float* scale_x_y, const float* const* pred,
+                                       int n_images, dnn_detection* dets, int max_det, int* counts, int nms_mode,
+                                       int labels_mode) {
+  const char* who = "dnn_yolo_postprocess_multi_xy_host";
+  if (!xy_modes_ok(nms_mode, labels_mode, who)) return -2;
+  return dnnhip::yolo_multi_host(who, m, scale_x_y, pred, n_images, dets, max_det, counts, nms_mode, labels_mode);
 }
 
 }  // extern "C"

@@ -116,8 +116,10 @@ __global__ void __launch_bounds__(PW_DEC_THREADS) yolo_wide_clear_kernel(int* co
 
 template <int MODE>
 __global__ void __launch_bounds__(PW_DEC_THREADS)
-yolo_wide_decode_kernel(const dnn_yolo_multi mh, const MultiPred pred, char* workspace, int nb, int n_images) {
+yolo_wide_decode_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pred, char* workspace, int nb,
+                        int n_images) {
   __shared__ ScaleTab t;
+  __shared__ float s_xs[DNN_YOLO_MAX_SCALES], s_xb[DNN_YOLO_MAX_SCALES];
   const int img = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
   const int S = mh.n_scales, C = mh.scale[0].n_classes, stride = 5 + C;
   const bool logistic = mh.class_mode == 1;
@@ -132,6 +134,10 @@ yolo_wide_decode_kernel(const dnn_yolo_multi mh, const MultiPred pred, char* wor
   unsigned long long* keys = ws_keys(workspace, img, nb, n_images);
 
   fill_scale_tab(t, mh, pred, img, stride, tid);
+  if (tid < DNN_YOLO_MAX_SCALES) {
+    s_xs[tid] = xy.s[tid];
+    s_xb[tid] = xy.b[tid];
+  }
   __syncthreads();
 
   // every thread stays to the end: the appends below are whole-wave operations
@@ -147,7 +153,7 @@ yolo_wide_decode_kernel(const dnn_yolo_multi mh, const MultiPred pred, char* wor
     q = t.pred[s] + (size_t)kk * stride;
     const int b = kk % A, cell = kk / A, col = cell % gw, row = cell / gw;
     long long c4[4];
-    if (!decode_corners(q, b, col, row, t.anchors[s], t.cell[s], c4, &conf)) ctr[1] = 1;
+    if (!decode_corners(q, b, col, row, t.anchors[s], t.cell[s], s_xs[s], s_xb[s], c4, &conf)) ctr[1] = 1;
     box[k][0] = c4[0];
     box[k][1] = c4[1];
     box[k][2] = c4[2];
@@ -479,20 +485,24 @@ static bool wide_modes_ok(int nms_mode, int labels_mode, const char* who) {
 }
 
 template <int MODE>
-static void launch_wide_kernels(const dnn_yolo_multi& m, const MultiPred& mp, int n_images, dnn_detection* dets,
-                                int max_det, int* counts, char* ws, int nb, hipStream_t stream) {
+static void launch_wide_kernels(const dnn_yolo_multi& m, const XyScale& xy, const MultiPred& mp, int n_images,
+                                dnn_detection* dets, int max_det, int* counts, char* ws, int nb, hipStream_t stream) {
   const dim3 grid((nb + PW_DEC_THREADS - 1) / PW_DEC_THREADS, n_images);
-  hipLaunchKernelGGL(yolo_wide_decode_kernel<MODE>, grid, dim3(PW_DEC_THREADS), 0, stream, m, mp, ws, nb, n_images);
+  hipLaunchKernelGGL(yolo_wide_decode_kernel<MODE>, grid, dim3(PW_DEC_THREADS), 0, stream, m, xy, mp, ws, nb,
+                     n_images);
   hipLaunchKernelGGL(yolo_wide_nms_kernel<MODE>, dim3(n_images), dim3(PM_THREADS), 0, stream, m, mp, dets, max_det,
                      counts, ws, nb, n_images);
 }
 
-static int launch_yolo_wide(const char* who, const dnn_yolo_multi* m, const float* const* pred, int n_images,
+static int launch_yolo_wide(const char* who, const dnn_yolo_multi* m, const float* scale_x_y,
+                            const float* const* pred, int n_images,
                             dnn_detection* dets, int max_det, int* counts, void* workspace,
                             unsigned long long workspace_bytes, int nms_mode, int labels_mode, hipStream_t stream) {
   const int nb = wide_boxes(m, who);
   if (nb < 0) return nb;
   if (!wide_modes_ok(nms_mode, labels_mode, who)) return -2;
+  XyScale xy;
+  if (!xy_scale_from(scale_x_y, m->n_scales, who, &xy)) return -2;
   if (n_images < 0 || max_det < 0 || (n_images > 0 && (!pred || !counts || (max_det > 0 && !dets)))) {
     set_error("%s: bad arguments (n_images=%d max_det=%d)", who, n_images, max_det);
     return -2;
@@ -524,11 +534,11 @@ static int launch_yolo_wide(const char* who, const dnn_yolo_multi* m, const floa
   // serve them all
   const bool one = m->scale[0].n_classes == 1;
   if (labels_mode == DNN_YOLO_LABELS_MULTI && !one)
-    launch_wide_kernels<PW_MULTI>(*m, mp, n_images, dets, max_det, counts, ws, nb, stream);
+    launch_wide_kernels<PW_MULTI>(*m, xy, mp, n_images, dets, max_det, counts, ws, nb, stream);
   else if (nms_mode == DNN_YOLO_NMS_PER_CLASS && !one)
-    launch_wide_kernels<PW_PER_CLASS>(*m, mp, n_images, dets, max_det, counts, ws, nb, stream);
+    launch_wide_kernels<PW_PER_CLASS>(*m, xy, mp, n_images, dets, max_det, counts, ws, nb, stream);
   else
-    launch_wide_kernels<PW_ANY>(*m, mp, n_images, dets, max_det, counts, ws, nb, stream);
+    launch_wide_kernels<PW_ANY>(*m, xy, mp, n_images, dets, max_det, counts, ws, nb, stream);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("launch yolo_wide: %s", hipGetErrorString(e));
@@ -538,11 +548,16 @@ static int launch_yolo_wide(const char* who, const dnn_yolo_multi* m, const floa
 }
 
 // Host pointers, synchronous: allocates the scratch, copies in, runs, copies out.
-static int yolo_wide_host(const char* who, const dnn_yolo_multi* m, const float* const* pred, int n_images,
+static int yolo_wide_host(const char* who, const dnn_yolo_multi* m, const float* scale_x_y,
+                          const float* const* pred, int n_images,
                           dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode) {
   const int nb = wide_boxes(m, who);
   if (nb < 0) return nb;
   if (!wide_modes_ok(nms_mode, labels_mode, who)) return -2;
+  {
+    XyScale xy;
+    if (!xy_scale_from(scale_x_y, m->n_scales, who, &xy)) return -2;
+  }
   DNN_REQUIRE(n_images >= 0 && max_det >= 0, "%s: bad arguments", who);
   if (n_images == 0) return 0;
   DNN_REQUIRE(pred && counts && (max_det == 0 || dets), "%s: NULL pointer", who);
@@ -571,8 +586,8 @@ static int yolo_wide_host(const char* who, const dnn_yolo_multi* m, const float*
       rc = -1;
     }
   }
-  if (!rc) rc = launch_yolo_wide(who, m, d_pred, n_images, d_dets, max_det, d_counts, buf + pb + db + cb, wb, nms_mode,
-                                   labels_mode, nullptr);
+  if (!rc) rc = launch_yolo_wide(who, m, scale_x_y, d_pred, n_images, d_dets, max_det, d_counts, buf + pb + db + cb, wb,
+                                   nms_mode, labels_mode, nullptr);
   if (!rc && (hipMemcpy(counts, d_counts, (size_t)n_images * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
               (db && hipMemcpy(dets, d_dets, db, hipMemcpyDeviceToHost) != hipSuccess))) {
     set_error("%s: copy out failed", who);
@@ -599,14 +614,28 @@ int dnn_yolo_wide_workspace(const dnn_yolo_multi* m, int n_images, unsigned long
 int dnn_yolo_postprocess_wide(const dnn_yolo_multi* m, const float* const* pred, int n_images, dnn_detection* dets,
                               int max_det, int* counts, void* workspace, unsigned long long workspace_bytes,
                               int nms_mode, int labels_mode, void* stream) {
-  return dnnhip::launch_yolo_wide("dnn_yolo_postprocess_wide", m, pred, n_images, dets, max_det, counts, workspace,
-                                  workspace_bytes, nms_mode, labels_mode, static_cast<hipStream_t>(stream));
+  return dnnhip::launch_yolo_wide("dnn_yolo_postprocess_wide", m, nullptr, pred, n_images, dets, max_det, counts,
+                                  workspace, workspace_bytes, nms_mode, labels_mode, static_cast<hipStream_t>(stream));
 }
 
 int dnn_yolo_postprocess_wide_host(const dnn_yolo_multi* m, const float* const* pred, int n_images,
                                    dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode) {
-  return dnnhip::yolo_wide_host("dnn_yolo_postprocess_wide_host", m, pred, n_images, dets, max_det, counts, nms_mode,
-                                labels_mode);
+  return dnnhip::yolo_wide_host("dnn_yolo_postprocess_wide_host", m, nullptr, pred, n_images, dets, max_det, counts,
+                                nms_mode, labels_mode);
+}
+
+int dnn_yolo_postprocess_wide_xy(const dnn_yolo_multi* m, const float* scale_x_y, const float* const* pred,
+                                 int n_images, dnn_detection* dets, int max_det, int* counts, void* workspace,
+                                 unsigned long long workspace_bytes, int nms_mode, int labels_mode, void* stream) {
+  return dnnhip::launch_yolo_wide("dnn_yolo_postprocess_wide_xy", m, scale_x_y, pred, n_images, dets, max_det, counts,
+                                  workspace, workspace_bytes, nms_mode, labels_mode, static_cast<hipStream_t>(stream));
+}
+
+int dnn_yolo_postprocess_wide_xy_host(const dnn_yolo_multi* m, const float* scale_x_y, const float* const* pred,
+                                      int n_images, dnn_detection* dets, int max_det, int* counts, int nms_mode,
+                                      int labels_mode) {
+  return dnnhip::yolo_wide_host("dnn_yolo_postprocess_wide_xy_host", m, scale_x_y, pred, n_images, dets, max_det,
+                                counts, nms_mode, labels_mode);
 }
 
 }  // extern "C"

@@ -26,14 +26,20 @@ steps in fp32, the fold rounds once.
 
 Sections: [net] (width, height, channels; the caller's in_shape overrides width and height, as
 Darknet's own resizing does), [convolutional] (activation leaky or linear), [shortcut] (linear),
-[route] (one layer: that tensor again; two: their channel concat; four: the SPP pattern, three
-stride-1 max pools of one tensor plus the tensor, which is one dnn_hip.Spp node in Darknet's
-order), [upsample], [maxpool] (where Darknet's window placement is the engine's SAME pool's: 2/2,
-2/1 and odd sizes at stride 1) and [yolo] (mask, anchors, classes).  The conv before each [yolo]
-is an output of the plan, in cfg order (at most 4, what the decode takes: the last one the plan's
-output, the others taps).  The head is a yolo_post.MultiHead with logistic class scores, the masked anchors
-divided by the scale's stride, per-class NMS, multi-label output, score 0.5 and IoU 0.45
-(Darknet's detector defaults).
+[route] (one layer: that tensor again, or with groups / group_id its channels
+[group_id * c / groups, (group_id + 1) * c / groups), one dnn_hip.ChannelSlice node: the split of a
+CSP block; two: their channel concat; four: the SPP pattern, three stride-1 max pools of one tensor
+plus the tensor, which is one dnn_hip.Spp node in Darknet's order), [upsample], [maxpool] (where
+Darknet's window placement is the engine's SAME pool's: 2/2, 2/1 and odd sizes at stride 1) and
+[yolo] (mask, anchors, classes, scale_x_y; new_coords must be 0 and nms_kind absent, default or
+greedynms).  The conv before each [yolo] is an output of the plan, in cfg order (at most 4, what
+the decode takes: the last one the plan's output, the others taps).  The head is a
+yolo_post.MultiHead with logistic class scores, the masked anchors divided by the scale's stride,
+per-class NMS, multi-label output, score 0.5 and IoU 0.45 (Darknet's detector defaults); a
+scale_x_y other than 1 goes into the head per scale
+(yolo_post.MultiHead's scale_x_y: the box centre's logistic becomes sig * s - 0.5 * (s - 1)).
+Importable stock models: YOLOv3, YOLOv3-SPP, YOLOv3-tiny and YOLOv4-tiny (cfg_text has their public
+definitions).
 
 Weight files (load_weights / save_weights): three int32 `major, minor, revision`, then `seen` (8
 bytes when major * 10 + minor >= 2, else 4), then per [convolutional] in cfg order biases[n],
@@ -45,7 +51,12 @@ Out of scope:
 
   * YOLOv2's [reorg] and [region]: Darknet's reorg channel order is not the route kernel's
     (TensorFlow's space_to_depth), so yolov2.py's weights are not Darknet's either;
-  * grouped convs (`groups` > 1);
+  * grouped convs (`groups` > 1 in a [convolutional]);
+  * the mish activation and with it full YOLOv4 (cfg_text("yolov4") raises);
+  * [route] with groups > 1 over more than one layer (Darknet slices each layer then; no stock cfg
+    does it);
+  * [yolo] with new_coords = 1 (the scaled-YOLOv4 box form) and nms_kind = diounms (DIoU NMS): both
+    raise DarknetError, since ignoring either gives wrong boxes;
   * image file decoding: detect_images takes H x W x 3 uint8 arrays of any sizes, letterboxes them
     on the device as Darknet's letterbox_image does and returns boxes in each image's own pixels
     (ingest.RaggedIngest, yolo_post.DetectionBuffers.correct); reading a JPEG into such an array
@@ -67,7 +78,8 @@ import yolov3
 SECTION_TYPES = ("net", "convolutional", "shortcut", "route", "upsample", "maxpool", "yolo")
 BN_EPS = 1e-6  # normalize_cpu's .000001f, added to sqrt(var)
 SCORE_THR, IOU_THR = 0.5, 0.45  # Darknet's detector defaults (-thresh .5, nms .45)
-MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny")
+MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny", "yolov4-tiny")
+NMS_KINDS = ("default", "greedynms")  # [yolo] nms_kind values that are the decode's greedy NMS
 
 
 class DarknetError(ValueError):
@@ -195,6 +207,42 @@ def maxpool_params(sec, in_h, in_w):
     return size, stride
 
 
+def route_group(sec, n_layers, c):
+    """(first, channels) of the channel range a [route] section takes of its c input channels:
+    groups (default 1) and group_id (default 0) select [group_id * c / groups, (group_id + 1) * c /
+    groups).  DarknetError, naming the line, when groups does not divide c, group_id is outside
+    0..groups-1, or groups > 1 comes with more than one layer."""
+    groups, gid = _int(sec, "groups", 1), _int(sec, "group_id", 0)
+    where = f"[route] at line {sec['line']}"
+    if groups < 1:
+        raise DarknetError(f"{where}: groups = {groups}: need >= 1")
+    if not 0 <= gid < groups:
+        raise DarknetError(f"{where}: group_id = {gid} is outside 0..{groups - 1} (groups = {groups})")
+    if groups > 1 and n_layers != 1:
+        raise DarknetError(f"{where}: groups = {groups} with {n_layers} layers is not supported (one layer only)")
+    if c % groups:
+        raise DarknetError(f"{where}: groups = {groups} does not divide the layer's {c} channels")
+    return gid * (c // groups), c // groups
+
+
+def yolo_params(sec):
+    """scale_x_y (default 1) of a [yolo] section, after refusing what the decode does not implement:
+    new_coords other than 0 and an nms_kind outside NMS_KINDS."""
+    where = f"[yolo] at line {sec['line']}"
+    if _int(sec, "new_coords", 0) != 0:
+        raise DarknetError(f"{where}: new_coords = {sec['new_coords']} is not supported (only 0)")
+    kind = sec.get("nms_kind", "default")
+    if kind not in NMS_KINDS:
+        raise DarknetError(f"{where}: nms_kind = {kind} is not supported ({', '.join(NMS_KINDS)})")
+    try:
+        s = float(sec.get("scale_x_y", 1))
+    except ValueError:
+        raise DarknetError(f"{where}: scale_x_y = {sec['scale_x_y']!r} is not a number")
+    if not (s > 0 and s < float("inf")):
+        raise DarknetError(f"{where}: scale_x_y = {s}: need a finite value > 0")
+    return s
+
+
 def layer_shapes(sections, in_shape=None):
     """Per layer (every section after [net]) its output's (h, w, c), walking the cfg as Darknet's
     parser does; raises DarknetError for a section that does not fit its input."""
@@ -223,7 +271,8 @@ def layer_shapes(sections, in_shape=None):
             srcs = [shapes[i] for i in idx]
             if any(s[:2] != srcs[0][:2] for s in srcs):
                 raise DarknetError(f"[route] at line {sec['line']}: layers of sizes {srcs} cannot be concatenated")
-            h, w, c = srcs[0][0], srcs[0][1], sum(s[2] for s in srcs)
+            h, w = srcs[0][:2]
+            c = route_group(sec, len(idx), sum(s[2] for s in srcs))[1]
         elif kind == "upsample":
             f = _int(sec, "stride", 2)
             if not 1 <= f <= dnn_hip.MAX_UPSAMPLE_FACTOR:
@@ -235,6 +284,7 @@ def layer_shapes(sections, in_shape=None):
         elif kind == "yolo":
             if at == 0 or sections[at]["type"] != "convolutional":
                 raise DarknetError(f"[yolo] at line {sec['line']}: it must follow a [convolutional] section")
+            yolo_params(sec)
         shapes.append((h, w, c))
     return shapes
 
@@ -412,7 +462,9 @@ def build_graph(builder_cls, sections, layers, in_shape):
         elif kind == "route":
             srcs = [out[_layer_index(sec, v, at, "layers")] for v in _ints(sec, "layers")]
             if len(srcs) == 1:
-                cur = srcs[0]
+                src_c = shapes[_layer_index(sec, _ints(sec, "layers")[0], at, "layers")][2]
+                first, channels = route_group(sec, 1, src_c)
+                cur = srcs[0] if channels == src_c else g.create_channel_slice(node(srcs[0]), first, channels)
             elif len(srcs) == 2:
                 cur = g.create_concat([node(srcs[0]), node(srcs[1])])
             else:
@@ -458,8 +510,9 @@ def multi_head(yolos, in_h, in_w, score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per
     """The yolo_post.MultiHead of build_graph's `yolos` for an in_h x in_w input: per [yolo] the
     anchors its mask picks, in pixels, divided by the scale's stride (input / grid).  With `wide`
     a yolo_post.WideHead (up to 65,536 boxes, the grid-wide decode), whatever the box count."""
-    scales = []
+    scales, xy = [], []
     for y in yolos:
+        xy.append(yolo_params(y))
         gh, gw = y["grid"]
         if in_h % gh or in_w % gw or in_h // gh != in_w // gw:
             raise DarknetError(f"[yolo] at line {y['line']}: a {gh} x {gw} grid does not divide the {in_h} x {in_w} "
@@ -475,7 +528,8 @@ def multi_head(yolos, in_h, in_w, score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per
         px = [a for m in mask for a in anchors[2 * m:2 * m + 2]]
         scales.append(yolo_post.Scale(gh, gw, len(mask), _int(y, "classes", 20), tuple(a / stride for a in px),
                                       float(stride), score_thr, iou_thr))
-    return (yolo_post.WideHead if wide else yolo_post.MultiHead)(scales, "logistic", nms, labels)
+    kw = {} if all(s == 1.0 for s in xy) else {"scale_x_y": tuple(xy)}
+    return (yolo_post.WideHead if wide else yolo_post.MultiHead)(scales, "logistic", nms, labels, **kw)
 
 
 _AUTO = object()
@@ -541,7 +595,9 @@ class DarknetModel(yolov3.YOLO_V3):
         Darknet's letterbox_image does (ingest.RaggedIngest) into the plan's input, the plan and
         the multi-scale decode run as in `detect`, and the rows are corrected in place
         (yolo_post.DetectionBuffers.correct).  order "bgr" (cv2 frames) or "rgb".  Leaves dets /
-        counts in self.buffers, ready for its pack()."""
+        counts in self.buffers, ready for its pack().  (AlexeyAB's detector stretches an image to
+        the network's size by default where this letterboxes, so boxes for YOLOv4-tiny compare
+        with its -letter_box runs; not pinned by a test.)"""
         import torch
         import ingest
         self._need_head()
@@ -611,14 +667,21 @@ class _Cfg(object):
                         ("num", len(anchors.split(",")) // 2), ("jitter", ".3"), ("ignore_thresh", ".7"),
                         ("truth_thresh", 1), ("random", 1))
 
+    def yolo_v4(self, mask, anchors, classes):
+        return self.add("yolo", ("mask", mask), ("anchors", anchors), ("classes", classes),
+                        ("num", len(anchors.split(",")) // 2), ("jitter", ".3"), ("scale_x_y", "1.05"),
+                        ("cls_normalizer", "1.0"), ("iou_normalizer", "0.07"), ("iou_loss", "ciou"),
+                        ("ignore_thresh", ".7"), ("truth_thresh", 1), ("random", 0), ("resize", "1.5"),
+                        ("nms_kind", "greedynms"), ("beta_nms", "0.6"))
+
     def text(self):
         return "\n".join(self.lines)
 
 
 def cfg_text(model, classes=80, width=416, height=416, width_div=1):
-    """The public definition of `model` ("yolov3", "yolov3-spp" or "yolov3-tiny") as cfg text, for
-    `classes` classes and a width x height input; width_div divides every channel count except the
-    heads' 3 x (5 + classes) (a narrow model of the same topology)."""
+    """The public definition of `model` ("yolov3", "yolov3-spp", "yolov3-tiny" or "yolov4-tiny") as cfg
+    text, for `classes` classes and a width x height input; width_div divides every channel count
+    except the heads' 3 x (5 + classes) (a narrow model of the same topology)."""
     if model not in MODELS:
         raise ValueError(f"model {model!r}: one of {MODELS} expected")
     n_out = 3 * (5 + int(classes))
@@ -641,6 +704,32 @@ def cfg_text(model, classes=80, width=416, height=416, width_div=1):
         c.conv(256, 3)
         c.conv(n_out, 1, head=True)
         c.yolo("0,1,2", _TINY_ANCHORS, classes)
+        return c.text()
+    if model == "yolov4-tiny":
+        c.conv(32, 3, stride=2)
+        c.conv(64, 3, stride=2)
+        for f in (64, 128, 256):  # CSP blocks: A, B = conv(second half of A), C, D = conv 1x1 of [C, B], [A, D], pool
+            c.conv(f, 3)
+            c.add("route", ("layers", "-1"), ("groups", 2), ("group_id", 1))
+            c.conv(f // 2, 3)
+            c.conv(f // 2, 3)
+            c.add("route", ("layers", "-1,-2"))
+            lateral = c.conv(f, 1)
+            c.add("route", ("layers", "-6,-1"))
+            c.add("maxpool", ("size", 2), ("stride", 2))
+        c.conv(512, 3)
+        c.lines.append("##################################")
+        c.conv(256, 1)
+        c.conv(512, 3)
+        c.conv(n_out, 1, head=True)
+        c.yolo_v4("3,4,5", _TINY_ANCHORS, classes)
+        c.add("route", ("layers", "-4"))
+        c.conv(128, 1)
+        c.add("upsample", ("stride", 2))
+        c.add("route", ("layers", f"-1, {lateral}"))
+        c.conv(256, 3)
+        c.conv(n_out, 1, head=True)
+        c.yolo_v4("1,2,3", _TINY_ANCHORS, classes)
         return c.text()
     c.conv(32, 3)
     stage_end = []

@@ -88,6 +88,8 @@ def _bind_plan_api(lib):
         "dnn_shortcut_host": (i, [vp, vp, vp, i, i, i, i, i]),
         "dnn_upsample_host": (i, [vp, vp, i, i, i, i, i]),
         "dnn_plan_add_spp": (i, [vp, i, P(i), i]),
+        "dnn_plan_add_slice": (i, [vp, i, i]),
+        "dnn_slice_host": (i, [vp, vp, i, i, i, i, i, i]),
         "dnn_spp_host": (i, [vp, vp, i, i, i, i, i, P(i), i]),
         "dnn_plan_output_shape": (i, [vp, P(i), P(i), P(i), P(i)]),
         "dnn_plan_describe": (i, [vp, ctypes.c_char_p, i]),
@@ -291,6 +293,7 @@ class DnnGraphBuilder(object):
         self.G = nx.DiGraph() if nx is not None else _DiGraph()
         self.name_num = {"conv2d": 0, "bias_add": 0, "max_pool2d": 0, "batch_norm": 0, "leaky_relu": 0,
                          "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0, "spp": 0,
+                         "channel_slice": 0,
                          "conv2d_padded": 0, "scale_shift": 0, "leaky_relu_f32": 0}
         self.in_node = None
         self.out_node = None
@@ -368,6 +371,11 @@ class DnnGraphBuilder(object):
 
     def create_upsample(self, in_node, factor):
         out_node = Upsample(self.get_name("upsample"), in_node, factor)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_channel_slice(self, in_node, first, channels):
+        out_node = ChannelSlice(self.get_name("channel_slice"), in_node, first, channels)
         self.G.add_edge(in_node, out_node)
         return out_node
 
@@ -727,6 +735,31 @@ class Upsample(DnnNode):
         _check(rc, self.name)
 
 
+class ChannelSlice(DnnNode):
+    """Not in the reference (a CSP block's split needs it; Darknet's [route] with groups / group_id):
+    a channel range, [n, H, W, C] -> [n, H, W, channels], out[..., k] = in[..., first + k] with
+    0 <= first, channels >= 1 and first + channels <= C.  run() -> dnn_slice_host."""
+
+    def __init__(self, name, in_node, first, channels):
+        if len(in_node.result.shape) != 4:
+            raise ValueError
+        for v in (first, channels):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError
+        batch, h, w, c = in_node.result.shape
+        if first < 0 or channels < 1 or first + channels > c:
+            raise ValueError
+        self.in_node = in_node
+        self.first, self.channels = int(first), int(channels)
+        self.result = np.zeros((batch, h, w, self.channels), dtype='float32')
+        self.name = name
+
+    def run(self):
+        a = np.ascontiguousarray(self.in_node.result, dtype=np.float32)
+        rc = mylib.dnn_slice_host(_vp(a), _vp(self.result), *map(int, a.shape), self.first, self.channels)
+        _check(rc, self.name)
+
+
 MAX_SPP_SIZES = 3  # DNN_SPP_MAX_SIZES: pools per spp entry
 MAX_SPP_K = 13     # DNN_SPP_MAX_K: the largest pool window (sizes are odd, 3..13)
 
@@ -874,6 +907,14 @@ class SppEntry(object):
         self.nodes = list(nodes)
 
 
+class SliceEntry(object):
+    """dnn_plan_add_slice: channels [first, first + channels) of the current tensor."""
+
+    def __init__(self, first, channels, nodes=()):
+        self.first, self.channels = int(first), int(channels)
+        self.nodes = list(nodes)
+
+
 class TapEntry(object):
     """dnn_plan_add_tap: the current tensor becomes the plan's extra output `index` (no kernel);
     `node` is the graph node it is the result of (None in plans assembled by hand)."""
@@ -952,6 +993,8 @@ def _lower_one(g, nxt):
         return RouteEntry(nxt.block, nodes=[nxt]), nxt
     if isinstance(nxt, Upsample):
         return UpsampleEntry(nxt.factor, nodes=[nxt]), nxt
+    if isinstance(nxt, ChannelSlice):
+        return SliceEntry(nxt.first, nxt.channels, nodes=[nxt]), nxt
     if isinstance(nxt, Spp):
         return SppEntry(nxt.ksizes, nxt.x_first, nodes=[nxt]), nxt
     return None  # a standalone element-wise op: not expressible as a fused entry
@@ -969,13 +1012,15 @@ def _lower_chain(g, chain):
     return es
 
 
-def _lower_fork(g, x, heads, live):
+def _lower_fork(g, x, heads, live, nested=False):
     """Node `x` has the two successors `heads`: lower the two chains up to the Concat or Add that
     joins them.  Returns (entries, the last node covered, live slots afterwards), or None for
     anything but two plain chains (either may be empty) meeting in one Concat or one Add.  `live`
-    is the set of slot numbers in use; new slots are the lowest free numbers.  A Concat keeps its
-    slots to the end of the plan; an Add block releases every slot it opens, so any number of them
-    fit in sequence."""
+    is the set of slot numbers in use; new slots are the lowest free numbers.  An Add block releases
+    every slot it opens, so any number of them fit in sequence.  A Concat fork keeps its slots to
+    the end of the plan, unless it is `nested`: lowered inside a pending long skip (another slot is
+    live then: a CSP block's inner fork), it gives them back with ReleaseEntry right after its
+    RouteEntry."""
     chains, joins = [], []
     for cur in heads:
         chain = []
@@ -1032,6 +1077,8 @@ def _lower_fork(g, x, heads, live):
         s2d = tail.pop()
         block, nodes = s2d.block, s2d.nodes + [join]
     entries += tail + [RouteEntry(block, b_slot, slot_first=(first == 0), nodes=nodes)]
+    if nested:  # the route has read both, and nothing later names them
+        return entries + [ReleaseEntry(s) for s in sorted(used)], join, live
     return entries, join, live | used
 
 
@@ -1078,11 +1125,11 @@ def _output_branch(g, head):
 def lower_graph(g):
     """Lower a builder graph to fused plan entries, or None if the plan cannot express it (then
     the node-by-node path runs).  Expressible: a chain of Conv2D (with its BiasAdd / BatchNorm /
-    LeakyReLU), MaxPool2D, SpaceToDepth, Upsample and Spp, and forks of two such chains (either may be
+    LeakyReLU), MaxPool2D, SpaceToDepth, Upsample, ChannelSlice and Spp, and forks of two such chains (either may be
     empty) joined by one Concat or one Add (with a LeakyReLU directly after it), any number of
-    them in sequence within the plan's slots (an Add block gives its slots back); nested forks are
-    not.  Graphs with extra outputs (add_out_node) add two patterns at a node x with two
-    successors:
+    them in sequence within the plan's slots (an Add block gives its slots back, and so does a
+    Concat fork lowered inside a pending long skip); forks nested in a fork's branch are not.
+    Graphs with extra outputs (add_out_node) add patterns at a node x with two successors:
 
       output branch  one successor starts a plain chain that ends in an extra output without
                      successors: Stash(x), the chain, Tap, Restore(x), Release(x), and the
@@ -1090,7 +1137,15 @@ def lower_graph(g):
       long skip      one successor is a Concat that takes x directly and whose other input the
                      main line produces later, whatever complete blocks lie in between:
                      Stash(x), the main line, Route(1, slot, slot_first = x is the Concat's first
-                     input), Release(slot).  A long skip into an Add is not expressible.
+                     input), Release(slot).  A long skip into an Add is not expressible.  A
+                     Concat-joined fork may lie inside a long skip (a CSP block: the skip is
+                     concat[A, D], the fork concat[C, B] inside it); it releases its slots after
+                     its Route, so a sequence of such blocks stays within the plan's slots;
+      arrival plus   x has two successors, the pending Concat of a long skip that the main line
+      a new skip     arrives at with x, and a Concat of a NEW long skip from x (YOLOv4-tiny's layer
+                     23: the end of the third CSP block and the lateral of the top-down merge):
+                     Stash(x), then the pending Route(1, slot, ...) and Release(slot); the new skip
+                     is resolved where the main line reaches its Concat.
 
     An extra output on the main line is a Tap after the entry that computes it.  Slots are the
     lowest free numbers; more than MAX_SLOTS live at once gives None.
@@ -1132,6 +1187,11 @@ def lower_graph(g):
     node = g.in_node
     while not g.is_out_node(node):
         succ = [s for s in g.G.successors(node) if (node, s) not in handled]
+        arriving = [s for s in succ if s in pending]
+        if len(succ) == 2 and len(arriving) == 1:  # arrival plus a new long skip from this node
+            if not long_skip([s for s in succ if s is not arriving[0]]):
+                return None
+            continue  # (the new skip's edge is handled: the arrival is the one successor left)
         if len(succ) == 1:
             nxt = succ[0]
             if nxt in pending:  # the main line arrives at a long skip's Concat
@@ -1153,7 +1213,7 @@ def lower_graph(g):
             node = r[1]
             tap(node)
         elif len(succ) == 2:
-            r = _lower_fork(g, node, succ, live)
+            r = _lower_fork(g, node, succ, live, nested=bool(pending))
             if r is not None:
                 entries += r[0]
                 node, live = r[1], set(r[2])
@@ -1221,7 +1281,7 @@ def _pad_code(padding):
 
 def _add_structural(lib, h, e, leaky_variant=1):
     """Emit a StashEntry / RestoreEntry / RouteEntry / ShortcutEntry / ReleaseEntry /
-    UpsampleEntry / SppEntry / TapEntry; False if `e` is none of them."""
+    UpsampleEntry / SppEntry / SliceEntry / TapEntry; False if `e` is none of them."""
     if isinstance(e, StashEntry):
         slot = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_stash(h, ctypes.byref(slot)), "dnn_plan_add_stash", lib)
@@ -1240,6 +1300,8 @@ def _add_structural(lib, h, e, leaky_variant=1):
     elif isinstance(e, SppEntry):
         sizes = (ctypes.c_int * len(e.ksizes))(*e.ksizes)
         _check(lib.dnn_plan_add_spp(h, len(e.ksizes), sizes, 1 if e.x_first else 0), "dnn_plan_add_spp", lib)
+    elif isinstance(e, SliceEntry):
+        _check(lib.dnn_plan_add_slice(h, e.first, e.channels), "dnn_plan_add_slice", lib)
     elif isinstance(e, TapEntry):
         index = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_tap(h, ctypes.byref(index)), "dnn_plan_add_tap", lib)

@@ -139,6 +139,15 @@ def _bind(lib):
     lib.dnn_yolo_postprocess_wide.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, i, vp]
     lib.dnn_yolo_postprocess_wide_host.restype = i
     lib.dnn_yolo_postprocess_wide_host.argtypes = [mp, pp, i, vp, i, vp, i, i]
+    fp = ctypes.POINTER(ctypes.c_float)
+    lib.dnn_yolo_postprocess_multi_xy.restype = i
+    lib.dnn_yolo_postprocess_multi_xy.argtypes = [mp, fp, pp, i, vp, i, vp, vp, u64, i, i, vp]
+    lib.dnn_yolo_postprocess_multi_xy_host.restype = i
+    lib.dnn_yolo_postprocess_multi_xy_host.argtypes = [mp, fp, pp, i, vp, i, vp, i, i]
+    lib.dnn_yolo_postprocess_wide_xy.restype = i
+    lib.dnn_yolo_postprocess_wide_xy.argtypes = [mp, fp, pp, i, vp, i, vp, vp, u64, i, i, vp]
+    lib.dnn_yolo_postprocess_wide_xy_host.restype = i
+    lib.dnn_yolo_postprocess_wide_xy_host.argtypes = [mp, fp, pp, i, vp, i, vp, i, i]
     sp = ctypes.POINTER(ImageSize)
     lib.dnn_yolo_correct_detections.restype = i
     lib.dnn_yolo_correct_detections.argtypes = [vp, vp, i, i, sp, i, i, vp]
@@ -241,13 +250,25 @@ class MultiHead(object):
     detection per class whose score conf * p[class] is above the threshold, so an image can have
     more rows than boxes (`max_det`; at most 16384 candidates, else the image's code is -3).  It
     needs nms="per_class": under the class-agnostic rule a box's second label is always suppressed
-    by its first.  Validates like the C side (dnn_yolo_multi_boxes) and raises ValueError."""
+    by its first.  scale_x_y is Darknet's [yolo] key of that name (YOLOv4, YOLOv4-tiny): None, or
+    one finite float > 0 per scale; the box centre's logistic becomes sig * s - 0.5 * (s - 1) in
+    fp32 (the dnn_yolo_postprocess_*_xy entries).  None calls exactly the entries without it.
+    Validates like the C side (dnn_yolo_multi_boxes) and raises ValueError."""
 
     MAX_BOXES = MULTI_MAX_BOXES         # the most boxes over all scales (WideHead: WIDE_MAX_BOXES)
     BOXES_ENTRY = "dnn_yolo_multi_boxes"  # the C function that validates the description and counts them
 
-    def __init__(self, scales, class_mode="logistic", nms="any", labels="argmax"):
+    def __init__(self, scales, class_mode="logistic", nms="any", labels="argmax", scale_x_y=None):
         scales = list(scales)
+        if scale_x_y is not None:
+            scale_x_y = tuple(float(v) for v in scale_x_y)
+            if len(scale_x_y) != len(scales):
+                raise ValueError(f"{len(scale_x_y)} scale_x_y values for {len(scales)} scales")
+            if not all(np.float32(v) > 0 and np.isfinite(np.float32(v)) for v in scale_x_y):
+                raise ValueError(f"scale_x_y {scale_x_y!r}: finite values > 0 expected")
+        self.scale_x_y = scale_x_y
+        # the host array the _xy entries read (NULL: every scale 1, the entries without the argument)
+        self.xy = None if scale_x_y is None else (ctypes.c_float * len(scale_x_y))(*scale_x_y)
         if not 1 <= len(scales) <= MAX_SCALES:
             raise ValueError(f"{len(scales)} scales: need 1..{MAX_SCALES}")
         if class_mode not in CLASS_MODES:
@@ -347,8 +368,9 @@ class MultiHead(object):
         grids = ", ".join(f"{s.grid_h}x{s.grid_w}x{s.n_anchors}" for s in self.scales)
         nms = "" if self.nms == "any" else f", NMS {self.nms}"
         labels = "" if self.labels == "argmax" else f", labels {self.labels}"
+        xy = "" if self.scale_x_y is None else ", scale_x_y " + ",".join(f"{v:g}" for v in self.scale_x_y)
         return (f"{type(self).__name__}({grids}; {self.n_classes} classes, {self.class_mode}, score > {self.score_thr:g}, "
-                f"IoU > {self.iou_thr:g}{nms}{labels})")
+                f"IoU > {self.iou_thr:g}{nms}{labels}{xy})")
 
 
 class WideHead(MultiHead):
@@ -386,6 +408,11 @@ def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
     dets = np.zeros((n, max_det), DETECTION_DTYPE)
     counts = np.zeros(n, np.int32)
     ptrs = (ctypes.c_void_p * len(ps))(*[p.ctypes.data for p in ps])
+    if head.xy is not None:
+        name = "dnn_yolo_postprocess_wide_xy_host" if isinstance(head, WideHead) else "dnn_yolo_postprocess_multi_xy_host"
+        dnn_hip._check(getattr(_lib, name)(ctypes.byref(head.c), head.xy, ptrs, n, dets.ctypes.data, max_det,
+                                           counts.ctypes.data, NMS_MODES[head.nms], LABEL_MODES[head.labels]), name)
+        return _rows(dets, counts, max_det, raise_errors)
     if isinstance(head, WideHead):
         dnn_hip._check(_lib.dnn_yolo_postprocess_wide_host(
             ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det, counts.ctypes.data, NMS_MODES[head.nms],
@@ -549,7 +576,8 @@ class MultiDetectionBuffers(DetectionBuffers):
     """DetectionBuffers for a MultiHead: `run(pred_ptrs, n, stream)` takes one device pointer per
     scale and goes through dnn_yolo_postprocess_multi_nms with head.nms, or with head.labels
     "multi" through dnn_yolo_postprocess_multi_labels, or for a WideHead through
-    dnn_yolo_postprocess_wide; dets, counts, `pack` and `to_rows` are the
+    dnn_yolo_postprocess_wide, and for a head with scale_x_y through the _xy entry of its kind;
+    dets, counts, `pack` and `to_rows` are the
     base class's (max_det defaults to head.max_det: head.boxes, or with "multi" the most
     candidates an image can have), so dnn_yolo_pack_detections and dist.gather_detections apply
     unchanged."""
@@ -570,6 +598,13 @@ class MultiDetectionBuffers(DetectionBuffers):
         if len(pred_ptrs) != len(self.head.scales):
             raise ValueError(f"{len(pred_ptrs)} prediction pointers for {len(self.head.scales)} scales")
         ptrs = (ctypes.c_void_p * len(pred_ptrs))(*[int(p) for p in pred_ptrs])
+        if self.head.xy is not None:
+            name = "dnn_yolo_postprocess_wide_xy" if isinstance(self.head, WideHead) else "dnn_yolo_postprocess_multi_xy"
+            dnn_hip._check(getattr(_lib, name)(
+                ctypes.byref(self.head.c), self.head.xy, ptrs, n, self.dets.data_ptr(), self.max_det,
+                self.counts.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), NMS_MODES[self.head.nms],
+                LABEL_MODES[self.head.labels], stream), name)
+            return
         if isinstance(self.head, WideHead):
             dnn_hip._check(_lib.dnn_yolo_postprocess_wide(
                 ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),

@@ -211,6 +211,26 @@ int dnn_plan_add_spp(dnn_plan* plan, int n_sizes, const int* sizes, int x_first)
 int dnn_spp_host(const float* a, float* out, int n, int h, int w, int c, int n_sizes, const int* sizes,
                  int x_first);
 
+/* Channel slice (fp32 plans, batch and latency mode; on an fp16 plan it fails).  The reference has
+ * no such node: it is Darknet's [route] with groups / group_id, the split that opens a CSP block
+ * of YOLOv4-tiny (groups=2, group_id=1: the second half of the channels).
+ *
+ * dnn_plan_add_slice: current [H, W, C] -> [H, W, channels], out[h, w, k] = in[h, w, first + k].
+ *   0 <= first, channels >= 1, first + channels <= C; the whole tensor (first 0, channels C) is
+ *   allowed and still copies.  One kernel ("slice%d" in dnn_plan_kernel_info, 0 flops, two output
+ *   tensors of bytes: what it reads and what it writes), 16-byte accesses when C, first and
+ *   channels are multiples of 4.  Input and output are plain NHWC fp32 (the entry stops the conv /
+ *   pool fusions like the fork / join entries); the input may be the caller's d_in, the output
+ *   goes to a slot or tap region when a stash or tap follows and to d_out when the entry is the
+ *   plan's last.  Fails, leaving the plan unchanged, on an fp16 plan, on a finalized plan and for
+ *   a range outside the current tensor's channels.  The copy is real: a consumer conv reading a
+ *   channel window of the wider tensor in place is not implemented.
+ * dnn_slice_host: the kernel on host tensors (H2D copy, launch, D2H copy, synchronise):
+ *   a [n, h, w, c] -> out [n, h, w, channels].  Each tensor must be below 2 GiB (refused from the
+ *   arguments, before any allocation). */
+int dnn_plan_add_slice(dnn_plan* plan, int first, int channels);
+int dnn_slice_host(const float* a, float* out, int n, int h, int w, int c, int first, int channels);
+
 /* Output shape of the plan so far (per image, plus the planned batch). */
 int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int* c);
 
@@ -222,7 +242,8 @@ int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int*
  * route line both shapes, the block and the slot with its shape, a shortcut line the shape, the
  * slot and the activation, an upsample line both shapes and the factor, a release line the
  * slot and its tensor's shape, a tap line ("tap HxWxC index=k") the shape and the tap's index,
- * an spp line ("spp HxWxC -> HxWx(k+1)C sizes=13,9,5 x=last") both shapes, the sizes and x's place.
+ * an spp line ("spp HxWxC -> HxWx(k+1)C sizes=13,9,5 x=last") both shapes, the sizes and x's place,
+ * a slice line ("slice HxWxC -> HxWxK first=f") both shapes and the first channel taken.
  * A 2x2/s2 MaxPool2D directly
  * after an implicit, patch or direct conv is folded into it; set DNN_HIP_FUSE=0 in the
  * environment before dnn_plan_create to keep every conv explicit and every pool separate

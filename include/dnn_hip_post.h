@@ -255,6 +255,45 @@ int dnn_yolo_postprocess_wide(const dnn_yolo_multi* multi, const float* const* p
 int dnn_yolo_postprocess_wide_host(const dnn_yolo_multi* multi, const float* const* pred, int n_images,
                                    dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode);
 
+/* ---- scale_x_y: Darknet's stretch of the box centre (YOLOv4, YOLOv4-tiny) ---------------
+ * Darknet's [yolo] key scale_x_y = s replaces the logistic of tx and ty (forward_yolo_layer,
+ * scal_add_cpu) by
+ *   sig * s + b,   b = -0.5f * (s - 1.0f)
+ * so that a centre can reach its cell's border: b is computed on the host in fp32 once per scale,
+ * and the device does one fp32 multiply then one fp32 add, never contracted, in place of
+ * sigmoid(tx) and sigmoid(ty).  Width, height, objectness and the class scores do not change.
+ *
+ * scale_x_y: a HOST array of multi->n_scales floats, read before the call returns; NULL means all
+ * 1.  Each value must be finite and > 0: otherwise the call returns -2 before any launch, like an
+ * invalid description, and dnn_last_error() names scale_x_y.  dnn_yolo_multi and dnn_yolo_head
+ * keep their layouts.  With s == 1, b is -0.0f and sig * 1.0f + -0.0f is sig bit for bit for every
+ * non-NaN sig: the entries above run the same kernels with that pair, and with every scale at 1
+ * (or NULL) an _xy entry gives their dets, counts and workspace byte for byte.
+ *
+ * nms_mode / labels_mode are the wide entry's pairs, for the _multi_xy entries too, each run by
+ * the kernel of the entry named:
+ *   (ANY_CLASS, ARGMAX)  dnn_yolo_postprocess_multi          / _wide in that mode
+ *   (PER_CLASS, ARGMAX)  dnn_yolo_postprocess_multi_nms      / _wide in that mode
+ *   (PER_CLASS, MULTI)   dnn_yolo_postprocess_multi_labels   / _wide in that mode
+ *   (ANY_CLASS, MULTI)   none: returns -2
+ * Limits, workspaces (dnn_yolo_multi_workspace and its _nms / _labels twins, all the same size;
+ * dnn_yolo_wide_workspace), codes and every other argument are those of the entries above. */
+int dnn_yolo_postprocess_multi_xy(const dnn_yolo_multi* multi, const float* scale_x_y, const float* const* pred,
+                                  int n_images, dnn_detection* dets, int max_det, int* counts, void* workspace,
+                                  unsigned long long workspace_bytes, int nms_mode, int labels_mode, void* stream);
+
+int dnn_yolo_postprocess_multi_xy_host(const dnn_yolo_multi* multi, const float* scale_x_y,
+                                       const float* const* pred, int n_images, dnn_detection* dets, int max_det,
+                                       int* counts, int nms_mode, int labels_mode);
+
+int dnn_yolo_postprocess_wide_xy(const dnn_yolo_multi* multi, const float* scale_x_y, const float* const* pred,
+                                 int n_images, dnn_detection* dets, int max_det, int* counts, void* workspace,
+                                 unsigned long long workspace_bytes, int nms_mode, int labels_mode, void* stream);
+
+int dnn_yolo_postprocess_wide_xy_host(const dnn_yolo_multi* multi, const float* scale_x_y,
+                                      const float* const* pred, int n_images, dnn_detection* dets, int max_det,
+                                      int* counts, int nms_mode, int labels_mode);
+
 /* ---- boxes back to each image's own pixels ----------------------------------------------
  * The reference's frames are stretched to the network's size and its boxes stay in network
  * pixels.  After a letterbox ingest (include/dnn_hip_ingest.h: dnn_letterbox_frames) image i of

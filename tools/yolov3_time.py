@@ -3,7 +3,9 @@
 alone), and the three-scale decode of the 10,647 boxes on typical inputs (a few hundred
 candidates per image) and on inputs where every box is a candidate.  --model picks the network:
 yolov3 (the default, as above), yolov3_spp (76 convs and the spp entry; the decode is YOLOv3's),
-yolov3_tiny (13 convs, two scales, 2,535 boxes) or all.
+yolov3_tiny (13 convs, two scales, 2,535 boxes), yolov4_tiny (the Darknet import of the public
+cfg with random weights: 21 convs, 3 slices, 7 routes; its decode with scale_x_y = 1.05) or all
+(the three YOLOv3 models).
 
   python tools/yolov3_time.py [--model yolov3] [--batch 1] [--reps 20] [--rounds 5] [--decode-only]
 
@@ -22,6 +24,7 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 import darknet53  # noqa: E402
+import darknet_import  # noqa: E402
 import dnn_hip  # noqa: E402
 import synth  # noqa: E402
 import yolo_post  # noqa: E402
@@ -85,13 +88,29 @@ def time_decode(batch, reps, rounds, head=None):
     return out
 
 
+def random_darknet_layers(sections, seed=0):
+    """He-scaled kernels and BatchNorm statistics near the identity for every conv of a cfg, in
+    load_weights' format (timing only: the values do not change what runs)."""
+    rng = np.random.default_rng(seed)
+    layers = []
+    for n, c, size, bn in darknet_import.conv_shapes(sections):
+        layer = {"biases": (rng.standard_normal(n) * 0.1).astype(np.float32),
+                 "weights": (rng.standard_normal((n, c, size, size)) * np.sqrt(2.0 / (c * size * size))).astype(np.float32)}
+        if bn:
+            layer.update(scales=rng.uniform(0.75, 1.25, n).astype(np.float32),
+                         rolling_mean=(rng.standard_normal(n) * 0.1).astype(np.float32),
+                         rolling_variance=rng.uniform(0.5, 1.5, n).astype(np.float32))
+        layers.append(layer)
+    return layers
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--decode-only", action="store_true")
-    ap.add_argument("--model", choices=("yolov3", "yolov3_spp", "yolov3_tiny", "all"), default="yolov3")
+    ap.add_argument("--model", choices=("yolov3", "yolov3_spp", "yolov3_tiny", "yolov4_tiny", "all"), default="yolov3")
     a = ap.parse_args()
     shape = (a.batch, 416, 416, 3)
     res = {"batch": a.batch}
@@ -99,6 +118,12 @@ def main():
         res["decode"] = time_decode(a.batch, a.reps, a.rounds)
     if a.model in ("yolov3_tiny", "all"):
         res["decode_tiny"] = time_decode(a.batch, a.reps, a.rounds, yolo_post.MultiHead.yolov3_tiny(416, 416))
+    if a.model == "yolov4_tiny":
+        secs = darknet_import.parse_cfg(darknet_import.cfg_text("yolov4-tiny"))
+        g, _, yolos = darknet_import.build_graph(dnn_hip.DnnGraphBuilder, secs, random_darknet_layers(secs), shape)
+        res["decode_v4_tiny"] = time_decode(a.batch, a.reps, a.rounds, darknet_import.multi_head(yolos, 416, 416))
+        if not a.decode_only:
+            res["yolov4_tiny_plan"] = time_plan(g, a.batch, a.reps, a.rounds)
     if not a.decode_only and a.model in ("yolov3_spp", "all"):
         ws = yolov3_spp.validate(synth.yolov3_spp_weights())
         res["yolov3_spp_plan"] = time_plan(yolov3_spp.build_graph(dnn_hip.DnnGraphBuilder, ws, in_shape=shape)[0],
