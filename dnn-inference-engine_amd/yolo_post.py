@@ -92,67 +92,41 @@ def _sizes(sizes):
 
 
 def _bind(lib):
-    vp, i = ctypes.c_void_p, ctypes.c_int
-    hp, u64 = ctypes.POINTER(HeadStruct), ctypes.c_ulonglong
-    lib.dnn_yolo_head_voc.restype = i
-    lib.dnn_yolo_head_voc.argtypes = [i, i, hp]
-    lib.dnn_yolo_head_boxes.restype = i
-    lib.dnn_yolo_head_boxes.argtypes = [hp]
-    lib.dnn_yolo_head_workspace.restype = i
-    lib.dnn_yolo_head_workspace.argtypes = [hp, i, ctypes.POINTER(u64)]
-    lib.dnn_yolo_postprocess_head.restype = i
-    lib.dnn_yolo_postprocess_head.argtypes = [hp, vp, i, vp, i, vp, vp, u64, vp]
-    lib.dnn_yolo_postprocess_head_host.restype = i
-    lib.dnn_yolo_postprocess_head_host.argtypes = [hp, vp, i, vp, i, vp]
-    lib.dnn_yolo_postprocess.restype = i
-    lib.dnn_yolo_postprocess.argtypes = [vp, i, vp, i, vp, vp]
-    lib.dnn_yolo_postprocess_host.restype = i
-    lib.dnn_yolo_postprocess_host.argtypes = [vp, i, vp, i, vp]
-    lib.dnn_yolo_pack_detections.restype = i
-    lib.dnn_yolo_pack_detections.argtypes = [vp, vp, i, i, vp, vp, vp]
-    mp, pp = ctypes.POINTER(MultiStruct), ctypes.POINTER(vp)
-    lib.dnn_yolo_multi_boxes.restype = i
-    lib.dnn_yolo_multi_boxes.argtypes = [mp]
-    lib.dnn_yolo_multi_workspace.restype = i
-    lib.dnn_yolo_multi_workspace.argtypes = [mp, i, ctypes.POINTER(u64)]
-    lib.dnn_yolo_postprocess_multi.restype = i
-    lib.dnn_yolo_postprocess_multi.argtypes = [mp, pp, i, vp, i, vp, vp, u64, vp]
-    lib.dnn_yolo_postprocess_multi_host.restype = i
-    lib.dnn_yolo_postprocess_multi_host.argtypes = [mp, pp, i, vp, i, vp]
-    lib.dnn_yolo_multi_nms_workspace.restype = i
-    lib.dnn_yolo_multi_nms_workspace.argtypes = [mp, i, i, ctypes.POINTER(u64)]
-    lib.dnn_yolo_postprocess_multi_nms.restype = i
-    lib.dnn_yolo_postprocess_multi_nms.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, vp]
-    lib.dnn_yolo_postprocess_multi_nms_host.restype = i
-    lib.dnn_yolo_postprocess_multi_nms_host.argtypes = [mp, pp, i, vp, i, vp, i]
-    lib.dnn_yolo_multi_labels_workspace.restype = i
-    lib.dnn_yolo_multi_labels_workspace.argtypes = [mp, i, i, ctypes.POINTER(u64)]
-    lib.dnn_yolo_postprocess_multi_labels.restype = i
-    lib.dnn_yolo_postprocess_multi_labels.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, vp]
-    lib.dnn_yolo_postprocess_multi_labels_host.restype = i
-    lib.dnn_yolo_postprocess_multi_labels_host.argtypes = [mp, pp, i, vp, i, vp, i]
-    lib.dnn_yolo_wide_boxes.restype = i
-    lib.dnn_yolo_wide_boxes.argtypes = [mp]
-    lib.dnn_yolo_wide_workspace.restype = i
-    lib.dnn_yolo_wide_workspace.argtypes = [mp, i, ctypes.POINTER(u64)]
-    lib.dnn_yolo_postprocess_wide.restype = i
-    lib.dnn_yolo_postprocess_wide.argtypes = [mp, pp, i, vp, i, vp, vp, u64, i, i, vp]
-    lib.dnn_yolo_postprocess_wide_host.restype = i
-    lib.dnn_yolo_postprocess_wide_host.argtypes = [mp, pp, i, vp, i, vp, i, i]
-    fp = ctypes.POINTER(ctypes.c_float)
-    lib.dnn_yolo_postprocess_multi_xy.restype = i
-    lib.dnn_yolo_postprocess_multi_xy.argtypes = [mp, fp, pp, i, vp, i, vp, vp, u64, i, i, vp]
-    lib.dnn_yolo_postprocess_multi_xy_host.restype = i
-    lib.dnn_yolo_postprocess_multi_xy_host.argtypes = [mp, fp, pp, i, vp, i, vp, i, i]
-    lib.dnn_yolo_postprocess_wide_xy.restype = i
-    lib.dnn_yolo_postprocess_wide_xy.argtypes = [mp, fp, pp, i, vp, i, vp, vp, u64, i, i, vp]
-    lib.dnn_yolo_postprocess_wide_xy_host.restype = i
-    lib.dnn_yolo_postprocess_wide_xy_host.argtypes = [mp, fp, pp, i, vp, i, vp, i, i]
-    sp = ctypes.POINTER(ImageSize)
-    lib.dnn_yolo_correct_detections.restype = i
-    lib.dnn_yolo_correct_detections.argtypes = [vp, vp, i, i, sp, i, i, vp]
-    lib.dnn_yolo_correct_detections_host.restype = i
-    lib.dnn_yolo_correct_detections_host.argtypes = [vp, vp, i, i, sp, i, i]
+    vp, i, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong
+    hp, mp, pp = ctypes.POINTER(HeadStruct), ctypes.POINTER(MultiStruct), ctypes.POINTER(vp)
+    fp, sp, bp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ImageSize), ctypes.POINTER(u64)
+    for name, argtypes in {  # every entry returns int
+            "dnn_yolo_head_voc": [i, i, hp],
+            "dnn_yolo_head_boxes": [hp],
+            "dnn_yolo_head_workspace": [hp, i, bp],
+            "dnn_yolo_postprocess_head": [hp, vp, i, vp, i, vp, vp, u64, vp],
+            "dnn_yolo_postprocess_head_host": [hp, vp, i, vp, i, vp],
+            "dnn_yolo_postprocess": [vp, i, vp, i, vp, vp],
+            "dnn_yolo_postprocess_host": [vp, i, vp, i, vp],
+            "dnn_yolo_pack_detections": [vp, vp, i, i, vp, vp, vp],
+            "dnn_yolo_multi_boxes": [mp],
+            "dnn_yolo_multi_workspace": [mp, i, bp],
+            "dnn_yolo_postprocess_multi": [mp, pp, i, vp, i, vp, vp, u64, vp],
+            "dnn_yolo_postprocess_multi_host": [mp, pp, i, vp, i, vp],
+            "dnn_yolo_multi_nms_workspace": [mp, i, i, bp],
+            "dnn_yolo_postprocess_multi_nms": [mp, pp, i, vp, i, vp, vp, u64, i, vp],
+            "dnn_yolo_postprocess_multi_nms_host": [mp, pp, i, vp, i, vp, i],
+            "dnn_yolo_multi_labels_workspace": [mp, i, i, bp],
+            "dnn_yolo_postprocess_multi_labels": [mp, pp, i, vp, i, vp, vp, u64, i, vp],
+            "dnn_yolo_postprocess_multi_labels_host": [mp, pp, i, vp, i, vp, i],
+            "dnn_yolo_wide_boxes": [mp],
+            "dnn_yolo_wide_workspace": [mp, i, bp],
+            "dnn_yolo_postprocess_wide": [mp, pp, i, vp, i, vp, vp, u64, i, i, vp],
+            "dnn_yolo_postprocess_wide_host": [mp, pp, i, vp, i, vp, i, i],
+            "dnn_yolo_postprocess_multi_xy": [mp, fp, pp, i, vp, i, vp, vp, u64, i, i, vp],
+            "dnn_yolo_postprocess_multi_xy_host": [mp, fp, pp, i, vp, i, vp, i, i],
+            "dnn_yolo_postprocess_wide_xy": [mp, fp, pp, i, vp, i, vp, vp, u64, i, i, vp],
+            "dnn_yolo_postprocess_wide_xy_host": [mp, fp, pp, i, vp, i, vp, i, i],
+            "dnn_yolo_correct_detections": [vp, vp, i, i, sp, i, i, vp],
+            "dnn_yolo_correct_detections_host": [vp, vp, i, i, sp, i, i],
+    }.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = i, argtypes
     return lib
 
 
@@ -353,15 +327,29 @@ class MultiHead(object):
         head.names = None if isinstance(classes, (int, np.integer)) else tuple(classes)
         return head
 
+    def _entry(self, form):
+        """form "device", "host" or "workspace" -> (the C entry of that form for this head's modes, its
+        trailing mode arguments): the _xy entry with scale_x_y, else the _labels entry for labels
+        "multi", else the _nms entry."""
+        nms, labels = NMS_MODES[self.nms], LABEL_MODES[self.labels]
+        if self.xy is not None and form != "workspace":
+            kind, tail = "_xy", (nms, labels)
+        else:
+            kind, tail = ("_labels", (labels,)) if self.labels == "multi" else ("_nms", (nms,))
+        if form == "workspace":
+            return f"dnn_yolo_multi{kind}_workspace", tail
+        return "dnn_yolo_postprocess_multi" + kind + ("_host" if form == "host" else ""), tail
+
+    def _call(self, form, args, last=()):
+        """Calls _entry(form): the description (and scale_x_y, where the entry takes it), args, the mode
+        arguments, last."""
+        name, tail = self._entry(form)
+        lead = (ctypes.byref(self.c),) if self.xy is None or form == "workspace" else (ctypes.byref(self.c), self.xy)
+        dnn_hip._check(getattr(_lib, name)(*lead, *args, *tail, *last), name)
+
     def workspace_bytes(self, n_images):
         b = ctypes.c_ulonglong(0)
-        if self.labels == "multi":
-            dnn_hip._check(_lib.dnn_yolo_multi_labels_workspace(ctypes.byref(self.c), n_images,
-                                                                LABEL_MODES[self.labels], ctypes.byref(b)),
-                           "dnn_yolo_multi_labels_workspace")
-            return int(b.value)
-        dnn_hip._check(_lib.dnn_yolo_multi_nms_workspace(ctypes.byref(self.c), n_images, NMS_MODES[self.nms],
-                                                         ctypes.byref(b)), "dnn_yolo_multi_nms_workspace")
+        self._call("workspace", (n_images,), (ctypes.byref(b),))
         return int(b.value)
 
     def __repr__(self):
@@ -384,11 +372,11 @@ class WideHead(MultiHead):
     MAX_BOXES = WIDE_MAX_BOXES
     BOXES_ENTRY = "dnn_yolo_wide_boxes"
 
-    def workspace_bytes(self, n_images):
-        b = ctypes.c_ulonglong(0)
-        dnn_hip._check(_lib.dnn_yolo_wide_workspace(ctypes.byref(self.c), n_images, ctypes.byref(b)),
-                       "dnn_yolo_wide_workspace")
-        return int(b.value)
+    def _entry(self, form):
+        if form == "workspace":
+            return "dnn_yolo_wide_workspace", ()
+        return ("dnn_yolo_postprocess_wide" + ("" if self.xy is None else "_xy") + ("_host" if form == "host" else ""),
+                (NMS_MODES[self.nms], LABEL_MODES[self.labels]))
 
 
 def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
@@ -408,24 +396,7 @@ def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
     dets = np.zeros((n, max_det), DETECTION_DTYPE)
     counts = np.zeros(n, np.int32)
     ptrs = (ctypes.c_void_p * len(ps))(*[p.ctypes.data for p in ps])
-    if head.xy is not None:
-        name = "dnn_yolo_postprocess_wide_xy_host" if isinstance(head, WideHead) else "dnn_yolo_postprocess_multi_xy_host"
-        dnn_hip._check(getattr(_lib, name)(ctypes.byref(head.c), head.xy, ptrs, n, dets.ctypes.data, max_det,
-                                           counts.ctypes.data, NMS_MODES[head.nms], LABEL_MODES[head.labels]), name)
-        return _rows(dets, counts, max_det, raise_errors)
-    if isinstance(head, WideHead):
-        dnn_hip._check(_lib.dnn_yolo_postprocess_wide_host(
-            ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det, counts.ctypes.data, NMS_MODES[head.nms],
-            LABEL_MODES[head.labels]), "dnn_yolo_postprocess_wide_host")
-        return _rows(dets, counts, max_det, raise_errors)
-    if head.labels == "multi":
-        dnn_hip._check(_lib.dnn_yolo_postprocess_multi_labels_host(
-            ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det, counts.ctypes.data, LABEL_MODES[head.labels]),
-            "dnn_yolo_postprocess_multi_labels_host")
-        return _rows(dets, counts, max_det, raise_errors)
-    dnn_hip._check(_lib.dnn_yolo_postprocess_multi_nms_host(ctypes.byref(head.c), ptrs, n, dets.ctypes.data, max_det,
-                                                            counts.ctypes.data, NMS_MODES[head.nms]),
-                   "dnn_yolo_postprocess_multi_nms_host")
+    head._call("host", (ptrs, n, dets.ctypes.data, max_det, counts.ctypes.data))
     return _rows(dets, counts, max_det, raise_errors)
 
 
@@ -598,26 +569,5 @@ class MultiDetectionBuffers(DetectionBuffers):
         if len(pred_ptrs) != len(self.head.scales):
             raise ValueError(f"{len(pred_ptrs)} prediction pointers for {len(self.head.scales)} scales")
         ptrs = (ctypes.c_void_p * len(pred_ptrs))(*[int(p) for p in pred_ptrs])
-        if self.head.xy is not None:
-            name = "dnn_yolo_postprocess_wide_xy" if isinstance(self.head, WideHead) else "dnn_yolo_postprocess_multi_xy"
-            dnn_hip._check(getattr(_lib, name)(
-                ctypes.byref(self.head.c), self.head.xy, ptrs, n, self.dets.data_ptr(), self.max_det,
-                self.counts.data_ptr(), self.workspace.data_ptr(), self.workspace.numel(), NMS_MODES[self.head.nms],
-                LABEL_MODES[self.head.labels], stream), name)
-            return
-        if isinstance(self.head, WideHead):
-            dnn_hip._check(_lib.dnn_yolo_postprocess_wide(
-                ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
-                self.workspace.data_ptr(), self.workspace.numel(), NMS_MODES[self.head.nms],
-                LABEL_MODES[self.head.labels], stream), "dnn_yolo_postprocess_wide")
-            return
-        if self.head.labels == "multi":
-            dnn_hip._check(_lib.dnn_yolo_postprocess_multi_labels(
-                ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
-                self.workspace.data_ptr(), self.workspace.numel(), LABEL_MODES[self.head.labels], stream),
-                "dnn_yolo_postprocess_multi_labels")
-            return
-        dnn_hip._check(_lib.dnn_yolo_postprocess_multi_nms(
-            ctypes.byref(self.head.c), ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
-            self.workspace.data_ptr(), self.workspace.numel(), NMS_MODES[self.head.nms], stream),
-            "dnn_yolo_postprocess_multi_nms")
+        self.head._call("device", (ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
+                                   self.workspace.data_ptr(), self.workspace.numel()), (stream,))

@@ -234,6 +234,38 @@ def edge():
     return preds, (MO.detect_or_code([preds[0][0]], multi),)
 
 
+# ------------------------------------------------------------------ the one-workgroup entries' small cases
+# The per-class phases are one set of device helpers for both index widths (csrc/post_multi_dev.h), so
+# the wide entry also runs the cases that were built for the one-workgroup kernels: name -> mode.
+#   dense, dense80   post_multilabel_cases.DENSE: every segment above the whole-workgroup threshold
+#                    and a merge of three chunks; every segment one wave's and a merge of two
+#   bounds           post_classwise_cases: segments of 1, 63, 64, 0, 65 and 129 candidates
+#   threshold        the same around the whole-workgroup threshold: 256, 257, 255, 320
+#   small_softmax    post_multilabel_cases.SEEDED's softmax case (no seeded softmax case has more than
+#                    1024 rows): the merge's softmax scores
+SMALL = {"dense": "multi", "dense80": "multi", "bounds": "per_class", "threshold": "per_class",
+         "small_softmax": "multi"}
+
+
+@functools.lru_cache(maxsize=None)
+def small(name):
+    """(description, preds per scale [n, ...], mode, per image the mode's oracle rows or code, the
+    oracle's stats of a one-image case: candidates and their classes)."""
+    import post_classwise_cases as CK
+    import post_multilabel_cases as LK
+    mode = SMALL[name]
+    if name in ("dense", "dense80"):
+        preds, rows, stats = LK.dense(name)
+        return LK.dense_multi(name), preds, mode, (rows,), stats
+    if name == "small_softmax":
+        preds, refs = LK.seeded(name)
+        return LK.seeded_multi(name), preds, mode, refs, None
+    sizes = CK.BOUNDS_SIZES if name == "bounds" else CK.THRESHOLD_SIZES
+    multi, preds, stats = CK.bounds_multi(sizes), [CK.bounds_preds(sizes)], {}
+    preds[0].setflags(write=False)
+    return multi, preds, mode, (tuple(CO.detect([preds[0][0]], multi, stats)),), stats
+
+
 # ------------------------------------------------------------------ end to end
 def e2e_model():
     """(cfg text, sections, layers, frame [1, 1088, 1088, 3])."""

@@ -114,6 +114,24 @@ def test_same_bytes_as_the_existing_entries_below_their_cap(name):
     assert any(c < 0 for c in seen)  # codes were compared too
 
 
+@pytest.mark.parametrize("name", sorted(W.SMALL))
+def test_small_cases_of_the_one_workgroup_entries_through_the_wide_entry(name):
+    """The cases built for the one-workgroup kernels' segment scheduling and merges (post_wide_cases.
+    SMALL) through the wide entry, whose index field is 16 bits wide: the oracle's rows and codes,
+    and counts and rows [0, count) byte for byte those of the existing entry."""
+    multi, preds, mode, want, _ = W.small(name)
+    wide = W.device_head(multi, mode)
+    old = W.device_head(multi, mode, yolo_post.MultiHead)
+    assert wide.boxes == old.boxes <= W.OLD_CAP and wide.max_det == old.max_det
+    got, ref = _run_guarded(wide, preds), _run_guarded(old, preds)
+    print(f"{name} {mode}: wide {got[0]}, existing {ref[0]}, oracle {W.counts_of(want)}")
+    _check_images(got[0], got[1], want, f"{name} {mode}")
+    assert got[0] == ref[0] and any(c > 0 for c in got[0])
+    for i, c in enumerate(got[0]):
+        if c > 0:
+            assert got[1][i, :c].tobytes() == ref[1][i, :c].tobytes(), f"{name} {mode} image {i}"
+
+
 # ------------------------------------------------------------------ 2. above the old cap, against the oracles
 @pytest.mark.parametrize("name", sorted(W.ABOVE))
 def test_above_the_old_cap_against_the_oracles(name):

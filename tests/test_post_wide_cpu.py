@@ -186,6 +186,34 @@ def test_above_cases_have_a_coded_image_and_rows_of_high_boxes(name):
         assert all(int(o) % 64 for o in offs)
 
 
+def test_small_cases_keep_the_properties_they_were_chosen_for():
+    """From the oracles: what each case of post_wide_cases.SMALL sends through the device's phases
+    (csrc/post_multi_dev.h: PC_BIG = 256 candidates, merge chunks of 1024 rows)."""
+    big, chunk = 256, 1024
+    per, rows = {}, {}
+    for name in W.SMALL:
+        multi, preds, mode, want, stats = W.small(name)
+        assert W.boxes_of(multi) <= W.OLD_CAP and mode == W.SMALL[name] and len(want) == preds[0].shape[0]
+        rows[name] = W.counts_of(want)
+        if stats is not None:
+            per[name] = tuple(np.bincount(stats["classes"], minlength=multi.scales[0].n_classes))
+    # every segment goes to the whole workgroup; the merge expands three chunks from the top down
+    assert len(per["dense"]) == 12 and min(per["dense"]) > big and rows["dense"][0] > 2 * chunk
+    # every segment is one wave's, none empty; the merge has a second chunk
+    assert len(per["dense80"]) == 80 and 1 <= min(per["dense80"]) and max(per["dense80"]) <= big
+    assert rows["dense80"][0] > chunk
+    assert per["bounds"] == (1, 63, 64, 0, 65, 129) and rows["bounds"][0] > 0
+    assert per["threshold"] == (big, big + 1, big - 1, 320) and rows["threshold"][0] > chunk // 2
+    # softmax multi-label rows beside a code; small_softmax stands in for a softmax case of more than
+    # 1024 rows only while post_multilabel_cases.SEEDED has none
+    import post_multilabel_cases as LK
+    for seeded, spec in LK.SEEDED.items():
+        if spec[5] == "softmax":
+            assert max(LK.counts_of(LK.seeded(seeded)[1])) <= chunk, seeded
+    assert W.small("small_softmax")[0].class_mode == "softmax"
+    assert any(c > 0 for c in rows["small_softmax"]) and any(c < 0 for c in rows["small_softmax"])
+
+
 def test_608_x_80_case_gives_rows_in_every_mode():
     preds, refs = W.coco608()
     assert W.boxes_of(W.coco608_multi()) == 22743 and preds[2].shape == (1, 76, 76, 255)
