@@ -204,19 +204,7 @@ conv3x3_x3_ktile_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __res
 #pragma unroll
       for (int jb = 0; jb < 2; ++jb) red[((((kg - 1) * NG + wg) * TM + i) * 2 + jb) * 64 + lane] = acc[i][jb];
   }
-  for (int r = threadIdx.x; r < NO; r += NT) {
-    int o;
-    if constexpr (POOL) {
-      const int py = (y0 >> 1) + r / (TW / 2), px = (x0 >> 1) + r % (TW / 2);
-      o = (py >= g.PH || px >= g.PW) ? -1
-          : g.out_mode == 1         ? (b * (g.PH + 2) + py + 1) * (g.PW + 2) + px + 1
-                                    : (b * g.PH + py) * g.PW + px;
-    } else {
-      const int oy = y0 + r / TW, ox = x0 + r % TW;
-      o = (oy >= g.H || ox >= g.W) ? -1 : g.out_mode == 1 ? (b * (g.H + 2) + oy + 1) * Wp + ox + 1 : (b * g.H + oy) * g.W + ox;
-    }
-    orow[r] = o;
-  }
+  x3_tile_orows<TW, POOL, NO, NT>(orow, b, y0, x0, g);
   __syncthreads();
   if (kg > 0) return;
 #pragma unroll
@@ -305,36 +293,8 @@ conv3x3_x3_ktile_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __res
 #pragma unroll
   for (int jb = 0; jb < 2; ++jb) {
     const int n = n0 + 16 * jb + fr;
-    const float pb = ecp[jb].pb, pm = ecp[jb].pm, ps = ecp[jb].ps, pg = ecp[jb].pg;
-    const int cofs = (n >> 5) * 96 + (n & 31);
-    auto put = [&](int o, float v) {
-      if (g.out_mode == 1) {
-        unsigned short s0_, s1_, s2_;
-        split3(v, s0_, s1_, s2_);
-        bf16_bits* d = out_split + (size_t)o * (3 * N) + cofs;
-        d[0] = s0_;
-        d[32] = s1_;
-        d[64] = s2_;
-      } else {
-        out[(size_t)o * N + n] = v;
-      }
-    };
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int rb = 16 * (wm * TM + i);
-      if constexpr (POOL) {
-        const int w = rb / 4 + fq;
-        const int o = w < NO ? orow[w] : -1;
-        if (o >= 0) put(o, pool_then_epilogue_t<FL>(acc[i][jb], pb, pm, ps, pg, epi.flags));
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = rb + 4 * fq + r;
-          const int o = row < NO ? orow[row] : -1;
-          if (o >= 0) put(o, apply_epilogue_t<FL>(acc[i][jb][r], pb, pm, ps, pg, epi.flags));
-        }
-      }
-    }
+    x3_tile_put_col<FL, POOL, NO>(acc, jb, ecp[jb], epi.flags, n, N, out, out_split, 3 * N, (n >> 5) * 96 + (n & 31),
+                                  g.out_mode, orow, 16 * wm * TM, fq);
   }
   KT_STAMP(3)
 }

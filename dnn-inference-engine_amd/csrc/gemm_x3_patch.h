@@ -196,6 +196,80 @@ __device__ __forceinline__ void x3_pool_split_store(const float* stg, const int*
 // lane's 4 accumulator registers (rows 4 q .. 4 q + 3 of its 16 x 16 block) are one window:
 // pooled before the epilogue (pool_then_epilogue, as the fp32 GEMMs' fused pools).
 
+// ---- The tail of a 2-D tile (16-channel, tile2, ktile and ping-pong kernels) ----
+
+// (b, y0, x0) of tile t of a batch x tilesY x tilesX grid of TH x TW tiles
+template <int TH, int TW>
+__device__ __forceinline__ void x3_tile_xy(int t, int tilesX, int tilesY, int& b, int& y0, int& x0) {
+  const int tx = t % tilesX, tt = t / tilesX, ty = tt % tilesY;
+  b = tt / tilesY;
+  y0 = ty * TH;
+  x0 = tx * TW;
+}
+
+// The output record of row r of the tile at (b, y0, x0): r a pooled window (POOL; rows are
+// pool-window-major) or a raster row; the record of the zero-bordered split-plane buffer (out_mode
+// 1) or of the plain [M][N] output; -1 past the frame.  MODE >= 0: out_mode known at compile time.
+template <int TW, bool POOL, int MODE = -1>
+__device__ __forceinline__ int x3_tile_orow(int r, int b, int y0, int x0, const X3Geom& g) {
+  const bool planes = (MODE < 0 ? g.out_mode : MODE) == 1;
+  if constexpr (POOL) {
+    const int py = (y0 >> 1) + r / (TW / 2), px = (x0 >> 1) + r % (TW / 2);
+    return (py >= g.PH || px >= g.PW) ? -1
+           : planes                   ? (b * (g.PH + 2) + py + 1) * (g.PW + 2) + px + 1
+                                      : (b * g.PH + py) * g.PW + px;
+  } else {
+    const int oy = y0 + r / TW, ox = x0 + r % TW;
+    return (oy >= g.H || ox >= g.W) ? -1
+           : planes                 ? (b * (g.H + 2) + oy + 1) * (g.W + 2) + ox + 1
+                                    : (b * g.H + oy) * g.W + ox;
+  }
+}
+// ... of all NO rows, into the workgroup's (NT threads) row table
+template <int TW, bool POOL, int NO, int NT>
+__device__ __forceinline__ void x3_tile_orows(int* orow, int b, int y0, int x0, const X3Geom& g) {
+  for (int r = threadIdx.x; r < NO; r += NT) orow[r] = x3_tile_orow<TW, POOL>(r, b, y0, x0, g);
+}
+
+// The unstaged epilogue of column block jb (column n, parameters ec) of a wave's TM row blocks
+// (rows from rb0 = 16 wm TM): per lane the pooled window (POOL) or the 4 raster rows of each block,
+// through the row table, as plain fp32 at out + o N + n or (out_mode 1) as three scalar split-plane
+// stores at out_split + o n3 + cofs.
+template <int FL, bool POOL, int NO, int TM>
+__device__ __forceinline__ void x3_tile_put_col(const f32x4 (&acc)[TM][2], int jb, const X3EpiCol& ec, int flags,
+                                                int n, int N, float* __restrict__ out,
+                                                bf16_bits* __restrict__ out_split, int n3, int cofs, int out_mode,
+                                                const int* orow, int rb0, int fq) {
+  auto put = [&](int o, float v) {
+    if (out_mode == 1) {
+      unsigned short s0, s1, s2;
+      split3(v, s0, s1, s2);
+      bf16_bits* d = out_split + (size_t)o * n3 + cofs;
+      d[0] = s0;
+      d[32] = s1;
+      d[64] = s2;
+    } else {
+      out[(size_t)o * N + n] = v;
+    }
+  };
+#pragma unroll
+  for (int i = 0; i < TM; ++i) {
+    const int rb = rb0 + 16 * i;
+    if constexpr (POOL) {
+      const int w = rb / 4 + fq;
+      const int o = w < NO ? orow[w] : -1;
+      if (o >= 0) put(o, pool_then_epilogue_t<FL>(acc[i][jb], ec.pb, ec.pm, ec.ps, ec.pg, flags));
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = rb + 4 * fq + r;
+        const int o = row < NO ? orow[row] : -1;
+        if (o >= 0) put(o, apply_epilogue_t<FL>(acc[i][jb][r], ec.pb, ec.pm, ec.ps, ec.pg, flags));
+      }
+    }
+  }
+}
+
 // 16-channel layers (YOLOv2-tiny conv1, 208x208x16 -> 32): the input is the producer's plain
 // fp32 NHWC (no split planes), split into the three bf16 pieces while the patch is staged
 // (frame padding = the descriptor's zeros).  K = 144 runs as 5 steps of 32: step s feeds k
@@ -207,29 +281,209 @@ __device__ __forceinline__ void x3_pool_split_store(const float* stg, const int*
 // streaming them from L2 (73 B per MFMA at 2 waves per tile).  One chunk: no double buffer;
 // two workgroups per CU overlap each other's staging.  Same product order per step as the
 // kernels above; 32 columns (WN = 1), WM waves of TM 16-row blocks.
+//
+// The phases below are shared by the 16-channel kernels; each kernel keeps its own schedule around
+// them.  The persistent and the ping-pong kernel take all of them, the one-tile kernel the tile
+// origin, the fragment rows and the fragment reads (it keeps four phases of its own, see there).
+
+// Compile-time geometry of a TH x TW tile on WM waves (one team) of TM row blocks
+template <int TH_, int TW_, int WM_, int TM_>
+struct C16Geom {
+  static constexpr int TH = TH_, TW = TW_, WM = WM_, TM = TM_;
+  static constexpr int NT = 64 * WM, PB = 96, PW2 = TW + 2, PR = (TH + 2) * PW2, T = TH * TW, NS = 5;
+  static constexpr int ITEMS = PR * 4, PPT = (ITEMS + NT - 1) / NT;  // item = (patch pixel, channel quad)
+  static constexpr int BB = 2 * NS * 3 * 1024, PATCH = PR * PB;      // weight bytes, split patch bytes
+  static_assert(WM * TM * 16 >= T && (WM * TM - 3) * 16 < T, "shape");
+};
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+// weights: the packed [n/16][step][piece][lane][8] block of columns 0-31 is contiguous; copied into
+// LDS by the workgroup's NTW threads
+template <class G, int NTW>
+__device__ __forceinline__ void c16_weights_to_lds(unsigned char* smem, const bf16_bits* Bt) {
+  constexpr int BPT = (G::BB / 16 + NTW - 1) / NTW;  // 16-B loads per thread
+  u32x4 w[BPT];
+#pragma unroll
+  for (int u = 0; u < BPT; ++u) {
+    int e = threadIdx.x + u * NTW;
+    e = e < G::BB / 16 ? e : G::BB / 16 - 1;
+    w[u] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(Bt) + 16 * e);
+  }
+#pragma unroll
+  for (int u = 0; u < BPT; ++u) {
+    int e = threadIdx.x + u * NTW;
+    e = e < G::BB / 16 ? e : G::BB / 16 - 1;
+    *reinterpret_cast<u32x4*>(smem + 16 * e) = w[u];
+  }
+}
+
+// the patch items of team thread tt (item e = tt + d NT: pixel e / 4 of the patch of the tile at (b,
+// y0, x0), channel quad e % 4; past the last: the last again) into registers; frame padding = the
+// descriptor's zeros.  (conv3x3_x3_c16_kernel spells the same addressing out, four items at a time.)
+template <class G>
+__device__ __forceinline__ void c16_load_items(f32x4 (&v)[G::PPT], __amdgpu_buffer_rsrc_t rsA, int tt, int b, int y0,
+                                               int x0, const X3Geom& g) {
+#pragma unroll
+  for (int d = 0; d < G::PPT; ++d) {
+    int e = tt + d * G::NT;
+    e = e < G::ITEMS ? e : G::ITEMS - 1;
+    const int pr = e >> 2, q = e & 3, py = pr / G::PW2, px = pr - py * G::PW2;
+    const int iy = y0 - 1 + py, ix = x0 - 1 + px;
+    const bool ok = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
+    const unsigned vo = ok ? (unsigned)((((b * g.H + iy) * g.W + ix) * 16 + 4 * q) * 4) : OOB_OFF;
+    v[d] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, vo, 0, 0));
+  }
+}
+// ... split into the patch area: 16-B fp32 channel quad -> three 8-B bf16 quads (pieces at 32 p +
+// 8 q of the 96-B pixel).  TRUNC (X3DIAG 128, diagnostic): a truncating 2-piece "split", 2 v_perm
+// per pair (wrong results)
+template <class G, bool TRUNC = false>
+__device__ __forceinline__ void c16_split_items(const f32x4 (&v)[G::PPT], unsigned char* patch, int tt) {
+  bool ok = true;
+#pragma unroll
+  for (int d = 0; d < G::PPT; ++d)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) ok = ok && x3_split_ok(v[d][c]);
+  const bool fast = __builtin_amdgcn_ballot_w64(!ok) == 0;  // (pairs of one v_cvt_pk per piece)
+#pragma unroll
+  for (int d = 0; d < G::PPT; ++d) {
+    int e = tt + d * G::NT;
+    e = e < G::ITEMS ? e : G::ITEMS - 1;
+    const int dst = (e >> 2) * G::PB + 8 * (e & 3);
+    uint2 w[3];
+    if constexpr (TRUNC) {
+      const unsigned a0 = __builtin_bit_cast(unsigned, v[d][0]), a1 = __builtin_bit_cast(unsigned, v[d][1]);
+      const unsigned a2 = __builtin_bit_cast(unsigned, v[d][2]), a3 = __builtin_bit_cast(unsigned, v[d][3]);
+      w[0] = uint2{__builtin_amdgcn_perm(a1, a0, 0x07060302u), __builtin_amdgcn_perm(a3, a2, 0x07060302u)};
+      w[1] = uint2{__builtin_amdgcn_perm(a1, a0, 0x05040100u), __builtin_amdgcn_perm(a3, a2, 0x05040100u)};
+      w[2] = uint2{0u, 0u};
+      (void)fast;
+    } else {
+      split3_pack2(fast, v[d][0], v[d][1], w[0].x, w[1].x, w[2].x);
+      split3_pack2(fast, v[d][2], v[d][3], w[0].y, w[1].y, w[2].y);
+    }
+#pragma unroll
+    for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(patch + dst + 32 * p) = w[p];
+  }
+}
+
+// fragment row: byte offset in the patch of the tap-(1, 1) pixel of row (wm TM + i) 16 + fr of the
+// tile (rows past the tile: the last), pool-window-major or raster
+template <class G, bool POOL>
+__device__ __forceinline__ int c16_row_off(int wm, int i, int fr) {
+  int r = (wm * G::TM + i) * 16 + fr;
+  r = r < G::T ? r : G::T - 1;
+  int ly, lx;
+  if constexpr (POOL) {
+    const int w = r >> 2, q = r & 3;
+    ly = 2 * (w / (G::TW / 2)) + (q >> 1);
+    lx = 2 * (w % (G::TW / 2)) + (q & 1);
+  } else {
+    ly = r / G::TW;
+    lx = r % G::TW;
+  }
+  return ((ly + 1) * G::PW2 + lx + 1) * G::PB;
+}
+// ... the lane's TM of them packed two per register (byte offsets < PATCH < 2^16; the persistent
+// kernels are at the register limit)
+template <class G, bool POOL>
+struct C16PackedRows {
+  static_assert(G::PATCH < 65536, "16-bit patch offsets");
+  unsigned w2[(G::TM + 1) / 2];
+  __device__ __forceinline__ C16PackedRows(int wm, int fr) {
+#pragma unroll
+    for (int k = 0; k < (G::TM + 1) / 2; ++k) w2[k] = 0;
+#pragma unroll
+    for (int i = 0; i < G::TM; ++i) w2[i / 2] |= (unsigned)c16_row_off<G, POOL>(wm, i, fr) << (16 * (i % 2));
+  }
+  __device__ __forceinline__ int operator()(int i) const {
+    unsigned w = w2[i / 2];
+    asm volatile("" : "+v"(w));
+    return (int)((w >> (16 * (i % 2))) & 0xffffu);
+  }
+};
+
+// the tap offset (bytes) of full step s for lane group th = fq >> 1: tap 2 s or 2 s + 1 (tap 9: zero
+// weights, reads tap 8)
+template <class G>
+__device__ __forceinline__ int c16_toff(int s, int th) {
+  const int ta = 2 * s, tb = 2 * s + 1 < 9 ? 2 * s + 1 : 8;
+  const int oa = ((ta / 3 - 1) * G::PW2 + (ta % 3 - 1)) * G::PB, ob = ((tb / 3 - 1) * G::PW2 + (tb % 3 - 1)) * G::PB;
+  return th ? ob : oa;
+}
+// A fragment: the three pieces' 8 channels at q
+__device__ __forceinline__ void c16_frag(const unsigned char* q, bf16x8 (&a)[3]) {
+#pragma unroll
+  for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(q + 32 * p);
+}
+// B fragments of step s (both column blocks) from the LDS weights
+template <class G>
+__device__ __forceinline__ void c16_bfrag(const unsigned char* smem, int s, int lane, bf16x8 (&bb)[3][2]) {
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      bb[p][j] = *reinterpret_cast<const bf16x8*>(smem + (j * G::NS * 3 + s * 3 + p) * 1024 + lane * 16);
+}
+
+// The K = 16 step (tap 8 alone, k 128-143, channels 4 fq .. 4 fq + 3) on v_mfma_f32_16x16x16_bf16:
+// A 8 B at the lane's pixel + c16_hoff (tap (2, 2) relative to (1, 1), 8 fq in the pixel), B 8 B of
+// the packed step 4 (lane fr + 16 (fq >> 1), element 4 (fq & 1))
+template <class G>
+__device__ __forceinline__ int c16_hoff(int fq) {
+  return (G::PW2 + 1) * G::PB + 8 * fq;
+}
+__device__ __forceinline__ void c16_hfrag(const unsigned char* q, s16x4 (&a)[3]) {
+#pragma unroll
+  for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const s16x4*>(q + 32 * p);
+}
+template <class G>
+__device__ __forceinline__ void c16_hbfrag(const unsigned char* smem, int fr, int fq, s16x4 (&hbq)[3][2]) {
+  const int hb = (fr + 16 * (fq >> 1)) * 16 + 8 * (fq & 1);
+#pragma unroll
+  for (int p = 0; p < 3; ++p)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      hbq[p][j] = *reinterpret_cast<const s16x4*>(smem + (j * G::NS * 3 + 4 * 3 + p) * 1024 + hb);
+}
+// ... one row block, both column blocks: x3_step<true>'s product order
+__device__ __forceinline__ void c16_half_step(f32x4 (&acc)[2], f32x4 (&accc)[2], const s16x4 (&a)[3],
+                                              const s16x4 (&hbq)[3][2]) {
+#pragma unroll
+  for (int jb = 0; jb < 2; ++jb) {
+    f32x4 c = accc[jb];
+    c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[2], hbq[0][jb], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], hbq[1][jb], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], hbq[2][jb], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], hbq[0][jb], c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], hbq[1][jb], c, 0, 0, 0);
+    accc[jb] = c;
+    acc[jb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], hbq[0][jb], acc[jb], 0, 0, 0);
+  }
+}
+
+// One tile per workgroup (the single-frame plans, and DNN_HIP_X3_C16P=0).
 template <int TH, int TW, int WM, int TM, bool POOL, bool A2 = true>  // A2: as the tile kernel
 __global__ void __launch_bounds__(64 * WM, 2)  // (waves per SIMD) two: <= 256 registers
 conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict__ Bt, float* __restrict__ out,
                       bf16_bits* __restrict__ out_split, int N, EpiParams epi, int tilesX, int tilesY, X3Geom g,
                       unsigned in_bytes) {
-  constexpr int NT = 64 * WM, PB = 96, PW2 = TW + 2, PR = (TH + 2) * PW2, T = TH * TW, NS = 5;
-  constexpr int ITEMS = PR * 4, PPT = (ITEMS + NT - 1) / NT;  // item = (patch pixel, channel quad)
-  constexpr int BB = 2 * NS * 3 * 1024, BPT = (BB / 16 + NT - 1) / NT;  // weight bytes, 16-B loads/thread
-  static_assert(TH % 2 == 0 && TW % 2 == 0 && WM * TM * 16 >= T && (WM * TM - 3) * 16 < T, "shape");
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[BB + PR * PB];
+  using G = C16Geom<TH, TW, WM, TM>;
+  constexpr int NT = G::NT, T = G::T, NS = G::NS, PPT = G::PPT, BB = G::BB, PATCH = G::PATCH;
+  static_assert(TH % 2 == 0 && TW % 2 == 0, "shape");
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[BB + PATCH];
   unsigned char* const patch = smem + BB;
 
   const int lane = threadIdx.x & 63;
   const int wm = wave_uniform(threadIdx.x >> 6);
-  int t = xcd_tile(blockIdx.x, gridDim.x);
-  const int tx = t % tilesX;
-  t /= tilesX;
-  const int ty = t % tilesY;
-  const int b = t / tilesY;
-  const int y0 = ty * TH, x0 = tx * TW;
+  int b, y0, x0;
+  x3_tile_xy<TH, TW>(xcd_tile(blockIdx.x, gridDim.x), tilesX, tilesY, b, y0, x0);
 
-  // weights: the packed [n/16][step][piece][lane][8] block of columns 0-31 is contiguous
-  {
+  // This kernel keeps its own copy of the weight copy, the patch load + split, the row table and the
+  // unstaged epilogue: through the shared helpers its instruction stream changed and the latency
+  // plan's conv1 (the 4 x 26 form) measured over its limit in both runs
+  {  // weights (as c16_weights_to_lds)
+    constexpr int BPT = (BB / 16 + NT - 1) / NT;
     u32x4 w[BPT];
 #pragma unroll
     for (int u = 0; u < BPT; ++u) {
@@ -244,9 +498,9 @@ conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict_
       *reinterpret_cast<u32x4*>(smem + 16 * e) = w[u];
     }
   }
-  {  // patch: 16-B fp32 channel quad -> three 8-B bf16 quads (pieces at 32 p + 8 q of the pixel)
+  {  // patch (as c16_load_items / c16_split_items), four items in flight per thread
     const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)in_bytes, 0x00020000);
-    constexpr int SB = 4;  // items in flight per thread
+    constexpr int SB = 4;
 #pragma unroll
     for (int u0 = 0; u0 < PPT; u0 += SB) {
       f32x4 v[SB];
@@ -254,13 +508,13 @@ conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict_
 #pragma unroll
       for (int d = 0; d < SB; ++d) {
         int e = threadIdx.x + (u0 + d) * NT;
-        e = e < ITEMS ? e : ITEMS - 1;
-        const int pr = e >> 2, q = e & 3, py = pr / PW2, px = pr - py * PW2;
+        e = e < G::ITEMS ? e : G::ITEMS - 1;
+        const int pr = e >> 2, q = e & 3, py = pr / G::PW2, px = pr - py * G::PW2;
         const int iy = y0 - 1 + py, ix = x0 - 1 + px;
         const bool ok = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
         const unsigned vo = ok ? (unsigned)((((b * g.H + iy) * g.W + ix) * 16 + 4 * q) * 4) : OOB_OFF;
         v[d] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, vo, 0, 0));
-        dst[d] = pr * PB + 8 * q;
+        dst[d] = pr * G::PB + 8 * q;
       }
       bool ok = true;
 #pragma unroll
@@ -282,20 +536,7 @@ conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict_
   const int fr = lane & 15, fq = lane >> 4, th = fq >> 1;  // th: this lane's tap within a step pair
   int prow[TM];
 #pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    int r = (wm * TM + i) * 16 + fr;
-    r = r < T ? r : T - 1;
-    int ly, lx;
-    if constexpr (POOL) {
-      const int w = r >> 2, q = r & 3;
-      ly = 2 * (w / (TW / 2)) + (q >> 1);
-      lx = 2 * (w % (TW / 2)) + (q & 1);
-    } else {
-      ly = r / TW;
-      lx = r % TW;
-    }
-    prow[i] = ((ly + 1) * PW2 + lx + 1) * PB + 16 * (fq & 1);
-  }
+  for (int i = 0; i < TM; ++i) prow[i] = c16_row_off<G, POOL>(wm, i, fr) + 16 * (fq & 1);
 
   f32x4 acc[TM][2], accc[TM][2];
 #pragma unroll
@@ -304,31 +545,17 @@ conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict_
     for (int j = 0; j < 2; ++j) acc[i][j] = accc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
 
-  auto toff = [&](int s) {  // this lane's tap offset (bytes) in step s
-    const int ta = 2 * s, tb = 2 * s + 1 < 9 ? 2 * s + 1 : 8;  // (tap 9: zero weights)
-    const int oa = ((ta / 3 - 1) * PW2 + (ta % 3 - 1)) * PB, ob = ((tb / 3 - 1) * PW2 + (tb % 3 - 1)) * PB;
-    return th ? ob : oa;
-  };
   auto frag = [&](int i, int off, bf16x8 (&a)[3]) {
     int pr = prow[i];
     asm volatile("" : "+v"(pr));
-    const unsigned char* q = patch + pr + off;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(q + 32 * p);
-  };
-  auto bfrag = [&](int s, bf16x8 (&bb)[3][2]) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        bb[p][j] = *reinterpret_cast<const bf16x8*>(smem + (j * NS * 3 + s * 3 + p) * 1024 + lane * 16);
+    c16_frag(patch + pr + off, a);
   };
   bf16x8 af[2][3], bq[2][3][2];
-  frag(0, toff(0), af[0]);
-  bfrag(0, bq[0]);
+  frag(0, c16_toff<G>(0, th), af[0]);
+  c16_bfrag<G>(smem, 0, lane, bq[0]);
 #pragma unroll
   for (int s = 0; s < NS; ++s) {
-    const int off = toff(s), off_next = toff(s + 1 < NS ? s + 1 : s);
+    const int off = c16_toff<G>(s, th), off_next = c16_toff<G>(s + 1 < NS ? s + 1 : s, th);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       const int cur = (s * TM + i) & 1, nxt = cur ^ 1;
@@ -336,7 +563,7 @@ conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict_
         frag(i + 1, off, af[nxt]);
       else if (s + 1 < NS)
         frag(0, off_next, af[nxt]);
-      if (i == 0 && s + 1 < NS) bfrag(s + 1, bq[(s + 1) & 1]);  // next step's weights
+      if (i == 0 && s + 1 < NS) c16_bfrag<G>(smem, s + 1, lane, bq[(s + 1) & 1]);  // next step's weights
       const bf16x8(&bb)[3][2] = bq[s & 1];
 #pragma unroll
       for (int jb = 0; jb < 2; ++jb) x3_step<A2>(acc[i][jb], accc[i][jb], af[cur], bb, jb);
@@ -350,7 +577,7 @@ conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict_
   __syncthreads();
   constexpr int NO = POOL ? T / 4 : T;
   const int Wp = g.W + 2;
-  for (int r = threadIdx.x; r < NO; r += NT) {
+  for (int r = threadIdx.x; r < NO; r += NT) {  // (as x3_tile_orows; the stores below as x3_tile_put_col)
     int o;
     if constexpr (POOL) {
       const int py = (y0 >> 1) + r / (TW / 2), px = (x0 >> 1) + r % (TW / 2);
@@ -359,25 +586,24 @@ conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict_
                                     : (b * g.PH + py) * g.PW + px;
     } else {
       const int oy = y0 + r / TW, ox = x0 + r % TW;
-      o = (oy >= g.H || ox >= g.W) ? -1 : g.out_mode == 1 ? (b * (g.H + 2) + oy + 1) * Wp + ox + 1 : (b * g.H + oy) * g.W + ox;
+      o = (oy >= g.H || ox >= g.W) ? -1
+          : g.out_mode == 1        ? (b * (g.H + 2) + oy + 1) * Wp + ox + 1
+                                   : (b * g.H + oy) * g.W + ox;
     }
     orow[r] = o;
   }
   __syncthreads();
   if constexpr (POOL) {
     if (g.out_mode == 1) {  // staged 16-B split-plane stores (x3_pool_split_store)
-      static_assert(1024 + WM * TM * 4 * X3_STG_ROW * 4 <= BB + PR * PB && NO * 4 <= 1024, "stage");
+      static_assert(1024 + WM * TM * 4 * X3_STG_ROW * 4 <= BB + PATCH && NO * 4 <= 1024, "stage");
       float* stg = reinterpret_cast<float*>(smem + 1024) + wm * (TM * 4 * X3_STG_ROW);
 #pragma unroll
       for (int jb = 0; jb < 2; ++jb) {
-        const int n = 16 * jb + fr;
-        const float pb = (epi.flags & EPI_BIAS) ? epi.bias[n] : 0.f;
-        const float pm = (epi.flags & (EPI_BN | EPI_BN_AB)) ? epi.mean[n] : 0.f;
-        const float ps = (epi.flags & (EPI_BN | EPI_BN_AB)) ? epi.sq[n] : 1.f;
-        const float pg = (epi.flags & EPI_BN) ? epi.gamma[n] : 1.f;
+        const X3EpiCol ec = x3_epi_col(epi, epi.flags, 16 * jb + fr);
 #pragma unroll
         for (int i = 0; i < TM; ++i)
-          stg[(4 * i + fq) * X3_STG_ROW + 16 * jb + fr] = pool_then_epilogue(acc[i][jb], pb, pm, ps, pg, epi.flags);
+          stg[(4 * i + fq) * X3_STG_ROW + 16 * jb + fr] =
+              pool_then_epilogue(acc[i][jb], ec.pb, ec.pm, ec.ps, ec.pg, epi.flags);
       }
       x3_pool_split_store<TM>(stg, orow, NO, 4 * wm * TM, out_split, 96, 0, lane);
       return;
@@ -386,10 +612,7 @@ conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict_
 #pragma unroll
   for (int jb = 0; jb < 2; ++jb) {
     const int n = 16 * jb + fr;
-    const float pb = (epi.flags & EPI_BIAS) ? epi.bias[n] : 0.f;
-    const float pm = (epi.flags & (EPI_BN | EPI_BN_AB)) ? epi.mean[n] : 0.f;
-    const float ps = (epi.flags & (EPI_BN | EPI_BN_AB)) ? epi.sq[n] : 1.f;
-    const float pg = (epi.flags & EPI_BN) ? epi.gamma[n] : 1.f;
+    const X3EpiCol ec = x3_epi_col(epi, epi.flags, n);
     auto put = [&](int o, float v) {
       if (g.out_mode == 1) {
         unsigned short s0, s1, s2;
@@ -408,13 +631,13 @@ conv3x3_x3_c16_kernel(const float* __restrict__ in, const bf16_bits* __restrict_
       if constexpr (POOL) {
         const int w = rb / 4 + fq;
         const int o = w < NO ? orow[w] : -1;
-        if (o >= 0) put(o, pool_then_epilogue(acc[i][jb], pb, pm, ps, pg, epi.flags));
+        if (o >= 0) put(o, pool_then_epilogue(acc[i][jb], ec.pb, ec.pm, ec.ps, ec.pg, epi.flags));
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = rb + 4 * fq + r;
           const int o = row < NO ? orow[row] : -1;
-          if (o >= 0) put(o, apply_epilogue(acc[i][jb][r], pb, pm, ps, pg, epi.flags));
+          if (o >= 0) put(o, apply_epilogue(acc[i][jb][r], ec.pb, ec.pm, ec.ps, ec.pg, epi.flags));
         }
       }
     }
@@ -440,12 +663,10 @@ conv3x3_x3_c16p_kernel(const float* __restrict__ in, const bf16_bits* __restrict
                        bf16_bits* __restrict__ out_split, int N, EpiParams epi, int tilesX, int tilesY, int ntiles,
                        X3Geom g, unsigned in_bytes) {
   constexpr int TH = 16, TW = 26, WM = 4, TM = 7;
-  constexpr int NT = 64 * WM, PB = 96, PW2 = TW + 2, PR = (TH + 2) * PW2, T = TH * TW, NS = 5;
-  constexpr int ITEMS = PR * 4, PPT = (ITEMS + NT - 1) / NT;  // item = (patch pixel, channel quad)
-  constexpr int BB = 2 * NS * 3 * 1024, BPT = (BB / 16 + NT - 1) / NT;
+  using G = C16Geom<TH, TW, WM, TM>;
+  constexpr int NT = G::NT, T = G::T, NS = G::NS, PPT = G::PPT, BB = G::BB, PATCH = G::PATCH;
   constexpr int NO = POOL ? T / 4 : T;
-  constexpr int PATCH = PR * PB;
-  static_assert(WM * TM * 16 >= T && (WM * TM - 3) * 16 < T && PPT == 8, "shape");
+  static_assert(PPT == 8, "shape");
   static_assert(WM * TM * 4 * X3_STG_ROW * 4 <= PATCH, "epilogue stage inside the patch area");
   __shared__ __attribute__((aligned(1024))) unsigned char smem[BB + PATCH + NO * 4];
   unsigned char* const patch = smem + BB;
@@ -455,7 +676,6 @@ conv3x3_x3_c16p_kernel(const float* __restrict__ in, const bf16_bits* __restrict
   const int eflags = FL < 0 ? epi.flags : FL;  // FL: the epilogue flag set compiled in (-1: runtime)
   const int wm = wave_uniform(threadIdx.x >> 6);
   const int fr = lane & 15, fq = lane >> 4, th = fq >> 1;
-  const int Wp = g.W + 2;
   // the 32 columns' epilogue parameters, into LDS once per workgroup (registers would spill;
   // a load at each tile's epilogue is a memory round trip there)
   __shared__ f32x4 epl[32];
@@ -464,127 +684,21 @@ conv3x3_x3_c16p_kernel(const float* __restrict__ in, const bf16_bits* __restrict
     epl[threadIdx.x] = f32x4{c.pb, c.pm, c.ps, c.pg};
   }
 
-  // weights once: the packed [n/16][step][piece][lane][8] block of columns 0-31 is contiguous
-  {
-    u32x4 w[BPT];
-#pragma unroll
-    for (int u = 0; u < BPT; ++u) {
-      int e = threadIdx.x + u * NT;
-      e = e < BB / 16 ? e : BB / 16 - 1;
-      w[u] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(Bt) + 16 * e);
-    }
-#pragma unroll
-    for (int u = 0; u < BPT; ++u) {
-      int e = threadIdx.x + u * NT;
-      e = e < BB / 16 ? e : BB / 16 - 1;
-      *reinterpret_cast<u32x4*>(smem + 16 * e) = w[u];
-    }
-  }
+  c16_weights_to_lds<G, NT>(smem, Bt);  // once
 
-  // per-lane patch items (fixed per thread): pixel pr, channel quad q; dst in the split patch
+  // the next tile's patch items, staged in registers under this tile's MFMAs
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)in_bytes, 0x00020000);
-  auto tile_xy = [&](int t, int& b, int& y0, int& x0) {
-    const int tx = t % tilesX, tt = t / tilesX, ty = tt % tilesY;
-    b = tt / tilesY;
-    y0 = ty * TH;
-    x0 = tx * TW;
-  };
   f32x4 stg[PPT];
   auto load_tile = [&](int t) {
     int b, y0, x0;
-    tile_xy(t, b, y0, x0);
-#pragma unroll
-    for (int d = 0; d < PPT; ++d) {
-      int e = threadIdx.x + d * NT;
-      e = e < ITEMS ? e : ITEMS - 1;
-      const int pr = e >> 2, q = e & 3, py = pr / PW2, px = pr - py * PW2;
-      const int iy = y0 - 1 + py, ix = x0 - 1 + px;
-      const bool ok = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
-      const unsigned vo = ok ? (unsigned)((((b * g.H + iy) * g.W + ix) * 16 + 4 * q) * 4) : OOB_OFF;
-      stg[d] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, vo, 0, 0));
-    }
-  };
-  auto split_tile = [&]() {  // 16-B fp32 channel quad -> three 8-B bf16 quads (pieces at 32 p + 8 q)
-    bool ok = true;
-#pragma unroll
-    for (int d = 0; d < PPT; ++d)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) ok = ok && x3_split_ok(stg[d][c]);
-    const bool fast = __builtin_amdgcn_ballot_w64(!ok) == 0;  // (pairs of one v_cvt_pk per piece)
-#pragma unroll
-    for (int d = 0; d < PPT; ++d) {
-      int e = threadIdx.x + d * NT;
-      e = e < ITEMS ? e : ITEMS - 1;
-      const int dst = (e >> 2) * PB + 8 * (e & 3);
-      uint2 w[3];
-      if constexpr ((X3DIAG & 128) != 0) {  // (diagnostic: truncating 2-piece "split", 2 v_perm per pair)
-        const unsigned a0 = __builtin_bit_cast(unsigned, stg[d][0]), a1 = __builtin_bit_cast(unsigned, stg[d][1]);
-        const unsigned a2 = __builtin_bit_cast(unsigned, stg[d][2]), a3 = __builtin_bit_cast(unsigned, stg[d][3]);
-        w[0] = uint2{__builtin_amdgcn_perm(a1, a0, 0x07060302u), __builtin_amdgcn_perm(a3, a2, 0x07060302u)};
-        w[1] = uint2{__builtin_amdgcn_perm(a1, a0, 0x05040100u), __builtin_amdgcn_perm(a3, a2, 0x05040100u)};
-        w[2] = uint2{0u, 0u};
-        (void)fast;
-      } else {
-        split3_pack2(fast, stg[d][0], stg[d][1], w[0].x, w[1].x, w[2].x);
-        split3_pack2(fast, stg[d][2], stg[d][3], w[0].y, w[1].y, w[2].y);
-      }
-#pragma unroll
-      for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(patch + dst + 32 * p) = w[p];
-    }
+    x3_tile_xy<TH, TW>(t, tilesX, tilesY, b, y0, x0);
+    c16_load_items<G>(stg, rsA, threadIdx.x, b, y0, x0, g);
   };
 
-  // fragment rows (fixed per lane): the pixel of tap (1, 1) of row (wm TM + i) 16 + fr
-  // (packed two per register: byte offsets < PR PB < 2^16; the other offsets are uniform or per lane)
-  constexpr int NPP = (TM + 1) / 2;
-  static_assert(PR * PB < 65536, "16-bit patch offsets");
-  unsigned prow2[NPP];
-#pragma unroll
-  for (int k = 0; k < NPP; ++k) prow2[k] = 0;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    int r = (wm * TM + i) * 16 + fr;
-    r = r < T ? r : T - 1;
-    int ly, lx;
-    if constexpr (POOL) {
-      const int w = r >> 2, q = r & 3;
-      ly = 2 * (w / (TW / 2)) + (q >> 1);
-      lx = 2 * (w % (TW / 2)) + (q & 1);
-    } else {
-      ly = r / TW;
-      lx = r % TW;
-    }
-    prow2[i / 2] |= (unsigned)(((ly + 1) * PW2 + lx + 1) * PB) << (16 * (i % 2));
-  }
-  auto prow = [&](int i) {
-    unsigned w = prow2[i / 2];
-    asm volatile("" : "+v"(w));
-    return (int)((w >> (16 * (i % 2))) & 0xffffu);
-  };
+  const C16PackedRows<G, POOL> prow(wm, fr);  // fragment rows (fixed per lane)
   const int fqo = 16 * (fq & 1);
-  auto toff = [&](int s) {  // this lane's tap offset (bytes) in full step s
-    const int ta = 2 * s, tb = 2 * s + 1 < 9 ? 2 * s + 1 : 8;
-    const int oa = ((ta / 3 - 1) * PW2 + (ta % 3 - 1)) * PB, ob = ((tb / 3 - 1) * PW2 + (tb % 3 - 1)) * PB;
-    return th ? ob : oa;
-  };
-  auto frag = [&](int i, int off, bf16x8 (&a)[3]) {
-    const unsigned char* q = patch + prow(i) + fqo + off;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(q + 32 * p);
-  };
-  auto bfrag = [&](int s, bf16x8 (&bb)[3][2]) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        bb[p][j] = *reinterpret_cast<const bf16x8*>(smem + (j * NS * 3 + s * 3 + p) * 1024 + lane * 16);
-  };
-  // HALF: the K = 16 step (tap 8, channels 4 fq .. 4 fq + 3): A 8 B at the lane's pixel + tap 8,
-  // B 8 B of the packed step 4 (lane fr + 16 (fq >> 1), element 4 (fq & 1))
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  const int hoff = (PW2 + 1) * PB + 8 * fq;  // tap (2, 2) relative to (1, 1), 8 fq in the pixel
-  const int hb = (fr + 16 * (fq >> 1)) * 16 + 8 * (fq & 1);
 
-  const int G = gridDim.x;
+  const int nwg = gridDim.x;
   int t = blockIdx.x;
 #if (X3DIAG & 32) != 0  // per-phase s_memtime sums (c16_diag_stamps)
   unsigned long long dg[C16_DIAG_SLOTS] = {}, dg_t1 = 0;
@@ -604,7 +718,7 @@ conv3x3_x3_c16p_kernel(const float* __restrict__ in, const bf16_bits* __restrict
     ++dg[8];
 #endif
     int b, y0, x0;
-    tile_xy(t, b, y0, x0);
+    x3_tile_xy<TH, TW>(t, tilesX, tilesY, b, y0, x0);
     // all of this wave's memory operations retired: the staged loads, and the previous tile's
     // stores (X3DIAG 32: ~80 cycles, they are done by now).  (Round 4, measured: leaving those
     // stores in flight -- a fixed store count per wave, so that the wait could leave them
@@ -612,21 +726,9 @@ conv3x3_x3_c16p_kernel(const float* __restrict__ in, const bf16_bits* __restrict
     // per tile: conv1 0.152 -> 0.19 ms.)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     C16_STAMP(0)
-    split_tile();
-    for (int r = threadIdx.x; r < NO; r += NT) {
-      int o;
-      if constexpr (POOL) {
-        const int py = (y0 >> 1) + r / (TW / 2), px = (x0 >> 1) + r % (TW / 2);
-        o = (py >= g.PH || px >= g.PW) ? -1
-            : g.out_mode == 1         ? (b * (g.PH + 2) + py + 1) * (g.PW + 2) + px + 1
-                                      : (b * g.PH + py) * g.PW + px;
-      } else {
-        const int oy = y0 + r / TW, ox = x0 + r % TW;
-        o = (oy >= g.H || ox >= g.W) ? -1 : g.out_mode == 1 ? (b * (g.H + 2) + oy + 1) * Wp + ox + 1 : (b * g.H + oy) * g.W + ox;
-      }
-      orow[r] = o;
-    }
-    const int tn = t + G;
+    c16_split_items<G, (X3DIAG & 128) != 0>(stg, patch, threadIdx.x);
+    x3_tile_orows<TW, POOL, NO, NT>(orow, b, y0, x0, g);
+    const int tn = t + nwg;
     if (tn < ntiles) load_tile(tn);  // in flight during this tile's MFMAs
     C16_STAMP(1)
     __syncthreads();                 // the patch, the row table (and, first time, the weights) written
@@ -641,48 +743,32 @@ conv3x3_x3_c16p_kernel(const float* __restrict__ in, const bf16_bits* __restrict
     // B fragments single-buffered (read at each step's start; the other workgroup's waves cover
     // the latency): the staging registers of the next tile take the second buffer's room
     bf16x8 af[2][3], bq[3][2];
-    frag(0, toff(0), af[0]);
+    c16_frag(patch + prow(0) + fqo + c16_toff<G>(0, th), af[0]);
 #pragma unroll
     for (int s = 0; s < NSF; ++s) {
-      const int off = toff(s), off_next = toff(s + 1 < NSF ? s + 1 : s);
-      bfrag(s, bq);
+      const int off = c16_toff<G>(s, th), off_next = c16_toff<G>(s + 1 < NSF ? s + 1 : s, th);
+      c16_bfrag<G>(smem, s, lane, bq);
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int cur = (s * TM + i) & 1, nxt = cur ^ 1;
         if (i + 1 < TM)
-          frag(i + 1, off, af[nxt]);
+          c16_frag(patch + prow(i + 1) + fqo + off, af[nxt]);
         else if (s + 1 < NSF)
-          frag(0, off_next, af[nxt]);
+          c16_frag(patch + prow(0) + fqo + off_next, af[nxt]);
         const bf16x8(&bb)[3][2] = bq;
 #pragma unroll
         for (int jb = 0; jb < 2; ++jb) x3_step<true>(acc[i][jb], accc[i][jb], af[cur], bb, jb);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-    if constexpr (HALF) {
+    if constexpr (HALF) {  // the K = 16 step, its A fragments read in the loop
       s16x4 hbq[3][2];
-#pragma unroll
-      for (int p = 0; p < 3; ++p)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          hbq[p][j] = *reinterpret_cast<const s16x4*>(smem + (j * NS * 3 + 4 * 3 + p) * 1024 + hb);
+      c16_hbfrag<G>(smem, fr, fq, hbq);
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        const int pr = prow(i);
         s16x4 a[3];
-#pragma unroll
-        for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const s16x4*>(patch + pr + hoff + 32 * p);
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb) {
-          f32x4 c = accc[i][jb];
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[2], hbq[0][jb], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], hbq[1][jb], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], hbq[2][jb], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], hbq[0][jb], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], hbq[1][jb], c, 0, 0, 0);
-          accc[i][jb] = c;
-          acc[i][jb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], hbq[0][jb], acc[i][jb], 0, 0, 0);
-        }
+        c16_hfrag(patch + prow(i) + c16_hoff<G>(fq), a);
+        c16_half_step(acc[i], accc[i], a, hbq);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -721,38 +807,8 @@ conv3x3_x3_c16p_kernel(const float* __restrict__ in, const bf16_bits* __restrict
 #pragma unroll
     for (int jb = 0; jb < 2; ++jb) {
       const int n = 16 * jb + fr;
-      const float pb = (eflags & EPI_BIAS) ? epi.bias[n] : 0.f;
-      const float pm = (eflags & (EPI_BN | EPI_BN_AB)) ? epi.mean[n] : 0.f;
-      const float ps = (eflags & (EPI_BN | EPI_BN_AB)) ? epi.sq[n] : 1.f;
-      const float pg = (eflags & EPI_BN) ? epi.gamma[n] : 1.f;
-      auto put = [&](int o, float v) {
-        if (g.out_mode == 1) {
-          unsigned short s0, s1, s2;
-          split3(v, s0, s1, s2);
-          bf16_bits* d = out_split + (size_t)o * 96 + n;
-          d[0] = s0;
-          d[32] = s1;
-          d[64] = s2;
-        } else {
-          out[(size_t)o * N + n] = v;
-        }
-      };
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int rb = 16 * (wm * TM + i);
-        if constexpr (POOL) {
-          const int w = rb / 4 + fq;
-          const int o = w < NO ? orow[w] : -1;
-          if (o >= 0) put(o, pool_then_epilogue_t<FL>(acc[i][jb], pb, pm, ps, pg, epi.flags));
-        } else {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int row = rb + 4 * fq + r;
-            const int o = row < NO ? orow[row] : -1;
-            if (o >= 0) put(o, apply_epilogue_t<FL>(acc[i][jb][r], pb, pm, ps, pg, epi.flags));
-          }
-        }
-      }
+      x3_tile_put_col<FL, POOL, NO>(acc, jb, x3_epi_col(epi, eflags, n), epi.flags, n, N, out, out_split, 96, n,
+                                    g.out_mode, orow, 16 * wm * TM, fq);
     }
     __syncthreads();  // the row table is rewritten by the next tile
     t = tn;
@@ -789,11 +845,10 @@ conv3x3_x3_c16pp_kernel(const float* __restrict__ in, const bf16_bits* __restric
                         bf16_bits* __restrict__ out_split, EpiParams epi, int tilesX, int tilesY, int ntiles,
                         X3Geom g, unsigned in_bytes, int ppprio) {
   constexpr int TH = 16, TW = 26, WM = 4, TM = 7;
-  constexpr int NT = 64 * WM, PB = 96, PW2 = TW + 2, PR = (TH + 2) * PW2, T = TH * TW, NS = 5;
-  constexpr int ITEMS = PR * 4, PPT = (ITEMS + NT - 1) / NT;  // item = (patch pixel, channel quad), per team
-  constexpr int BB = 2 * NS * 3 * 1024, BPT = (BB / 16 + 2 * NT - 1) / (2 * NT);
-  constexpr int NO = T / 4, PATCH = PR * PB, STGW = TM * 4 * X3_STG_ROW;  // stage floats per wave
-  static_assert(WM * TM * 16 >= T && (WM * TM - 3) * 16 < T && PPT == 8, "shape");
+  using G = C16Geom<TH, TW, WM, TM>;  // per team
+  constexpr int NT = G::NT, T = G::T, NS = G::NS, PPT = G::PPT, BB = G::BB, PATCH = G::PATCH;
+  constexpr int NO = T / 4, STGW = TM * 4 * X3_STG_ROW;  // stage floats per wave
+  static_assert(PPT == 8, "shape");
   static_assert(BB + 2 * PATCH + WM * STGW * 4 + 32 * 16 <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(1024))) unsigned char smem[BB + 2 * PATCH + WM * STGW * 4];
   __shared__ f32x4 epl[32];
@@ -814,110 +869,26 @@ conv3x3_x3_c16pp_kernel(const float* __restrict__ in, const bf16_bits* __restric
     const X3EpiCol c = x3_epi_col(epi, eflags, threadIdx.x);
     epl[threadIdx.x] = f32x4{c.pb, c.pm, c.ps, c.pg};
   }
-  {  // weights once (both teams): the packed [n/16][step][piece][lane][8] block of columns 0-31
-    u32x4 w[BPT];
-#pragma unroll
-    for (int u = 0; u < BPT; ++u) {
-      int e = threadIdx.x + u * 2 * NT;
-      e = e < BB / 16 ? e : BB / 16 - 1;
-      w[u] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const unsigned char*>(Bt) + 16 * e);
-    }
-#pragma unroll
-    for (int u = 0; u < BPT; ++u) {
-      int e = threadIdx.x + u * 2 * NT;
-      e = e < BB / 16 ? e : BB / 16 - 1;
-      *reinterpret_cast<u32x4*>(smem + 16 * e) = w[u];
-    }
-  }
+  c16_weights_to_lds<G, 2 * NT>(smem, Bt);  // once, both teams
 
   const auto rsA = __builtin_amdgcn_make_buffer_rsrc((void*)in, 0, (int)in_bytes, 0x00020000);
   auto tile_of = [&](int k, int& b, int& y0, int& x0) {
-    const int t = lo + team + 2 * k;
-    const int tx = t % tilesX, t2 = t / tilesX, ty = t2 % tilesY;
-    b = t2 / tilesY;
-    y0 = ty * TH;
-    x0 = tx * TW;
+    x3_tile_xy<TH, TW>(lo + team + 2 * k, tilesX, tilesY, b, y0, x0);
   };
   f32x4 stg[PPT];
   auto load_tile = [&](int k) {
     int b, y0, x0;
     tile_of(k, b, y0, x0);
-#pragma unroll
-    for (int d = 0; d < PPT; ++d) {
-      int e = tt + d * NT;
-      e = e < ITEMS ? e : ITEMS - 1;
-      const int pr = e >> 2, q = e & 3, py = pr / PW2, px = pr - py * PW2;
-      const int iy = y0 - 1 + py, ix = x0 - 1 + px;
-      const bool ok = (unsigned)iy < (unsigned)g.H && (unsigned)ix < (unsigned)g.W;
-      const unsigned vo = ok ? (unsigned)((((b * g.H + iy) * g.W + ix) * 16 + 4 * q) * 4) : OOB_OFF;
-      stg[d] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsA, vo, 0, 0));
-    }
-  };
-  auto split_tile = [&]() {  // 16-B fp32 channel quad -> three 8-B bf16 quads (pieces at 32 p + 8 q)
-    bool ok = true;
-#pragma unroll
-    for (int d = 0; d < PPT; ++d)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) ok = ok && x3_split_ok(stg[d][c]);
-    const bool fast = __builtin_amdgcn_ballot_w64(!ok) == 0;
-#pragma unroll
-    for (int d = 0; d < PPT; ++d) {
-      int e = tt + d * NT;
-      e = e < ITEMS ? e : ITEMS - 1;
-      const int dst = (e >> 2) * PB + 8 * (e & 3);
-      uint2 w[3];
-      split3_pack2(fast, stg[d][0], stg[d][1], w[0].x, w[1].x, w[2].x);
-      split3_pack2(fast, stg[d][2], stg[d][3], w[0].y, w[1].y, w[2].y);
-#pragma unroll
-      for (int p = 0; p < 3; ++p) *reinterpret_cast<uint2*>(patch + dst + 32 * p) = w[p];
-    }
+    c16_load_items<G>(stg, rsA, tt, b, y0, x0, g);
   };
 
-  // fragment rows as conv3x3_x3_c16p_kernel (pool-window-major rows)
-  constexpr int NPP = (TM + 1) / 2;
-  static_assert(PR * PB < 65536, "16-bit patch offsets");
-  unsigned prow2[NPP];
-#pragma unroll
-  for (int k = 0; k < NPP; ++k) prow2[k] = 0;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    int r = (wm * TM + i) * 16 + fr;
-    r = r < T ? r : T - 1;
-    const int w = r >> 2, q = r & 3;
-    const int ly = 2 * (w / (TW / 2)) + (q >> 1), lx = 2 * (w % (TW / 2)) + (q & 1);
-    prow2[i / 2] |= (unsigned)(((ly + 1) * PW2 + lx + 1) * PB) << (16 * (i % 2));
-  }
-  auto prow = [&](int i) {
-    unsigned w = prow2[i / 2];
-    asm volatile("" : "+v"(w));
-    return (int)((w >> (16 * (i % 2))) & 0xffffu);
-  };
+  const C16PackedRows<G, true> prow(wm, fr);  // fragment rows (pool-window-major)
   const int fqo = 16 * (fq & 1);
-  auto toff = [&](int s) {
-    const int ta = 2 * s, tb = 2 * s + 1 < 9 ? 2 * s + 1 : 8;
-    const int oa = ((ta / 3 - 1) * PW2 + (ta % 3 - 1)) * PB, ob = ((tb / 3 - 1) * PW2 + (tb % 3 - 1)) * PB;
-    return th ? ob : oa;
-  };
-  auto frag = [&](int i, int off, bf16x8 (&a)[3]) {
-    const unsigned char* q = patch + prow(i) + fqo + off;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const bf16x8*>(q + 32 * p);
-  };
-  auto bfrag = [&](int s, bf16x8 (&bb)[3][2]) {
-#pragma unroll
-    for (int p = 0; p < 3; ++p)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-        bb[p][j] = *reinterpret_cast<const bf16x8*>(smem + (j * NS * 3 + s * 3 + p) * 1024 + lane * 16);
-  };
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  const int hoff = (PW2 + 1) * PB + 8 * fq;
-  const int hb = (fr + 16 * (fq >> 1)) * 16 + 8 * (fq & 1);
 
   // prologue: each team's first patch split into its area
   if (nmine > 0) {
     load_tile(0);
-    split_tile();
+    c16_split_items<G>(stg, patch, tt);
   }
   __syncthreads();  // weights, epl, both teams' first patches
 
@@ -953,53 +924,32 @@ conv3x3_x3_c16pp_kernel(const float* __restrict__ in, const bf16_bits* __restric
       constexpr int NSF = NS - 1;  // full 16x16x32 steps; tap 8 alone on 16x16x16 below
       bf16x8 af[2][3], bq[2][3][2];
       s16x4 hbq[3][2];
-      frag(0, toff(0), af[0]);
-      bfrag(0, bq[0]);
+      c16_frag(patch + prow(0) + fqo + c16_toff<G>(0, th), af[0]);
+      c16_bfrag<G>(smem, 0, lane, bq[0]);
 #pragma unroll
       for (int s = 0; s < NSF; ++s) {
-        const int off = toff(s), off_next = toff(s + 1 < NSF ? s + 1 : s);
+        const int off = c16_toff<G>(s, th), off_next = c16_toff<G>(s + 1 < NSF ? s + 1 : s, th);
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
           const int cur = (s * TM + i) & 1, nxt = cur ^ 1;
-          if (i == 0 && s + 1 < NSF) bfrag(s + 1, bq[(s + 1) & 1]);
-          if (i == 0 && s + 1 == NSF) {
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-#pragma unroll
-              for (int j = 0; j < 2; ++j)
-                hbq[p][j] = *reinterpret_cast<const s16x4*>(smem + (j * NS * 3 + 4 * 3 + p) * 1024 + hb);
-          }
+          if (i == 0 && s + 1 < NSF) c16_bfrag<G>(smem, s + 1, lane, bq[(s + 1) & 1]);
+          if (i == 0 && s + 1 == NSF) c16_hbfrag<G>(smem, fr, fq, hbq);
           if (i + 1 < TM)
-            frag(i + 1, off, af[nxt]);
+            c16_frag(patch + prow(i + 1) + fqo + off, af[nxt]);
           else if (s + 1 < NSF)
-            frag(0, off_next, af[nxt]);
+            c16_frag(patch + prow(0) + fqo + off_next, af[nxt]);
 #pragma unroll
           for (int jb = 0; jb < 2; ++jb) x3_step<true>(acc[i][jb], accc[i][jb], af[cur], bq[s & 1], jb);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
       s16x4 ha[2][3];
-      auto hfrag = [&](int i, s16x4 (&a)[3]) {
-        const int pr = prow(i);
-#pragma unroll
-        for (int p = 0; p < 3; ++p) a[p] = *reinterpret_cast<const s16x4*>(patch + pr + hoff + 32 * p);
-      };
-      hfrag(0, ha[0]);
+      const int hoff = c16_hoff<G>(fq);
+      c16_hfrag(patch + prow(0) + hoff, ha[0]);
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        if (i + 1 < TM) hfrag(i + 1, ha[(i + 1) & 1]);
-        const s16x4(&a)[3] = ha[i & 1];
-#pragma unroll
-        for (int jb = 0; jb < 2; ++jb) {
-          f32x4 c = accc[i][jb];
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[2], hbq[0][jb], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], hbq[1][jb], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], hbq[2][jb], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[1], hbq[0][jb], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], hbq[1][jb], c, 0, 0, 0);
-          accc[i][jb] = c;
-          acc[i][jb] = __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a[0], hbq[0][jb], acc[i][jb], 0, 0, 0);
-        }
+        if (i + 1 < TM) c16_hfrag(patch + prow(i + 1) + hoff, ha[(i + 1) & 1]);
+        c16_half_step(acc[i], accc[i], ha[i & 1], hbq);
         __builtin_amdgcn_sched_barrier(0);
       }
       wait_lgkm0();
@@ -1023,13 +973,10 @@ conv3x3_x3_c16pp_kernel(const float* __restrict__ in, const bf16_bits* __restric
       }
       pool_epilogue_batch<FL>(acc, epb, epm, eps, epg, epi.flags,
                               [&](int i, int jb, float v) { stgp[(4 * i + fq) * X3_STG_ROW + 16 * jb + fr] = v; });
-      auto orow_of = [&](int w) {
-        const int py = (y0 >> 1) + w / (TW / 2), px = (x0 >> 1) + w % (TW / 2);
-        return (py >= g.PH || px >= g.PW) ? -1 : (b * (g.PH + 2) + py + 1) * (g.PW + 2) + px + 1;
-      };
+      auto orow_of = [&](int w) { return x3_tile_orow<TW, true, 1>(w, b, y0, x0, g); };  // (rows on the fly)
       x3_pool_split_store_f<TM>(stgp, orow_of, NO, 4 * wm * TM, out_split, 96, 0, lane);
       C16PP_MARK(2)
-      if (k + 1 < nmine) split_tile();
+      if (k + 1 < nmine) c16_split_items<G>(stg, patch, tt);
       wait_lgkm0();  // the split patch written, the stage read
       C16PP_MARK(1)
     }
@@ -1242,19 +1189,7 @@ conv3x3_x3_tile2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __res
   __syncthreads();
   T2_STAMP(12, __builtin_amdgcn_s_memtime())
   constexpr int NO = POOL ? T / 4 : T;
-  for (int r = threadIdx.x; r < NO; r += NT) {
-    int o;
-    if constexpr (POOL) {
-      const int py = (y0 >> 1) + r / (TW / 2), px = (x0 >> 1) + r % (TW / 2);
-      o = (py >= g.PH || px >= g.PW) ? -1
-          : g.out_mode == 1         ? (b * (g.PH + 2) + py + 1) * (g.PW + 2) + px + 1
-                                    : (b * g.PH + py) * g.PW + px;
-    } else {
-      const int oy = y0 + r / TW, ox = x0 + r % TW;
-      o = (oy >= g.H || ox >= g.W) ? -1 : g.out_mode == 1 ? (b * (g.H + 2) + oy + 1) * Wp + ox + 1 : (b * g.H + oy) * g.W + ox;
-    }
-    orow[r] = o;
-  }
+  x3_tile_orows<TW, POOL, NO, NT>(orow, b, y0, x0, g);
   __syncthreads();
   T2_STAMP(13, __builtin_amdgcn_s_memtime())
   if constexpr (POOL) {
@@ -1288,36 +1223,8 @@ conv3x3_x3_tile2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __res
       const f32x4 e = epl[wn * 32 + 16 * jb + fr];
       ec = X3EpiCol{e[0], e[1], e[2], e[3]};
     }
-    const float pb = ec.pb, pm = ec.pm, ps = ec.ps, pg = ec.pg;
-    const int cofs = (n >> 5) * 96 + (n & 31);
-    auto put = [&](int o, float v) {
-      if (g.out_mode == 1) {
-        unsigned short s0, s1, s2;
-        split3(v, s0, s1, s2);
-        bf16_bits* d = out_split + (size_t)o * (3 * N) + cofs;
-        d[0] = s0;
-        d[32] = s1;
-        d[64] = s2;
-      } else {
-        out[(size_t)o * N + n] = v;
-      }
-    };
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int rb = 16 * (wm * TM + i);
-      if constexpr (POOL) {
-        const int w = rb / 4 + fq;
-        const int o = w < NO ? orow[w] : -1;
-        if (o >= 0) put(o, pool_then_epilogue_t<FL>(acc[i][jb], pb, pm, ps, pg, epi.flags));
-      } else {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = rb + 4 * fq + r;
-          const int o = row < NO ? orow[row] : -1;
-          if (o >= 0) put(o, apply_epilogue_t<FL>(acc[i][jb][r], pb, pm, ps, pg, epi.flags));
-        }
-      }
-    }
+    x3_tile_put_col<FL, POOL, NO>(acc, jb, ec, epi.flags, n, N, out, out_split, 3 * N, (n >> 5) * 96 + (n & 31),
+                                  g.out_mode, orow, 16 * wm * TM, fq);
   }
   T2_STAMP(4, __builtin_amdgcn_s_memtime())
   T2_STAMP(5, __builtin_amdgcn_s_memrealtime())
@@ -1380,11 +1287,7 @@ conv3x3_x3_pp_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __restri
     rowoff[i] = (ly * RU + lx * PU) * 16 + 16 * fq;
   }
   auto tile_of = [&](int k, int& b, int& y0, int& x0) {
-    const int t = lo + team + 2 * k;
-    const int tx = t % tilesX, tt = t / tilesX, ty = tt % tilesY;
-    b = tt / tilesY;
-    y0 = ty * TH;
-    x0 = tx * TW;
+    x3_tile_xy<TH, TW>(lo + team + 2 * k, tilesX, tilesY, b, y0, x0);
   };
 
   // patch DMA: LDS unit U of a chunk's buffer = patch row U / RU, pixel (U % RU) / PU, unit
@@ -1523,10 +1426,7 @@ conv3x3_x3_pp_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __restri
       }
       pool_epilogue_batch<FL>(acc, pb, pm, ps, pg, epi.flags,
                               [&](int i, int jb, float v) { stg[(4 * i + fq) * X3_STG_ROW + 16 * jb + fr] = v; });
-      auto orow_of = [&](int w) {
-        const int py = (y0 >> 1) + w / (TW / 2), px = (x0 >> 1) + w % (TW / 2);
-        return (py >= g.PH || px >= g.PW) ? -1 : (b * (g.PH + 2) + py + 1) * (g.PW + 2) + px + 1;
-      };
+      auto orow_of = [&](int w) { return x3_tile_orow<TW, true, 1>(w, b, y0, x0, g); };
       x3_pool_split_store_f<TM>(stg, orow_of, NO, 4 * wm * TM, out_split, 3 * (size_t)N, (n0 >> 5) * 96, lane);
       if (k + 1 < nmine) {
         load_b(0, bq[0]);  // (after the epilogue: registers)

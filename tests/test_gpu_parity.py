@@ -2011,6 +2011,62 @@ def test_x3_tile_kernel_vs_oracle(monkeypatch, case):
     assert errs["1"] <= 1.25 * errs["0"] and errs.get("lat", 0.0) <= 1.25 * errs["0"], errs
 
 
+def test_x3_c16_pooled_plain_output_vs_oracle(monkeypatch):
+    """A pooled 16-channel x3 conv whose output is the plan's plain fp32 output (nothing after its
+    pool: the unstaged pooled epilogue with out_mode 0), tiles ragged in both directions against
+    16 x 26: the persistent kernel (batch plan), the one-tile kernel (DNN_HIP_X3_C16P=0) and the
+    latency plan's 4 x 26 tiles.  Each arm within the fp32 tolerance of the float64 oracle and
+    within 1.25x of the fp32-MFMA plan's error (DNN_HIP_X3=0), negative-gamma channels, repeat runs
+    identical.  (The arms are not bit-equal to each other: the K = 16 step sums differently.)"""
+    B, H, W = 2, 36, 44
+    rng = np.random.default_rng(B * 31 + H + W)
+    x = rng.standard_normal((B, H, W, 16)).astype(np.float32)
+    k = (rng.standard_normal((3, 3, 16, 32)) * np.sqrt(2.0 / (9 * 16))).astype(np.float32)
+    b = rng.standard_normal(32).astype(np.float32) * 0.1
+    gam = rng.uniform(0.5, 1.5, 32).astype(np.float32)
+    gam[::5] *= -1
+    n = (rng.standard_normal(32).astype(np.float32) * 0.1, rng.uniform(0.5, 1.5, 32).astype(np.float32), gam)
+
+    def graph():
+        g = dnn_hip.DnnGraphBuilder()
+        y = g.create_input([B, H, W, 16])
+        y = g.create_max_pool2d(y, [1, 2, 2, 1], [1, 1, 1, 1], "SAME")  # (conv1 is never a plan's first layer)
+        y = g.create_conv2d(y, k, [1, 1, 1, 1], "SAME")
+        y = g.create_bias_add(y, b)
+        y = g.create_batch_norm(y, *n, 1e-5)
+        y = g.create_leaky_relu(y)
+        y = g.create_max_pool2d(y, [1, 2, 2, 1], [1, 2, 2, 1], "SAME")
+        g.set_out_node(y)
+        return g
+
+    ref = R.max_pool2d(x, [1, 2, 2, 1], [1, 1, 1, 1], "SAME")
+    ref = R.leaky_relu(R.batch_norm(R.bias_add(R.conv2d(ref, k), b), *n, 1e-5))
+    ref = R.max_pool2d(ref, [1, 2, 2, 1], [1, 2, 2, 1], "SAME")
+
+    def run(latency):
+        eng = dnn_hip.DnnInferenceEngine(graph(), False, latency=latency)
+        conv = [ln for ln in eng.plan().describe().splitlines() if ln.startswith("conv")]
+        y = eng.run(x)
+        assert np.array_equal(eng.run(x), y)
+        return conv, R.normwise_err(y, ref)
+
+    monkeypatch.setenv("DNN_HIP_X3", "0")
+    _, e0 = run(False)
+    monkeypatch.setenv("DNN_HIP_X3", "1")
+    errs = {}
+    conv, errs["c16p"] = run(False)
+    assert len(conv) == 1 and "mode=patch_x3" in conv[0] and "+pool2x2s2" in conv[0] and "latency" not in conv[0], conv
+    monkeypatch.setenv("DNN_HIP_X3_C16P", "0")
+    _, errs["c16"] = run(False)
+    monkeypatch.delenv("DNN_HIP_X3_C16P")
+    conv, errs["lat"] = run(True)
+    assert "mode=patch_x3" in conv[0] and "+pool2x2s2" in conv[0] and "latency" in conv[0], conv
+    print("c16 pooled plain output: normwise err", errs, "fp32 MFMA %.3e" % e0)
+    assert e0 < 3 * LAYER_TOL, e0
+    for arm, e in errs.items():
+        assert e < 3 * LAYER_TOL and e <= 1.25 * e0, (arm, errs, e0)
+
+
 @pytest.mark.parametrize("B", [24, 21])
 def test_x3_pingpong_equals_tile_kernel(monkeypatch, B):
     """conv3x3_x3_pp_kernel (N = 64 from one 32-channel chunk, pooled into split planes, batch

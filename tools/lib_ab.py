@@ -6,6 +6,7 @@ median over rounds of each kernel's mean time and of the forward.
 
   python tools/lib_ab.py --lib libdnn_hip.so --lib diag/libdnn_hip_old.so [--rounds 4] [--precision fp16]
   python tools/lib_ab.py --env DNN_HIP_X3_IMG=1,0   (plan-time switches: one child per arm)
+  python tools/lib_ab.py --latency --lib ... --lib ...   (batch 1 on a latency plan; --json FILE keeps the arms' records)
 """
 import argparse
 import json
@@ -29,9 +30,11 @@ def child(a):
     g, _ = yolo_graph.build_graph(dnn_hip.DnnGraphBuilder, ws, in_shape=(a.batch, 416, 416, 3))
     entries = dnn_hip.lower_graph(g)
     kw = {"precision": a.precision} if a.precision != "fp32" else {}
+    if a.latency:
+        kw["latency"] = True
     wb, sb = dnn_hip.Plan.memory(a.batch, (416, 416, 3), entries, **kw)
     wbuf = torch.empty(wb, dtype=torch.uint8, device=dev)
-    sbuf = torch.empty(sb, dtype=torch.uint8, device=dev)
+    sbuf = torch.empty(max(sb, 1), dtype=torch.uint8, device=dev)
     plan = dnn_hip.Plan(a.batch, (416, 416, 3), entries, device=0, weights_ptr=wbuf.data_ptr(),
                         workspace_ptr=sbuf.data_ptr(), **kw)
     x = torch.rand((a.batch, 416, 416, 3), device=dev)
@@ -67,8 +70,12 @@ def main():
     ap.add_argument("--preheat", type=float, default=2.0)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--precision", default="fp32")
+    ap.add_argument("--latency", action="store_true", help="batch 1 on a latency plan")
+    ap.add_argument("--json", default=None, help="write the arms' records to this file")
     ap.add_argument("--child", action="store_true")
     a = ap.parse_args()
+    if a.latency:
+        a.batch = 1
     if a.child:
         child(a)
         return
@@ -84,7 +91,8 @@ def main():
         for lib, over in order:
             env = dict(os.environ, **over)
             out = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--iters", str(a.iters),
-                                  "--preheat", str(a.preheat), "--batch", str(a.batch), "--precision", a.precision],
+                                  "--preheat", str(a.preheat), "--batch", str(a.batch), "--precision", a.precision] +
+                                 (["--latency"] if a.latency else []),
                                  env=env, capture_output=True, text=True, timeout=600)
             line = [ln for ln in out.stdout.splitlines() if ln.startswith("RESULT ")]
             if out.returncode != 0 or not line:
@@ -92,11 +100,16 @@ def main():
                 sys.exit(1)
             res[lib].append(json.loads(line[0][7:]))
             print("round", r, lib, "fwd %.4f" % res[lib][-1]["fwd_ms"], flush=True)
+    recs = []
     for lib, rs in res.items():
         ks = rs[0]["kernels"].keys()
         med = {k: round(statistics.median(x["kernels"][k] for x in rs), 4) for k in ks}
-        print(json.dumps({"arm": lib, "fwd_ms_median": round(statistics.median(x["fwd_ms"] for x in rs), 4),
-                          "kernels_ms_median": med}))
+        recs.append({"arm": lib, "batch": a.batch, "latency": a.latency, "rounds": a.rounds,
+                     "fwd_ms_median": round(statistics.median(x["fwd_ms"] for x in rs), 4), "kernels_ms_median": med})
+        print(json.dumps(recs[-1]))
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(recs, f, indent=1)
 
 
 if __name__ == "__main__":
