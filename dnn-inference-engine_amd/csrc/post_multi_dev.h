@@ -1,37 +1,33 @@
 // Shared by the multi-scale YOLO decodes (postprocess_multi.hip: everything of an image in one
-// workgroup; postprocess_wide.hip: a grid-wide decode kernel, then one NMS workgroup per image).
-// Every phase of those kernels is written ONCE here and called from both files, templated on the
-// width of the key's index field (PC_IDX_BITS in postprocess_multi.hip, PW_IDX_BITS in
-// postprocess_wide.hip) where it matters:
+// workgroup; postprocess_wide.hip: a grid-wide decode kernel, then one NMS workgroup per image):
+// what needs a scale table or a class-major key.  What a single-scale decode needs too (the per-box
+// arithmetic, BoxStore, key_any, emit_row, bitonic_sort, nms_workgroup, NmsState, nms_any_emit) is
+// post_dev.h, included here; those two files call its workgroup helpers with PM_THREADS.  Every
+// phase is written ONCE, here or there, templated on the width of the key's index field
+// (PC_IDX_BITS in postprocess_multi.hip, PW_IDX_BITS in postprocess_wide.hip) where it matters:
 //
-//   per box     decode_corners, class_argmax, label_score; ScaleTab / fill_scale_tab (the per-scale
-//               parameters in LDS), box_at (global box index -> scale, cell, anchor, values), BoxStore
-//               (an image's boxes in the workspace), the three key layouts, emit_row
-//   phase 2     bitonic_sort
-//   phase 3     nms_workgroup, nms_wave; nms_any_emit (the class-agnostic rule through emit);
-//               nms_segments (per class: waves on tickets, then the long segments by the workgroup)
+//   per box     label_score; ScaleTab / fill_scale_tab (the per-scale parameters in LDS), box_at
+//               (global box index -> scale, cell, anchor, values), decode_corners_at /
+//               decode_single_at (decode and store), the class-major and merge key layouts
+//   phase 3     nms_wave; nms_segments with its state ClassState (per class: waves on tickets, then
+//               the long segments by the workgroup)
 //   phase 4     gather_kept, merge_single, merge_labels (the in-place expansion and its invariant)
 //
 // so a box decodes to the same bits and a sorted segment gives the same kept list in either file.
 // The host-side checks and the host staging of both files' entries are declared here too
 // (postprocess_multi.hip defines them).
 #pragma once
-#include <hip/hip_runtime.h>
-#include <cstdint>
 #include <type_traits>
-#include "dnn_common.h"
-#include "post_math.h"
-#include "../../include/dnn_hip_post.h"
+#include "post_dev.h"
 
 namespace dnnhip {
 
 int yolo_head_boxes(const dnn_yolo_head* h, const char* who, long long max_boxes);  // postprocess_head.hip
 
 constexpr int PM_THREADS = 1024;
-constexpr int PM_WAVES = PM_THREADS / 64;
 constexpr int PM_CAP = DNN_YOLO_MULTI_MAX_BOXES;  // keys: 16384 x 8 B = 128 KiB; + 640 B of per-scale
                                                   // parameters, 128 B of ballot words, 16 B of counters
-constexpr int PM_BOX_BYTES = 40;                  // 4 x int64 corners + fp32 score + int class
+constexpr int PM_BOX_BYTES = POST_BOX_BYTES;
 static_assert((PM_CAP & (PM_CAP - 1)) == 0, "the bitonic sort needs a power of two");
 
 struct MultiPred {
@@ -87,65 +83,6 @@ bool multi_modes_ok(int nms_mode, int labels_mode, const char* who);
 int check_multi_call(const MultiCall& c, const MultiKind& kind, bool host, MultiArgs* out);
 // Host pointers, synchronous: checks, allocates the scratch, copies in, kind.launch, copies out.
 int yolo_multi_host(const MultiCall& c, const MultiKind& kind);
-
-// Geometry and objectness of one box of one scale (q: its 5 + C values; b, col, row: its anchor and
-// cell): corners truncated to int64 in out[0..3] (false when one is not finite or out of range) and
-// conf = sigmoid(q[4]).  xs, xb: the scale's XyScale pair, one fp32 multiply then one fp32 add (the
-// file is built without contraction).  Shared by all kernels below so that they round alike.
-__device__ __forceinline__ bool decode_corners(const float* q, int b, int col, int row, const float* anchors_s,
-                                               float cell_px, float xs, float xb, long long* out, float* conf) {
-  const float cx = ((float)col + (sigmoid_ref(q[0]) * xs + xb)) * cell_px;
-  const float cy = ((float)row + (sigmoid_ref(q[1]) * xs + xb)) * cell_px;
-  const float rw = (np_expf(q[2]) * anchors_s[2 * b]) * cell_px;
-  const float rh = (np_expf(q[3]) * anchors_s[2 * b + 1]) * cell_px;
-  *conf = sigmoid_ref(q[4]);
-  const float hw = rw / 2.0f, hh = rh / 2.0f;
-  long long l = 0, t = 0, r = 0, bt = 0;
-  const bool ok = trunc_i64(cx - hw, &l) && trunc_i64(cx + hw, &r) && trunc_i64(cy - hh, &t) &&
-                  trunc_i64(cy + hh, &bt);
-  out[0] = l;
-  out[1] = t;
-  out[2] = r;
-  out[3] = bt;
-  return ok;
-}
-
-// The ONE label of a box from its C class logits: the arg-max class in *cls and its p(class).
-__device__ __forceinline__ float class_argmax(const float* lg, int C, bool logistic, int* cls) {
-  int best = 0;
-  float bp;
-  if (logistic) {
-    bp = sigmoid_ref(lg[0]);
-    for (int c = 1; c < C; ++c) {
-      const float pc = sigmoid_ref(lg[c]);
-      if (pc > bp) {  // first index of the largest rounded value
-        bp = pc;
-        best = c;
-      }
-    }
-  } else {
-    float m = lg[0];
-    for (int c = 1; c < C; ++c) m = lg[c] > m ? lg[c] : m;
-    const float sum = softmax_sum(lg, C, m);
-    bp = np_expf(lg[0] - m) / sum;
-    for (int c = 1; c < C; ++c) {
-      const float pc = np_expf(lg[c] - m) / sum;
-      if (pc > bp) {  // first index of the max quotient
-        bp = pc;
-        best = c;
-      }
-    }
-  }
-  *cls = best;
-  return bp;
-}
-
-// The largest class logit of a box, the softmax's shift (class_argmax's loop).
-__device__ __forceinline__ float logit_max(const float* lg, int C) {
-  float m = lg[0];
-  for (int c = 1; c < C; ++c) m = lg[c] > m ? lg[c] : m;
-  return m;
-}
 
 // Multi-label score of a class from its logit: conf * p[c], one fp32 multiply, p[c] as class_argmax
 // computes it (m and sum: the box's logit_max and softmax_sum, unused in logistic mode).  The decode
@@ -224,20 +161,6 @@ __device__ __forceinline__ BoxAt box_at(const ScaleTab& t, int S, int k, int str
   return at;
 }
 
-// The boxes of one image in the workspace, PM_BOX_BYTES a box: nb x 4 corners, then a plane of nb
-// floats and a plane of nb ints.  Single-label kernels keep the score and the class there; the
-// multi-label ones the conf and, in softmax mode, the box's sum (sum()).
-struct BoxStore {
-  long long (*box)[4];
-  float* score;
-  int* cls;
-  __device__ __forceinline__ float* sum() const { return reinterpret_cast<float*>(cls); }
-};
-__device__ __forceinline__ BoxStore box_store(char* w, int nb) {
-  return {reinterpret_cast<long long (*)[4]>(w), reinterpret_cast<float*>(w + (size_t)nb * 32),
-          reinterpret_cast<int*>(w + (size_t)nb * 36)};
-}
-
 // decode_corners of the box at `at`, the corners stored as box k; a bad corner sets *bad (before
 // the stores, as these kernels always had it: after them the compiler splits the stores over the
 // two outcomes).
@@ -270,8 +193,8 @@ __device__ __forceinline__ void decode_single_at(const ScaleTab& t, const BoxAt&
   bs.cls[k] = *cls;
 }
 
-// The sort keys.  A score above score_thr >= 0 is positive, so larger float bits are a larger score
-// and ~bits sorts descending; every candidate's key stays below the padding ~0ull.
+// The sort keys beside key_any (post_dev.h: ~score (32) | index (32), the class-agnostic key and the
+// single-label merge's), with the same ~bits rule; every candidate's key stays below the padding ~0ull.
 constexpr int PC_CLS_BITS = 7;
 constexpr int PC_IDX_BITS = 14;  // postprocess_multi.hip: up to DNN_YOLO_MULTI_MAX_BOXES boxes
 constexpr int PW_IDX_BITS = 16;  // postprocess_wide.hip: up to DNN_YOLO_WIDE_MAX_BOXES
@@ -281,12 +204,6 @@ static_assert(DNN_YOLO_MULTI_MAX_BOXES <= (1 << PC_IDX_BITS) && DNN_YOLO_WIDE_MA
 static_assert(PC_CLS_BITS + 32 + PC_IDX_BITS < 64 && PC_CLS_BITS + 32 + PW_IDX_BITS < 64,
               "a candidate's key must stay below ~0ull");
 static_assert(PC_CLS_BITS + PC_IDX_BITS < 31 && PC_CLS_BITS + PW_IDX_BITS < 31, "a kept entry (index | class) is an int");
-
-// class-agnostic, and the single-label merge: ~score (32) | index (32)
-__device__ __forceinline__ unsigned long long key_any(float sc, int k) {
-  return ((unsigned long long)(~__float_as_uint(sc)) << 32) | (unsigned)k;
-}
-__device__ __forceinline__ int key_any_index(unsigned long long key) { return (int)(key & 0xffffffffu); }
 
 // class-major, what the per-class NMS sorts: class (7) | ~score (32) | index (IDX_BITS)
 template <int IDX_BITS>
@@ -314,89 +231,6 @@ __device__ __forceinline__ int key_merge_index(unsigned long long key) {
   return (int)(key >> PC_CLS_BITS) & ((1 << IDX_BITS) - 1);
 }
 __device__ __forceinline__ int key_merge_class(unsigned long long key) { return (int)key & ((1 << PC_CLS_BITS) - 1); }
-
-// The one place that writes a detection.
-__device__ __forceinline__ void emit_row(dnn_detection* row, int cls, float score, const long long* corners) {
-  dnn_detection d;
-  d.cls = cls;
-  d.score = score;
-  d.left = corners[0];
-  d.top = corners[1];
-  d.right = corners[2];
-  d.bottom = corners[3];
-  *row = d;
-}
-
-// Bitonic sort of keys[0 .. ns) (ns a power of two) by the whole workgroup, ascending.
-__device__ __forceinline__ void bitonic_sort(unsigned long long* keys, int ns, int tid) {
-  for (int kk = 2; kk <= ns; kk <<= 1) {
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < ns; i += PM_THREADS) {
-        const int ij = i ^ j;
-        if (ij > i) {
-          const unsigned long long a = keys[i], c = keys[ij];
-          if (((i & kk) == 0) == (a > c)) {
-            keys[i] = c;
-            keys[ij] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// Blocked greedy NMS of the n sorted candidates seg[0 .. n) by the whole workgroup (every thread
-// calls it; *n_kept == 0 on entry, published by a barrier).  The box index is the key's low
-// IDX_BITS bits.  The kept list (int box indices) is written in place over seg (see the top of
-// postprocess_multi.hip); *n_kept is its length after the closing barrier.
-template <int IDX_BITS>
-__device__ __forceinline__ void nms_workgroup(unsigned long long* seg, int n, const long long (*box)[4],
-                                              double iou_thr, unsigned long long* hitw, int* n_kept, int* zero_den,
-                                              int lane, int wid) {
-  int* kept = reinterpret_cast<int*>(seg);
-  for (int base = 0; base < n; base += 64) {
-    const int m = n - base < 64 ? n - base : 64;
-    const int nk = *n_kept;  // kept from earlier blocks: final
-    const bool live = lane < m;
-    const int mine = live ? (int)(seg[base + lane] & ((1ull << IDX_BITS) - 1ull)) : 0;
-    long long bi[4] = {0, 0, 0, 0};
-    if (live) {
-      bi[0] = box[mine][0];
-      bi[1] = box[mine][1];
-      bi[2] = box[mine][2];
-      bi[3] = box[mine][3];
-    }
-    bool hit = false, zd = false;
-    for (int j = wid; j < nk; j += PM_WAVES) {
-      const int kj = kept[j];  // wave-uniform
-      const long long bj[4] = {box[kj][0], box[kj][1], box[kj][2], box[kj][3]};
-      if (live && iou_gt(bi, bj, iou_thr, &zd)) hit = true;
-    }
-    const unsigned long long hw_ = __ballot(hit);
-    if (lane == 0) hitw[wid] = hw_;
-    if (__any(zd) && lane == 0) *zero_den = 1;
-    __syncthreads();  // every wave has read its keys of this block and the kept list
-    if (wid == 0) {
-      unsigned long long dropped = m < 64 ? ~((1ull << m) - 1ull) : 0ull;
-#pragma unroll
-      for (int wv = 0; wv < PM_WAVES; ++wv) dropped |= hitw[wv];
-      bool zt = false;
-      for (int i = 0; i < m; ++i) {
-        if ((dropped >> i) & 1ull) continue;  // wave-uniform: candidate i is kept
-        const int ki = __shfl(mine, i);       // (no key is read here: the list below overwrites them)
-        const long long bk[4] = {box[ki][0], box[ki][1], box[ki][2], box[ki][3]};
-        const bool h = live && lane > i && iou_gt(bi, bk, iou_thr, &zt);
-        dropped |= __ballot(h);
-      }
-      const unsigned long long keep = ~dropped;
-      if ((keep >> lane) & 1ull) kept[nk + __popcll(keep & ((1ull << lane) - 1ull))] = mine;
-      if (__any(zt) && lane == 0) *zero_den = 1;
-      if (lane == 0) *n_kept = nk + __popcll(keep);
-    }
-    __syncthreads();
-  }
-}
 
 // Candidates of one class above which the whole workgroup takes the segment.  A wave alone pays for
 // every kept box of its segment itself, so long chains are cheaper split over 16 waves even with
@@ -479,12 +313,9 @@ __device__ __forceinline__ int nms_wave(unsigned long long* seg, int len, const 
   return nk;
 }
 
-// ---- the NMS state of a kernel in LDS: declared __shared__ there, passed by reference ------------
-struct NmsState {  // class-agnostic
-  unsigned long long hitw[PM_WAVES];
-  int n_kept, zero_den;
-};
-struct ClassState : NmsState {  // per class
+// ---- the NMS state of a per-class kernel in LDS (NmsState with the class segments): declared
+// __shared__ there, passed by reference ------------------------------------------------------------
+struct ClassState : NmsState {
   int cls_cnt[DNN_YOLO_MAX_CLASSES];        // candidates per class
   int seg_start[DNN_YOLO_MAX_CLASSES + 1];  // their prefix sum: class c is keys[seg_start[c] .. seg_start[c+1])
   int seg_kept[DNN_YOLO_MAX_CLASSES];       // kept per class
@@ -493,12 +324,6 @@ struct ClassState : NmsState {  // per class
 };
 
 // By the whole workgroup; the caller's next barrier publishes it.
-__device__ __forceinline__ void reset_state(NmsState& st, int tid) {
-  if (tid == 0) {
-    st.n_kept = 0;
-    st.zero_den = 0;
-  }
-}
 __device__ __forceinline__ void reset_state(ClassState& st, int tid) {
   reset_state(static_cast<NmsState&>(st), tid);
   if (tid == 0) st.ticket = 0;
@@ -506,28 +331,6 @@ __device__ __forceinline__ void reset_state(ClassState& st, int tid) {
     st.cls_cnt[tid] = 0;
     st.seg_kept[tid] = 0;
   }
-}
-
-// Phases 2 and 3 of the class-agnostic rule, and the emit: sorts the n candidates of keys (key_any,
-// padded with ~0ull to pow2 >= n), runs nms_workgroup and writes the first max_det kept boxes to
-// rows and their number (-2: a zero IoU denominator) to *count.
-__device__ __forceinline__ void nms_any_emit(unsigned long long* keys, int n, const BoxStore& bs, double iou_thr,
-                                             NmsState& st, dnn_detection* rows, int max_det, int* count, int tid) {
-  int ns = 1;
-  while (ns < n) ns <<= 1;
-  bitonic_sort(keys, ns, tid);
-  nms_workgroup<32>(keys, n, bs.box, iou_thr, st.hitw, &st.n_kept, &st.zero_den, tid & 63, tid >> 6);
-  if (st.zero_den) {
-    if (tid == 0) *count = -2;
-    return;
-  }
-  const int* kept = reinterpret_cast<const int*>(keys);  // in place over the consumed keys
-  const int nk = st.n_kept, nw = nk < max_det ? nk : max_det;
-  for (int r = tid; r < nw; r += PM_THREADS) {
-    const int k = kept[r];
-    emit_row(rows + r, bs.cls[k], bs.score[k], bs.box[k]);
-  }
-  if (tid == 0) *count = nk;
 }
 
 // Phase 3 of the per-class rule on the class-major sorted keys (key_class<IDX_BITS>; st.seg_start
@@ -560,7 +363,7 @@ __device__ __forceinline__ int nms_segments(unsigned long long* keys, int C, con
     const int s0 = __builtin_amdgcn_readfirstlane(st.seg_start[c]);
     const int len = __builtin_amdgcn_readfirstlane(st.seg_start[c + 1]) - s0;
     if (len <= PC_BIG) continue;  // workgroup-uniform
-    nms_workgroup<IDX_BITS>(keys + s0, len, box, iou_thr, st.hitw, &st.n_kept, &st.zero_den, lane, wid);
+    nms_workgroup<IDX_BITS, PM_THREADS>(keys + s0, len, box, iou_thr, st.hitw, &st.n_kept, &st.zero_den, lane, wid);
     if (tid == 0) {
       st.seg_kept[c] = st.n_kept;
       st.n_kept = 0;
@@ -611,7 +414,7 @@ __device__ __forceinline__ void merge_single(unsigned long long* keys, const int
       keys[p] = ~0ull;
   }
   __syncthreads();
-  bitonic_sort(keys, ns2, tid);
+  bitonic_sort<PM_THREADS>(keys, ns2, tid);
   const int nw = nk < max_det ? nk : max_det;
   for (int r = tid; r < nw; r += PM_THREADS) {
     const int k = key_any_index(keys[r]);
@@ -657,7 +460,7 @@ __device__ __forceinline__ void merge_labels(unsigned long long* keys, const int
     if (p < nk) keys[p] = key;
   }
   __syncthreads();
-  bitonic_sort(keys, ns2, tid);
+  bitonic_sort<PM_THREADS>(keys, ns2, tid);
   const int nw = nk < max_det ? nk : max_det;
   for (int r = tid; r < nw; r += PM_THREADS) {
     const unsigned long long key = keys[r];

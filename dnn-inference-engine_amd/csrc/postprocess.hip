@@ -17,11 +17,16 @@
 //            box" (yolov2tiny.py:197-226).  IoU is the reference's integer formula (+1 widths,
 //            negative overlaps not clamped) in exact 64/128-bit integers, converted to double
 //            with correct rounding like Python's int -> float.
-#include <hip/hip_runtime.h>
-#include <cstdint>
-#include "dnn_common.h"
-#include "post_math.h"
-#include "../../include/dnn_hip_post.h"
+//
+// The key, the sort, the row emit and the anchor table are post_dev.h's (key_any, bitonic_sort,
+// emit_row, VOC_ANCHORS), shared with every other decode.  This kernel's own: the softmax over a
+// register array (20 classes fit; post_dev.h's class_argmax reads memory three times), the full
+// suppression bitmask (845 x 14 words fit in LDS), and its copy of decode_corners' arithmetic:
+// with the call the compiler schedules the whole decode loop of this kernel, the benchmark's,
+// differently, so the seven lines stay here, split around the class loop.
+//
+// This file also defines the host staging of the two single-scale host entries.
+#include "post_dev.h"
 
 namespace dnnhip {
 
@@ -29,8 +34,6 @@ constexpr int PP_THREADS = 512;
 constexpr int PP_WAVES = PP_THREADS / 64;
 constexpr int PP_WORDS = (DNN_YOLO_BOXES + 63) / 64;  // 14 keep / suppression words
 constexpr int PP_SORT = 1024;  // >= DNN_YOLO_BOXES, power of two
-
-__constant__ float kAnchorsF32[10] = {1.08f, 1.19f, 3.42f, 4.41f, 6.63f, 11.38f, 9.42f, 5.11f, 16.62f, 10.52f};
 
 // numpy's float32 add.reduce of a contiguous 20-vector: 8 partial sums over the first 16,
 // combined pairwise, then the 4 tail elements in order
@@ -68,10 +71,11 @@ yolo_postprocess_kernel(const float* __restrict__ pred, dnn_detection* __restric
   for (int k = tid; k < DNN_YOLO_BOXES; k += PP_THREADS) {
     const float* q = p + k * 25;
     const int b = k % 5, cell = k / 5, col = cell % 13, row = cell / 13;
+    // (decode_corners' arithmetic, kept as this kernel's own copy around the class loop: see above)
     const float cx = ((float)col + sigmoid_ref(q[0])) * 32.0f;
     const float cy = ((float)row + sigmoid_ref(q[1])) * 32.0f;
-    const float rw = (np_expf(q[2]) * kAnchorsF32[2 * b]) * 32.0f;
-    const float rh = (np_expf(q[3]) * kAnchorsF32[2 * b + 1]) * 32.0f;
+    const float rw = (np_expf(q[2]) * VOC_ANCHORS[2 * b]) * 32.0f;
+    const float rh = (np_expf(q[3]) * VOC_ANCHORS[2 * b + 1]) * 32.0f;
     const float conf = sigmoid_ref(q[4]);
     float m = q[5];
 #pragma unroll
@@ -104,8 +108,7 @@ yolo_postprocess_kernel(const float* __restrict__ pred, dnn_detection* __restric
     cls_of[k] = best;
     if (sc > 0.3f) {  // float32 comparison, as numpy compares a float32 with a Python float
       const int pos = atomicAdd(&n_cand, 1);
-      // positive scores: larger float bits = larger score; ~bits sorts descending
-      keys[pos] = ((unsigned long long)(~__float_as_uint(sc)) << 32) | (unsigned)k;
+      keys[pos] = key_any(sc, k);
     }
   }
   __syncthreads();
@@ -118,33 +121,19 @@ yolo_postprocess_kernel(const float* __restrict__ pred, dnn_detection* __restric
   // ---- phase 2: bitonic sort of the first pow2 >= n keys (yolov2tiny.py:146)
   int ns = 1;
   while (ns < n) ns <<= 1;
-  for (int kk = 2; kk <= ns; kk <<= 1) {
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < ns; i += PP_THREADS) {
-        const int ij = i ^ j;
-        if (ij > i) {
-          const unsigned long long a = keys[i], c = keys[ij];
-          if (((i & kk) == 0) == (a > c)) {
-            keys[i] = c;
-            keys[ij] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  bitonic_sort<PP_THREADS>(keys, ns, tid);
 
   // ---- phase 3a: suppression bitmask, all waves (yolov2tiny.py:197-216 evaluates every pair
   // (candidate i, kept j < i); here every pair j < i, the keep mask selects below)
   const int lane = tid & 63, wid = tid >> 6;
   for (int i = wid; i < n; i += PP_WAVES) {
-    const int ki = (int)(keys[i] & 0xffffffffu);
+    const int ki = key_any_index(keys[i]);
     const long long bi[4] = {box[ki][0], box[ki][1], box[ki][2], box[ki][3]};
     bool zany = false;
     for (int w = 0; w * 64 < i; ++w) {
       const int j = w * 64 + lane;
       bool hit = false;
-      if (j < i) hit = iou_gt(bi, box[(int)(keys[j] & 0xffffffffu)], 0.3, &zany);
+      if (j < i) hit = iou_gt(bi, box[key_any_index(keys[j])], 0.3, &zany);
       const unsigned long long m = __ballot(hit);
       if (lane == 0) sup[i][w] = m;
     }
@@ -162,11 +151,11 @@ yolo_postprocess_kernel(const float* __restrict__ pred, dnn_detection* __restric
       const unsigned long long row = lane < nwi ? sup[i][lane] : 0ull;
       const bool drop = __any((row & kw) != 0ull);
       if (zrow[i]) {  // rare: a zero IoU denominator against a KEPT box raises in the reference
-        const int ki = (int)(keys[i] & 0xffffffffu);
+        const int ki = key_any_index(keys[i]);
         bool zd = false;
         for (unsigned long long bits = lane < nwi ? kw : 0ull; bits; bits &= bits - 1) {
           const int j = lane * 64 + __builtin_ctzll(bits);
-          (void)iou_gt(box[ki], box[(int)(keys[j] & 0xffffffffu)], 0.3, &zd);
+          (void)iou_gt(box[ki], box[key_any_index(keys[j])], 0.3, &zd);
         }
         zero_hit |= zd;
       }
@@ -189,15 +178,8 @@ yolo_postprocess_kernel(const float* __restrict__ pred, dnn_detection* __restric
     for (unsigned long long bits = kw; bits; bits &= bits - 1, ++r) {
       const int i = lane * 64 + __builtin_ctzll(bits);
       if (r >= max_det) break;
-      const int k = (int)(keys[i] & 0xffffffffu);
-      dnn_detection d;
-      d.cls = cls_of[k];
-      d.score = score_of[k];
-      d.left = box[k][0];
-      d.top = box[k][1];
-      d.right = box[k][2];
-      d.bottom = box[k][3];
-      dets[(size_t)img * max_det + r] = d;
+      const int k = key_any_index(keys[i]);
+      emit_row(dets + (size_t)img * max_det + r, cls_of[k], score_of[k], box[k]);
     }
     if (lane == 0) counts[img] = nk;
   }
@@ -271,6 +253,31 @@ int launch_yolo_postprocess(const float* pred, int n_images, dnn_detection* dets
   return 0;
 }
 
+int yolo_single_host(const SingleCall& c, const float* pred, size_t pred_bytes, dnn_detection* dets, size_t det_bytes,
+                     int* counts, size_t count_bytes, SingleLaunch launch) {
+  const size_t pb = (pred_bytes + 7) & ~(size_t)7;  // keeps dets and the workspace 8-byte aligned
+  const size_t cb = (count_bytes + 7) & ~(size_t)7;
+  char* buf = nullptr;
+  DNN_HIP_TRY(hipMalloc(&buf, pb + det_bytes + cb + c.ws_bytes));
+  dnn_detection* d_dets = reinterpret_cast<dnn_detection*>(buf + pb);
+  int* d_counts = reinterpret_cast<int*>(buf + pb + det_bytes);
+  int rc = 0;
+  if (hipMemcpy(buf, pred, pred_bytes, hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("%s: copy in failed", c.who);
+    rc = -1;
+  }
+  if (!rc)
+    rc = launch(c, reinterpret_cast<const float*>(buf), d_dets, d_counts,
+                c.ws_bytes ? buf + pb + det_bytes + cb : nullptr);
+  if (!rc && (hipMemcpy(counts, d_counts, count_bytes, hipMemcpyDeviceToHost) != hipSuccess ||
+              (det_bytes && hipMemcpy(dets, d_dets, det_bytes, hipMemcpyDeviceToHost) != hipSuccess))) {
+    set_error("%s: copy out failed", c.who);
+    rc = -1;
+  }
+  (void)hipFree(buf);
+  return rc;
+}
+
 }  // namespace dnnhip
 
 extern "C" {
@@ -289,26 +296,13 @@ int dnn_yolo_postprocess_host(const float* pred, int n_images, dnn_detection* de
   DNN_REQUIRE(n_images >= 0 && max_det >= 0, "dnn_yolo_postprocess_host: bad arguments");
   if (n_images == 0) return 0;
   DNN_REQUIRE(pred && counts && (max_det == 0 || dets), "dnn_yolo_postprocess_host: NULL pointer");
-  const size_t pb = (size_t)n_images * DNN_YOLO_BOXES * 25 * sizeof(float);
-  const size_t db = (size_t)n_images * max_det * sizeof(dnn_detection), cb = (size_t)n_images * sizeof(int);
-  char* buf = nullptr;
-  DNN_HIP_TRY(hipMalloc(&buf, pb + db + cb));
-  float* d_pred = reinterpret_cast<float*>(buf);
-  dnn_detection* d_dets = reinterpret_cast<dnn_detection*>(buf + pb);
-  int* d_counts = reinterpret_cast<int*>(buf + pb + db);
-  int rc = 0;
-  if (hipMemcpy(d_pred, pred, pb, hipMemcpyHostToDevice) != hipSuccess) {
-    dnnhip::set_error("dnn_yolo_postprocess_host: copy in failed");
-    rc = -1;
-  }
-  if (!rc) rc = dnnhip::launch_yolo_postprocess(d_pred, n_images, d_dets, max_det, d_counts, nullptr);
-  if (!rc && (hipMemcpy(counts, d_counts, cb, hipMemcpyDeviceToHost) != hipSuccess ||
-              (db && hipMemcpy(dets, d_dets, db, hipMemcpyDeviceToHost) != hipSuccess))) {
-    dnnhip::set_error("dnn_yolo_postprocess_host: copy out failed");
-    rc = -1;
-  }
-  (void)hipFree(buf);
-  return rc;
+  return dnnhip::yolo_single_host(
+      {"dnn_yolo_postprocess_host", nullptr, n_images, max_det, 0}, pred,
+      (size_t)n_images * DNN_YOLO_BOXES * 25 * sizeof(float), dets, (size_t)n_images * max_det * sizeof(dnn_detection),
+      counts, (size_t)n_images * sizeof(int),
+      [](const dnnhip::SingleCall& c, const float* d_pred, dnn_detection* d_dets, int* d_counts, void*) {
+        return dnnhip::launch_yolo_postprocess(d_pred, c.n_images, d_dets, c.max_det, d_counts, nullptr);
+      });
 }
 
 }  // extern "C"

@@ -72,7 +72,7 @@ yolo_multi_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pre
   }
 
   // ---- phases 2 and 3, the kept list in place over keys[0 .. base); emit
-  nms_any_emit(keys, n_cand, bs, mh.scale[0].iou_thr, st, dets + (size_t)img * max_det, max_det, &counts[img], tid);
+  nms_any_emit<PM_THREADS>(keys, n_cand, bs, mh.scale[0].iou_thr, st, dets + (size_t)img * max_det, max_det, &counts[img], tid);
 }
 
 // ---- per-class NMS (DNN_YOLO_NMS_PER_CLASS) ----------------------------------------------------
@@ -140,7 +140,7 @@ yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const XyScale xy, const Mul
   // ---- phase 2: bitonic sort of the first pow2 >= n keys: class-major
   int ns = 1;
   while (ns < n) ns <<= 1;
-  bitonic_sort(keys, ns, tid);
+  bitonic_sort<PM_THREADS>(keys, ns, tid);
   __syncthreads();  // seg_start too (the sort has no barrier when n <= 1)
 
   // ---- phase 3: every class segment alone; phase 4: merge the kept lists by (score, global index)
@@ -264,7 +264,7 @@ yolo_multi_labels_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiP
   while (ns < n) ns <<= 1;
   for (int i = n + tid; i < ns; i += PM_THREADS) keys[i] = ~0ull;
   __syncthreads();  // the padding and seg_start (the sort has no barrier when n <= 1)
-  bitonic_sort(keys, ns, tid);
+  bitonic_sort<PM_THREADS>(keys, ns, tid);
 
   // ---- phase 3: every class segment alone; phase 4: merge by (score, global index, class)
   const int nk = nms_segments<PC_IDX_BITS>(keys, C, bs.box, mh.scale[0].iou_thr, st, tid);

@@ -230,12 +230,12 @@ yolo_wide_nms_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detectio
   __syncthreads();
 
   if constexpr (MODE == PW_ANY) {
-    nms_any_emit(keys, n, bs, iou_thr, st, rows, max_det, &counts[img], tid);
+    nms_any_emit<PM_THREADS>(keys, n, bs, iou_thr, st, rows, max_det, &counts[img], tid);
   } else {
     if (wid == 0) wave_scan_128(st.cls_cnt, C, st.seg_start, lane);
 
     // ---- phase 2: class-major bitonic sort
-    bitonic_sort(keys, ns, tid);
+    bitonic_sort<PM_THREADS>(keys, ns, tid);
     __syncthreads();  // seg_start too (the sort has no barrier when n <= 1)
 
     // ---- phase 3: every class segment alone; phase 4: merge by (score, global index[, class])

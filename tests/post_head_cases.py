@@ -20,6 +20,13 @@ CAP        the largest head the library takes, 1 x 1024 cells x 8 anchors x 1 cl
            oracle needs 11 s for it, so its rows are recorded in
            tests/golden/post_cap8192_golden.json (`python tests/post_head_cases.py` rewrites
            the file from the oracle) instead of being computed in the test.
+DENSE      every candidate kept, the tightest case for a kept list written in place over its own
+           keys (it grows by 64 for every 64 keys consumed; saturated inputs suppress most boxes
+           and never reach this): 1 x n cells for n around the 64-candidate block, one anchor
+           (0.25, 0.25), two classes, tx = ty = tw = th = 0, class logits (6, 0), objectness a
+           seeded permutation of linspace(2, 8, n).  The boxes are 8 pixels wide in 32-pixel
+           cells of one row: disjoint horizontally, overlapping vertically, so no IoU denominator
+           is zero and no pair exceeds the threshold.
 """
 import functools
 import json
@@ -59,6 +66,13 @@ SATURATED = {
 CAP = (((1, 1024), ANCHORS8, 1), 302, 0.5)  # head parameters, seed, scale of the box-size logits
 CAP_GOLDEN = os.path.join(GOLDEN, "post_cap8192_golden.json")
 
+DENSE = (63, 64, 65, 128, 129)  # n: one block short by one, one block, one over, two, two and one
+DENSE_SEED = 401
+
+
+def dense_spec(n):
+    return ((1, n), (0.25, 0.25), 2)
+
 
 def oracle_head(spec, score_thr=0.3, iou_thr=0.3):
     (gh, gw), anchors, classes = spec
@@ -94,6 +108,17 @@ def saturated(name):
     except ZeroDivisionError:
         rows = -2
     return pred, rows, stats.get("candidates")
+
+
+@functools.lru_cache(maxsize=None)
+def dense(n):
+    """(pred [1, n, 7], the oracle's rows or its negative code)."""
+    head = oracle_head(dense_spec(n))
+    pred = np.zeros((1, n, 7), np.float32)
+    pred[0, :, 4] = np.random.default_rng(DENSE_SEED + n).permutation(np.linspace(2.0, 8.0, n)).astype(np.float32)
+    pred[0, :, 5] = 6.0
+    pred.setflags(write=False)
+    return pred, O.detect_or_code(pred, head)
 
 
 def cap8192(compute=False):

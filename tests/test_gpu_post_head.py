@@ -79,6 +79,24 @@ def test_head_saturated_at_the_box_cap():
     K.same_rows(yolo_post.detect_batch(pred, head=head, raise_errors=False)[0], ref, "cap8192")
 
 
+@pytest.mark.parametrize("n", K.DENSE)
+def test_head_dense_every_candidate_kept(n):
+    """The kept list in place over the consumed keys, growing by 64 for every 64 keys: the rows equal
+    the oracle's (all n candidates), and two launches are byte-equal."""
+    pred, ref = K.dense(n)
+    head = K.device_head(K.dense_spec(n))
+    assert head.boxes == n and len(ref) == n
+    K.same_rows(yolo_post.detect_batch(pred, head=head, raise_errors=False)[0], ref, f"dense {n}")
+    out = []
+    for _ in range(2):
+        dets = np.zeros((1, n), yolo_post.DETECTION_DTYPE)
+        counts = np.zeros(1, np.int32)
+        assert dnn_hip.mylib.dnn_yolo_postprocess_head_host(ctypes.byref(head.c), pred.ctypes.data, 1, dets.ctypes.data,
+                                                            n, counts.ctypes.data) == 0, dnn_hip.last_error()
+        out.append((dets.tobytes(), int(counts[0])))
+    assert out[0] == out[1] and out[0][1] == n
+
+
 # ------------------------------------------------------------------ 4. old entry == new entry
 def _raw(preds, head=None):
     p = np.ascontiguousarray(preds, np.float32)

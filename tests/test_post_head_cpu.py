@@ -77,6 +77,17 @@ def test_saturated_19x19_cases(name):
         assert cand == 1805 and 100 < len(rows) < 400
 
 
+@pytest.mark.parametrize("n", K.DENSE)
+def test_dense_cases_keep_every_candidate(n):
+    """n rows with n distinct scores and no error code: what makes the kept list grow as fast as the
+    keys are consumed."""
+    pred, rows = K.dense(n)
+    assert pred.shape == (1, n, 7)
+    assert not isinstance(rows, int), rows
+    assert len(rows) == n
+    assert len({r[5] for r in rows}) == n
+
+
 def test_yolo_head_properties_and_validation():
     h = yolo_post.YoloHead.for_input(608, 608)
     assert (h.grid_h, h.grid_w, h.boxes, h.pred_shape, h.n_out) == (19, 19, 1805, (19, 19, 125), 125)
