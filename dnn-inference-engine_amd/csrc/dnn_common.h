@@ -252,7 +252,19 @@ int launch_pack_weights_x3(const float* w, unsigned short* out, int K, int N, in
 int x3_splits(int N, int K);  // split-K of an x3 batch-plan layer: a function of (N, K) only
 int launch_conv_x3(const unsigned short* in_split, const unsigned short* Bt, float* out, unsigned short* out_split,
                    long long M, int N, int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream,
-                   int splits = 1, int pool = 0, bool lat = false);  // lat: latency-plan tile shapes allowed
+                   int splits = 1, int pool = 0, bool lat = false,  // lat: latency-plan tile shapes allowed
+                   int out_h2 = 0, unsigned* range_flag = nullptr);  // out_h2: `out_split` as h2 planes (below)
+// The wide x3 conv on two fp16 pieces per operand, three MFMA products per fp32 product
+// (gemm_x3_h2.h): activations [B][H+2][W+2][C/32][2][32] fp16 (g0, g1 of split2h), weights packed
+// by launch_pack_weights_h2.  Its producers (itself, the wide x3 kernel's unpooled form, the
+// whole-image kernel) write those planes with out_h2 and raise *range_flag where a value does not
+// fit fp16 (|v| >= 65520 or non-finite).
+bool conv_x3_h2_supported(int C, int OC, int H, int W);
+size_t x3_h2_act_bytes(long long nimg, int H, int W, int C);
+int launch_pack_weights_h2(const float* w, unsigned short* out, int K, int N, int Npad, int C, hipStream_t s);
+int launch_conv_x3_h2(const unsigned short* in_h2, const unsigned short* Bt, float* out, unsigned short* out_split,
+                      int out_h2, long long M, int N, int Npad, int K, int H, int W, int C, const EpiParams& epi,
+                      hipStream_t stream, unsigned* range_flag);
 bool conv_x3_pool_supported(int OC, int C, int H, int W);  // an x3 conv of this size can fuse a 2x2/s2 pool
 // x3 workgroups of a layer (batch-1 latency plans take x3 only where they fill half the chip)
 long long x3_tiles(long long batch, int OH, int OW, int OC, int C, int K);
@@ -273,7 +285,8 @@ int launch_conv_x3_ktile(const unsigned short* in_split, const unsigned short* B
 // pool5), one image x 128 columns per workgroup over the whole K, split planes out
 bool conv_x3_img_supported(int C, int OC, int H, int W);
 int launch_conv_x3_img(const unsigned short* in_split, const unsigned short* Bt, float* out, unsigned short* out_split,
-                       int n, int N, int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream);
+                       int n, int N, int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream,
+                       int out_h2 = 0, unsigned* range_flag = nullptr);
 bool conv_x3_lat_supported(long long batch, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh,
                            int sw, int pt, int pl);
 int x3_lat_splits(int N, int K);

@@ -106,6 +106,36 @@ __device__ __forceinline__ void split3_pack2(bool fast, float a, float b, unsign
   }
 }
 
+// Two-piece fp16 split of fp32 (the "h2" form of the wide x3 conv, gemm_x3_h2.h): g0 = rn16(x),
+// g1 = rn16((x - g0) * 2048), both round-to-nearest-even; x - float(g0) is exact in fp32 (g0 holds
+// x's top 11 significand bits) and the scaling by 2^11 is exact, so |g0 + g1 / 2048 - x| <=
+// 2^-23 |x| for 2^-12 <= |x| < 65504 (g1's own rounding: 2^-11 of a residual <= 2^-12 |x|) and <=
+// 2^-36 absolutely below that, where g0 is a subnormal half (quantum 2^-24) and g1 carries the
+// residual on the same quantum.  Range: h2_split_ok(x) is |x| < 65520, the fp16 rounding
+// threshold (false for NaN); outside it the top piece is rn16's +-inf (or NaN) and the second
+// piece zero, so a consumer's output is non-finite as it would be for an fp32 infinity, never a
+// wrong finite number.
+typedef _Float16 h2_h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ bool h2_split_ok(float x) { return __builtin_fabsf(x) < 65520.f; }  // false for NaN
+__device__ __forceinline__ void split2h(float x, unsigned short& g0, unsigned short& g1) {
+  const _Float16 h = (_Float16)x;
+  g0 = __builtin_bit_cast(unsigned short, h);
+  const float r = h2_split_ok(x) ? (x - (float)h) * 2048.f : 0.f;
+  g1 = __builtin_bit_cast(unsigned short, (_Float16)r);
+}
+// split2h of two values at once, packed (value a in the low half of each word).  `fast`
+// (wave-uniform): every value of the wave passed h2_split_ok, so the range selects are dropped.
+__device__ __forceinline__ void split2h_pack2(bool fast, float a, float b, unsigned& p0, unsigned& p1) {
+  const h2_h2 t = __builtin_convertvector((x3_f2){a, b}, h2_h2);
+  p0 = __builtin_bit_cast(unsigned, t);
+  float ra = (a - (float)t[0]) * 2048.f, rb = (b - (float)t[1]) * 2048.f;
+  if (!fast) {
+    ra = h2_split_ok(a) ? ra : 0.f;
+    rb = h2_split_ok(b) ? rb : 0.f;
+  }
+  p1 = __builtin_bit_cast(unsigned, __builtin_convertvector((x3_f2){ra, rb}, h2_h2));
+}
+
 __device__ __forceinline__ float apply_epilogue(float v, float bias, float mean, float sq, float gamma,
                                                 int flags) {
   if (flags & EPI_BIAS) v = v + bias;

@@ -82,7 +82,7 @@ template <int BM, int NPR, bool POOL, int FL = -1>
 __global__ void __launch_bounds__(512, 2)
 conv3x3_x3_acc2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __restrict__ Bt, float* __restrict__ out,
                        bf16_bits* __restrict__ out_split, int M, int N, int K, EpiParams epi, int tilesM, X3Geom g,
-                       unsigned in_bytes, unsigned b_bytes) {
+                       unsigned in_bytes, unsigned b_bytes, unsigned* __restrict__ range_flag) {
   constexpr int BN = 256, TM = BM / 16, RB = 192, NJ = 2, NW = 8, LP = 224;
   constexpr int NQW = (NPR * LP + NW * 1024 - 1) / (NW * 1024);  // 1-KiB DMA pieces per wave per patch
   constexpr int BUFB = NQW * NW * 1024;                            // one patch buffer (>= NPR LP)
@@ -348,14 +348,15 @@ conv3x3_x3_acc2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __rest
   }
   if (threadIdx.x < BM) {
     const int m = m0 + threadIdx.x;
-    orow[threadIdx.x] = m >= M ? -1 : (g.out_mode == 1 ? padded(m) : m);
+    orow[threadIdx.x] = m >= M ? -1 : (g.out_mode == 1 || g.out_mode == 3 ? padded(m) : m);
   }
   __syncthreads();
   // Each row block's 16 x 32 outputs of the wave pass through a wave-private LDS stage (fp32 rows
   // of 36: the MFMA-layout writes are conflict-free) and leave as 16-B stores: lane l takes row
   // l / 4, columns 8 (l % 4) .. + 7 -- 2 stores of fp32, or 3 of split planes (one per piece), per
   // row block where the MFMA layout stored one scalar per output (3 per output as split planes).
-  // Same epilogue arithmetic and split per value as before.
+  // Same epilogue arithmetic and split per value as before.  out_mode 3: the two fp16 pieces of a
+  // following h2 layer (h2_store8), 2 stores.
   static_assert(BM * 4 <= 1024, "row table below the stages");
   float* const stg = reinterpret_cast<float*>(smem + 1024) + wid * (16 * 36);
   float pb[NJ], pm[NJ], ps[NJ], pg[NJ];
@@ -404,6 +405,9 @@ conv3x3_x3_acc2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __rest
         const size_t d = (size_t)o * (3 * N) + (n0 >> 5) * 96 + c8;  // (halves)
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) store16_at(out_split, 2 * (d + 32 * pc), q[pc]);
+      } else if (g.out_mode == 3) {
+        const float v8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        h2_store8(v8, out_split, (size_t)o * (4 * (size_t)N) + (n0 >> 5) * 128 + 2 * c8, range_flag);
       } else {
         const size_t d = ((size_t)(g.out_mode == 2 ? split * M : 0) + o) * N + n0 + c8;  // (floats)
         store16_at(out, 4 * d, __builtin_bit_cast(u32x4, lo));

@@ -21,7 +21,8 @@
 // Epilogue: the folded sums into an LDS stage [H W][128 + 4], then per (pixel, 8 columns): the
 // window max (min for a decreasing channel, pool_then_epilogue), the epilogue with one
 // wave-uniform division check, the exact split and three 16-B stores of the next layer's planes
-// (or two fp32 16-B stores when the layer is the plan's last).
+// (or two fp32 16-B stores when the layer is the plan's last; `out_h2`: the two fp16 pieces of a
+// following h2 layer, two 16-B stores, h2_store8).
 #pragma once
 #include "gemm_x3_acc2.h"
 
@@ -42,7 +43,7 @@ template <int H, int W, int FL = -1>
 __global__ void __launch_bounds__(512, 1)
 conv3x3_x3_img_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __restrict__ Bt, float* __restrict__ out,
                       bf16_bits* __restrict__ out_split, int N, int K, EpiParams epi, int C, unsigned in_bytes,
-                      unsigned b_bytes) {
+                      unsigned b_bytes, int out_h2, unsigned* __restrict__ range_flag) {
   constexpr int NW = 8, LP = 224, PU = LP / 16, WP = W + 2, PR = (H + 2) * WP, HW = H * W, TM = (HW + 15) / 16, SR = 132;
   // LDS: padded image row y at unit RU y, pixel x of it at + PU x (the SK units after an image
   // row's pixels are never read): tools/lds_conflict_model.py, 13-wide images, 16 consecutive
@@ -212,6 +213,11 @@ conv3x3_x3_img_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __restr
       const size_t d = ((size_t)b * HW + pix) * N + n;  // (floats)
       store16_at(out, 4 * d, __builtin_bit_cast(u32x4, f32x4{o[0], o[1], o[2], o[3]}));
       store16_at(out, 4 * d + 16, __builtin_bit_cast(u32x4, f32x4{o[4], o[5], o[6], o[7]}));
+      continue;
+    }
+    if (out_h2) {  // the two fp16 pieces of a following h2 layer (gemm_x3_h2.h)
+      h2_store8(o, out_split, ((size_t)b * PR + (y + 1) * WP + x + 1) * (4 * (size_t)N) + (n >> 5) * 128 + 2 * (n & 31),
+                range_flag);
       continue;
     }
     bool ok = true;

@@ -86,7 +86,8 @@ struct X3Geom {
   int H, W, C;     // conv input = output spatial size (3x3, stride 1, SAME), channels
   int out_mode;    // 0: fp32 [M][N] after the epilogue; 1: split planes into a zero-bordered
                    // [B][H+2][W+2] buffer (next x3 layer); 2: raw fp32 partial of split-K slice
-                   // s at out + s*M*N (no epilogue; x3_combine_kernel finishes)
+                   // s at out + s*M*N (no epilogue; x3_combine_kernel finishes); 3: as 1 in the
+                   // two-piece fp16 format of a following h2 layer (gemm_x3_h2.h)
   int splits;      // K split into this many contiguous chunk ranges (grid = tiles x splits)
   int PH, PW;      // POOL kernels: the 2x2/s2 pooled output (rows are pool-window-major)
 };
@@ -129,6 +130,30 @@ __device__ __forceinline__ void x3_fold(f32x4 (&acc)[TM][NB], const f32x4 (&accc
     for (int j = 0; j < NB; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[i][j][r] = acc[i][j][r] + accc[i][j][r];
+}
+
+// Eight consecutive channels of one pixel into the two-piece fp16 planes of an h2 layer's input
+// (per pixel and 32-channel chunk: 64 B of g0, then 64 B of g1; gemm_x3_h2.h): split2h of each
+// value and one 16-B store per piece at `off` (bytes: the g0 slot of the first channel).  A wave
+// that holds a value outside fp16's range (h2_split_ok) takes the slow form, whose top pieces are
+// +-inf / NaN, and raises the plan's sticky range word with a plain store of 1.
+__device__ __forceinline__ void h2_store8(const float (&v)[8], bf16_bits* __restrict__ out_split, size_t off,
+                                          unsigned* __restrict__ range_flag) {
+  bool ok = true;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) ok = ok && h2_split_ok(v[e]);
+  const bool fast = __builtin_amdgcn_ballot_w64(!ok) == 0;  // (over the active lanes: uniform among them)
+  u32x4 q0, q1;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    unsigned w0, w1;
+    split2h_pack2(fast, v[2 * e], v[2 * e + 1], w0, w1);
+    q0[e] = w0;
+    q1[e] = w1;
+  }
+  if (!fast && range_flag != nullptr) *range_flag = 1u;
+  store16_at(out_split, off, q0);
+  store16_at(out_split, off + 64, q1);
 }
 
 // One output column's epilogue parameters (bias, mean, sqrt(var + eps), gamma; absent terms the

@@ -8,6 +8,7 @@
 #include "gemm_x3_1x1.h"
 #include "gemm_x3_ktile.h"
 #include "gemm_x3_img.h"
+#include "gemm_x3_h2.h"
 
 #include <cfloat>
 #include <cstdlib>
@@ -338,6 +339,38 @@ int launch_pack_weights_x3(const float* w, bf16_bits* out, int K, int N, int Npa
   return check_x3("pack_weights_x3");
 }
 
+// h2 layers (gemm_x3_h2.h): the two fp16 pieces of split2h, [n/16][step][piece(2)][lane][8], the
+// step order of pack_weights_x3_kernel (3x3 only)
+__global__ void pack_weights_h2_kernel(const float* __restrict__ w, bf16_bits* __restrict__ out, int K, int N, int Npad,
+                                       int C) {
+  const int nk = K / 32;
+  const long long total = (long long)(Npad / 16) * nk * 2 * 512;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int e = (int)(i & 7), lane = (int)((i >> 3) & 63);
+    const long long q = i >> 9;
+    const int p = (int)(q & 1);
+    const long long r = q >> 1;
+    const int s = (int)(r % nk), nb = (int)(r / nk);
+    const int n = nb * 16 + (lane & 15);
+    const int chunk = s / 9, tap = s - chunk * 9, c = chunk * 32 + 8 * (lane >> 4) + e;
+    const float v = n < N ? w[((size_t)tap * C + c) * N + n] : 0.f;
+    unsigned short g0, g1;
+    split2h(v, g0, g1);
+    out[i] = p == 0 ? g0 : g1;
+  }
+}
+
+int launch_pack_weights_h2(const float* w, bf16_bits* out, int K, int N, int Npad, int C, hipStream_t s) {
+  if (K != 9 * C || C % 32 != 0 || Npad % 256 != 0 || Npad < N) {
+    set_error("pack_weights_h2: unsupported K=%d N=%d Npad=%d C=%d", K, N, Npad, C);
+    return -2;
+  }
+  const long long total = (long long)(Npad / 16) * (K / 32) * 2 * 512;
+  hipLaunchKernelGGL(pack_weights_h2_kernel, dim3(grid_x3(total)), dim3(256), 0, s, w, out, K, N, Npad, C);
+  return check_x3("pack_weights_h2");
+}
+
 // ---- the conv
 constexpr int X3_BM = 176, X3_NPR = 320;
 
@@ -421,6 +454,8 @@ long long x3_tiles(long long batch, int OH, int OW, int OC, int C, int K) {
 }
 
 size_t x3_act_bytes(long long nimg, int H, int W, int C) { return (size_t)nimg * (H + 2) * (W + 2) * C * 6; }
+// ... of an h2 layer's input: two fp16 pieces, 4 B per element
+size_t x3_h2_act_bytes(long long nimg, int H, int W, int C) { return (size_t)nimg * (H + 2) * (W + 2) * C * 4; }
 
 // N = 512 (conv5): 62 x 2 = 124 tiles of 176 x 256 at batch 64, half the chip -> 2 K slices;
 // wider layers fill it alone, narrower ones (N = 256: 246 tiles) too
@@ -429,8 +464,12 @@ int x3_splits(int N, int K) { return (N % 256 == 0 && N > 256 && N <= 512 && (K 
 
 int launch_conv_x3(const bf16_bits* in_split, const bf16_bits* Bt, float* out, bf16_bits* out_split, long long M,
                    int N, int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream, int splits,
-                   int pool, bool lat) {
+                   int pool, bool lat, int out_h2, unsigned* range_flag) {
   if (M == 0 || N == 0) return 0;
+  if (out_h2 && (x3_kind(N, C) != 0 || pool || splits != 1 || !out_split)) {  // (the wide kernel's unpooled form only)
+    set_error("conv_x3: h2 planes from an unsupported form (N=%d C=%d pool=%d splits=%d)", N, C, pool, splits);
+    return -2;
+  }
   // pool: M counts GEMM rows, 4 per pooled pixel
   const int PH = pool ? (H + 1) / 2 : 0, PW = pool ? (W + 1) / 2 : 0;
   const long long per_img = pool ? 4LL * PH * PW : (long long)H * W;
@@ -597,11 +636,11 @@ int launch_conv_x3(const bf16_bits* in_split, const bf16_bits* Bt, float* out, b
   }
   const int tilesM = (int)((M + X3_BM - 1) / X3_BM), tilesN = N / 256;
   // splits > 1: `out` receives the raw partials [splits][M][N] (x3_combine_kernel finishes).
-  const X3Geom xg{H, W, C, splits > 1 ? 2 : out_split ? 1 : 0, splits, PH, PW};
+  const X3Geom xg{H, W, C, splits > 1 ? 2 : out_split ? (out_h2 ? 3 : 1) : 0, splits, PH, PW};
   const dim3 grid(tilesM * tilesN * (pool ? 1 : splits));
 #define X3AF(NPR_, POOL_, FL_)                                                                                    \
   hipLaunchKernelGGL((conv3x3_x3_acc2_kernel<X3_BM, NPR_, POOL_, FL_>), grid, dim3(512), 0, stream, in_split, Bt, \
-                     out, out_split, (int)M, N, K, epi, tilesM, xg, (unsigned)in_bytes, (unsigned)b_bytes)
+                     out, out_split, (int)M, N, K, epi, tilesM, xg, (unsigned)in_bytes, (unsigned)b_bytes, range_flag)
   if (epi.flags == X3_YOLO_FL && xg.out_mode != 2) {  // YOLO's set compiled in
     if (pool)
       X3AF(X3_NPR_POOL, true, X3_YOLO_FL);
@@ -615,6 +654,42 @@ int launch_conv_x3(const bf16_bits* in_split, const bf16_bits* Bt, float* out, b
   }
 #undef X3AF
   return check_x3("conv_x3");
+}
+
+// ---- the wide conv on two fp16 pieces (gemm_x3_h2.h): the wide kernel's tiles, h2 planes in
+// (x3_h2_act_bytes), weights from launch_pack_weights_h2; out_h2: `out_split` takes h2 planes too
+// Shape only: the skewed LDS rows of a tile's patch must fit one buffer for any batch.
+bool conv_x3_h2_supported(int C, int OC, int H, int W) {
+  const long long units = (long long)X3_NPR * (X3H2_LP / 16) + X3H2_SK * (X3_NPR / (W + 2) + 2);
+  const long long bufb = ((long long)X3_NPR * X3H2_LP + 8191) / 8192 * 8192;
+  return x3_kind(OC, C) == 0 && C % 32 == 0 && 16 * units <= bufb && x3_span(2LL * H * W + X3_BM, H, W) <= X3_NPR;
+}
+
+int launch_conv_x3_h2(const bf16_bits* in_h2, const bf16_bits* Bt, float* out, bf16_bits* out_split, int out_h2,
+                      long long M, int N, int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream,
+                      unsigned* range_flag) {
+  if (M == 0 || N == 0) return 0;
+  const long long per_img = (long long)H * W, nimg = M / per_img;
+  const long long in_bytes = (long long)x3_h2_act_bytes(nimg, H, W, C);
+  const long long b_bytes = (long long)(Npad / 16) * (K / 32) * 2048;
+  if (M % per_img != 0 || K != 9 * C || Npad != N || !conv_x3_h2_supported(C, N, H, W) || in_bytes >= 0x80000000LL ||
+      b_bytes >= 0x80000000LL || M > 0x7fffffffLL || x3_span(M, H, W) > X3_NPR ||
+      (out_split == nullptr) == (out == nullptr) || x3_act_bytes(nimg, H, W, N) >= 0x80000000ULL) {
+    set_error("conv_x3_h2: unsupported shape M=%lld N=%d K=%d %dx%dx%d", M, N, K, H, W, C);
+    return -2;
+  }
+  const int tilesM = (int)((M + X3_BM - 1) / X3_BM), tilesN = N / 256;
+  const X3Geom xg{H, W, C, out_split ? (out_h2 ? 3 : 1) : 0, 1, 0, 0};
+  const dim3 grid(tilesM * tilesN);
+#define X3H2(FL_)                                                                                              \
+  hipLaunchKernelGGL((conv3x3_x3_h2_kernel<X3_BM, X3_NPR, FL_>), grid, dim3(512), 0, stream, in_h2, Bt, out, \
+                     out_split, (int)M, N, K, epi, tilesM, xg, (unsigned)in_bytes, (unsigned)b_bytes, range_flag)
+  if (epi.flags == X3_YOLO_FL)  // YOLO's set compiled in
+    X3H2(X3_YOLO_FL);
+  else
+    X3H2(-1);
+#undef X3H2
+  return check_x3("conv_x3_h2");
 }
 
 // ---- small-M x3 conv (latency plans, gemm_x3_lat.h): 64-column tiles (NCP = 2), one or two
@@ -676,7 +751,8 @@ bool conv_x3_img_supported(int C, int OC, int H, int W) {
 }
 
 int launch_conv_x3_img(const bf16_bits* in_split, const bf16_bits* Bt, float* out, bf16_bits* out_split, int n, int N,
-                       int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream) {
+                       int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream, int out_h2,
+                       unsigned* range_flag) {
   if (n == 0 || N == 0) return 0;
   const long long in_bytes = (long long)x3_act_bytes(n, H, W, C);
   const long long b_bytes = (long long)(Npad / 16) * (K / 32) * 3072;
@@ -692,10 +768,11 @@ int launch_conv_x3_img(const bf16_bits* in_split, const bf16_bits* Bt, float* ou
   }
   if (epi.flags == X3_YOLO_FL)
     hipLaunchKernelGGL((conv3x3_x3_img_kernel<13, 13, X3_YOLO_FL>), dim3((unsigned)blocks), dim3(512), 0, stream,
-                       in_split, Bt, out, out_split, N, K, epi, C, (unsigned)in_bytes, (unsigned)b_bytes);
+                       in_split, Bt, out, out_split, N, K, epi, C, (unsigned)in_bytes, (unsigned)b_bytes, out_h2,
+                       range_flag);
   else
     hipLaunchKernelGGL((conv3x3_x3_img_kernel<13, 13, -1>), dim3((unsigned)blocks), dim3(512), 0, stream, in_split, Bt,
-                       out, out_split, N, K, epi, C, (unsigned)in_bytes, (unsigned)b_bytes);
+                       out, out_split, N, K, epi, C, (unsigned)in_bytes, (unsigned)b_bytes, out_h2, range_flag);
   return check_x3("conv_x3_img");
 }
 

@@ -186,6 +186,11 @@ struct PlanLayer {
   bool xpad = false;  // explicit pads (dnn_plan_add_conv_padded): shown by dnn_plan_describe
   bool out_padded = false;  // output written zero-bordered (the next layer reads_split_planes / is
                             // patch16 / tile16; fp32 plans: as x3 split planes)
+  // The wide x3 conv on two fp16 pieces (gemm_x3_h2.h).  h2_ok is fixed when the layer is added
+  // (DNN_HIP_X3_H2 as read at plan creation, host weights all inside fp16's range); h2 (this layer
+  // runs the h2 kernel) and out_h2 (its split planes are the next layer's h2 planes) follow from
+  // the layer and its neighbour (resolve_h2), never from the batch
+  bool h2_ok = false, h2 = false, out_h2 = false;
   size_t pad_off = 0;       // its zero-bordered output region: float offset inside the pad area
   int PH = 0, PW = 0;
   size_t w_off = 0, epi_off = 0;  // float offsets in the weight arena
@@ -261,6 +266,7 @@ struct dnn_plan {
   int fp16 = 0;  // 1: fp16 activations/weights, fp16 MFMA, fp32 accumulate + epilogue
   bool direct_out = false;  // fp16: the last layer writes the fp32 output itself (fp16_direct_out)
   bool latency = false;  // split K by M too (dnn_plan_set_latency_mode): batch-1 latency plans
+  bool x3_h2 = true;     // DNN_HIP_X3_H2 (read once, at creation): eligible wide x3 layers run on two fp16 pieces
   std::vector<PlanLayer> layers;
   std::vector<Step> steps;  // what a run launches, in order (layout())
   // fork / join: slots by number (at most kMaxSlots, a released number is reused); regions (one
@@ -361,7 +367,32 @@ static void place_outputs(dnn_plan* p) {
 // Lowers the layers to the step list and sizes the weight arena and the workspace.  The peepholes
 // rewrite layers until finalize and dnn_plan_memory / dnn_plan_num_kernels ask before it, so this
 // derives everything from the layers each time it is called.
+// Which wide x3 layers run on two fp16 pieces (h2): a CONV_X3 layer of the wide kernel's unpooled,
+// unsplit form (the batch kernel), whose weights fit fp16's range and whose producer can write h2
+// planes -- the whole-image kernel, the wide kernel's unpooled unsplit form or the h2 kernel.  A
+// separate pool, the tile kernels and the implicit GEMM write bf16 planes only: their consumers stay
+// on x3.  Derived from the layers each time (the peepholes fuse pools into them until finalize).
+static void resolve_h2(dnn_plan* p) {
+  for (auto& L : p->layers) L.h2 = L.out_h2 = false;
+  // (latency plans: their own kernels, x3_lat / x3_ktile, never take h2; a layer that fills the
+  // chip runs the batch kernel there too and chooses as in a batch plan)
+  if (p->fp16 || !p->x3_h2) return;
+  auto wide = [](const PlanLayer& q) {
+    return q.is(CONV_X3) && conv_x3_kind(q.OC, q.C) == 0 && q.pool == POOL_NONE && q.splits == 1;
+  };
+  for (size_t i = 1; i < p->layers.size(); ++i) {
+    PlanLayer& L = p->layers[i];
+    PlanLayer& q = p->layers[i - 1];
+    if (wide(L) && L.h2_ok && q.out_padded && conv_x3_h2_supported(L.C, L.OC, L.H, L.W) &&
+        (q.is(CONV_X3_IMG) || wide(q))) {
+      L.h2 = true;
+      q.out_h2 = true;
+    }
+  }
+}
+
 static void layout(dnn_plan* p) {
+  resolve_h2(p);
   p->direct_out = fp16_direct_out(p);
   place_outputs(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
@@ -477,7 +508,10 @@ static void layout(dnn_plan* p) {
   p->ticket_floats = align_up(tickets, 64);  // unsigned tickets of the fused split-K layers
   // zero-bordered activations feeding patch16 / tile16 (fp16, 2 B per element) / x3 (3 bf16
   // pieces, 6 B) layers: one region per producer (zeroed once at finalize; each producer
-  // rewrites only its own interior, so its borders stay zero whatever the layers' shapes)
+  // rewrites only its own interior, so its borders stay zero whatever the layers' shapes).  A
+  // region that feeds an h2 layer (two fp16 pieces, 4 B per element) keeps the 6-B size: the
+  // planes take its first two thirds and the producer's sticky range word the word after them
+  // (range_word), so dnn_plan_memory does not depend on which layers take h2
   size_t pad_total = 0;
   for (auto& L : p->layers)
     if (L.out_padded) {
@@ -506,6 +540,14 @@ static void layout(dnn_plan* p) {
   m.regions = m.pad + p->pad_floats;
   m.zero = m.regions + p->slot_floats;
   p->ws_floats = m.zero + dnn_plan::kZeroFloats;
+}
+
+// The sticky range word of a producer of h2 planes: the first word after the planes of the planned
+// batch (4 B per element) inside its 6-B-per-element region.  Zeroed with the pad area at finalize;
+// no kernel writes there but the producer's wave-uniform slow branch (h2_store8).
+static unsigned* range_word(const dnn_plan* p, const PlanLayer& L) {
+  const size_t elems = (size_t)p->batch * (L.out_h() + 2) * (L.out_w() + 2) * L.OC;
+  return reinterpret_cast<unsigned*>(p->ws + p->at.pad + L.pad_off + elems);
 }
 
 // While adding: the layer about to be pushed (index layers.size()) consumes or replaces the current
@@ -548,6 +590,7 @@ int dnn_plan_create(int batch, int in_h, int in_w, int in_c, dnn_plan** out) {
   const char* pe = getenv("DNN_HIP_PATCH");
   p->patch = !(pe && pe[0] == '0');
   p->splitk_fused = !getenv_flag_off("DNN_HIP_SPLITK_FUSED");
+  p->x3_h2 = !getenv_flag_off("DNN_HIP_X3_H2");
   *out = p;
   return 0;
 }
@@ -790,9 +833,14 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
   // the affine entry (fp32 plans): v * scale + shift as EPI_BN_AB's v * alpha - beta with
   // beta = -shift (the negation is exact, so both round alike)
   if (ep.scale) L.epi_flags |= EPI_BN_AB;
+  // (a shape-only layer, kernel == NULL, takes the choice of in-range weights: its arena comes
+  // from a plan that checked them)
+  L.h2_ok = p->x3_h2 && L.variant == CONV_X3;
   if (kernel) {
     L.have_host = true;
     L.w.assign(kernel, kernel + (size_t)L.K * od);
+    if (L.h2_ok)  // h2's range contract: every weight finite and |w| < 65520
+      for (float w : L.w) L.h2_ok = L.h2_ok && std::fabs(w) < 65520.f;  // (false for NaN)
     const int np = std::max(L.Npad, 32);
     L.bias.assign(np, 0.f);
     L.mean.assign(np, 0.f);
@@ -1284,6 +1332,9 @@ static int upload_weights(dnn_plan* p) {
         if (!rc)
           rc = launch_f32_to_f16(packed32, reinterpret_cast<half_t*>(p->weights + L.w_off),
                                  (long long)L.Npad * L.Kpad, 0);
+      } else if (!rc && pack == PACK_X3 && L.h2) {  // (two fp16 pieces: 2/3 of the slot)
+        rc = launch_pack_weights_h2(tmp, reinterpret_cast<unsigned short*>(p->weights + L.w_off), L.K, L.OC, L.Npad,
+                                    L.C, 0);
       } else if (!rc && pack == PACK_X3) {
         rc = launch_pack_weights_x3(tmp, reinterpret_cast<unsigned short*>(p->weights + L.w_off), L.K, L.OC, L.Npad,
                                     L.C, 0);
@@ -1372,6 +1423,25 @@ int dnn_plan_finalize(dnn_plan* p, int device, void* weights, void* workspace) {
   }
   DNN_HIP_TRY(hipDeviceSynchronize());
   p->finalized = true;
+  return 0;
+}
+
+int dnn_plan_range_events(dnn_plan* p, unsigned* events) {
+  DNN_REQUIRE(p && p->finalized && events, "dnn_plan_range_events: plan not finalized, or events is NULL");
+  *events = 0;
+  bool synced = false;
+  for (auto& L : p->layers) {  // one word per producer of h2 planes
+    if (!L.out_h2) continue;
+    if (!synced) {
+      DNN_HIP_TRY(hipSetDevice(p->device));
+      DNN_HIP_TRY(hipDeviceSynchronize());
+      synced = true;
+    }
+    unsigned w = 0;
+    DNN_HIP_TRY(hipMemcpy(&w, range_word(p, L), sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (w) DNN_HIP_TRY(hipMemset(range_word(p, L), 0, sizeof(unsigned)));
+    *events += w ? 1u : 0u;
+  }
   return 0;
 }
 
@@ -1563,6 +1633,8 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
   const unsigned short* cur3 = reinterpret_cast<const unsigned short*>(cur);  // (x3 convs: split planes in,
   const unsigned short* wt3 = reinterpret_cast<const unsigned short*>(wt);    //  three bf16 pieces per weight)
   const DirectGeom dg{n, L.H, L.W, L.OH, L.OW, L.PH, L.PW, L.pt, L.pl};
+  const int oh2 = dsplit && L.out_h2 ? 1 : 0;  // (a producer of h2 planes: it gets its range word)
+  unsigned* const range = oh2 ? range_word(p, L) : nullptr;
   switch (L.variant) {
     case CONV_GEMM:
       return launch_gemm(L.cfg, p->ws + p->at.col, L.Kpad, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s, L.splits,
@@ -1600,17 +1672,21 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
     case CONV_X3_1X1_KTILE:
       return launch_conv_x3_1x1_ktile(cur3, wt3, dst, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s);
     case CONV_X3_IMG:
-      return launch_conv_x3_img(cur3, wt3, dsplit ? nullptr : dst, dsplit, n, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s);
+      return launch_conv_x3_img(cur3, wt3, dsplit ? nullptr : dst, dsplit, n, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s,
+                                oh2, range);
     case CONV_X3_KTILE:
       return launch_conv_x3_ktile(cur3, wt3, dsplit ? nullptr : dst, dsplit, L.rows(n), L.OC, L.Npad, L.K, L.H, L.W,
                                   L.C, epi, s, L.pool);
     case CONV_X3_LAT:  // (always split: raw partials into the slab; the next pool's step or a combine step finishes)
       return launch_conv_x3_lat(cur3, wt3, slab, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, L.splits, s);
     case CONV_X3:
+      if (L.h2)  // two fp16 pieces per operand (resolve_h2)
+        return launch_conv_x3_h2(cur3, wt3, dsplit ? nullptr : dst, dsplit, oh2, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C,
+                                 epi, s, range);
       if (L.splits > 1)  // raw partials into the slab, as above
         return launch_conv_x3(cur3, wt3, slab, nullptr, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s, L.splits);
       return launch_conv_x3(cur3, wt3, dsplit ? nullptr : dst, dsplit, L.rows(n), L.OC, L.Npad, L.K, L.H, L.W, L.C, epi,
-                            s, 1, L.pool == POOL_S2 ? 1 : 0, p->latency && fused_splitk(p));
+                            s, 1, L.pool == POOL_S2 ? 1 : 0, p->latency && fused_splitk(p), oh2, range);
     default:
       set_error("dnn_plan_run: fp32 plan has an unsupported conv mode %d", L.variant);
       return -2;
@@ -1751,6 +1827,26 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
     } else
       snprintf(line, sizeof(line), "pool %dx%dx%d -> %dx%dx%d k%dx%d s%d%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.kh,
                L.kw, L.sh, p->fp16 ? " fp16" : "");
+    s += line;
+  }
+  snprintf(buf, buf_len, "%s", s.c_str());
+  return 0;
+}
+
+// One line per conv layer, in dnn_plan_describe's order: the operand pieces of the x3 arithmetic
+// ("pieces=h2", "pieces=x3") or "pieces=-" for a layer on another path.  Its own call: the text of
+// dnn_plan_describe is pinned by recorded plans.
+int dnn_plan_describe_pieces(const dnn_plan* pc, char* buf, int buf_len) {
+  DNN_REQUIRE(pc && buf && buf_len > 0, "dnn_plan_describe_pieces: bad args");
+  dnn_plan* p = const_cast<dnn_plan*>(pc);
+  if (!p->finalized) resolve_h2(p);
+  std::string s;
+  char line[64];
+  int nconv = 0;
+  for (auto& L : p->layers) {
+    if (!L.is_conv()) continue;
+    snprintf(line, sizeof(line), "conv%d pieces=%s\n", nconv++,
+             L.h2 ? "h2" : (!p->fp16 && reads_split_planes(L.variant)) ? "x3" : "-");
     s += line;
   }
   snprintf(buf, buf_len, "%s", s.c_str());

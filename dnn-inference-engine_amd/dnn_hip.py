@@ -116,6 +116,11 @@ def _bind_plan_api(lib):
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args
+    if hasattr(lib, "dnn_plan_range_events"):  # (tools/lib_ab.py also loads libraries from before it)
+        lib.dnn_plan_range_events.restype = i
+        lib.dnn_plan_range_events.argtypes = [vp, P(ctypes.c_uint)]
+        lib.dnn_plan_describe_pieces.restype = i
+        lib.dnn_plan_describe_pieces.argtypes = [vp, ctypes.c_char_p, i]
     return lib
 
 
@@ -1389,8 +1394,9 @@ class Plan(object):
         return cls(g.in_node.in_shape[0], tuple(g.in_node.in_shape[1:]), entries, device=device, **kw)
 
     @staticmethod
-    def _declared(batch, in_shape, entries, lib, precision, latency):
-        """A plan handle with the entries' shapes declared (no weights, not finalized: no device)."""
+    def _declared(batch, in_shape, entries, lib, precision, latency, kernels=False):
+        """A plan handle with the entries' shapes declared (no weights, not finalized: no device).
+        `kernels`: the conv kernels are passed too (the pieces choice checks their range)."""
         h = ctypes.c_void_p()
         _check(lib.dnn_plan_create(int(batch), *in_shape, ctypes.byref(h)), "dnn_plan_create", lib)
         try:
@@ -1410,8 +1416,9 @@ class Plan(object):
                 elif isinstance(e, ConvEntry):
                     kh, kw, _, od = e.conv.kernel.shape
                     _check(lib.dnn_plan_add_conv(h, kh, kw, od, int(e.conv.strides[1]), int(e.conv.strides[2]),
-                                                 _pad_code(e.conv.padding), None, None, None, None, None, 0.0,
-                                                 1 if e.leaky else 0), "dnn_plan_add_conv", lib)
+                                                 _pad_code(e.conv.padding), _vp(e.conv.kernel) if kernels else None,
+                                                 None, None, None, None, 0.0, 1 if e.leaky else 0),
+                           "dnn_plan_add_conv", lib)
                 else:
                     p = e.pool
                     _check(lib.dnn_plan_add_max_pool(h, int(p.ksize[1]), int(p.ksize[2]), int(p.strides[1]),
@@ -1446,10 +1453,36 @@ class Plan(object):
         finally:
             lib.dnn_plan_destroy(h)
 
+    @staticmethod
+    def lowering_pieces(batch, in_shape, entries, lib=None, precision="fp32", latency=False):
+        """dnn_plan_describe_pieces' lines for a plan of this shape and these conv kernels,
+        without finalizing (needs no device)."""
+        lib = lib or mylib
+        h = Plan._declared(batch, in_shape, entries, lib, precision, latency, kernels=True)
+        try:
+            buf = ctypes.create_string_buffer(65536)
+            _check(lib.dnn_plan_describe_pieces(h, buf, 65536), "dnn_plan_describe_pieces", lib)
+            return buf.value.decode().splitlines()
+        finally:
+            lib.dnn_plan_destroy(h)
+
+    def pieces(self):
+        """Per conv layer "convN pieces=h2|x3|-" (dnn_plan_describe_pieces)."""
+        buf = ctypes.create_string_buffer(65536)
+        _check(self.lib.dnn_plan_describe_pieces(self.h, buf, 65536), "dnn_plan_describe_pieces", self.lib)
+        return buf.value.decode().splitlines()
+
     def describe(self):
         buf = ctypes.create_string_buffer(65536)
         _check(self.lib.dnn_plan_describe(self.h, buf, 65536), "dnn_plan_describe", self.lib)
         return buf.value.decode()
+
+    def range_events(self):
+        """Non-zero if a producer of an h2 layer's fp16 planes met a value outside fp16's range
+        since the last call (dnn_plan_range_events: synchronises, reads and clears the word)."""
+        ev = ctypes.c_uint()
+        _check(self.lib.dnn_plan_range_events(self.h, ctypes.byref(ev)), "dnn_plan_range_events", self.lib)
+        return ev.value
 
     def weight_buffer(self):
         p, n = ctypes.c_void_p(), ctypes.c_size_t()

@@ -267,6 +267,25 @@ int dnn_plan_weight_buffer(const dnn_plan* plan, void** ptr, size_t* bytes);
  * pointers, asynchronously on `stream` (a hipStream_t; NULL = default stream). */
 int dnn_plan_run(dnn_plan* plan, int n, const float* d_in, float* d_out, void* stream);
 
+/* Which operand pieces each conv layer's arithmetic runs on, one line per conv in
+ * dnn_plan_describe's order: "conv6 pieces=h2" (two fp16 pieces, three MFMA products per fp32
+ * product: the wide x3 layers whose producer can write such planes), "pieces=x3" (three bf16
+ * pieces, six products) or "pieces=-" (another path).  dnn_plan_describe's own text does not show
+ * it.  The choice depends on the layer and its neighbour, never on the batch, and changes neither
+ * dnn_plan_memory nor the kernel list. */
+int dnn_plan_describe_pieces(const dnn_plan* plan, char* buf, int buf_len);
+
+/* Range events of the two-piece fp16 ("h2", dnn_plan_describe_pieces) layers.  Their inputs
+ * are held as fp16 pairs, which cover |v| < 65520 only: a producer that meets a non-finite value
+ * or a larger one writes infinite pieces (the consumer's outputs become non-finite, as for an fp32
+ * infinity) and raises a sticky word in the workspace.  This call synchronises the device, stores
+ * that word (0: no event since the last call or finalize) in *events and clears it.  Weights are
+ * checked when a layer with host weights is added: such a layer stays on three bf16 pieces.  A
+ * shape-only layer (kernel == NULL) takes the choice of in-range weights, so its arena must come
+ * from a plan whose dnn_plan_describe_pieces text equals its own.  DNN_HIP_X3_H2=0 at dnn_plan_create keeps every
+ * layer on three bf16 pieces. */
+int dnn_plan_range_events(dnn_plan* plan, unsigned* events);
+
 /* Host-pointer convenience: H2D copy, run, D2H copy, synchronise. */
 int dnn_plan_run_host(dnn_plan* plan, int n, const float* h_in, float* h_out);
 
