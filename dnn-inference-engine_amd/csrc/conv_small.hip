@@ -409,7 +409,7 @@ bool conv0_mfma_supported(int cin, int nout, int kh, int kw, int sh, int sw) {
 }
 
 template <bool F16, typename OutT>
-static int launch_conv0(const float* in, const float* w, OutT* out, const DirectGeom& g, int cin,
+static int launch_conv0(const Switches& sws, const float* in, const float* w, OutT* out, const DirectGeom& g, int cin,
                         const EpiParams& epi, hipStream_t s) {
   if (g.B == 0) return 0;
   const int tilesX = (g.OW + SC_T - 1) / SC_T, tilesY = (g.OH + SC_T - 1) / SC_T;
@@ -421,11 +421,11 @@ static int launch_conv0(const float* in, const float* w, OutT* out, const Direct
   // persistent: 8 workgroups per CU loop over the tiles (weights loaded once per workgroup,
   // the next tile's patch prefetched into registers during the current tile's MFMAs)
   const int nt = (int)blocks;
-  const char* eg = getenv("DNN_HIP_C0_GRID");  // (tuning experiments: workgroups of the launch)
+  // (Switches::c0_grid, tuning experiments: workgroups of the launch)
   // (fp16 conv0 at batch 64: 2048 89.4 us, 4096 85.1, 8192 87.2; the fp32 form of this kernel is only
   // the fallback of launch_conv0_mfma -- YOLO's fp32 conv0 runs conv0_packed_pool_kernel -- and
   // keeps its round-4 cap of 2048)
-  const int gmax = eg && atoi(eg) > 0 ? atoi(eg) : F16 ? 4096 : 2048;
+  const int gmax = sws.c0_grid > 0 ? sws.c0_grid : F16 ? 4096 : 2048;
   const dim3 grid((unsigned)(nt < gmax ? nt : gmax));
   switch (cin) {
     case 1: hipLaunchKernelGGL((conv0_mfma_pool_kernel<1, F16, OutT>), grid, dim3(256), 0, s, in, w, out, g, tilesX, tilesY, nt, epi); break;
@@ -440,16 +440,16 @@ static int launch_conv0(const float* in, const float* w, OutT* out, const Direct
   return 0;
 }
 
-int launch_conv0_mfma(const float* in, const float* w, float* out, const DirectGeom& g, int cin, const float* zero,
+int launch_conv0_mfma(const Switches& sws, const float* in, const float* w, float* out, const DirectGeom& g, int cin, const float* zero,
                       const EpiParams& epi, hipStream_t s) {
   if (cin != 3 || !zero)
-    return launch_conv0<false, float>(in, w, out, g, cin, epi, s);
+    return launch_conv0<false, float>(sws, in, w, out, g, cin, epi, s);
   if (g.B == 0) return 0;
   const int tilesX = (g.OW + SC_T - 1) / SC_T, tilesY = (g.OH + SC_T - 1) / SC_T;
   const long long blocks = (long long)g.B * tilesX * tilesY;
   if ((size_t)g.B * g.PH * g.PW * 16 * sizeof(float) >= OOB_OFF ||
       (size_t)g.B * g.H * g.W * cin * sizeof(float) >= OOB_OFF)  // 32-bit load / store offsets
-    return launch_conv0<false, float>(in, w, out, g, cin, epi, s);
+    return launch_conv0<false, float>(sws, in, w, out, g, cin, epi, s);
   if (blocks > 0x7fffffffLL || g.PH != (g.OH + 1) / 2 || g.PW != (g.OW + 1) / 2) {
     set_error("conv0_packed: unsupported shape");
     return -2;
@@ -468,21 +468,18 @@ int launch_conv0_mfma(const float* in, const float* w, float* out, const DirectG
   // that finish early.  Measured at batch 64 (workgroups per CU: ms): one resident round 7:
   // 0.185, 8 (the 8th as a lone second round): 0.168, 14: 0.153, 28: 0.1485, 56: 0.153, one tile
   // per workgroup (169): 0.184.
-  // (cached per instantiation and device: the occupancy query runs on a device's first launch)
-  auto slots_of = [](const void* kern, long long (&cache)[64]) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (cache[dev] > 0) return cache[dev];
+  // (cached per instantiation: the occupancy query runs on its first launch)
+  auto per_cu_of = [](const void* kern, int& cache) {
+    if (cache > 0) return cache;
     int v = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, 0) != hipSuccess || v < 1) v = 1;
-    v = 4 * (v < 8 ? v : 8);
-    return cache[dev] = (long long)v * device_cu_count();
+    return cache = 4 * (v < 8 ? v : 8);
   };
 #define C0PN(FL_, EV_, D16_, NB_)                                                                               \
   do {                                                                                                           \
-    static long long cache[64] = {};                                                                             \
-    const long long slots =                                                                                      \
-        slots_of(reinterpret_cast<const void*>(conv0_packed_pool_kernel<3, FL_, EV_, D16_, NB_>), cache);        \
+    static int cache = 0;                                                                                        \
+    const long long slots = (long long)device_cu_count() *                                                       \
+        per_cu_of(reinterpret_cast<const void*>(conv0_packed_pool_kernel<3, FL_, EV_, D16_, NB_>), cache);       \
     const unsigned grid = (unsigned)(blocks < slots ? blocks : slots);                                           \
     hipLaunchKernelGGL((conv0_packed_pool_kernel<3, FL_, EV_, D16_, NB_>), dim3(grid), dim3(256), 0, s, in, w,    \
                        out, g, tilesX, tilesY, (int)blocks, zero, epi, mags);                                    \
@@ -492,8 +489,8 @@ int launch_conv0_mfma(const float* in, const float* w, float* out, const DirectG
   // more of the DMA latency than the deeper ring)
 #define C0P(FL_, EV_, D16_) C0PN(FL_, EV_, D16_, 3)
   // 16-B patch-row DMAs (D16) where units cannot straddle the frame edge: W % 4 == 0, one pixel of
-  // left padding (SAME 3x3).  DNN_HIP_C0_D16=0 (read per launch, A/B): the 4-B row DMAs; same bits
-  const bool d16 = g.W % 4 == 0 && g.pl == 1 && !getenv_flag_off("DNN_HIP_C0_D16");
+  // left padding (SAME 3x3).  Switches::c0_d16 off (A/B): the 4-B row DMAs; same bits
+  const bool d16 = g.W % 4 == 0 && g.pl == 1 && sws.c0_d16;
   if (epi.flags == YOLO && even) {
     if (d16)
       C0P(YOLO, true, true);
@@ -519,9 +516,9 @@ int launch_conv0_mfma(const float* in, const float* w, float* out, const DirectG
   }
   return 0;
 }
-int launch_conv0_mfma_f16(const float* in, const float* w, half_t* out, const DirectGeom& g, int cin,
+int launch_conv0_mfma_f16(const Switches& sws, const float* in, const float* w, half_t* out, const DirectGeom& g, int cin,
                           const EpiParams& epi, hipStream_t s) {
-  return launch_conv0<true, half_t>(in, w, out, g, cin, epi, s);
+  return launch_conv0<true, half_t>(sws, in, w, out, g, cin, epi, s);
 }
 
 // ------------------------------------------------------------------------------ conv1 fp16
@@ -534,7 +531,7 @@ int launch_conv0_mfma_f16(const float* in, const float* w, half_t* out, const Di
 // Round 5: persistent workgroups (conv1 is memory-bound: 16 x 16 tiles of 40 MFMAs per wave, so
 // a one-tile workgroup spent most of its life waiting for its patch and loading its weights):
 // weights loaded once per workgroup, tile t + 1's patch DMA'd into the other buffer while tile t
-// computes.  Same products, same order: same bits as the one-tile form (DNN_HIP_C1F16_WGS=0).
+// computes.  Same products, same order: same bits as the one-tile form (Switches::c1f16_wgs = 0).
 __global__ void __launch_bounds__(256)
 conv1_patch_f16_kernel(const half_t* __restrict__ in, const half_t* __restrict__ Bt, int ldb,
                        half_t* __restrict__ out, DirectGeom g, int tilesX, int tilesY, const float* __restrict__ zero,
@@ -661,7 +658,7 @@ bool conv1_patch_f16_supported(int C, int OC, int H, int W, int OH, int OW, int 
          OW == W && OH % 2 == 0 && OW % 2 == 0;
 }
 
-int launch_conv1_patch_f16(const half_t* in, const half_t* Bt, int ldb, half_t* out, const DirectGeom& g,
+int launch_conv1_patch_f16(const Switches& sws, const half_t* in, const half_t* Bt, int ldb, half_t* out, const DirectGeom& g,
                            const float* zero, const EpiParams& epi, hipStream_t s, int opad) {
   if (g.B == 0) return 0;
   if (ldb < 144 || ldb % 8 || g.OH % 2 || g.OW % 2 || g.PH != g.OH / 2 || g.PW != g.OW / 2 || g.pt != 1 ||
@@ -675,13 +672,10 @@ int launch_conv1_patch_f16(const half_t* in, const half_t* Bt, int ldb, half_t* 
     set_error("conv1_patch_f16: too many tiles");
     return -2;
   }
-  // persistent workgroups per CU (DNN_HIP_C1F16_WGS; 0: one tile per workgroup)
-  const char* ev = getenv("DNN_HIP_C1F16_WGS");
-  const int wpc = ev ? atoi(ev) : 8;  // (batch 64: one-tile 73.9 us, 4 per CU 59.9, 8 per CU 56.0)
-  int dev = 0, cus = 256;
-  if (wpc > 0 && hipGetDevice(&dev) == hipSuccess)
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const long long blocks = wpc > 0 ? std::min<long long>(tiles, (long long)wpc * cus) : tiles;
+  // persistent workgroups per CU (0: one tile per workgroup; batch 64: one-tile 73.9 us, 4 per CU
+  // 59.9, 8 per CU 56.0)
+  const int wpc = sws.c1f16_wgs;
+  const long long blocks = wpc > 0 ? std::min<long long>(tiles, (long long)wpc * device_cu_count()) : tiles;
   hipLaunchKernelGGL(conv1_patch_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, in, Bt, ldb, out, g, tilesX,
                      tilesY, zero, epi, opad, (int)tiles);
   hipError_t e = hipGetLastError();

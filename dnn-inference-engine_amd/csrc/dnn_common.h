@@ -6,16 +6,58 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <utility>
+#include <vector>
 
 namespace dnnhip {
 
 // ---------------------------------------------------------------- errors
 void set_error(const char* fmt, ...);
 const char* last_error();
-// true when environment variable `name` is set and starts with '0' (experiment switches)
-bool getenv_flag_off(const char* name);
-// compute units of the current HIP device (persistent-kernel grids)
+// compute units of the current HIP device (persistent-kernel grids), cached; 256 on error
 int device_cu_count();
+
+// ---------------------------------------------------------------- switches
+// Every DNN_HIP_* switch the library reads, resolved.  read_switches() is the only reader of the
+// environment: dnn_plan_create calls it once into the plan, each per-op entry once per call, and
+// the *_supported functions and launchers take the result as an argument.  So a plan keeps running
+// what it chose if the environment changes later, and describe() determines its kernels.
+struct Switches {
+  // plan structure
+  bool fuse = true;          // FUSE=0: explicit im2col + GEMM, every pool its own kernel
+  bool patch = true;         // PATCH=0: patch-eligible layers (conv1) stay on the implicit GEMM
+  bool splitk_fused = true;  // SPLITK_FUSED=0: split-K partials summed by a reduce kernel, not in the GEMM
+  std::vector<std::pair<int, int>> cfg;    // CFG="K:cfg,...": GEMM tile config of the layers with that K
+  std::vector<std::pair<int, int>> split;  // SPLIT="K:splits,...": split count of such latency-plan layers
+  // fp32 x3 convs (kernels_x3.hip): which layers take them
+  bool x3 = true;            // X3=0: every layer stays on the fp32 MFMA (implicit GEMM)
+  bool x3_tile = true;       // X3_TILE=0: no 2-D tile kernels (N = 64 / N % 128 == 0 layers)
+  bool x3_c16 = true;        // X3_C16=0: no 16-channel kernel (conv1)
+  bool x3_img = true;        // X3_IMG=0: 13 x 13 frames keep the wide kernel's K slices + the pool5 combine
+  bool x3_1x1 = true;        // X3_1X1=0: a 1x1 conv behind an x3 conv stays on the fp32 GEMM
+  bool x3_h2 = true;         // X3_H2=0: wide layers never run on two fp16 pieces (gemm_x3_h2.h)
+  int x3l_cpw = 0;           // X3L_CPW=1|2: chunks per workgroup of the small-M kernel (0: by the grid)
+  long long x3_lat_minwg = 128;  // X3_LAT_MINWG=n: fewest workgroups at which a latency plan takes that kernel
+  // fp32 x3 convs: the form a launch takes
+  bool x3_c16p = true;       // X3_C16P=0: 16-channel kernel, one tile per workgroup (not persistent)
+  bool x3_c16pp = true;      // X3_C16PP=0: batch grids keep the two-workgroup persistent kernel (no ping-pong)
+  bool x3_pp = true;         // X3_PP=0: conv2's batch grids keep the tile kernel (no ping-pong)
+  bool x3_pp_prio = true;    // X3_PP_PRIO=0: the ping-pong kernels' MFMA steps at the default priority
+  // fp16 plans
+  bool patch16 = true;       // PATCH16=0|1: the patch kernel for eligible layers (conv6 0.1415 -> 0.1286 ms at batch 64)
+  bool tile16 = true;        // TILE16=0: conv2-conv5 stay on the implicit fp16 GEMM
+  bool img16 = true;         // IMG16=0: no whole-frame form of the tile kernel (conv5 + pool5)
+  bool f16_direct_out = true;  // F16_DIRECT_OUT=0: the last layer never writes the fp32 output itself
+  int tile16_wgs = 2;        // TILE16_WGS=n: persistent tile-kernel workgroups per CU (0: one tile each)
+  int c1f16_wgs = 8;         // C1F16_WGS=n: persistent conv1 workgroups per CU (0: one tile each)
+  // GEMMs and the small kernels
+  bool gemm_buf = true;      // GEMM_BUF=0: flat 64-bit DMA addresses, no buffer descriptors
+  int persist = 1;           // PERSIST=0 off, 1 persistent GEMM where it measured faster, 2 every covered config
+  bool im2col_rows = true;   // IM2COL_ROWS=0: no row-staged im2col for scalar-channel layers
+  int c0_grid = 0;           // C0_GRID=n: workgroups of the MFMA conv0 launch (0: 4096 fp16, 2048 fp32)
+  bool c0_d16 = true;        // C0_D16=0: conv0's patch rows by 4-B DMAs, not 16-B; same bits
+};
+Switches read_switches();
 
 #define DNN_HIP_TRY(x)                                                             \
   do {                                                                             \
@@ -135,7 +177,7 @@ enum GemmMode : int { GEMM_DENSE = 0, GEMM_IMPLICIT = 1, GEMM_IMPLICIT_POOL = 2 
 
 // ---------------------------------------------------------------- launchers
 // All launchers are asynchronous on `stream` and return 0 / negative on launch error.
-int launch_im2col(const float* in, float* col, const ConvGeom& g, hipStream_t stream);
+int launch_im2col(const Switches& sws, const float* in, float* col, const ConvGeom& g, hipStream_t stream);
 // K order (ic, kh, kw), K == Kpad, one image on a padded input (the per-op im2col ABI)
 int launch_im2col_ckk(const float* in, float* col, const ConvGeom& g, hipStream_t stream);
 // With splits > 1 (LDS-DMA configs only) the GEMM writes `splits` raw fp32 partials
@@ -149,20 +191,20 @@ void choose_latency_plan(long long M, int N, int K, int* cfg, int* splits, bool 
 bool generic_combine_cfg(int cfg);
 // tile order of a GEMM launch (SplitK::nmajor): 1 = N-major
 int nmajor_order(int N, int tilesN);
-// Persistent implicit GEMM for unsplit short-K layers (gemm_persist.h; DNN_HIP_PERSIST=0 off):
+// Persistent implicit GEMM for unsplit short-K layers (gemm_persist.h; Switches::persist):
 // same arguments and bits as launch_gemm_implicit with splits = 1; -3 = not covered (fall back).
-int launch_gemm_persist(int cfg, int mode, const float* in, const ImplicitConv& ic, const float* Bt, int ldb,
+int launch_gemm_persist(const Switches& sws, int cfg, int mode, const float* in, const ImplicitConv& ic, const float* Bt, int ldb,
                         float* C, int ldc, long long M, int N, int Kpad, const EpiParams& epi, hipStream_t stream);
 // With `tickets` (>= the cfg's tile count of unsigned, zero before the first launch and left
 // zero by every launch) the split-K GEMM finishes itself: the last-arriving split of each tile
 // sums the partials in split order and writes C with the epilogue (splitk_combine, gemm_f32.h),
 // so no reduce kernel follows; `slab` must then hold splitk_fused_slab_floats() floats.
-int launch_gemm(int cfg, const float* A, int lda, const float* Bt, int ldb, float* C, int ldc,
+int launch_gemm(const Switches& sws, int cfg, const float* A, int lda, const float* Bt, int ldb, float* C, int ldc,
                 long long M, int N, int Kpad, const EpiParams& epi, hipStream_t stream, int splits = 1,
                 float* slab = nullptr, unsigned* tickets = nullptr);
 // implicit conv (mode GEMM_IMPLICIT / GEMM_IMPLICIT_POOL) on the LDS-DMA configs 3..6;
 // `in` is the NHWC input, M = B*OH*OW (or B*PH*PW*4 with pool; no split-K with pool)
-int launch_gemm_implicit(int cfg, int mode, const float* in, const ImplicitConv& ic, const float* Bt, int ldb,
+int launch_gemm_implicit(const Switches& sws, int cfg, int mode, const float* in, const ImplicitConv& ic, const float* Bt, int ldb,
                          float* C, int ldc, long long M, int N, int Kpad, const EpiParams& epi, hipStream_t stream,
                          int splits = 1, float* slab = nullptr, unsigned* tickets = nullptr);
 // slab floats and tickets a fused split-K launch of (cfg, M, N, splits) needs
@@ -225,7 +267,7 @@ int gemm16_cfg_bn(int cfg);
 bool gemm16_f32out_supported(int splits, int Npad);
 int launch_gemm16_f32out(const half_t* A, int lda, const half_t* Bt, int ldb, int Npad, float* C, int ldc, long long M,
                          int N, int Kpad, const EpiParams& epi, hipStream_t stream);
-int launch_gemm16(int cfg, int mode, const half_t* A, int lda, const ImplicitConv& ic, const half_t* Bt, int ldb,
+int launch_gemm16(const Switches& sws, int cfg, int mode, const half_t* A, int lda, const ImplicitConv& ic, const half_t* Bt, int ldb,
                   half_t* C, int ldc, long long M, int N, int Kpad, const EpiParams& epi, hipStream_t stream,
                   int splits = 1, float* slab = nullptr, unsigned* tickets = nullptr);
 long long splitk16_fused_slab_floats(int cfg, long long M, int N, int splits);
@@ -238,19 +280,19 @@ int launch_maxpool16(const half_t* in, half_t* out, const PoolGeom& g, hipStream
 // fp16 3x3/s1/SAME conv with a zero-bordered input [B][H+2][W+2][C] (C % 64 == 0, N % 256 == 0),
 // weights packed K-order (chunk, tap, c) (launch_pack_weights order 2); out_padded: write the
 // output zero-bordered too (gemm_f16_acc.h)
-bool conv_patch16_supported(int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
+bool conv_patch16_supported(const Switches& sws, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
                             int pl);
 // fp32 path "x3" conv (kernels_x3.hip, gemm_x3_patch.h): fp32 operands split exactly into three
 // bf16 pieces, six bf16 MFMA products, fp32 accumulation; activations in split planes
 // [B][H+2][W+2][C/32][3][32] bf16 (zero-bordered), weights packed by launch_pack_weights_x3
 // which x3 kernel family runs a layer (kernels_x3.hip x3_kind): 0 wide rows, 1 / 2 2-D tiles, 3 16-channel; -1 none
 int conv_x3_kind(int OC, int C);
-bool conv_x3_supported(int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt, int pl);
+bool conv_x3_supported(const Switches& sws, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt, int pl);
 size_t x3_act_bytes(long long nimg, int H, int W, int C);
 int launch_maxpool_x3(const float* in, unsigned short* out, const PoolGeom& g, hipStream_t s);
 int launch_pack_weights_x3(const float* w, unsigned short* out, int K, int N, int Npad, int C, hipStream_t s);
 int x3_splits(int N, int K);  // split-K of an x3 batch-plan layer: a function of (N, K) only
-int launch_conv_x3(const unsigned short* in_split, const unsigned short* Bt, float* out, unsigned short* out_split,
+int launch_conv_x3(const Switches& sws, const unsigned short* in_split, const unsigned short* Bt, float* out, unsigned short* out_split,
                    long long M, int N, int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream,
                    int splits = 1, int pool = 0, bool lat = false,  // lat: latency-plan tile shapes allowed
                    int out_h2 = 0, unsigned* range_flag = nullptr);  // out_h2: `out_split` as h2 planes (below)
@@ -271,27 +313,27 @@ long long x3_tiles(long long batch, int OH, int OW, int OC, int C, int K);
 // small-M x3 conv of the latency plans (gemm_x3_lat.h): raw partials [splits][M][N] of
 // x3_lat_splits(N, K) K slices into `part`, summed with the epilogue by launch_x3_combine
 // latency plans' 1x1 head on x3 split planes, K split inside the workgroup (gemm_x3_ktile.h)
-bool conv_x3_1x1_ktile_supported(int C, int OC, int H, int W);
+bool conv_x3_1x1_ktile_supported(const Switches& sws, int C, int OC, int H, int W);
 int launch_conv_x3_1x1_ktile(const unsigned short* in_split, const unsigned short* Bt, float* out, long long M, int N,
                              int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream);
 // latency plans' mid layers: x3 with the K split inside the workgroup (gemm_x3_ktile.h), one
 // launch, no partials; deterministic, tolerance against the batch plans
-bool conv_x3_ktile_supported(long long batch, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh,
+bool conv_x3_ktile_supported(const Switches& sws, long long batch, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh,
                              int sw, int pt, int pl, int pool);  // pool: 0, 1 (2x2/s2), 2 (2x2/s1 SAME)
 int launch_conv_x3_ktile(const unsigned short* in_split, const unsigned short* Bt, float* out,
                          unsigned short* out_split, long long M, int N, int Npad, int K, int H, int W, int C,
                          const EpiParams& epi, hipStream_t stream, int pool);
 // batch plans' small-frame x3 conv with its 2x2/s1 SAME pool fused (gemm_x3_img.h: conv5 +
 // pool5), one image x 128 columns per workgroup over the whole K, split planes out
-bool conv_x3_img_supported(int C, int OC, int H, int W);
+bool conv_x3_img_supported(const Switches& sws, int C, int OC, int H, int W);
 int launch_conv_x3_img(const unsigned short* in_split, const unsigned short* Bt, float* out, unsigned short* out_split,
                        int n, int N, int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream,
                        int out_h2 = 0, unsigned* range_flag = nullptr);
-bool conv_x3_lat_supported(long long batch, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh,
+bool conv_x3_lat_supported(const Switches& sws, long long batch, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh,
                            int sw, int pt, int pl);
-int x3_lat_splits(int N, int K);
+int x3_lat_splits(const Switches& sws, int N, int K);
 // 1x1 x3 conv (gemm_x3_1x1.h: conv8) on the producer's zero-bordered split planes, fp32 out [M][N]
-bool conv_x3_1x1_supported(int C, int OC, int H, int W);
+bool conv_x3_1x1_supported(const Switches& sws, int C, int OC, int H, int W);
 int launch_conv_x3_1x1(const unsigned short* in_split, const unsigned short* Bt, float* out, long long M, int N,
                        int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream);
 int launch_conv_x3_lat(const unsigned short* in_split, const unsigned short* Bt, float* part, long long M, int N,
@@ -302,11 +344,11 @@ int patch16_pack_order();  // launch_pack_weights order of the patch kernel's MF
 // fp16 3x3/s1/SAME conv + 2x2/s2 pool on 2-D tiles (gemm_f16_tile.h: conv2-conv4 of the fp16 path),
 // zero-bordered input [B][H+2][W+2][C] (C % 32 == 0, N % 64 == 0, H, W even), weights packed
 // by launch_pack_weights order 5; out_padded: the pooled output zero-bordered too
-bool conv_tile16_supported(int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
+bool conv_tile16_supported(const Switches& sws, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
                            int pl);
 // pool: 1 = 2x2/s2 (2-D tiles), 2 = 2x2/s1 SAME (whole 13 x 13 frames, conv_img16_supported)
-bool conv_img16_supported(int C, int OC, int H, int W);
-int launch_conv_tile16(const half_t* in_padded, const half_t* Bt, int ldb, half_t* out, int out_padded, int n, int N,
+bool conv_img16_supported(const Switches& sws, int C, int OC, int H, int W);
+int launch_conv_tile16(const Switches& sws, const half_t* in_padded, const half_t* Bt, int ldb, half_t* out, int out_padded, int n, int N,
                        int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream, int pool);
 int launch_conv_patch16(const half_t* in_padded, const half_t* Bt, int ldb, half_t* out, int out_padded, long long M,
                         int N, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream);
@@ -317,15 +359,15 @@ int launch_conv3x3_pool2_direct_f16out(const float* in, const float* w, half_t* 
 // conv_small.hip: conv0 on MFMA (cin <= 3, 16 outputs, fp32 frames in, pool fused) and the
 // fp16 path's conv1 patch kernel (C = 16 -> 32, pool fused)
 bool conv0_mfma_supported(int cin, int nout, int kh, int kw, int sh, int sw);
-int launch_conv0_mfma(const float* in, const float* w, float* out, const DirectGeom& g, int cin, const float* zero,
+int launch_conv0_mfma(const Switches& sws, const float* in, const float* w, float* out, const DirectGeom& g, int cin, const float* zero,
                       const EpiParams& epi, hipStream_t s);
-int launch_conv0_mfma_f16(const float* in, const float* w, half_t* out, const DirectGeom& g, int cin,
+int launch_conv0_mfma_f16(const Switches& sws, const float* in, const float* w, half_t* out, const DirectGeom& g, int cin,
                           const EpiParams& epi, hipStream_t s);
 // clock.hip: nwg one-wave workgroups each storing {s_memtime, s_memrealtime, XCC_ID, HW_ID}
 int launch_clock_stamp(hipStream_t s, unsigned long long* out, int nwg);
 bool conv1_patch_f16_supported(int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
                                int pl);
-int launch_conv1_patch_f16(const half_t* in, const half_t* Bt, int ldb, half_t* out, const DirectGeom& g,
+int launch_conv1_patch_f16(const Switches& sws, const half_t* in, const half_t* Bt, int ldb, half_t* out, const DirectGeom& g,
                            const float* zero, const EpiParams& epi, hipStream_t s, int opad = 0);
 
 // route.hip: space-to-depth of a [n, H, W, Ca] (TensorFlow channel order, (dy*block + dx)*Ca + c),

@@ -177,7 +177,7 @@ im2col_rows_kernel(const float* __restrict__ in, float* __restrict__ col, ConvGe
   }
 }
 
-int launch_im2col(const float* in, float* col, const ConvGeom& g, hipStream_t stream) {
+int launch_im2col(const Switches& sws, const float* in, float* col, const ConvGeom& g, hipStream_t stream) {
   long long M = (long long)g.B * g.OH * g.OW;
   if (M == 0) return 0;
   if (g.Kpad % 4 != 0 || g.Kpad < g.K) {
@@ -187,7 +187,7 @@ int launch_im2col(const float* in, float* col, const ConvGeom& g, hipStream_t st
   const bool vec = (g.C % 4) == 0;
   const long long row_floats = (long long)g.kh * ((g.OW - 1) * g.sw + g.kw) * g.C;
   if (!vec && g.Kpad <= 1024 && 256 % (g.Kpad / 4) == 0 && row_floats <= 16384 &&
-      (long long)g.B * g.OH < 0x7fffffffLL && !getenv_flag_off("DNN_HIP_IM2COL_ROWS")) {
+      (long long)g.B * g.OH < 0x7fffffffLL && sws.im2col_rows) {
     hipLaunchKernelGGL(im2col_rows_kernel, dim3((unsigned)(g.B * g.OH)), dim3(256), (size_t)row_floats * 4, stream,
                        in, col, g);
     return check_launch("im2col_rows");
@@ -440,8 +440,6 @@ static int launch_glds(int cfg, const float* A, int lda, const float* Bt, int ld
 
 // buffer descriptors fit (offsets are 32-bit, OOB_OFF = 2^31 marks padding taps)?
 static bool fits_buf(long long bytes) { return bytes > 0 && bytes < 0x80000000LL; }
-// DNN_HIP_GEMM_BUF=0: flat 64-bit DMA addresses (experiments and the equivalence tests)
-static bool abuf_enabled() { return !getenv_flag_off("DNN_HIP_GEMM_BUF"); }
 // front pads the implicit GEMMs' shifted descriptor base (one row + one pixel before the input)
 // covers: the first window's top-left pixel (-pt, -pl) must not lie before it
 bool buf_pads_ok(const ImplicitConv& ic) { return (1LL - ic.pt) * ic.W + 1 - ic.pl >= 0; }
@@ -500,7 +498,7 @@ static int split_setup(int cfg, long long M, int N, int Kpad, int splits, float*
   return 0;
 }
 
-int launch_gemm(int cfg, const float* A, int lda, const float* Bt, int ldb, float* C, int ldc,
+int launch_gemm(const Switches& sws, int cfg, const float* A, int lda, const float* Bt, int ldb, float* C, int ldc,
                 long long M, int N, int Kpad, const EpiParams& epi, hipStream_t stream, int splits, float* slab,
                 unsigned* tickets) {
   if (M == 0 || N == 0) return 0;
@@ -534,7 +532,7 @@ int launch_gemm(int cfg, const float* A, int lda, const float* Bt, int ldb, floa
     default: {
       const long long a_bytes = (M * (long long)lda) * 4, b_bytes = (long long)tilesN * ci.bn * ldb * 4;
       BufDesc bd{A, (unsigned)a_bytes, (unsigned)b_bytes};
-      const bool abuf = abuf_enabled() && fits_buf(a_bytes) && fits_buf(b_bytes);
+      const bool abuf = sws.gemm_buf && fits_buf(a_bytes) && fits_buf(b_bytes);
       return launch_glds<GEMM_DENSE>(cfg, A, lda, Bt, ldb, sk.steps ? slab : C, sk.steps ? N : ldc, m, N, Kpad,
                                      epi, tilesN, ImplicitConv{}, sk, abuf ? &bd : nullptr, grid, stream);
     }
@@ -542,7 +540,7 @@ int launch_gemm(int cfg, const float* A, int lda, const float* Bt, int ldb, floa
   return check_launch("gemm");
 }
 
-int launch_gemm_implicit(int cfg, int mode, const float* in, const ImplicitConv& ic_in, const float* Bt, int ldb,
+int launch_gemm_implicit(const Switches& sws, int cfg, int mode, const float* in, const ImplicitConv& ic_in, const float* Bt, int ldb,
                          float* C, int ldc, long long M, int N, int Kpad, const EpiParams& epi, hipStream_t stream,
                          int splits, float* slab, unsigned* tickets) {
   if (M == 0 || N == 0) return 0;
@@ -563,7 +561,8 @@ int launch_gemm_implicit(int cfg, int mode, const float* in, const ImplicitConv&
   if (int rc = split_setup(cfg, M, N, Kpad, splits, slab, tickets, C, ldc, epi.flags, &sk, &g, &tilesN)) return rc;
   float* out = sk.steps ? slab : C;
   const int ldo = sk.steps ? N : ldc;
-  // buffer-addressed DMA when each K-step is one tap (C % 32 == 0) and the descriptors fit.
+  // buffer-addressed DMA when each K-step is one tap (C % 32 == 0) and the descriptors fit
+  // (Switches::gemm_buf off: flat 64-bit addresses, experiments and the equivalence tests).
   // The descriptor base sits one row and one pixel before the input, which keeps a lane's
   // unsigned offset (its window's top-left pixel) non-negative for a top pad of at most 1; a
   // larger one (a 5x5 or 5x1 SAME conv) would wrap it into the range that reads as padding for
@@ -573,7 +572,7 @@ int launch_gemm_implicit(int cfg, int mode, const float* in, const ImplicitConv&
   const long long a_bytes = ((nimg * ic.H * ic.W + ic.W + 1) * (long long)ic.C) * 4;
   const long long b_bytes = (long long)tilesN * ci.bn * ldb * 4;
   BufDesc bd{in - (size_t)(ic.W + 1) * ic.C, (unsigned)a_bytes, (unsigned)b_bytes};
-  const BufDesc* pbd = (abuf_enabled() && ic.C % 32 == 0 && buf_pads_ok(ic) && fits_buf(a_bytes) && fits_buf(b_bytes))
+  const BufDesc* pbd = (sws.gemm_buf && ic.C % 32 == 0 && buf_pads_ok(ic) && fits_buf(a_bytes) && fits_buf(b_bytes))
                            ? &bd
                            : nullptr;
   if (mode == GEMM_IMPLICIT)
@@ -584,18 +583,6 @@ int launch_gemm_implicit(int cfg, int mode, const float* in, const ImplicitConv&
 }
 
 // ---- persistent short-K implicit GEMM (gemm_persist.h)
-static int device_cus() {
-  static int cus[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
-  if (!cus[dev]) {
-    int v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) v = 0;
-    cus[dev] = v;
-  }
-  return cus[dev];
-}
-
 template <int BM, int BN, int WM, int WN, int MF, int NS, int MODE, int NTN>
 static int launch_persist_t(const float* Bt, int ldb, float* C, int ldc, int M, int N, int Kpad,
                             const EpiParams& epi, int tilesN, int ntiles, const ImplicitConv& ic, const BufDesc& bd,
@@ -608,7 +595,7 @@ static int launch_persist_t(const float* Bt, int ldb, float* C, int ldc, int M, 
     per_cu = v;
   }
   const int wgs = per_cu;
-  long long grid = (long long)device_cus() * wgs;
+  long long grid = (long long)device_cu_count() * wgs;
   // fewer than two tiles per workgroup: the tail of the ones holding two costs more than the
   // pipelining gains (conv4 at batch 64: 452 tiles on 448 slots, 0.224 -> 0.317 ms)
   if (ntiles < 2 * grid || Kpad / 32 < NS) return -3;
@@ -619,22 +606,15 @@ static int launch_persist_t(const float* Bt, int ldb, float* C, int ldc, int M, 
   return check_launch("gemm_persist");
 }
 
-// DNN_HIP_PERSIST: 0 off, 1 (default) on the configs where it measured faster (256x64: conv2
-// 0.236 -> 0.228 ms; on 64x128 the static tile split lost to the hardware's dynamic one, conv3
-// 0.214 -> 0.224), 2 on every covered config (tests, experiments)
-static int persist_level() {
-  const char* e = getenv("DNN_HIP_PERSIST");
-  return e ? atoi(e) : 1;
-}
-bool persist_enabled() { return persist_level() > 0; }
-
 // Persistent launch of an unsplit implicit conv on the batch configs conv2-conv4 use;
 // returns -3 (caller falls back to launch_gemm_implicit) when the shape or config is not one
-// it covers.
-int launch_gemm_persist(int cfg, int mode, const float* in, const ImplicitConv& ic_in, const float* Bt, int ldb,
+// it covers.  Switches::persist: 0 off, 1 (default) on the configs where it measured faster
+// (256x64: conv2 0.236 -> 0.228 ms; on 64x128 the static tile split lost to the hardware's
+// dynamic one, conv3 0.214 -> 0.224), 2 on every covered config (tests, experiments)
+int launch_gemm_persist(const Switches& sws, int cfg, int mode, const float* in, const ImplicitConv& ic_in, const float* Bt, int ldb,
                         float* C, int ldc, long long M, int N, int Kpad, const EpiParams& epi, hipStream_t stream) {
   if (M == 0 || N == 0) return 0;
-  if (!persist_enabled() || (mode != GEMM_IMPLICIT && mode != GEMM_IMPLICIT_POOL) || ic_in.C % 32 != 0 ||
+  if (sws.persist <= 0 || (mode != GEMM_IMPLICIT && mode != GEMM_IMPLICIT_POOL) || ic_in.C % 32 != 0 ||
       !buf_pads_ok(ic_in) ||  // (buffer addresses only: see launch_gemm_implicit)
       M > 0x7fffffffLL || Kpad % 32 != 0 || !implicit_conv_supported(ic_in.C, ic_in.kh, ic_in.kw) ||
       (mode == GEMM_IMPLICIT_POOL && M % 4 != 0) || (epi.flags & EPI_OUT_X3))  // (split-plane output: tile kernel)
@@ -666,7 +646,7 @@ int launch_gemm_persist(int cfg, int mode, const float* in, const ImplicitConv& 
     DNN_PERSIST_N(BM_, BN_, WM_, WN_, MF_, NS_, 1);                                                                   \
   }                                                                                                                   \
   DNN_PERSIST_N(BM_, BN_, WM_, WN_, MF_, NS_, 2)
-  if (cfg != GEMM_G256x64_K32 && persist_level() < 2) return -3;
+  if (cfg != GEMM_G256x64_K32 && sws.persist < 2) return -3;
   switch (cfg) {
     case GEMM_G256x64_K32: DNN_PERSIST(256, 64, 4, 2, 32, 2);
     case GEMM_64x128_K32: DNN_PERSIST(64, 128, 2, 2, 32, 2);

@@ -104,7 +104,7 @@ static int launch16_any(int cfg, const half_t* A, int lda, const half_t* Bt, int
                                st);
 }
 
-int launch_gemm16(int cfg, int mode, const half_t* A, int lda, const ImplicitConv& ic_in, const half_t* Bt, int ldb,
+int launch_gemm16(const Switches& sws, int cfg, int mode, const half_t* A, int lda, const ImplicitConv& ic_in, const half_t* Bt, int ldb,
                   half_t* C, int ldc, long long M, int N, int Kpad, const EpiParams& epi, hipStream_t stream,
                   int splits, float* slab, unsigned* tickets) {
   if (M == 0 || N == 0) return 0;
@@ -129,7 +129,7 @@ int launch_gemm16(int cfg, int mode, const half_t* A, int lda, const ImplicitCon
   const long long b_bytes = (long long)((N + 511) / 512) * 512 * ldb * 2;
   // (a top pad above 1 would take a lane's offset below the shifted base: flat addresses)
   const bool shape_ok = mode == GEMM_DENSE || ((ic.C % 64 == 0 || ic.C == 32) && buf_pads_ok(ic));
-  const bool abuf = !getenv_flag_off("DNN_HIP_GEMM_BUF") && shape_ok && a_bytes > 0 && a_bytes < 0x80000000LL &&
+  const bool abuf = sws.gemm_buf && shape_ok && a_bytes > 0 && a_bytes < 0x80000000LL &&
                     b_bytes > 0 && b_bytes < 0x80000000LL;
   if (cfg == GEMM16_128x512_W16 && !abuf) cfg = GEMM16_128x128;  // same MFMA family and K order
   const Cfg16Info ci = kCfg16[cfg];
@@ -300,13 +300,8 @@ int launch_maxpool16(const half_t* in, half_t* out, const PoolGeom& g, hipStream
 // v_mfma_f32_16x16x32_f16; weights packed in order 4 ([n/16][k/32][lane][8])
 constexpr int P16_NPR = 320, P16_BM = 176;
 int patch16_pack_order() { return 4; }
-constexpr bool P16_DEFAULT = true;  // measured: conv6 0.1415 -> 0.1286 ms, conv7 equal (batch 64)
-
-// DNN_HIP_PATCH16=0/1 overrides the default choice of the patch kernel for eligible layers
-static bool patch16_enabled() {
-  const char* e = getenv("DNN_HIP_PATCH16");
-  return e ? e[0] == '1' : P16_DEFAULT;
-}
+// (eligible layers take it unless Switches::patch16 is off; measured at batch 64: conv6 0.1415 ->
+// 0.1286 ms, conv7 equal)
 
 // rows of the padded input one bm-row tile spans (tap offsets included)
 static int patch16_span(long long M, int H, int W) {
@@ -348,10 +343,10 @@ static bool patch16_fits(long long span, int W) {
   return span <= P16_NPR && span * 10 + 12 * (span / (W + 2) + 2) <= 7 * 8 * 64;
 }
 
-bool conv_patch16_supported(int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
+bool conv_patch16_supported(const Switches& sws, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
                             int pl) {
   return kh == 3 && kw == 3 && sh == 1 && sw == 1 && pt == 1 && pl == 1 && OH == H && OW == W && C % 64 == 0 &&
-         OC % 256 == 0 && patch16_enabled() && H > 0 && W > 0 &&
+         OC % 256 == 0 && sws.patch16 && H > 0 && W > 0 &&
          patch16_fits(patch16_span_any(H, W, P16_BM), W);
 }
 
@@ -390,12 +385,6 @@ struct Tile16Shape {
 };
 static constexpr Tile16Shape kTile16[] = {{8, 52, 4, 7}, {4, 52, 2, 7}, {8, 26, 2, 7}};
 
-// DNN_HIP_TILE16=0 keeps these layers on the implicit fp16 GEMM (A/B experiments)
-static bool tile16_enabled() {
-  const char* e = getenv("DNN_HIP_TILE16");
-  return !(e && e[0] == '0');
-}
-
 // the tile shape computing the fewest rows for the frame (ties: the first, the widest workgroup)
 static int tile16_shape(int H, int W) {
   int best = 0;
@@ -408,16 +397,17 @@ static int tile16_shape(int H, int W) {
   return best;
 }
 
-// shape limits only (the launcher's check); the plan also applies the DNN_HIP_TILE16 switch
+// shape limits only (the launcher's check); the plan also applies Switches::tile16 (off: these
+// layers stay on the implicit fp16 GEMM, A/B experiments)
 static bool tile16_shape_ok(int C, int OC, int H, int W) {
   return C % 32 == 0 && OC % 64 == 0 && H % 2 == 0 && W % 2 == 0 && H >= 2 && W >= 2 &&
          (long long)(H + 2) * (W + 2) * C * 2 < 0x40000000LL && (long long)OC * 9 * C * 2 < 0x80000000LL;
 }
 
-bool conv_tile16_supported(int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
+bool conv_tile16_supported(const Switches& sws, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
                            int pl) {
   return kh == 3 && kw == 3 && sh == 1 && sw == 1 && pt == 1 && pl == 1 && OH == H && OW == W &&
-         tile16_shape_ok(C, OC, H, W) && tile16_enabled();
+         tile16_shape_ok(C, OC, H, W) && sws.tile16;
 }
 
 template <int SH, int WN, int FL>
@@ -429,13 +419,6 @@ static void tile16_launch(dim3 grid, hipStream_t s, const half_t* in, const half
                      Bt, ldb, out, N, epi, tilesX, tilesY, tilesN, nsp, g, in_bytes, b_bytes);
 }
 
-// persistent workgroups per CU (two: the kernel's registers allow two waves per SIMD);
-// DNN_HIP_TILE16_WGS=n overrides it, 0 = one tile per workgroup
-static int tile16_wgs_per_cu() {
-  const char* e = getenv("DNN_HIP_TILE16_WGS");
-  return e ? atoi(e) : 2;
-}
-
 #ifndef IMG16_BR
 #define IMG16_BR 3
 #endif
@@ -443,12 +426,13 @@ static int tile16_wgs_per_cu() {
 static bool img16_shape_ok(int C, int OC, int H, int W) {
   return H == 13 && W == 13 && C % 32 == 0 && OC % 64 == 0 && (long long)OC * 9 * C * 2 < 0x80000000LL;
 }
-bool conv_img16_supported(int C, int OC, int H, int W) {
-  const char* e = getenv("DNN_HIP_IMG16");
-  return img16_shape_ok(C, OC, H, W) && tile16_enabled() && !(e && e[0] == '0');
+bool conv_img16_supported(const Switches& sws, int C, int OC, int H, int W) {
+  return img16_shape_ok(C, OC, H, W) && sws.tile16 && sws.img16;
 }
 
-static int launch_img16(const half_t* in_padded, const half_t* Bt, int ldb, half_t* out, int out_padded, int n, int N,
+// wpc: persistent workgroups per CU (Switches::tile16_wgs; two: the kernel's registers allow two
+// waves per SIMD), 0 = one tile per workgroup
+static int launch_img16(int wpc, const half_t* in_padded, const half_t* Bt, int ldb, half_t* out, int out_padded, int n, int N,
                         int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream) {
   if (!img16_shape_ok(C, N, H, W) || K != 9 * C || ldb < K || ldb % 32 != 0) {
     set_error("conv_img16: unsupported shape N=%d K=%d %dx%dx%d ldb=%d", N, K, H, W, C, ldb);
@@ -460,9 +444,7 @@ static int launch_img16(const half_t* in_padded, const half_t* Bt, int ldb, half
   const long long img_out = (long long)(H + 2 * out_padded) * (W + 2 * out_padded) * N;  // halves
   const unsigned b_bytes = (unsigned)((long long)N * ldb * 2);
   constexpr int F16YOLO = EPI_BN_AB | EPI_LEAKY_F32;
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int wpc = tile16_wgs_per_cu();
+  const int cus = device_cu_count();
   const int per = (int)std::min<long long>(n, 0x7fffffffLL / img_in);
   for (int f0 = 0; f0 < n; f0 += per) {
     const int nf = std::min(per, n - f0);
@@ -483,10 +465,10 @@ static int launch_img16(const half_t* in_padded, const half_t* Bt, int ldb, half
   return 0;
 }
 
-int launch_conv_tile16(const half_t* in_padded, const half_t* Bt, int ldb, half_t* out, int out_padded, int n, int N,
+int launch_conv_tile16(const Switches& sws, const half_t* in_padded, const half_t* Bt, int ldb, half_t* out, int out_padded, int n, int N,
                        int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream, int pool) {
   if (n == 0 || N == 0) return 0;
-  if (pool == 2) return launch_img16(in_padded, Bt, ldb, out, out_padded, n, N, K, H, W, C, epi, stream);
+  if (pool == 2) return launch_img16(sws.tile16_wgs, in_padded, Bt, ldb, out, out_padded, n, N, K, H, W, C, epi, stream);
   if (pool != 1 || !tile16_shape_ok(C, N, H, W) || K != 9 * C || ldb < K ||
       ldb % 32 != 0) {
     set_error("conv_tile16: unsupported shape N=%d K=%d %dx%dx%d ldb=%d", N, K, H, W, C, ldb);
@@ -501,9 +483,7 @@ int launch_conv_tile16(const half_t* in_padded, const half_t* Bt, int ldb, half_
   const long long img_out = (long long)(H / 2 + 2 * out_padded) * (W / 2 + 2 * out_padded) * N;  // halves
   const unsigned b_bytes = (unsigned)((long long)N * ldb * 2);
   constexpr int F16YOLO = EPI_BN_AB | EPI_LEAKY_F32;  // the fp16 path's folded epilogue, compiled in
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const int wpc = tile16_wgs_per_cu();
+  const int cus = device_cu_count(), wpc = sws.tile16_wgs;
   // frames per launch: the input's byte offsets stay 32-bit
   const int per = (int)std::min<long long>(n, 0x7fffffffLL / img_in);
   for (int f0 = 0; f0 < n; f0 += per) {

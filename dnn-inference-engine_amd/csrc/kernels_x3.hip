@@ -374,13 +374,9 @@ int launch_pack_weights_h2(const float* w, bf16_bits* out, int K, int N, int Npa
 // ---- the conv
 constexpr int X3_BM = 176, X3_NPR = 320;
 
-// DNN_HIP_X3=0 keeps these layers on the fp32 MFMA (implicit GEMM).  The DNN_HIP_* switches are
-// read by the *_supported functions the plan calls when it chooses a layer's kernel; launchers
-// check shape limits only, so a plan keeps running what it chose if the environment changes later.
-static bool x3_enabled() {
-  const char* e = getenv("DNN_HIP_X3");
-  return !(e && e[0] == '0');
-}
+// Switches::x3 off keeps these layers on the fp32 MFMA (implicit GEMM).  The *_supported functions
+// apply the plan's switches when it chooses a layer's kernel; launch_conv_x3 takes the same
+// Switches for the form of a launch, the other launchers check shape limits only.
 
 constexpr int X3_NPR_POOL = 352;  // pool-window-major tiles span more rows (26x26: 350)
 
@@ -413,7 +409,7 @@ constexpr int X3T_TM = 7;  // row blocks of 16 per wave
 // which kernel runs an x3 layer: 0 the row-run kernel (N % 256 == 0), 1 tile kernel N = 64 from
 // one 32-channel chunk, 2 tile kernel N % 128 == 0 (double-buffered chunks), 3 the 16-channel
 // kernel (fp32 input, split while staged); -1 none (the layer stays on the fp32 MFMA).  Shape
-// only: DNN_HIP_X3_C16=0 is applied by conv_x3_supported at plan time.
+// only: Switches::x3_c16 is applied by conv_x3_supported.
 static int x3_kind(int N, int C) {
   if (C == 16) return N == 32 ? 3 : -1;
   if (N % 256 == 0) return 0;
@@ -424,13 +420,12 @@ static int x3_kind(int N, int C) {
 
 int conv_x3_kind(int OC, int C) { return x3_kind(OC, C); }
 
-bool conv_x3_supported(int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt, int pl) {
+bool conv_x3_supported(const Switches& sws, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt, int pl) {
   if (!(kh == 3 && kw == 3 && sh == 1 && sw == 1 && pt == 1 && pl == 1 && OH == H && OW == W &&
-        (C % 32 == 0 || C == 16) && x3_enabled()))
+        (C % 32 == 0 || C == 16) && sws.x3))
     return false;
   const int kind = x3_kind(OC, C);
-  if (kind < 0 || ((kind == 1 || kind == 2) && getenv_flag_off("DNN_HIP_X3_TILE")) ||
-      (kind == 3 && getenv_flag_off("DNN_HIP_X3_C16")))
+  if (kind < 0 || ((kind == 1 || kind == 2) && !sws.x3_tile) || (kind == 3 && !sws.x3_c16))
     return false;
   // a tile must fit the patch for any batch: spans grow with M only until a tile crosses whole
   // images, so two images' worth of rows decides it (tile kernel: fixed patch)
@@ -462,7 +457,7 @@ size_t x3_h2_act_bytes(long long nimg, int H, int W, int C) { return (size_t)nim
 int x3_splits(int N, int K) { return (N % 256 == 0 && N > 256 && N <= 512 && (K / 288) % 2 == 0) ? 2 : 1; }
 
 
-int launch_conv_x3(const bf16_bits* in_split, const bf16_bits* Bt, float* out, bf16_bits* out_split, long long M,
+int launch_conv_x3(const Switches& sws, const bf16_bits* in_split, const bf16_bits* Bt, float* out, bf16_bits* out_split, long long M,
                    int N, int Npad, int K, int H, int W, int C, const EpiParams& epi, hipStream_t stream, int splits,
                    int pool, bool lat, int out_h2, unsigned* range_flag) {
   if (M == 0 || N == 0) return 0;
@@ -494,8 +489,8 @@ int launch_conv_x3(const bf16_bits* in_split, const bf16_bits* Bt, float* out, b
     const X3Geom xg{H, W, C, out_split ? 1 : 0, 1, PH, PW};
     const float* in32p = reinterpret_cast<const float*>(in_split);
     (void)b16;
-    // (two accumulators per output, gemm_x3_patch.h x3_step).  DNN_HIP_X3_C16P=0 (read per
-    // launch, experiments): one tile per workgroup (conv3x3_x3_c16_kernel); default: persistent
+    // (two accumulators per output, gemm_x3_patch.h x3_step).  Switches::x3_c16p off
+    // (experiments): one tile per workgroup (conv3x3_x3_c16_kernel); default: persistent
     // (conv3x3_x3_c16p_kernel, the last K step on 16x16x16; measured at batch 64: conv1 0.164 ->
     // 0.152 ms, forward -14 us), same bits up to the K = 16 step's summation
     // latency plans (one frame: 104 tiles of 16 x 26): 4 x 26 tiles, 4 waves of 2 row blocks, 416
@@ -506,20 +501,19 @@ int launch_conv_x3(const bf16_bits* in_split, const bf16_bits* Bt, float* out, b
       const int ty4 = (H + 3) / 4;
       hipLaunchKernelGGL((conv3x3_x3_c16_kernel<4, 26, 4, 2, true>), dim3((unsigned)(nimg * tilesX * ty4)), dim3(256), 0,
                          stream, in32p, Bt, out, out_split, N, epi, tilesX, ty4, xg, (unsigned)in32);
-    } else if (pool && out_split && blocks >= 4LL * device_cu_count() && !getenv_flag_off("DNN_HIP_X3_C16PP") &&
-               !getenv_flag_off("DNN_HIP_X3_C16P")) {
+    } else if (pool && out_split && blocks >= 4LL * device_cu_count() && sws.x3_c16pp && sws.x3_c16p) {
       // batch grids (>= 4 tiles per CU): the ping-pong form, one 512-thread workgroup per CU, the
-      // persistent kernel's bits (conv3x3_x3_c16pp_kernel).  DNN_HIP_X3_C16PP=0 (read per launch,
-      // A/B) keeps the two-workgroup persistent kernel; DNN_HIP_X3_PP_PRIO=0 the default priority
+      // persistent kernel's bits (conv3x3_x3_c16pp_kernel).  Switches::x3_c16pp off (A/B) keeps
+      // the two-workgroup persistent kernel; x3_pp_prio off the default priority
       const int G = device_cu_count();
-      const int prio = !getenv_flag_off("DNN_HIP_X3_PP_PRIO");
+      const int prio = sws.x3_pp_prio;
       if (epi.flags == X3_YOLO_FL)
         hipLaunchKernelGGL((conv3x3_x3_c16pp_kernel<X3_YOLO_FL>), dim3((unsigned)G), dim3(512), 0, stream, in32p, Bt,
                            out_split, epi, tilesX, tilesY, (int)blocks, xg, (unsigned)in32, prio);
       else
         hipLaunchKernelGGL((conv3x3_x3_c16pp_kernel<-1>), dim3((unsigned)G), dim3(512), 0, stream, in32p, Bt,
                            out_split, epi, tilesX, tilesY, (int)blocks, xg, (unsigned)in32, prio);
-    } else if (getenv_flag_off("DNN_HIP_X3_C16P") || !pool) {  // (the persistent kernel: the pooled form, conv1)
+    } else if (!sws.x3_c16p || !pool) {  // (the persistent kernel: the pooled form, conv1)
       if (pool)
         hipLaunchKernelGGL((conv3x3_x3_c16_kernel<16, 26, 4, 7, true>), dim3((unsigned)blocks), dim3(256), 0, stream,
                            in32p, Bt, out, out_split, N, epi, tilesX, tilesY, xg, (unsigned)in32);
@@ -575,15 +569,15 @@ int launch_conv_x3(const bf16_bits* in_split, const bf16_bits* Bt, float* out, b
     const bool yolo = epi.flags == X3_YOLO_FL;  // YOLO's epilogue set compiled in for the pooled forms
     // N = 64 from one chunk (conv2), pooled into split planes, batch grids of >= 4 tiles per CU:
     // the ping-pong kernel, one workgroup per CU (conv3x3_x3_pp_kernel; the tile kernel's bits).
-    // DNN_HIP_X3_PP=0 (read per launch, A/B) keeps the tile kernel, DNN_HIP_X3_PP_PRIO=0 its MFMA
-    // steps at the default priority.  (conv3's shape -- N = 128, two chunks, 192-B skewed rows --
+    // Switches::x3_pp off (A/B) keeps the tile kernel, x3_pp_prio off its MFMA steps at the
+    // default priority.  (conv3's shape -- N = 128, two chunks, 192-B skewed rows --
     // measured slower on it, 0.1199 vs 0.1133 ms: its MFMA steps are 3.6x its store steps, so the
     // two tile-kernel workgroups per CU already keep the MFMA pipes fed, and one workgroup per CU
     // serialises the CUs' 6.5 tiles.)
-    if (pool && out_split && !small && blocks >= 4LL * device_cu_count() && !getenv_flag_off("DNN_HIP_X3_PP") &&
+    if (pool && out_split && !small && blocks >= 4LL * device_cu_count() && sws.x3_pp &&
         kind == 1 && C == 32 && N == 64) {
       const int G = device_cu_count();
-      const int prio = !getenv_flag_off("DNN_HIP_X3_PP_PRIO");
+      const int prio = sws.x3_pp_prio;
 #define X3PP(TH_, WM_, WN_, NCH_, PU_, SK_, FL_, LEAD_)                                                             \
   hipLaunchKernelGGL((conv3x3_x3_pp_kernel<TH_, 26, WM_, WN_, X3T_TM, NCH_, PU_, SK_, FL_, LEAD_>), dim3((unsigned)G), \
                      dim3(512), 0, stream, in_split, Bt, out_split, N, epi, tilesX, tilesY, (int)blocks, xg,         \
@@ -695,24 +689,22 @@ int launch_conv_x3_h2(const bf16_bits* in_h2, const bf16_bits* Bt, float* out, b
 // ---- small-M x3 conv (latency plans, gemm_x3_lat.h): 64-column tiles (NCP = 2), one or two
 // chunks per workgroup, chosen so that a frame's layer is ~256 workgroups: two chunks when the
 // one-chunk grid would be >= 512 (conv7: 16 N tiles x 32 chunks), else one (conv6: 16 x 16).
-// DNN_HIP_X3L_CPW=1|2 forces it.  Read when a plan is built (x3_lat_splits fixes the layer's
-// slice count); the launch derives the chunks per workgroup from that count.
-static int x3_lat_cpw(int N, int K) {
-  const char* e = getenv("DNN_HIP_X3L_CPW");
-  const int force = e ? atoi(e) : 0;
+// Switches::x3l_cpw = 1 | 2 forces it.  x3_lat_splits fixes the layer's slice count when the plan
+// adds it; the launch derives the chunks per workgroup from that count.
+static int x3_lat_cpw(int force, int N, int K) {
   const int chunks = K / 288;
   if (force == 1 || force == 2) return chunks % force == 0 ? force : 1;
   return chunks % 2 == 0 && (long long)(N / 64) * chunks >= 512 ? 2 : 1;
 }
 
-int x3_lat_splits(int N, int K) { return (K / 288) / x3_lat_cpw(N, K); }
+int x3_lat_splits(const Switches& sws, int N, int K) { return (K / 288) / x3_lat_cpw(sws.x3l_cpw, N, K); }
 
 constexpr int X3L_NPR_SMALL = 240;  // one 13x13 frame's tile spans 225 padded rows
 
-bool conv_x3_lat_supported(long long batch, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh,
+bool conv_x3_lat_supported(const Switches& sws, long long batch, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh,
                            int sw, int pt, int pl) {
   if (!(kh == 3 && kw == 3 && sh == 1 && sw == 1 && pt == 1 && pl == 1 && OH == H && OW == W && C % 32 == 0 &&
-        OC % 64 == 0 && x3_enabled()))
+        OC % 64 == 0 && sws.x3))
     return false;
   const long long M = batch * H * W;
   // only where one-chunk slices fill half the chip (conv6 / conv7 of a frame: 256 / 512): with
@@ -720,8 +712,7 @@ bool conv_x3_lat_supported(long long batch, int C, int OC, int H, int W, int OH,
   // batch 1) outweigh the x3 arithmetic (measured: conv3-conv5 at 64 workgroups, with their
   // pools in the combine, no faster than the fp32 MFMA's in-GEMM split-K)
   const long long wgs = (M + X3_BM - 1) / X3_BM * (OC / 64) * (C / 32);
-  const char* e = getenv("DNN_HIP_X3_LAT_MINWG");  // (experiments)
-  if (wgs < (e ? atoll(e) : 128)) return false;
+  if (wgs < sws.x3_lat_minwg) return false;
   return M <= 0x7fffffffLL && x3_span(M, H, W) <= X3_NPR;
 }
 
@@ -742,12 +733,12 @@ static int x3_ktile_shape(int C, int OC, int H, int W, int pool) {
 }
 
 // conv3x3_x3_img_kernel (gemm_x3_img.h): whole-image tiles, instantiated for YOLOv2-tiny's 13x13
-// frames.  DNN_HIP_X3_IMG=0 (plan time) keeps the wide kernel's K slices + the pool5 combine.
+// frames.  Switches::x3_img off keeps the wide kernel's K slices + the pool5 combine.
 static bool x3_img_shape_ok(int C, int OC, int H, int W) {
   return H == 13 && W == 13 && C % 32 == 0 && OC % 128 == 0;
 }
-bool conv_x3_img_supported(int C, int OC, int H, int W) {
-  return x3_img_shape_ok(C, OC, H, W) && x3_enabled() && !getenv_flag_off("DNN_HIP_X3_IMG");
+bool conv_x3_img_supported(const Switches& sws, int C, int OC, int H, int W) {
+  return x3_img_shape_ok(C, OC, H, W) && sws.x3 && sws.x3_img;
 }
 
 int launch_conv_x3_img(const bf16_bits* in_split, const bf16_bits* Bt, float* out, bf16_bits* out_split, int n, int N,
@@ -776,10 +767,10 @@ int launch_conv_x3_img(const bf16_bits* in_split, const bf16_bits* Bt, float* ou
   return check_x3("conv_x3_img");
 }
 
-bool conv_x3_ktile_supported(long long batch, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh,
+bool conv_x3_ktile_supported(const Switches& sws, long long batch, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh,
                              int sw, int pt, int pl, int pool) {
   if (!(kh == 3 && kw == 3 && sh == 1 && sw == 1 && pt == 1 && pl == 1 && OH == H && OW == W)) return false;
-  if (!x3_enabled() || x3_ktile_shape(C, OC, H, W, pool) < 0) return false;
+  if (!sws.x3 || x3_ktile_shape(C, OC, H, W, pool) < 0) return false;
   return (long long)x3_act_bytes(batch, H, W, C) < 0x80000000LL &&
          (long long)(OC / 16) * (9 * C / 32) * 3072 < 0x80000000LL;
 }
@@ -851,8 +842,8 @@ static bool x3_1x1_ktile_shape_ok(int C, int OC, int H, int W) {
   const int nq = C / 128;
   return C % 128 == 0 && (nq == 1 || nq == 2 || nq == 4 || nq == 8) && OC >= 1 && H >= 1 && W >= 1;
 }
-bool conv_x3_1x1_ktile_supported(int C, int OC, int H, int W) {
-  return x3_1x1_ktile_shape_ok(C, OC, H, W) && x3_enabled() && !getenv_flag_off("DNN_HIP_X3_1X1");
+bool conv_x3_1x1_ktile_supported(const Switches& sws, int C, int OC, int H, int W) {
+  return x3_1x1_ktile_shape_ok(C, OC, H, W) && sws.x3 && sws.x3_1x1;
 }
 
 int launch_conv_x3_1x1_ktile(const bf16_bits* in_split, const bf16_bits* Bt, float* out, long long M, int N, int Npad,
@@ -935,8 +926,8 @@ int launch_conv_x3_lat(const bf16_bits* in_split, const bf16_bits* Bt, float* pa
 namespace dnnhip {
 
 // ---- 1x1 x3 conv (gemm_x3_1x1.h): YOLOv2-tiny conv8 on its producer's split planes
-bool conv_x3_1x1_supported(int C, int OC, int H, int W) {
-  return C % 32 == 0 && C >= 32 && OC >= 1 && H >= 1 && W >= 1 && x3_enabled() && !getenv_flag_off("DNN_HIP_X3_1X1");
+bool conv_x3_1x1_supported(const Switches& sws, int C, int OC, int H, int W) {
+  return C % 32 == 0 && C >= 32 && OC >= 1 && H >= 1 && W >= 1 && sws.x3 && sws.x3_1x1;
 }
 
 int launch_conv_x3_1x1(const bf16_bits* in_split, const bf16_bits* Bt, float* out, long long M, int N, int Npad, int K,

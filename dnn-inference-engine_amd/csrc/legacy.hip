@@ -78,6 +78,7 @@ int legacy_conv(const float* in, const float* w, int order, float* out, int B, i
   DNN_REQUIRE((oh - 1) * sh + kh <= ih && (ow - 1) * sw + kw <= iw,
               "conv: output %dx%d does not fit the padded input %dx%d", oh, ow, ih, iw);
   if (B == 0) return 0;
+  const Switches sws = read_switches();  // per call: this ABI has no plan to keep them
   std::lock_guard<std::mutex> lk(g_mu);
   if (int rc = ensure_device()) return rc;
   const long long M = (long long)B * oh * ow;
@@ -95,7 +96,7 @@ int legacy_conv(const float* in, const float* w, int order, float* out, int B, i
   if (int rc = h2d(d_w, w, (size_t)K * od)) return rc;
   if (int rc = launch_pack_weights(d_w, d_bt, K, od, Kpad, Npad, order, kh, kw, ic, 0)) return rc;
   ConvGeom g{B, ih, iw, ic, oh, ow, kh, kw, sh, sw, 0, 0, K, Kpad};
-  if (int rc = launch_im2col(d_in, d_col, g, 0)) return rc;
+  if (int rc = launch_im2col(sws, d_in, d_col, g, 0)) return rc;
   EpiParams epi{nullptr, nullptr, nullptr, nullptr, 0};
   // same split-K rule as the plan, so per-op and fused results agree bit for bit
   const int splits = (cfg >= GEMM_128x128_K32 && Kpad == K) ? choose_splitk(od, K) : 1;
@@ -104,7 +105,7 @@ int legacy_conv(const float* in, const float* w, int order, float* out, int B, i
     d_slab = slot(5, (size_t)splits * M * od);
     if (!d_slab) return -1;
   }
-  if (int rc = launch_gemm(cfg, d_col, Kpad, d_bt, Kpad, d_out, od, M, od, Kpad, epi, 0, splits, d_slab)) return rc;
+  if (int rc = launch_gemm(sws, cfg, d_col, Kpad, d_bt, Kpad, d_out, od, M, od, Kpad, epi, 0, splits, d_slab)) return rc;
   if (splits > 1)
     if (int rc = launch_splitk_reduce(d_slab, splits, M, od, d_out, od, epi, 0)) return rc;
   return d2h(out, d_out, n_out);

@@ -89,9 +89,61 @@ void set_error(const char* fmt, ...) {
 }
 const char* last_error() { return g_last_error.c_str(); }
 
-bool getenv_flag_off(const char* name) {
-  const char* e = getenv(name);
-  return e && e[0] == '0';
+// The one reader of the environment (dnn_common.h: Switches holds the defaults).  DNN_HIP_LIB,
+// _DEVICE, _PRECISION, _LATENCY and _NO_TORCH belong to the Python package.
+Switches read_switches() {
+  Switches s;
+  // a switch that is on unless its variable starts with '0'
+  auto on = [](const char* name) {
+    const char* e = getenv(name);
+    return !(e && e[0] == '0');
+  };
+  auto num = [](const char* name, long long unset) {
+    const char* e = getenv(name);
+    return e ? atoll(e) : unset;
+  };
+  // "K:v,K:v,..." up to the first entry that does not parse
+  auto pairs = [](const char* name) {
+    std::vector<std::pair<int, int>> out;
+    const char* e = getenv(name);
+    for (const char* q = e ? e : ""; *q;) {
+      int k = 0, v = 0, n = 0;
+      if (sscanf(q, "%d:%d%n", &k, &v, &n) != 2) break;
+      out.emplace_back(k, v);
+      q += n;
+      if (*q == ',') ++q;
+    }
+    return out;
+  };
+  s.fuse = on("DNN_HIP_FUSE");
+  s.patch = on("DNN_HIP_PATCH");
+  s.splitk_fused = on("DNN_HIP_SPLITK_FUSED");
+  s.cfg = pairs("DNN_HIP_CFG");
+  s.split = pairs("DNN_HIP_SPLIT");
+  s.x3 = on("DNN_HIP_X3");
+  s.x3_tile = on("DNN_HIP_X3_TILE");
+  s.x3_c16 = on("DNN_HIP_X3_C16");
+  s.x3_img = on("DNN_HIP_X3_IMG");
+  s.x3_1x1 = on("DNN_HIP_X3_1X1");
+  s.x3_h2 = on("DNN_HIP_X3_H2");
+  s.x3l_cpw = (int)num("DNN_HIP_X3L_CPW", s.x3l_cpw);
+  s.x3_lat_minwg = num("DNN_HIP_X3_LAT_MINWG", s.x3_lat_minwg);
+  s.x3_c16p = on("DNN_HIP_X3_C16P");
+  s.x3_c16pp = on("DNN_HIP_X3_C16PP");
+  s.x3_pp = on("DNN_HIP_X3_PP");
+  s.x3_pp_prio = on("DNN_HIP_X3_PP_PRIO");
+  if (const char* e = getenv("DNN_HIP_PATCH16")) s.patch16 = e[0] == '1';
+  s.tile16 = on("DNN_HIP_TILE16");
+  s.img16 = on("DNN_HIP_IMG16");
+  s.f16_direct_out = on("DNN_HIP_F16_DIRECT_OUT");
+  s.tile16_wgs = (int)num("DNN_HIP_TILE16_WGS", s.tile16_wgs);
+  s.c1f16_wgs = (int)num("DNN_HIP_C1F16_WGS", s.c1f16_wgs);
+  s.gemm_buf = on("DNN_HIP_GEMM_BUF");
+  s.persist = (int)num("DNN_HIP_PERSIST", s.persist);
+  s.im2col_rows = on("DNN_HIP_IM2COL_ROWS");
+  s.c0_grid = (int)num("DNN_HIP_C0_GRID", s.c0_grid);
+  s.c0_d16 = on("DNN_HIP_C0_D16");
+  return s;
 }
 
 int device_cu_count() {
@@ -187,9 +239,9 @@ struct PlanLayer {
   bool out_padded = false;  // output written zero-bordered (the next layer reads_split_planes / is
                             // patch16 / tile16; fp32 plans: as x3 split planes)
   // The wide x3 conv on two fp16 pieces (gemm_x3_h2.h).  h2_ok is fixed when the layer is added
-  // (DNN_HIP_X3_H2 as read at plan creation, host weights all inside fp16's range); h2 (this layer
-  // runs the h2 kernel) and out_h2 (its split planes are the next layer's h2 planes) follow from
-  // the layer and its neighbour (resolve_h2), never from the batch
+  // (Switches::x3_h2, host weights all inside fp16's range); h2 (this layer runs the h2 kernel) and
+  // out_h2 (its split planes are the next layer's h2 planes) follow from the layer and its
+  // neighbour (resolve_h2), never from the batch
   bool h2_ok = false, h2 = false, out_h2 = false;
   size_t pad_off = 0;       // its zero-bordered output region: float offset inside the pad area
   int PH = 0, PW = 0;
@@ -260,13 +312,10 @@ struct WsMap {
 struct dnn_plan {
   int batch = 0, in_h = 0, in_w = 0, in_c = 0;
   int cur_h = 0, cur_w = 0, cur_c = 0;
-  bool fuse = true;
-  bool patch = true;
-  bool splitk_fused = true;  // fp32 split-K layers combine in the GEMM (no reduce kernel)
+  Switches sw;  // the DNN_HIP_* switches as dnn_plan_create read them: nothing later reads the environment
   int fp16 = 0;  // 1: fp16 activations/weights, fp16 MFMA, fp32 accumulate + epilogue
   bool direct_out = false;  // fp16: the last layer writes the fp32 output itself (fp16_direct_out)
   bool latency = false;  // split K by M too (dnn_plan_set_latency_mode): batch-1 latency plans
-  bool x3_h2 = true;     // DNN_HIP_X3_H2 (read once, at creation): eligible wide x3 layers run on two fp16 pieces
   std::vector<PlanLayer> layers;
   std::vector<Step> steps;  // what a run launches, in order (layout())
   // fork / join: slots by number (at most kMaxSlots, a released number is reused); regions (one
@@ -326,12 +375,10 @@ static void drop_graph(dnn_plan* p) {
   p->g_n = -1;
 }
 
-static bool fused_splitk(const dnn_plan* p) { return p->splitk_fused; }
-
 // fp16 plans whose last layer is a dense GEMM the fp32-output launcher covers (conv8): it writes
-// the plan's fp32 output itself, no output conversion kernel.  DNN_HIP_F16_DIRECT_OUT=0: off.
+// the plan's fp32 output itself, no output conversion kernel (Switches::f16_direct_out).
 static bool fp16_direct_out(const dnn_plan* p) {
-  if (!p->fp16 || p->layers.empty() || getenv_flag_off("DNN_HIP_F16_DIRECT_OUT")) return false;
+  if (!p->fp16 || p->layers.empty() || !p->sw.f16_direct_out) return false;
   const PlanLayer& L = p->layers.back();
   return L.is(CONV_DIRECT_A) && gemm16_f32out_supported(L.splits, L.Npad) && !L.out_padded;
 }
@@ -376,7 +423,7 @@ static void resolve_h2(dnn_plan* p) {
   for (auto& L : p->layers) L.h2 = L.out_h2 = false;
   // (latency plans: their own kernels, x3_lat / x3_ktile, never take h2; a layer that fills the
   // chip runs the batch kernel there too and chooses as in a batch plan)
-  if (p->fp16 || !p->x3_h2) return;
+  if (p->fp16 || !p->sw.x3_h2) return;
   auto wide = [](const PlanLayer& q) {
     return q.is(CONV_X3) && conv_x3_kind(q.OC, q.C) == 0 && q.pool == POOL_NONE && q.splits == 1;
   };
@@ -457,7 +504,7 @@ static void layout(dnn_plan* p) {
             step(i, STEP_X3_COMBINE, sum_flops, sum_bytes, LOC_NONE, out);
           }
         }
-      } else if (L.splits > 1 && fused_splitk(p)) {  // partials combined by the GEMM's last-arriving split
+      } else if (L.splits > 1 && p->sw.splitk_fused) {  // partials combined by the GEMM's last-arriving split
         const long long Mg = L.rows(p->batch);
         slab_fused = std::max(slab_fused, (size_t)(p->fp16 ? splitk16_fused_slab_floats(L.cfg, Mg, L.OC, L.splits)
                                                            : splitk_fused_slab_floats(L.cfg, Mg, L.OC, L.splits)));
@@ -585,12 +632,7 @@ int dnn_plan_create(int batch, int in_h, int in_w, int in_c, dnn_plan** out) {
   p->in_h = p->cur_h = in_h;
   p->in_w = p->cur_w = in_w;
   p->in_c = p->cur_c = in_c;
-  const char* f = getenv("DNN_HIP_FUSE");
-  p->fuse = !(f && f[0] == '0');
-  const char* pe = getenv("DNN_HIP_PATCH");
-  p->patch = !(pe && pe[0] == '0');
-  p->splitk_fused = !getenv_flag_off("DNN_HIP_SPLITK_FUSED");
-  p->x3_h2 = !getenv_flag_off("DNN_HIP_X3_H2");
+  p->sw = read_switches();
   *out = p;
   return 0;
 }
@@ -620,7 +662,7 @@ static void set_cfg(dnn_plan* p, PlanLayer& L) {
     L.cfg = 0;
     L.Kpad = L.C == 16 ? 160 : L.K;  // (16 channels: 5 steps of two taps)
     L.Npad = L.OC;  // (a multiple of 256, or of 32 / 64 / 128 for the tile kernels)
-    L.splits = L.variant == CONV_X3_KTILE ? 1 : L.variant == CONV_X3_LAT ? x3_lat_splits(L.OC, L.K) : x3_splits(L.OC, L.K);
+    L.splits = L.variant == CONV_X3_KTILE ? 1 : L.variant == CONV_X3_LAT ? x3_lat_splits(p->sw, L.OC, L.K) : x3_splits(L.OC, L.K);
     return;
   }
   if (p->fp16 && L.variant == CONV_PATCH16) {  // one config: 192x256 tiles, no split
@@ -638,39 +680,25 @@ static void set_cfg(dnn_plan* p, PlanLayer& L) {
     return;
   }
   L.cfg = L.variant == CONV_IMPLICIT ? choose_gemm_cfg_implicit(M, L.OC, L.K) : choose_gemm_cfg(M, L.OC, L.K);
-  if (const char* e = getenv("DNN_HIP_CFG")) {  // tuning experiments: "K:cfg,K:cfg,..."
-    for (const char* q = e; *q;) {
-      int k = 0, c = 0, n = 0;
-      if (sscanf(q, "%d:%d%n", &k, &c, &n) != 2) break;
-      if (k == L.K && c >= GEMM_128x128_K32 && c < GEMM_NUM_CFGS && c != GEMM_G64x32_K32) L.cfg = c;
-      q += n;
-      if (*q == ',') ++q;
-    }
-  }
+  for (const auto& [k, c] : p->sw.cfg)  // tuning experiments
+    if (k == L.K && c >= GEMM_128x128_K32 && c < GEMM_NUM_CFGS && c != GEMM_G64x32_K32) L.cfg = c;
   L.Kpad = (int)align_up(L.K, gemm_cfg_bk(L.cfg));
   L.Npad = (int)align_up(L.OC, gemm_cfg_bn(L.cfg));
-  L.splits = (L.cfg >= GEMM_128x128_K32 && L.Kpad == L.K) ? choose_splitk(L.OC, L.K, fused_splitk(p)) : 1;
+  L.splits = (L.cfg >= GEMM_128x128_K32 && L.Kpad == L.K) ? choose_splitk(L.OC, L.K, p->sw.splitk_fused) : 1;
   // one fp32 chain of K / 2 MFMAs misses the 2e-6 per-layer bar from K of about 4608 on (measured
   // 2.1e-6 .. 4.6e-6 at K = 4608 .. 9216, 2.7e-6 at 6125: DESIGN.md §2).  Long-K layers the
   // (N, K) rule leaves whole (N < 512; the explicit GEMM's zero-padded K too) are summed in three
   // or two parts like conv5-conv7: still a function of (N, K) and the config alone
-  if (L.splits == 1 && L.cfg >= GEMM_128x128_K32 && L.K >= 4608 && (fused_splitk(p) || L.OC % 4 == 0)) {
+  if (L.splits == 1 && L.cfg >= GEMM_128x128_K32 && L.K >= 4608 && (p->sw.splitk_fused || L.OC % 4 == 0)) {
     const int nk = L.Kpad / 32;
     L.splits = nk % 3 == 0 ? 3 : nk % 2 == 0 ? 2 : 1;
   }
-  if (p->latency && fused_splitk(p) && L.Kpad == L.K) {
+  if (p->latency && p->sw.splitk_fused && L.Kpad == L.K) {
     // a tile config and split for this M when the batch rule leaves the chip idle
     int cfg = L.cfg, sp = L.splits;
     choose_latency_plan(M, L.OC, L.K, &cfg, &sp, false);
-    if (const char* e = getenv("DNN_HIP_SPLIT")) {  // tuning experiments: "K:splits,..."
-      for (const char* q = e; *q;) {
-        int k = 0, v = 0, n = 0;
-        if (sscanf(q, "%d:%d%n", &k, &v, &n) != 2) break;
-        if (k == L.K && v >= 1 && v <= 32 && (L.Kpad / gemm_cfg_bk(cfg)) % v == 0 && cfg >= GEMM_128x128_K32) sp = v;
-        q += n;
-        if (*q == ',') ++q;
-      }
-    }
+    for (const auto& [k, v] : p->sw.split)  // tuning experiments
+      if (k == L.K && v >= 1 && v <= 32 && (L.Kpad / gemm_cfg_bk(cfg)) % v == 0 && cfg >= GEMM_128x128_K32) sp = v;
     L.cfg = cfg;
     L.splits = sp;
     L.Npad = (int)align_up(L.OC, gemm_cfg_bn(L.cfg));
@@ -751,7 +779,7 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
     // 3x3 wide layers whose producer (a separate pool or another such conv) can write a
     // zero-bordered output: the patch kernel (input staged once per 64-channel chunk)
     if (L.variant == CONV_IMPLICIT && !p->layers.empty() &&
-        conv_patch16_supported(L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt, L.pl)) {
+        conv_patch16_supported(p->sw, L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt, L.pl)) {
       PlanLayer& prev = p->layers.back();
       if (can_write_zero_bordered16(prev) && !prev.is(CONV_PATCH)) {  // (not behind the conv1 patch kernel)
         L.variant = CONV_PATCH16;
@@ -760,7 +788,7 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
     }
   } else if (one_by_one)
     L.variant = CONV_DIRECT_A;
-  else if (p->fuse && implicit_conv_supported(L.C, kh, kw) &&
+  else if (p->sw.fuse && implicit_conv_supported(L.C, kh, kw) &&
            choose_gemm_cfg_implicit((long long)p->batch * L.OH * L.OW, od, L.K) >= 0)
     L.variant = CONV_IMPLICIT;
   else
@@ -774,24 +802,24 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
   // conv6 / conv7 of a one-frame plan) when it makes at least two K slices
   bool x3_cand = false, x3_lat = false, x3_k = false;
   if (!p->fp16 && L.variant == CONV_IMPLICIT && !p->layers.empty()) {
-    const bool batch_ok = conv_x3_supported(L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt, L.pl);
+    const bool batch_ok = conv_x3_supported(p->sw, L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt, L.pl);
     // (the narrow kernels take small tiles in latency plans: batch_ok is enough.  conv1 at one
     // frame: the 16-channel kernel's 4 x 26 tiles 10.6 us, its 16 x 26 ones 11.7, the fp32 patch
     // conv 13.8 (HIP events, same box))
     const int xk = conv_x3_kind(od, L.C);
-    const bool lat = p->latency && fused_splitk(p);
+    const bool lat = p->latency && p->sw.splitk_fused;
     // latency plans: conv3-conv5 of a frame with the K split inside the workgroup (one launch, no
     // partials), first; conv1 / conv2 on the narrow kernels' small tiles; conv6 / conv7 on the
     // small-M kernel's K slices + combine
     const bool fills = batch_ok && x3_tiles(p->batch, L.OH, L.OW, od, L.C, L.K) >= 128;  // the batch tiles fill the chip
     x3_k = lat && !fills &&
-           conv_x3_ktile_supported(p->batch, L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt, L.pl, 0);
+           conv_x3_ktile_supported(p->sw, p->batch, L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt, L.pl, 0);
     if (x3_k) {
       x3_cand = true;
     } else if (lat && !(batch_ok && (xk > 0 || x3_tiles(p->batch, L.OH, L.OW, od, L.C, L.K) >= 128))) {
-      x3_lat = conv_x3_lat_supported(p->batch, L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt,
+      x3_lat = conv_x3_lat_supported(p->sw, p->batch, L.C, od, L.H, L.W, L.OH, L.OW, kh, kw, stride_h, stride_w, L.pt,
                                      L.pl) &&
-               x3_lat_splits(od, L.K) >= 2;
+               x3_lat_splits(p->sw, od, L.K) >= 2;
       x3_cand = x3_lat;
     } else {
       x3_cand = batch_ok;
@@ -804,10 +832,10 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
   // 21 us against 14)
   // (latency plans whose frame leaves those tiles few: the K-split 1x1 form, 16 x 32 tiles)
   const long long t1x1 = ((long long)p->batch * L.OH * L.OW + 31) / 32 * ((od + 127) / 128);
-  const bool lat1x1 = p->latency && fused_splitk(p) && t1x1 < 256;
+  const bool lat1x1 = p->latency && p->sw.splitk_fused && t1x1 < 256;
   if (!p->fp16 && L.variant == CONV_DIRECT_A && !p->layers.empty() && p->layers.back().is_conv() &&
       is_x3(p->layers.back().variant) &&
-      (lat1x1 ? conv_x3_1x1_ktile_supported(L.C, od, L.H, L.W) : conv_x3_1x1_supported(L.C, od, L.H, L.W))) {
+      (lat1x1 ? conv_x3_1x1_ktile_supported(p->sw, L.C, od, L.H, L.W) : conv_x3_1x1_supported(p->sw, L.C, od, L.H, L.W))) {
     L.variant = lat1x1 ? CONV_X3_1X1_KTILE : CONV_X3_1X1;
     p->layers.back().out_padded = true;
   }
@@ -835,7 +863,7 @@ static int add_conv_layer(dnn_plan* p, int kh, int kw, int od, int stride_h, int
   if (ep.scale) L.epi_flags |= EPI_BN_AB;
   // (a shape-only layer, kernel == NULL, takes the choice of in-range weights: its arena comes
   // from a plan that checked them)
-  L.h2_ok = p->x3_h2 && L.variant == CONV_X3;
+  L.h2_ok = p->sw.x3_h2 && L.variant == CONV_X3;
   if (kernel) {
     L.have_host = true;
     L.w.assign(kernel, kernel + (size_t)L.K * od);
@@ -935,21 +963,21 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
   out_pads(L.W, kw, stride_w, padding, &L.OW, &L.pl);
   DNN_REQUIRE(L.OH > 0 && L.OW > 0, "dnn_plan_add_max_pool: empty output");
   // fuse a 2x2/stride-2 pool (front pads are 0 for both SAME and VALID) into the conv before it
-  if (p->fuse && !p->layers.empty() && kh == 2 && kw == 2 && stride_h == 2 && stride_w == 2 && L.pt == 0 &&
+  if (p->sw.fuse && !p->layers.empty() && kh == 2 && kw == 2 && stride_h == 2 && stride_w == 2 && L.pt == 0 &&
       L.pl == 0) {
     PlanLayer& prev = p->layers.back();
     // (latency plans: a split implicit conv keeps its split, the combine pools)
     if (prev.is_conv() && !prev.pool &&
         (prev.splits == 1 ||
-         (prev.variant == CONV_IMPLICIT && !p->fp16 && fused_splitk(p) && generic_combine_cfg(prev.cfg)))) {
+         (prev.variant == CONV_IMPLICIT && !p->fp16 && p->sw.splitk_fused && generic_combine_cfg(prev.cfg)))) {
       bool ok = false;
       if (prev.variant == CONV_IMPLICIT) {
         ok = true;
-        if (!p->fp16 && p->patch && prev.splits == 1 && patch_conv_pool_supported(prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw,
+        if (!p->fp16 && p->sw.patch && prev.splits == 1 && patch_conv_pool_supported(prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw,
                                                   prev.sh, prev.sw, prev.pt, prev.pl) &&
             prev.Kpad == patch_conv_kpad(prev.C))
           prev.variant = CONV_PATCH;  // same packed weights (Bt[Npad][Kpad]) as the implicit GEMM
-        if (p->fp16 && p->patch &&
+        if (p->fp16 && p->sw.patch &&
             conv1_patch_f16_supported(prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw, prev.sh,
                                       prev.sw, prev.pt, prev.pl))
           prev.variant = CONV_PATCH;  // fp16 patch kernel on the same fp16 Bt
@@ -957,7 +985,7 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
         // conv1 patch kernel, another tile or patch16 conv): the 2-D tile kernel (its weights
         // packed in order 5 into the same Npad x Kpad slot)
         if (p->fp16 && prev.variant == CONV_IMPLICIT && prev.splits == 1 && p->layers.size() >= 2 &&
-            conv_tile16_supported(prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw, prev.sh,
+            conv_tile16_supported(p->sw, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw, prev.sh,
                                   prev.sw, prev.pt, prev.pl) &&
             prev.Kpad % 32 == 0) {
           PlanLayer& q = p->layers[p->layers.size() - 2];
@@ -967,7 +995,7 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
           }
         }
       } else if (p->fp16 && prev.variant == CONV_PATCH16 &&
-                 conv_tile16_supported(prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw, prev.sh,
+                 conv_tile16_supported(p->sw, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw, prev.sh,
                                        prev.sw, prev.pt, prev.pl)) {
         prev.variant = CONV_TILE16;  // (its producer already writes the zero-bordered input) the pool fused
         ok = true;
@@ -977,7 +1005,7 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
         prev.variant = CONV_DIRECT;
         ok = true;
       } else if (is_x3(prev.variant) && !p->fp16 &&
-                 (prev.variant == CONV_X3_KTILE ? conv_x3_ktile_supported(p->batch, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW,
+                 (prev.variant == CONV_X3_KTILE ? conv_x3_ktile_supported(p->sw, p->batch, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW,
                                                      prev.kh, prev.kw, prev.sh, prev.sw, prev.pt, prev.pl, 1)
                            : conv_x3_pool_supported(prev.OC, prev.C, prev.H, prev.W))) {
         ok = true;  // pool-window-major rows, pooled before the epilogue in the x3 kernel
@@ -994,11 +1022,11 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
   }
   // a 2x2/stride-1 SAME pool (YOLO's pool5) into a single-frame x3_ktile conv before it: the conv
   // computes the row below each tile too and pools before its epilogue
-  if (p->fuse && !p->layers.empty() && kh == 2 && kw == 2 && stride_h == 1 && stride_w == 1 && L.pt == 0 &&
+  if (p->sw.fuse && !p->layers.empty() && kh == 2 && kw == 2 && stride_h == 1 && stride_w == 1 && L.pt == 0 &&
       L.pl == 0 && L.OH == L.H && L.OW == L.W) {
     PlanLayer& prev = p->layers.back();
     if (prev.is(CONV_X3_KTILE) && !prev.pool &&
-        conv_x3_ktile_supported(p->batch, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw,
+        conv_x3_ktile_supported(p->sw, p->batch, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw,
                                 prev.sh, prev.sw, prev.pt, prev.pl, 2)) {
       prev.pool = POOL_S1;
       return 0;
@@ -1008,7 +1036,7 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
     if (p->fp16 && (prev.is(CONV_IMPLICIT) || prev.is(CONV_PATCH16)) && !prev.pool && p->layers.size() >= 2 &&
         prev.kh == 3 && prev.kw == 3 && prev.sh == 1 && prev.sw == 1 && prev.pt == 1 && prev.pl == 1 &&
         prev.OH == prev.H && prev.OW == prev.W && prev.Kpad % 32 == 0 &&
-        conv_img16_supported(prev.C, prev.OC, prev.H, prev.W)) {
+        conv_img16_supported(p->sw, prev.C, prev.OC, prev.H, prev.W)) {
       PlanLayer& q = p->layers[p->layers.size() - 2];
       if (can_write_zero_bordered16(q)) {
         prev.variant = CONV_IMG16;
@@ -1020,7 +1048,7 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
     }
     // ... into a batch-tile x3 conv of a small frame (conv5 + pool5): whole-image tiles over all
     // of K (gemm_x3_img.h) instead of K slices whose partials the pool combines
-    if (prev.is(CONV_X3) && !prev.pool && prev.C != 16 && conv_x3_img_supported(prev.C, prev.OC, prev.H, prev.W)) {
+    if (prev.is(CONV_X3) && !prev.pool && prev.C != 16 && conv_x3_img_supported(p->sw, prev.C, prev.OC, prev.H, prev.W)) {
       prev.variant = CONV_X3_IMG;
       prev.pool = POOL_S1;
       prev.splits = 1;
@@ -1515,7 +1543,7 @@ static EpiParams epilogue(const dnn_plan* p, const PlanLayer& L) {
 }
 
 static unsigned* ticket_area(const dnn_plan* p) {  // (NULL: split layers leave partials for a reduce step)
-  return fused_splitk(p) ? reinterpret_cast<unsigned*>(p->ws + p->at.tickets) : nullptr;
+  return p->sw.splitk_fused ? reinterpret_cast<unsigned*>(p->ws + p->at.tickets) : nullptr;
 }
 
 // fp16 plans: fp16 activations between layers, fp32 frames in / predictions out
@@ -1552,24 +1580,24 @@ static int launch_step16(dnn_plan* p, const Step& st, const RunArgs& r) {
   switch (L.variant) {
     case CONV_DIRECT:  // (conv0: its source is the fp32 frames, its weights stay fp32)
       return conv0_mfma_supported(L.C, L.OC, L.kh, L.kw, L.sh, L.sw)
-                 ? launch_conv0_mfma_f16(src32, p->weights + L.w_off, dst, dg, L.C, epi, s)
+                 ? launch_conv0_mfma_f16(p->sw, src32, p->weights + L.w_off, dst, dg, L.C, epi, s)
                  : launch_conv3x3_pool2_direct_f16out(src32, p->weights + L.w_off, dst, dg, L.C, L.OC, epi, s);
     case CONV_PATCH:
-      return launch_conv1_patch_f16(cur, wt, L.Kpad, dst, dg, zero, epi, s, padded);
+      return launch_conv1_patch_f16(p->sw, cur, wt, L.Kpad, dst, dg, zero, epi, s, padded);
     case CONV_DIRECT_A:
       if (st.dst == LOC_OUT)  // (direct_out: the last layer writes the fp32 output)
         return launch_gemm16_f32out(cur, L.C, wt, L.Kpad, L.Npad, dst32, L.OC, Mc, L.OC, L.Kpad, epi, s);
-      return launch_gemm16(L.cfg, GEMM_DENSE, cur, L.C, ImplicitConv{}, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s,
+      return launch_gemm16(p->sw, L.cfg, GEMM_DENSE, cur, L.C, ImplicitConv{}, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s,
                            L.splits, slab, ticket_area(p));
     case CONV_PATCH16:
       return launch_conv_patch16(cur, wt, L.Kpad, dst, padded, Mc, L.OC, L.K, L.H, L.W, L.C, epi, s);
     case CONV_TILE16:
     case CONV_IMG16:
-      return launch_conv_tile16(cur, wt, L.Kpad, dst, padded, n, L.OC, L.K, L.H, L.W, L.C, epi, s, L.pool);
+      return launch_conv_tile16(p->sw, cur, wt, L.Kpad, dst, padded, n, L.OC, L.K, L.H, L.W, L.C, epi, s, L.pool);
     case CONV_IMPLICIT: {
       ImplicitConv ic{zero, L.H, L.W, L.C, L.OH, L.OW, L.PH, L.PW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl,
                       L.pool == POOL_S2 ? 1 : 0};
-      return launch_gemm16(L.cfg, L.pool == POOL_S2 ? GEMM_IMPLICIT_POOL : GEMM_IMPLICIT, cur, 0, ic, wt, L.Kpad, dst,
+      return launch_gemm16(p->sw, L.cfg, L.pool == POOL_S2 ? GEMM_IMPLICIT_POOL : GEMM_IMPLICIT, cur, 0, ic, wt, L.Kpad, dst,
                            L.OC, L.rows(n), L.OC, L.Kpad, epi, s, L.splits, slab, ticket_area(p));
     }
     default:
@@ -1593,7 +1621,7 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
   switch (st.kind) {
     case STEP_IM2COL: {
       ConvGeom g{n, L.H, L.W, L.C, L.OH, L.OW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl, L.K, L.Kpad};
-      return launch_im2col(cur, p->ws + p->at.col, g, s);
+      return launch_im2col(p->sw, cur, p->ws + p->at.col, g, s);
     }
     case STEP_CONV:
       break;  // (below)
@@ -1637,10 +1665,10 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
   unsigned* const range = oh2 ? range_word(p, L) : nullptr;
   switch (L.variant) {
     case CONV_GEMM:
-      return launch_gemm(L.cfg, p->ws + p->at.col, L.Kpad, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s, L.splits,
+      return launch_gemm(p->sw, L.cfg, p->ws + p->at.col, L.Kpad, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s, L.splits,
                          slab, ticket_area(p));
     case CONV_DIRECT_A:
-      return launch_gemm(L.cfg, cur, L.C, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s, L.splits, slab,
+      return launch_gemm(p->sw, L.cfg, cur, L.C, wt, L.Kpad, dst, L.OC, Mc, L.OC, L.Kpad, epi, s, L.splits, slab,
                          ticket_area(p));
     case CONV_IMPLICIT: {
       ImplicitConv ic{zero, L.H, L.W, L.C, L.OH, L.OW, L.PH, L.PW, L.kh, L.kw, L.sh, L.sw, L.pt, L.pl,
@@ -1655,15 +1683,15 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
         o = reinterpret_cast<float*>(dsplit);
       }
       // unsplit layers: the persistent kernel (same bits) when it covers the config
-      int rc = L.splits == 1 ? launch_gemm_persist(L.cfg, gm, cur, ic, wt, L.Kpad, o, L.OC, M, L.OC, L.Kpad, ep, s) : -3;
+      int rc = L.splits == 1 ? launch_gemm_persist(p->sw, L.cfg, gm, cur, ic, wt, L.Kpad, o, L.OC, M, L.OC, L.Kpad, ep, s) : -3;
       if (rc == -3)
-        rc = launch_gemm_implicit(L.cfg, gm, cur, ic, wt, L.Kpad, o, L.OC, M, L.OC, L.Kpad, ep, s, L.splits, slab,
+        rc = launch_gemm_implicit(p->sw, L.cfg, gm, cur, ic, wt, L.Kpad, o, L.OC, M, L.OC, L.Kpad, ep, s, L.splits, slab,
                                   ticket_area(p));
       return rc;
     }
     case CONV_DIRECT:
       return conv0_mfma_supported(L.C, L.OC, L.kh, L.kw, L.sh, L.sw)
-                 ? launch_conv0_mfma(cur, wt, dst, dg, L.C, zero, epi, s)
+                 ? launch_conv0_mfma(p->sw, cur, wt, dst, dg, L.C, zero, epi, s)
                  : launch_conv3x3_pool2_direct(cur, wt, dst, dg, L.C, L.OC, epi, s);
     case CONV_PATCH:
       return launch_conv3x3_patch_pool(cur, wt, L.Kpad, dst, dg, L.C, L.OC, zero, epi, s, dsplit);
@@ -1684,9 +1712,9 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
         return launch_conv_x3_h2(cur3, wt3, dsplit ? nullptr : dst, dsplit, oh2, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C,
                                  epi, s, range);
       if (L.splits > 1)  // raw partials into the slab, as above
-        return launch_conv_x3(cur3, wt3, slab, nullptr, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s, L.splits);
-      return launch_conv_x3(cur3, wt3, dsplit ? nullptr : dst, dsplit, L.rows(n), L.OC, L.Npad, L.K, L.H, L.W, L.C, epi,
-                            s, 1, L.pool == POOL_S2 ? 1 : 0, p->latency && fused_splitk(p), oh2, range);
+        return launch_conv_x3(p->sw, cur3, wt3, slab, nullptr, Mc, L.OC, L.Npad, L.K, L.H, L.W, L.C, epi, s, L.splits);
+      return launch_conv_x3(p->sw, cur3, wt3, dsplit ? nullptr : dst, dsplit, L.rows(n), L.OC, L.Npad, L.K, L.H, L.W, L.C, epi,
+                            s, 1, L.pool == POOL_S2 ? 1 : 0, p->latency && p->sw.splitk_fused, oh2, range);
     default:
       set_error("dnn_plan_run: fp32 plan has an unsupported conv mode %d", L.variant);
       return -2;
@@ -1795,7 +1823,7 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
       snprintf(line, sizeof(line), "conv %dx%dx%d -> %dx%dx%d k%dx%d s%d mode=%s cfg=%d K=%d Kpad=%d%s%s%s%s%s%s\n", L.H,
                L.W, L.C, L.out_h(), L.out_w(), L.OC, L.kh, L.kw, L.sh, kVariantName[L.variant], L.cfg, L.K, L.Kpad,
                L.pool == POOL_S2 ? " +pool2x2s2" : L.pool == POOL_S1 ? " +pool2x2s1" : "", sk,
-               L.splits > 1 ? (is_x3(L.variant) ? " x3-combine" : fused_splitk(p) ? " combine" : "") : "",
+               L.splits > 1 ? (is_x3(L.variant) ? " x3-combine" : p->sw.splitk_fused ? " combine" : "") : "",
                p->fp16 ? " fp16" : "", p->latency ? " latency" : "", xp);
     } else if (L.type == LAYER_STASH || L.type == LAYER_RESTORE) {
       snprintf(line, sizeof(line), "%s %dx%dx%d slot=%d\n", L.type == LAYER_STASH ? "stash" : "restore", L.H, L.W, L.C,

@@ -240,6 +240,48 @@ def test_plan_x3_structure_host_only(monkeypatch):
     assert [i for i, ln in enumerate(conv) if "patch_x3" in ln] == [2, 3, 4, 6, 7] and "mode=patch " in conv[1] + " "
 
 
+def test_plan_reads_its_switches_at_creation(monkeypatch):
+    """A plan's kernels are a function of its calls and of the DNN_HIP_* switches as
+    dnn_plan_create found them: YOLOv2-tiny's batch plan created under one environment and given
+    its layers under another has the describe() and memory() of a plan built entirely under the
+    first, in both directions (clean, and DNN_HIP_X3_IMG=0 DNN_HIP_X3_TILE=0 DNN_HIP_FUSE=0)."""
+    switched = {"DNN_HIP_X3_IMG": "0", "DNN_HIP_X3_TILE": "0", "DNN_HIP_FUSE": "0"}
+    g, _ = yolo_graph.build_graph(dnn_hip.DnnGraphBuilder, synth.yolo_zero_weights(), in_shape=(64, 416, 416, 3))
+    entries = dnn_hip.lower_graph(g)
+    lib = dnn_hip.mylib
+
+    def set_env(env):
+        for k in switched:
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+
+    def build(env_create, env_add):
+        set_env(env_create)
+        h = ctypes.c_void_p()
+        assert lib.dnn_plan_create(64, 416, 416, 3, ctypes.byref(h)) == 0
+        try:
+            set_env(env_add)
+            for e in entries:
+                if isinstance(e, dnn_hip.ConvEntry):
+                    kh, kw, _, od = e.conv.kernel.shape
+                    assert lib.dnn_plan_add_conv(h, kh, kw, od, 1, 1, 1, None, None, None, None, None, 0.0, 1) == 0
+                else:
+                    assert lib.dnn_plan_add_max_pool(h, 2, 2, e.pool.strides[1], e.pool.strides[2], 1) == 0
+            buf = ctypes.create_string_buffer(8192)
+            assert lib.dnn_plan_describe(h, buf, 8192) == 0
+            wb, sb = ctypes.c_size_t(), ctypes.c_size_t()
+            assert lib.dnn_plan_memory(h, ctypes.byref(wb), ctypes.byref(sb)) == 0
+            return buf.value.decode(), (wb.value, sb.value)
+        finally:
+            lib.dnn_plan_destroy(h)
+
+    clean, under = build({}, {}), build(switched, switched)
+    assert clean != under  # (the three switches do change this plan)
+    assert build({}, switched) == clean
+    assert build(switched, {}) == under
+
+
 def test_plan_errors_are_reported():
     lib = dnn_hip.mylib
     h = ctypes.c_void_p()

@@ -375,8 +375,8 @@ def test_direct_conv0_pool_vs_oracle(monkeypatch, hw):
     assert R.normwise_err(y, ref) < LAYER_TOL
     assert np.array_equal(eng.run(x), y)
     if W % 4 == 0:
-        monkeypatch.setenv("DNN_HIP_C0_D16", "0")
-        assert np.array_equal(eng.run(x), y)
+        monkeypatch.setenv("DNN_HIP_C0_D16", "0")  # read when the plan is created: an engine of its own
+        assert np.array_equal(dnn_hip.DnnInferenceEngine(_chain(x.shape, k, **kw), False).run(x), y)
         monkeypatch.delenv("DNN_HIP_C0_D16")
     monkeypatch.setenv("DNN_HIP_FUSE", "0")
     y0 = dnn_hip.DnnInferenceEngine(_chain(x.shape, k, **kw), False).run(x)
@@ -1513,9 +1513,9 @@ def test_fp16_tile_conv_pool_vs_oracle(monkeypatch, case):
     assert err < 2 * FP16_LAYER_TOL
     y0 = dnn_hip.DnnInferenceEngine(graph((1,) + x.shape[1:]), False, precision="fp16").run(x[:1])
     assert np.array_equal(y0, y[:1])
-    for wgs in ("0", "1"):  # launch-time switch
+    for wgs in ("0", "1"):  # read when the plan is created: one engine per arm
         monkeypatch.setenv("DNN_HIP_TILE16_WGS", wgs)
-        assert np.array_equal(eng.run(x), y), wgs
+        assert np.array_equal(dnn_hip.DnnInferenceEngine(graph(x.shape), False, precision="fp16").run(x), y), wgs
 
 
 IMG16_CASES = [
@@ -1576,8 +1576,8 @@ def test_fp16_img_conv_pool1_vs_oracle(monkeypatch, case):
     assert err < 2 * FP16_LAYER_TOL
     y0 = dnn_hip.DnnInferenceEngine(graph((1,) + x.shape[1:]), False, precision="fp16").run(x[:1])
     assert np.array_equal(y0, y[:1])
-    monkeypatch.setenv("DNN_HIP_TILE16_WGS", "0")
-    assert np.array_equal(eng.run(x), y)
+    monkeypatch.setenv("DNN_HIP_TILE16_WGS", "0")  # read when the plan is created: an engine of its own
+    assert np.array_equal(dnn_hip.DnnInferenceEngine(graph(x.shape), False, precision="fp16").run(x), y)
 
 
 X3_CASES = [
@@ -2067,6 +2067,61 @@ def test_x3_c16_pooled_plain_output_vs_oracle(monkeypatch):
         assert e < 3 * LAYER_TOL and e <= 1.25 * e0, (arm, errs, e0)
 
 
+def test_engine_keeps_the_kernel_it_was_built_with(monkeypatch):
+    """A plan reads its switches once, at creation: on the graph and input of
+    test_x3_c16_pooled_plain_output_vs_oracle, an engine built under the default environment (the
+    persistent 16-channel kernel), one built under DNN_HIP_X3_C16P=0 (one tile per workgroup) and
+    one built under DNN_HIP_X3=0 (the fp32 MFMA) all stay alive, and each gives byte-equal outputs
+    with DNN_HIP_X3_C16P unset, 0 and 1 and with DNN_HIP_X3 unset and 0.
+    Measured on an MI355X, this commit and its parent alike: the first two engines' outputs are
+    byte-equal at this shape (0 of 25,344 elements differ at this seed and at seeds 0..47), so
+    they cannot show which kernel ran; the third engine's output differs from the first's, which
+    is what keeps the test from passing vacuously."""
+    B, H, W = 2, 36, 44
+    rng = np.random.default_rng(B * 31 + H + W)
+    x = rng.standard_normal((B, H, W, 16)).astype(np.float32)
+    k = (rng.standard_normal((3, 3, 16, 32)) * np.sqrt(2.0 / (9 * 16))).astype(np.float32)
+    b = rng.standard_normal(32).astype(np.float32) * 0.1
+    gam = rng.uniform(0.5, 1.5, 32).astype(np.float32)
+    gam[::5] *= -1
+    n = (rng.standard_normal(32).astype(np.float32) * 0.1, rng.uniform(0.5, 1.5, 32).astype(np.float32), gam)
+
+    def engine(x3):
+        g = dnn_hip.DnnGraphBuilder()
+        y = g.create_input([B, H, W, 16])
+        y = g.create_max_pool2d(y, [1, 2, 2, 1], [1, 1, 1, 1], "SAME")
+        y = g.create_conv2d(y, k, [1, 1, 1, 1], "SAME")
+        y = g.create_bias_add(y, b)
+        y = g.create_batch_norm(y, *n, 1e-5)
+        y = g.create_leaky_relu(y)
+        y = g.create_max_pool2d(y, [1, 2, 2, 1], [1, 2, 2, 1], "SAME")
+        g.set_out_node(y)
+        eng = dnn_hip.DnnInferenceEngine(g, False)
+        assert ("mode=patch_x3" in eng.plan().describe()) == x3  # (an engine builds its plan on first use: here)
+        return eng
+
+    monkeypatch.delenv("DNN_HIP_X3_C16P", raising=False)
+    monkeypatch.delenv("DNN_HIP_X3", raising=False)
+    eng_a = engine(True)
+    monkeypatch.setenv("DNN_HIP_X3_C16P", "0")
+    eng_b = engine(True)
+    monkeypatch.delenv("DNN_HIP_X3_C16P")
+    monkeypatch.setenv("DNN_HIP_X3", "0")
+    eng_c = engine(False)
+    monkeypatch.delenv("DNN_HIP_X3")
+    engines = (eng_a, eng_b, eng_c)
+    first = [e.run(x).tobytes() for e in engines]
+    assert first[0] != first[2]
+    for var, arms in (("DNN_HIP_X3_C16P", ("0", "1", None)), ("DNN_HIP_X3", ("0", None))):
+        for arm in arms:
+            if arm is None:
+                monkeypatch.delenv(var)
+            else:
+                monkeypatch.setenv(var, arm)
+            for e, y in zip(engines, first):
+                assert e.run(x).tobytes() == y, (var, arm)
+
+
 @pytest.mark.parametrize("B", [24, 21])
 def test_x3_pingpong_equals_tile_kernel(monkeypatch, B):
     """conv3x3_x3_pp_kernel (N = 64 from one 32-channel chunk, pooled into split planes, batch
@@ -2082,23 +2137,27 @@ def test_x3_pingpong_equals_tile_kernel(monkeypatch, B):
     gam[::5] *= -1
     n = (rng.standard_normal(64).astype(np.float32) * 0.1, rng.uniform(0.5, 1.5, 64).astype(np.float32), gam)
     k2 = (rng.standard_normal((3, 3, 64, 128)) * np.sqrt(2.0 / 576)).astype(np.float32)  # (x3 consumer)
-    g = dnn_hip.DnnGraphBuilder()
-    y = g.create_input(list(x.shape))
-    y = g.create_max_pool2d(y, [1, 2, 2, 1], [1, 1, 1, 1], "SAME")
-    y = g.create_conv2d(y, k, [1, 1, 1, 1], "SAME")
-    y = g.create_bias_add(y, b)
-    y = g.create_batch_norm(y, *n, 1e-5)
-    y = g.create_leaky_relu(y)
-    y = g.create_max_pool2d(y, [1, 2, 2, 1], [1, 2, 2, 1], "SAME")
-    y = g.create_conv2d(y, k2, [1, 1, 1, 1], "SAME")
-    y = g.create_leaky_relu(y)
-    g.set_out_node(y)
-    eng = dnn_hip.DnnInferenceEngine(g, False)
-    conv = [ln for ln in eng.plan().describe().splitlines() if ln.startswith("conv")]
-    assert "mode=patch_x3" in conv[0] and "+pool2x2s2" in conv[0] and "mode=patch_x3" in conv[1], conv
+
+    def graph():
+        g = dnn_hip.DnnGraphBuilder()
+        y = g.create_input(list(x.shape))
+        y = g.create_max_pool2d(y, [1, 2, 2, 1], [1, 1, 1, 1], "SAME")
+        y = g.create_conv2d(y, k, [1, 1, 1, 1], "SAME")
+        y = g.create_bias_add(y, b)
+        y = g.create_batch_norm(y, *n, 1e-5)
+        y = g.create_leaky_relu(y)
+        y = g.create_max_pool2d(y, [1, 2, 2, 1], [1, 2, 2, 1], "SAME")
+        y = g.create_conv2d(y, k2, [1, 1, 1, 1], "SAME")
+        y = g.create_leaky_relu(y)
+        g.set_out_node(y)
+        return g
+
     outs = {}
-    for pp in ("1", "0"):
+    for pp in ("1", "0"):  # read when the plan is created: one engine per arm
         monkeypatch.setenv("DNN_HIP_X3_PP", pp)
+        eng = dnn_hip.DnnInferenceEngine(graph(), False)
+        conv = [ln for ln in eng.plan().describe().splitlines() if ln.startswith("conv")]
+        assert "mode=patch_x3" in conv[0] and "+pool2x2s2" in conv[0] and "mode=patch_x3" in conv[1], conv
         outs[pp] = eng.run(x)
         assert np.array_equal(eng.run(x), outs[pp])
     assert np.array_equal(outs["1"], outs["0"])
@@ -2262,7 +2321,7 @@ def test_conv0_conv1_chain(monkeypatch, case):
         if pool:
             ref = R.max_pool2d(ref, [1, 2, 2, 1], [1, 2, 2, 1], "SAME")
     outs = {}
-    # conv1's kernel (DNN_HIP_X3_C16P, read per launch): 0 one tile per workgroup, 1 (default)
+    # conv1's kernel (DNN_HIP_X3_C16P, read when the plan is created): 0 one tile per workgroup, 1 (default)
     # persistent with the last K step on 16x16x16 (another MFMA for tap 8)
     for pv in ("0", "1"):
         monkeypatch.setenv("DNN_HIP_X3_C16P", pv)

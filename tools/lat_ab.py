@@ -1,6 +1,6 @@
 """In-process A/B of single-frame latency plans (BASELINE config 2): one plan per arm, each built
-with the arm's environment (switches read at plan build, e.g. DNN_HIP_CFG / DNN_HIP_SPLIT, take
-effect), captured as a HIP graph, then the arms' graph replays interleaved round by round.
+with the arm's environment (a plan reads every DNN_HIP_* switch once, when it is created, so any of
+them can be an arm, e.g. DNN_HIP_CFG / DNN_HIP_SPLIT), captured as a HIP graph, then the arms' graph replays interleaved round by round.
 
   python tools/lat_ab.py --env "DNN_HIP_SPLIT=;2304:4" [--rounds 8] [--reps 50]   (arm values split on ";")
 

@@ -1,10 +1,13 @@
-"""In-process A/B of launch-time switches on the batch-64 fp32 plan (cdna_hip_programming.md
+"""In-process A/B of DNN_HIP_* switches on the batch-64 fp32 plan (cdna_hip_programming.md
 §5.4 rule 24: variants interleaved in one process, after a >= 2 s pre-heat at the clock the
 chip holds under load).
 
   python tools/x3_ab.py --env DNN_HIP_X3_C16P=0,2 [--env DNN_AB_DUMMY=a,b] [--rounds 6] [--iters 20] [--preheat 3]
 
-Only switches read per launch take effect between arms (DNN_HIP_X3_C16P; a switch no code reads, e.g. DNN_AB_DUMMY, gives null arms: the noise floor).  Prints, per arm, the
+A plan reads every switch once, when it is created, so each arm gets a plan of its own, built up
+front under the arm's environment, and the rounds alternate the plans: any switch can be an arm,
+those that change the choice of kernel included (a switch no code reads, e.g. DNN_AB_DUMMY, gives
+null arms: the noise floor).  Prints, per arm, the
 median over rounds of each kernel's mean HIP-event time and of the forward.  With a library
 built with X3DIAG bit 16 (tools/build_diag.sh 16, DNN_HIP_LIB=diag/libdnn_hip_d16.so) it also
 reads the wide x3 kernel's per-workgroup s_memtime / s_memrealtime stamps of the last conv7
@@ -111,12 +114,6 @@ def main():
     B = a.batch
     ws = synth.yolo_weights()
     g, _ = yolo_graph.build_graph(dnn_hip.DnnGraphBuilder, ws, in_shape=(B, 416, 416, 3))
-    plan = dnn_hip.Plan.from_graph(g, device=0, precision=a.precision)
-    frames = torch.rand((B, 416, 416, 3), generator=torch.Generator(device=dev).manual_seed(7), device=dev)
-    out = torch.empty((B,) + plan.out_shape, device=dev)
-    stream = torch.cuda.Stream(dev)
-    sp = stream.cuda_stream
-    names = [k["name"] for k in plan.kernels()]
     base = dict(os.environ)
 
     def set_arm(arm):
@@ -127,12 +124,25 @@ def main():
                 os.environ.pop(k, None)
         os.environ.update(arm)
 
+    plans = {}
+    for arm in arms:
+        set_arm(arm)
+        plans[json.dumps(arm)] = dnn_hip.Plan.from_graph(g, device=0, precision=a.precision)
+    set_arm({})
+    plan = plans[json.dumps(arms[0])]
+    frames = torch.rand((B, 416, 416, 3), generator=torch.Generator(device=dev).manual_seed(7), device=dev)
+    out = torch.empty((B,) + plan.out_shape, device=dev)
+    stream = torch.cuda.Stream(dev)
+    sp = stream.cuda_stream
+    # per-kernel times are reported by name: arms whose plans have other kernels give forward times only
+    names = [k["name"] for k in plan.kernels()]
+    same = all([k["name"] for k in q.kernels()] == names for q in plans.values())
+
     def fwd(n):
         for _ in range(n):
             plan.run_device(B, frames.data_ptr(), out.data_ptr(), sp)
 
     t0 = time.time()
-    set_arm(arms[0])
     fwd(3)
     stream.synchronize()
     cold = clock_stamps(plan.lib, 4096)
@@ -147,7 +157,7 @@ def main():
         if r % 2:
             order = order[::-1]
         for arm in order:
-            set_arm(arm)
+            plan = plans[json.dumps(arm)]
             fwd(2)
             plan.timing_begin(a.iters)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -158,7 +168,7 @@ def main():
             ms, cnt = plan.timing_end()
             d = res[json.dumps(arm)]
             d["fwd_ms"].append(e0.elapsed_time(e1) / a.iters)
-            for i, n in enumerate(names):
+            for i, n in enumerate(names if same else []):
                 d["k"][n].append(ms[i] / max(cnt[i], 1))
             c = clock_stamps(plan.lib, 4096)
             if c:
@@ -166,7 +176,7 @@ def main():
             c = c16_phases(plan.lib)
             if c:
                 d.setdefault("c16", []).append(c)
-    want = [n for n in names if n.split(".")[0] in a.kernels.split(",")]
+    want = [n for n in names if same and n.split(".")[0] in a.kernels.split(",")]
     summary = {"cold_clock": cold, "arms": {}}
     for key, d in res.items():
         s = {"fwd_ms_median": round(statistics.median(d["fwd_ms"]), 4), "fwd_ms_min": round(min(d["fwd_ms"]), 4),
@@ -180,7 +190,8 @@ def main():
         summary["arms"][key] = s
         print(key, json.dumps(s), flush=True)
     print(json.dumps(summary))
-    plan.close()
+    for q in plans.values():
+        q.close()
 
 
 if __name__ == "__main__":
