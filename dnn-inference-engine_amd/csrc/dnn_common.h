@@ -277,6 +277,29 @@ int launch_splitk_reduce16(const float* slab, int splits, long long M, int N, ha
 int launch_f32_to_f16(const float* in, half_t* out, long long n, hipStream_t s);
 int launch_f16_to_f32(const half_t* in, float* out, long long n, hipStream_t s);
 int launch_maxpool16(const half_t* in, half_t* out, const PoolGeom& g, hipStream_t s, int opad = 0);
+// The wide 3x3 conv kernels (fp16, x3, h2): rows of the zero-bordered input that one tile of bm
+// consecutive output rows spans, tap offsets included, at its largest over the tiles of M rows;
+// pool: rows are 2x2 pool-window-major
+inline long long wide_tile_span(long long M, int H, int W, int bm, bool pool = false) {
+  const int Wp = W + 2, PH = (H + 1) / 2, PW = (W + 1) / 2;
+  auto padded = [&](long long m) {
+    if (pool) {
+      const long long w = m >> 2, q = m & 3, b = w / (PH * PW), r = w - b * PH * PW, py = r / PW, px = r - py * PW;
+      long long oy = 2 * py + (q >> 1), ox = 2 * px + (q & 1);
+      if (oy >= H || ox >= W) oy = 2 * py, ox = 2 * px;
+      return (b * (H + 2) + oy + 1) * Wp + ox + 1;
+    }
+    const long long b = m / (H * W), r = m - b * H * W, oy = r / W, ox = r - oy * W;
+    return (b * (H + 2) + oy + 1) * Wp + ox + 1;
+  };
+  long long mx = 0;
+  for (long long m0 = 0; m0 < M; m0 += bm) {
+    const long long last = m0 + bm - 1 < M ? m0 + bm - 1 : M - 1;
+    const long long v = padded(last) - padded(m0) + 2 * (Wp + 1) + 1;
+    mx = v > mx ? v : mx;
+  }
+  return mx;
+}
 // fp16 3x3/s1/SAME conv with a zero-bordered input [B][H+2][W+2][C] (C % 64 == 0, N % 256 == 0),
 // weights packed K-order (chunk, tap, c) (launch_pack_weights order 2); out_padded: write the
 // output zero-bordered too (gemm_f16_acc.h)

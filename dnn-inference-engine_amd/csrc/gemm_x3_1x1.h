@@ -15,7 +15,7 @@
 // bit-identical to batch-1 runs).
 #pragma once
 #include "gemm_x3_patch.h"
-#include "gemm_x3_acc2.h"  // static_for
+#include "conv_wide_dev.h"  // static_for
 
 namespace dnnhip {
 

@@ -14,8 +14,13 @@
 // a0 b0; accc over the same steps of (a2b0, a1b1, a1b0, a0b2, a0b1) in that order; then
 // accm + accc.  It depends on (N, K) only (batch rows are
 // bit-identical to batch-1 runs).
+//
+// This file owns the kernel's patch (plain 224-B rows, its DMA), its loop schedule, the pooled
+// tail and the X3DIAG / AC_STAMP hooks; the tile frame (WideFrame, with the split-K index), the
+// staged tail of the unpooled outputs (wide_staged_tail, x3_wide_store8), static_for and vm_wait
+// are conv_wide_dev.h's.
 #pragma once
-#include "gemm_x3_patch.h"
+#include "conv_wide_dev.h"
 
 // X3DIAG (diagnostic builds only, tools/build_diag.sh; wrong results unless noted): bit 1 drops
 // the loop's patch DMA (the patch keeps chunk 0), 2 its weight loads (tap 0's weights
@@ -44,19 +49,6 @@ __device__ unsigned long long acc2_diag_stamps[3 * AC_DIAG_WGS * 8];
 #define AC_STAMP(k, v)
 #endif
 
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-template <int N>
-__device__ __forceinline__ void vm_wait() {
-  static_assert(N >= 0 && N < 64, "vmcnt range");
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // Structure: BM x 256 tiles, 8 waves of BM x 32 (two per SIMD, 256 registers each: the two
 // accumulator sets take 176), the weights of the next tap loaded while this one runs (48), the
 // patch of one 32-channel chunk staged by LDS-DMA into a double buffer (no staging registers),
@@ -83,34 +75,21 @@ __global__ void __launch_bounds__(512, 2)
 conv3x3_x3_acc2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __restrict__ Bt, float* __restrict__ out,
                        bf16_bits* __restrict__ out_split, int M, int N, int K, EpiParams epi, int tilesM, X3Geom g,
                        unsigned in_bytes, unsigned b_bytes, unsigned* __restrict__ range_flag) {
-  constexpr int BN = 256, TM = BM / 16, RB = 192, NJ = 2, NW = 8, LP = 224;
+  constexpr int TM = BM / 16, RB = 192, NJ = 2, NW = 8, LP = 224;
   constexpr int NQW = (NPR * LP + NW * 1024 - 1) / (NW * 1024);  // 1-KiB DMA pieces per wave per patch
   constexpr int BUFB = NQW * NW * 1024;                            // one patch buffer (>= NPR LP)
   static_assert(BM % 16 == 0 && NQW <= 18 && NPR <= 1023, "shape");
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * BUFB];
 
-  const int lane = threadIdx.x & 63;
-  const int wid = wave_uniform(threadIdx.x >> 6);
   AC_STAMP(0, __builtin_amdgcn_s_memrealtime())
   AC_STAMP(1, __builtin_amdgcn_s_memtime())
   AC_STAMP(6, (unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11)))
   AC_STAMP(7, (unsigned)__builtin_amdgcn_s_getreg(20 | (31 << 11)))
-  const int tile_s = xcd_tile(blockIdx.x, gridDim.x), ntiles = gridDim.x / g.splits;
-  const int split = tile_s / ntiles, tile = tile_s - split * ntiles;
-  // tiles N-major inside each XCD's contiguous range (~31 M tiles of one N panel per XCD).
-  // (Round 4: 2 panels x ~16 M tiles per XCD, so each patch is fetched from beyond L2 by 2 XCDs
-  // instead of 4, measured within 0.5 % on conv4-conv7: the patch DMA's beyond-L2 bytes are not
-  // what costs -- tools/x3_ab.py, git history)
-  const int tn = tile / tilesM, tm = tile - tn * tilesM;
-  const int m0 = tm * BM, n0 = tn * BN + wid * 32;  // this wave's 32 columns
-  const int Wp = g.W + 2, HWo = g.H * g.W;
-  auto padded = [&](int m) {
-    const int b = m / HWo, r = m - b * HWo, oy = r / g.W, ox = r - oy * g.W;
-    return (b * (g.H + 2) + oy + 1) * Wp + ox + 1;
-  };
-  auto pixrow = [&](int m) {
+  const WideFrame<BM, true> f(tilesM, g);  // (with the split-K index)
+  const int lane = f.lane, wid = f.wid, fr = f.fr, fq = f.fq, m0 = f.m0, n0 = f.n0, Wp = f.Wp, split = f.split;
+  auto pixrow = [&](int m) {  // POOL: rows are pool-window-major
     if constexpr (!POOL) {
-      return padded(m);
+      return f.padded(m);
     } else {
       const int w = m >> 2, q = m & 3, PHW = g.PH * g.PW;
       const int b = w / PHW, r = w - b * PHW, py = r / g.PW, px = r - py * g.PW;
@@ -119,21 +98,16 @@ conv3x3_x3_acc2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __rest
       return (b * (g.H + 2) + oy + 1) * Wp + ox + 1;
     }
   };
-  const int P0 = pixrow(m0) - (Wp + 1);  // first patch row
+  const int P0 = POOL ? pixrow(m0) - (Wp + 1) : f.P0;  // first patch row
 
   // A fragment of row-block i: patch row of the lane's tap (0, 0) (rows past M repeat row M - 1),
   // packed three per register (10-bit fields: a patch row < NPR <= 1023); unpacked per use
-  const int fr = lane & 15, fq = lane >> 4;
   constexpr int NPK = (TM + 2) / 3;
   unsigned prk[NPK];
 #pragma unroll
   for (int k = 0; k < NPK; ++k) prk[k] = 0;
 #pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    int m = m0 + 16 * i + fr;
-    m = m < M ? m : M - 1;
-    prk[i / 3] |= (unsigned)(pixrow(m) - P0 - (Wp + 1)) << (10 * (i % 3));
-  }
+  for (int i = 0; i < TM; ++i) prk[i / 3] |= (unsigned)f.patch_row(pixrow(f.frag_m(i, M)), P0) << (10 * (i % 3));
   auto rowoff = [&](int i) {  // byte offset of block i's tap-(0, 0) fragment
     unsigned w = prk[i / 3];
     asm volatile("" : "+v"(w));  // unpacked per use: hoisted out of the tap loop it is 11 registers again
@@ -284,7 +258,6 @@ conv3x3_x3_acc2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __rest
     for (int jb = 0; jb < NJ; ++jb)
 #pragma unroll
       for (int r = 0; r < 4; ++r) accm[i][jb][r] = accm[i][jb][r] + accc[i][jb][r];
-  int* orow = reinterpret_cast<int*>(smem);
   if ((X3DIAG & 4) != 0 && g.out_mode == 0) {  // keep the sums live without storing them (fp32-out
     // layers only: a skipped producer would hand its consumer zeros, which clock higher)
     float z = 0.f;
@@ -295,8 +268,9 @@ conv3x3_x3_acc2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __rest
     if (z == 1.2345f) out[0] = z;
     return;
   }
-  __syncthreads();
   if constexpr (POOL) {
+    int* orow = reinterpret_cast<int*>(smem);
+    __syncthreads();
     if (threadIdx.x < BM / 4) {
       const int w = (m0 >> 2) + threadIdx.x, PHW = g.PH * g.PW;
       const int b = w / PHW, r = w - b * PHW, py = r / g.PW, px = r - py * g.PW;
@@ -322,99 +296,23 @@ conv3x3_x3_acc2_kernel(const bf16_bits* __restrict__ in, const bf16_bits* __rest
     static_for<0, NJ>([&](auto jbc) {
       constexpr int jb = decltype(jbc)::value;
       const int n = n0 + 16 * jb + fr;
-      const float pb = (epi.flags & EPI_BIAS) ? epi.bias[n] : 0.f;
-      const float pm = (epi.flags & (EPI_BN | EPI_BN_AB)) ? epi.mean[n] : 0.f;
-      const float ps = (epi.flags & (EPI_BN | EPI_BN_AB)) ? epi.sq[n] : 1.f;
-      const float pg = (epi.flags & EPI_BN) ? epi.gamma[n] : 1.f;
-      const int cofs = (n >> 5) * 96 + (n & 31);
-      static_for<0, TM>([&](auto ic) {
+      const X3EpiCol ec = x3_epi_col(epi, epi.flags, n);
+      static_for<0, TM>([&](auto ic) {  // (fp32 out: out_mode 1 left above)
         constexpr int i = decltype(ic)::value;
         const int o = orow[4 * i + fq];
         if (o < 0) return;
-        const float e = pool_then_epilogue_t<FL>(accm[i][jb], pb, pm, ps, pg, epi.flags);
-        if (g.out_mode == 1) {
-          unsigned short s0, s1, s2;
-          split3(e, s0, s1, s2);
-          bf16_bits* d = out_split + (size_t)o * (3 * N) + cofs;
-          d[0] = s0;
-          d[32] = s1;
-          d[64] = s2;
-        } else {
-          out[(size_t)o * N + n] = e;
-        }
+        out[(size_t)o * N + n] = pool_then_epilogue_t<FL>(accm[i][jb], ec.pb, ec.pm, ec.ps, ec.pg, epi.flags);
       });
     });
     return;
   }
-  if (threadIdx.x < BM) {
-    const int m = m0 + threadIdx.x;
-    orow[threadIdx.x] = m >= M ? -1 : (g.out_mode == 1 || g.out_mode == 3 ? padded(m) : m);
-  }
-  __syncthreads();
-  // Each row block's 16 x 32 outputs of the wave pass through a wave-private LDS stage (fp32 rows
-  // of 36: the MFMA-layout writes are conflict-free) and leave as 16-B stores: lane l takes row
-  // l / 4, columns 8 (l % 4) .. + 7 -- 2 stores of fp32, or 3 of split planes (one per piece), per
-  // row block where the MFMA layout stored one scalar per output (3 per output as split planes).
-  // Same epilogue arithmetic and split per value as before.  out_mode 3: the two fp16 pieces of a
-  // following h2 layer (h2_store8), 2 stores.
-  static_assert(BM * 4 <= 1024, "row table below the stages");
-  float* const stg = reinterpret_cast<float*>(smem + 1024) + wid * (16 * 36);
-  float pb[NJ], pm[NJ], ps[NJ], pg[NJ];
-#pragma unroll
-  for (int jb = 0; jb < NJ; ++jb) {
-    const int f = FL < 0 ? epi.flags : FL;
-    const int n = n0 + 16 * jb + fr;
-    pb[jb] = (f & EPI_BIAS) ? epi.bias[n] : 0.f;
-    pm[jb] = (f & (EPI_BN | EPI_BN_AB)) ? epi.mean[n] : 0.f;
-    ps[jb] = (f & (EPI_BN | EPI_BN_AB)) ? epi.sq[n] : 1.f;
-    pg[jb] = (f & EPI_BN) ? epi.gamma[n] : 1.f;
-  }
-  const int rr = lane >> 2, c8 = 8 * (lane & 3);
-  static_for<0, TM>([&](auto ic) {
-    constexpr int i = decltype(ic)::value;
-    float v[4][NJ];
-#pragma unroll
-    for (int jb = 0; jb < NJ; ++jb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r][jb] = accm[i][jb][r];
-    if (g.out_mode != 2) epilogue_batch<FL>(v, pb, pm, ps, pg, epi.flags);
-#pragma unroll
-    for (int jb = 0; jb < NJ; ++jb)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) stg[(4 * fq + r) * 36 + 16 * jb + fr] = v[r][jb];
-    wait_lgkm0();
-    const f32x4 lo = *reinterpret_cast<const f32x4*>(stg + rr * 36 + c8);
-    const f32x4 hi = *reinterpret_cast<const f32x4*>(stg + rr * 36 + c8 + 4);
-    const int o = orow[16 * i + rr];
-    wait_lgkm0();  // (the stage is rewritten by the next row block)
-    if (o >= 0) {
-      if (g.out_mode == 1) {
-        bool ok = true;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) ok = ok && x3_split_ok(lo[e]) && x3_split_ok(hi[e]);
-        const bool fast = __builtin_amdgcn_ballot_w64(!ok) == 0;  // (over the active lanes: uniform among them)
-        u32x4 q[3];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          unsigned w0, w1, w2;
-          split3_pack2(fast, e < 2 ? lo[2 * e] : hi[2 * e - 4], e < 2 ? lo[2 * e + 1] : hi[2 * e - 3], w0, w1, w2);
-          q[0][e] = w0;
-          q[1][e] = w1;
-          q[2][e] = w2;
-        }
-        const size_t d = (size_t)o * (3 * N) + (n0 >> 5) * 96 + c8;  // (halves)
-#pragma unroll
-        for (int pc = 0; pc < 3; ++pc) store16_at(out_split, 2 * (d + 32 * pc), q[pc]);
-      } else if (g.out_mode == 3) {
-        const float v8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        h2_store8(v8, out_split, (size_t)o * (4 * (size_t)N) + (n0 >> 5) * 128 + 2 * c8, range_flag);
-      } else {
-        const size_t d = ((size_t)(g.out_mode == 2 ? split * M : 0) + o) * N + n0 + c8;  // (floats)
-        store16_at(out, 4 * d, __builtin_bit_cast(u32x4, lo));
-        store16_at(out, 4 * d + 16, __builtin_bit_cast(u32x4, hi));
-      }
-    }
-  });
+  // the unpooled outputs: wide_staged_tail, with the epilogue (not on the raw partial of split-K
+  // slice `split`, out_mode 2, which lands at row split M + o)
+  wide_staged_tail<BM, 2 * BUFB, FL>(smem, f, M, g.out_mode == 1 || g.out_mode == 3, epi, g.out_mode != 2, accm,
+                                     [&](int o, f32x4 lo, f32x4 hi) {
+                                       x3_wide_store8(o, lo, hi, g.out_mode, (size_t)(g.out_mode == 2 ? split * M : 0), n0,
+                                                      wide_c8(lane), N, out, out_split, range_flag);
+                                     });
   AC_STAMP(4, __builtin_amdgcn_s_memtime())
   AC_STAMP(5, __builtin_amdgcn_s_memrealtime())
 }

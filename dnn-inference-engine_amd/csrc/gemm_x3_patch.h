@@ -156,6 +156,28 @@ __device__ __forceinline__ void h2_store8(const float (&v)[8], bf16_bits* __rest
   store16_at(out_split, off + 64, q1);
 }
 
+// Eight consecutive channels (lo, hi) of one pixel into the three bf16 planes of an x3 layer's input:
+// the exact split of each value and one 16-B store per piece at half `d` of out_split (the piece-0
+// slot of the first channel; the pieces 32 halves apart).  The values and splits are those of one
+// scalar store per piece and output.
+__device__ __forceinline__ void x3_store8(const f32x4& lo, const f32x4& hi, bf16_bits* __restrict__ out_split, size_t d) {
+  bool ok = true;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) ok = ok && x3_split_ok(lo[e]) && x3_split_ok(hi[e]);
+  const bool fast = __builtin_amdgcn_ballot_w64(!ok) == 0;  // (over the active lanes; pairs of one v_cvt_pk per piece)
+  u32x4 q[3];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    unsigned w0, w1, w2;
+    split3_pack2(fast, e < 2 ? lo[2 * e] : hi[2 * e - 4], e < 2 ? lo[2 * e + 1] : hi[2 * e - 3], w0, w1, w2);
+    q[0][e] = w0;
+    q[1][e] = w1;
+    q[2][e] = w2;
+  }
+#pragma unroll
+  for (int pc = 0; pc < 3; ++pc) store16_at(out_split, 2 * (d + 32 * pc), q[pc]);
+}
+
 // One output column's epilogue parameters (bias, mean, sqrt(var + eps), gamma; absent terms the
 // identity).  The single-frame kernels load them with their first operands, not at the epilogue:
 // at one frame a load issued there is a whole memory round trip (~1.5 us) on the critical path.
@@ -191,22 +213,7 @@ __device__ __forceinline__ void x3_pool_split_store_f(const float* stg, OF&& oro
     if (o < 0) continue;
     const f32x4 lo = *reinterpret_cast<const f32x4*>(stg + wl * X3_STG_ROW + c8);
     const f32x4 hi = *reinterpret_cast<const f32x4*>(stg + wl * X3_STG_ROW + c8 + 4);
-    bool ok = true;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) ok = ok && x3_split_ok(lo[e]) && x3_split_ok(hi[e]);
-    const bool fast = __builtin_amdgcn_ballot_w64(!ok) == 0;  // (pairs of one v_cvt_pk per piece)
-    u32x4 q[3];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      unsigned w0, w1, w2;
-      split3_pack2(fast, e < 2 ? lo[2 * e] : hi[2 * e - 4], e < 2 ? lo[2 * e + 1] : hi[2 * e - 3], w0, w1, w2);
-      q[0][e] = w0;
-      q[1][e] = w1;
-      q[2][e] = w2;
-    }
-    const size_t d = (size_t)o * n3 + col0 + c8;  // (halves)
-#pragma unroll
-    for (int pc = 0; pc < 3; ++pc) store16_at(out_split, 2 * (d + 32 * pc), q[pc]);
+    x3_store8(lo, hi, out_split, (size_t)o * n3 + col0 + c8);
   }
 }
 template <int TM>

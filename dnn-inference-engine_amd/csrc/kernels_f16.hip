@@ -303,22 +303,7 @@ int patch16_pack_order() { return 4; }
 // (eligible layers take it unless Switches::patch16 is off; measured at batch 64: conv6 0.1415 ->
 // 0.1286 ms, conv7 equal)
 
-// rows of the padded input one bm-row tile spans (tap offsets included)
-static int patch16_span(long long M, int H, int W) {
-  const int Wp = W + 2;
-  auto padded = [&](long long m) {
-    const long long b = m / (H * W), r = m - b * H * W, oy = r / W, ox = r - oy * W;
-    return (b * (H + 2) + oy + 1) * Wp + ox + 1;
-  };
-  long long mx = 0;
-  const int bm = P16_BM;
-  for (long long m0 = 0; m0 < M; m0 += bm) {
-    const long long last = m0 + bm - 1 < M ? m0 + bm - 1 : M - 1;
-    const long long v = padded(last) - padded(m0) + 2 * (Wp + 1) + 1;
-    mx = v > mx ? v : mx;
-  }
-  return (int)(mx < 0x7fffffff ? mx : 0x7fffffff);
-}
+// (a launch's tiles span wide_tile_span(M, H, W, P16_BM) rows of the padded input, dnn_common.h)
 
 // the most padded rows a bm-row tile can span at any start (every alignment to the image grid;
 // a batch's tiles start at multiples of bm, which reach many of them)
@@ -337,10 +322,11 @@ static int patch16_span_any(int H, int W, int bm) {
 }
 
 // the launcher's patch limits for any batch: the worst alignment decides it
-// (patch16_span_any); the row-skewed LDS patch holds
-// span * 10 + 12 * (span / Wp + 2) 16-B units (56 KiB).  A layer past them stays on the fp16 GEMM.
+// (patch16_span_any); the row-skewed LDS patch of `span` rows (SkewPatch, conv_wide_dev.h) must
+// fit the kernel's buffer (56 KiB).  A layer past them stays on the fp16 GEMM.
 static bool patch16_fits(long long span, int W) {
-  return span <= P16_NPR && span * 10 + 12 * (span / (W + 2) + 2) <= 7 * 8 * 64;
+  using SP = SkewPatch<160, 12>;
+  return span <= P16_NPR && 16 * SP::units(span, W + 2) <= SP::buf_bytes(P16_NPR);
 }
 
 bool conv_patch16_supported(const Switches& sws, int C, int OC, int H, int W, int OH, int OW, int kh, int kw, int sh, int sw, int pt,
@@ -356,7 +342,7 @@ int launch_conv_patch16(const half_t* in_padded, const half_t* Bt, int ldb, half
   const long long nimg = M / ((long long)H * W);
   const long long in_bytes = nimg * (H + 2) * (W + 2) * (long long)C * 2;
   if (M % ((long long)H * W) != 0 || K != 9 * C || C % 64 != 0 || N % 256 != 0 || ldb < K || ldb % 8 != 0 ||
-      in_bytes >= 0x80000000LL || M > 0x7fffffffLL || !patch16_fits(patch16_span(M, H, W), W)) {
+      in_bytes >= 0x80000000LL || M > 0x7fffffffLL || !patch16_fits(wide_tile_span(M, H, W, P16_BM), W)) {
     set_error("conv_patch16: unsupported shape M=%lld N=%d K=%d %dx%dx%d", M, N, K, H, W, C);
     return -2;
   }

@@ -382,24 +382,7 @@ constexpr int X3_NPR_POOL = 352;  // pool-window-major tiles span more rows (26x
 
 // rows of the padded input one BM-row tile spans (tap offsets included); pool: window-major
 static long long x3_span(long long M, int H, int W, bool pool = false) {
-  const int Wp = W + 2, PH = (H + 1) / 2, PW = (W + 1) / 2;
-  auto padded = [&](long long m) {
-    if (pool) {
-      const long long w = m >> 2, q = m & 3, b = w / (PH * PW), r = w - b * PH * PW, py = r / PW, px = r - py * PW;
-      long long oy = 2 * py + (q >> 1), ox = 2 * px + (q & 1);
-      if (oy >= H || ox >= W) oy = 2 * py, ox = 2 * px;
-      return (b * (H + 2) + oy + 1) * Wp + ox + 1;
-    }
-    const long long b = m / (H * W), r = m - b * H * W, oy = r / W, ox = r - oy * W;
-    return (b * (H + 2) + oy + 1) * Wp + ox + 1;
-  };
-  long long mx = 0;
-  for (long long m0 = 0; m0 < M; m0 += X3_BM) {
-    const long long last = m0 + X3_BM - 1 < M ? m0 + X3_BM - 1 : M - 1;
-    const long long v = padded(last) - padded(m0) + 2 * (Wp + 1) + 1;
-    mx = v > mx ? v : mx;
-  }
-  return mx;
+  return wide_tile_span(M, H, W, X3_BM, pool);
 }
 
 // narrow layers: the 2-D tile kernel (conv3x3_x3_tile2_kernel), 8 x 26 (N = 64) or 4 x 26
@@ -654,9 +637,8 @@ int launch_conv_x3(const Switches& sws, const bf16_bits* in_split, const bf16_bi
 // (x3_h2_act_bytes), weights from launch_pack_weights_h2; out_h2: `out_split` takes h2 planes too
 // Shape only: the skewed LDS rows of a tile's patch must fit one buffer for any batch.
 bool conv_x3_h2_supported(int C, int OC, int H, int W) {
-  const long long units = (long long)X3_NPR * (X3H2_LP / 16) + X3H2_SK * (X3_NPR / (W + 2) + 2);
-  const long long bufb = ((long long)X3_NPR * X3H2_LP + 8191) / 8192 * 8192;
-  return x3_kind(OC, C) == 0 && C % 32 == 0 && 16 * units <= bufb && x3_span(2LL * H * W + X3_BM, H, W) <= X3_NPR;
+  return x3_kind(OC, C) == 0 && C % 32 == 0 && 16 * X3H2Patch::units(X3_NPR, W + 2) <= X3H2Patch::buf_bytes(X3_NPR) &&
+         x3_span(2LL * H * W + X3_BM, H, W) <= X3_NPR;
 }
 
 int launch_conv_x3_h2(const bf16_bits* in_h2, const bf16_bits* Bt, float* out, bf16_bits* out_split, int out_h2,
