@@ -412,6 +412,18 @@ int launch_upsample(const float* in, float* out, int n, int H, int W, int C, int
 int launch_slice(const float* in, float* out, int n, int H, int W, int C, int first, int channels,
                  hipStream_t stream);
 
+// conv_grouped.hip: grouped / depthwise conv, in [n, H, W, C] -> out [n, OH, OW, OC], plain NHWC fp32, pads ph / pw on
+// every side, epilogue v * alpha - beta (flags & EPI_BN_AB) then apply_leaky(flags).  `w` is what
+// conv_grouped_pack made of the [kh][kw][C / groups][OC] kernel (conv_grouped_weight_floats floats:
+// lane-ordered 16-byte runs for the MFMA kernel, conv_grouped_mfma; the kernel as it is otherwise).
+// The kernel is chosen from the shape alone.  Every tensor < 2 GiB, 16-byte aligned when C % 4 == 0
+bool conv_grouped_mfma(int C, int OC, int groups);
+size_t conv_grouped_weight_floats(int C, int OC, int groups, int kh, int kw);
+void conv_grouped_pack(const float* w, float* packed, int C, int OC, int groups, int kh, int kw);
+int launch_conv_grouped(const float* in, const float* w, const float* alpha, const float* beta, float* out, int n, int H,
+                        int W, int C, int OH, int OW, int OC, int kh, int kw, int sh, int sw, int ph, int pw, int groups,
+                        int flags, hipStream_t stream);
+
 // spp.hip: spatial pyramid pooling in one pass.  out [n, H, W, (n_sizes + 1) * C]: channel block j
 // is the sizes[j] x sizes[j] / stride-1 / SAME max pool of a [n, H, W, C] (maxpool_nhwc_kernel's
 // bits: -FLT_MAX padding, row-major scan, m >= v ? m : v), and a itself is the last block, or the

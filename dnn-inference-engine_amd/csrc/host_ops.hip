@@ -1,5 +1,6 @@
 // The join / element-wise kernels on host tensors (include/dnn_hip_plan.h: dnn_spp_host,
-// dnn_route_host, dnn_shortcut_host, dnn_scale_shift_host, dnn_upsample_host, dnn_slice_host).  Host code only:
+// dnn_route_host, dnn_shortcut_host, dnn_scale_shift_host, dnn_upsample_host, dnn_slice_host,
+// dnn_conv_grouped_host).  Host code only:
 // each entry checks its arguments and hands on_device() its inputs and a launch.
 #include <hip/hip_runtime.h>
 #include <initializer_list>
@@ -17,7 +18,7 @@ struct HostTensor {
   size_t floats;
 };
 
-constexpr int kMaxInputs = 3;
+constexpr int kMaxInputs = 4;
 
 // One device allocation holding every input (64-float aligned) and `scratch` floats behind them;
 // uploads the inputs, calls launch(d, &result) with d[i] input i's device address and d[ins.size()]
@@ -168,6 +169,41 @@ int dnn_slice_host(const float* a, float* out, int n, int h, int w, int c, int f
     *res = d[1];
     return launch_slice(d[0], d[1], n, h, w, c, first, channels, nullptr);
   });
+}
+
+int dnn_conv_grouped_host(const float* x, const float* kernel, const float* scale, const float* shift, float* out, int n,
+                          int h, int w, int c, int kh, int kw, int od, int stride_h, int stride_w, int pad_h, int pad_w,
+                          int groups, int leaky) {
+  DNN_REQUIRE(x && kernel && out, "dnn_conv_grouped_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_conv_grouped_host: bad shape n=%d %dx%dx%d", n, h, w, c);
+  DNN_REQUIRE(kh > 0 && kw > 0 && od > 0 && stride_h > 0 && stride_w > 0, "dnn_conv_grouped_host: bad args");
+  DNN_REQUIRE(groups != 1, "dnn_conv_grouped_host: groups == 1 is a dense conv: use dnn_plan_add_conv_padded");
+  DNN_REQUIRE(groups >= 2 && c % groups == 0 && od % groups == 0,
+              "dnn_conv_grouped_host: groups %d must be >= 2 and divide the %d input and %d output channels", groups, c, od);
+  DNN_REQUIRE(pad_h >= 0 && pad_h < kh && pad_w >= 0 && pad_w < kw,
+              "dnn_conv_grouped_host: pads %d,%d outside [0, kernel) for a %dx%d kernel", pad_h, pad_w, kh, kw);
+  DNN_REQUIRE((scale == nullptr) == (shift == nullptr), "dnn_conv_grouped_host: scale and shift must be both set or both NULL");
+  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_conv_grouped_host: leaky must be 0, 1 or 2");
+  const int span_h = h + 2 * pad_h - kh, span_w = w + 2 * pad_w - kw;
+  DNN_REQUIRE(span_h >= 0 && span_w >= 0, "dnn_conv_grouped_host: empty output (%dx%d input, %dx%d kernel, pads %d,%d)", h, w,
+              kh, kw, pad_h, pad_w);
+  if (n == 0) return 0;
+  const int oh = span_h / stride_h + 1, ow = span_w / stride_w + 1;
+  const size_t xf = (size_t)n * h * w * c, of = (size_t)n * oh * ow * od;
+  DNN_REQUIRE(xf * 4 < k2GiB && of * 4 < k2GiB,
+              "dnn_conv_grouped_host: a tensor of n=%d %dx%dx%d -> %dx%dx%d is >= 2 GiB; split the batch", n, h, w, c, oh, ow,
+              od);
+  std::vector<float> packed(conv_grouped_weight_floats(c, od, groups, kh, kw)), beta(od);
+  conv_grouped_pack(kernel, packed.data(), c, od, groups, kh, kw);
+  for (int k = 0; k < od; ++k) beta[k] = scale ? -shift[k] : 0.f;  // v * alpha - beta, beta = -shift (exact)
+  const int flags = (scale ? EPI_BN_AB : 0) | (leaky == 1 ? EPI_LEAKY_F64 : leaky == 2 ? EPI_LEAKY_F32 : 0);
+  return on_device("dnn_conv_grouped_host",
+                   {{x, xf}, {packed.data(), packed.size()}, {scale, (size_t)od}, {scale ? beta.data() : nullptr, (size_t)od}},
+                   of, out, of, [&](float* const* d, const float** res) {
+                     *res = d[4];
+                     return launch_conv_grouped(d[0], d[1], d[2], d[3], d[4], n, h, w, c, oh, ow, od, kh, kw, stride_h,
+                                                stride_w, pad_h, pad_w, groups, flags, nullptr);
+                   });
 }
 
 }  // extern "C"

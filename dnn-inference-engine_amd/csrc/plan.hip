@@ -61,6 +61,10 @@
 //
 // Channel slice: a slice entry (slice.hip) copies a channel range of the current tensor (Darknet's
 // [route] with groups / group_id), one kernel, plain NHWC fp32 on both sides like the entries above.
+//
+// Grouped conv: a gconv entry (conv_grouped.hip) is Darknet's [convolutional] with groups > 1, one
+// kernel with its weights and its alpha / beta vectors in the weight arena; plain NHWC fp32 on both
+// sides, so it stops the peepholes too.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -223,7 +227,7 @@ enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, 
 
 enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
                        LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9,
-                       LAYER_SLICE = 10 };
+                       LAYER_SLICE = 10, LAYER_GCONV = 11 };
 
 struct PlanLayer {
   int type = LAYER_CONV;
@@ -256,11 +260,13 @@ struct PlanLayer {
   int slot_loc = LOC_NONE;  // where the slot's tensor lives when this entry is added (slot numbers are reused)
   int factor = 1;           // upsample
   int first = 0;            // slice: the first channel taken (OC channels from there)
+  int groups = 1;           // gconv
   int leaky = 0;            // shortcut: 0 none, 1 / 2 the conv epilogue's variants
   int n_sizes = 0, sizes[DNN_SPP_MAX_SIZES] = {0, 0, 0};  // spp: the pools' window sizes, in block order
   bool x_first = false;     // spp: the input's copy is the first channel block
   int dst_loc = 0;          // where this layer writes when its output is plain NHWC (LOC_*; layout())
   bool is_conv() const { return type == LAYER_CONV; }
+  bool has_weights() const { return type == LAYER_CONV || type == LAYER_GCONV; }
   bool is(int v) const { return type == LAYER_CONV && variant == v; }
   int out_h() const { return pool == POOL_S2 ? PH : OH; }
   int out_w() const { return pool == POOL_S2 ? PW : OW; }
@@ -292,7 +298,7 @@ enum StepKind : int {
   STEP_X3_COMBINE,       // an x3 conv's slab partials + its epilogue -> dst
   STEP_POOL,
   STEP_X3_COMBINE_POOL,  // a pool layer's step that also combines the partials of x3 conv `layer - 1`
-  STEP_ROUTE, STEP_SHORTCUT, STEP_UPSAMPLE, STEP_SPP, STEP_SLICE,
+  STEP_ROUTE, STEP_SHORTCUT, STEP_UPSAMPLE, STEP_SPP, STEP_SLICE, STEP_GCONV,
   STEP_CVT_OUT           // fp16 plans: the last activation to the fp32 output
 };
 
@@ -443,7 +449,7 @@ static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
   place_outputs(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
-  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0;
+  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0, ngconv = 0;
   // (kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7)
   p->steps.clear();
   const double B = p->batch;
@@ -540,6 +546,13 @@ static void layout(dnn_plan* p) {
     } else if (L.type == LAYER_SLICE) {  // reads the channels it writes: input bytes == output bytes
       snprintf(nm, sizeof(nm), "slice%d", nslice++);
       step(i, STEP_SLICE, 0.0, 2.0 * out_b, cur, out);
+    } else if (L.type == LAYER_GCONV) {  // packed weights, then alpha and beta (Npad floats each)
+      L.w_off = off;
+      off = align_up(off + conv_grouped_weight_floats(L.C, L.OC, L.groups, L.kh, L.kw), 64);
+      L.epi_off = off;
+      off = align_up(off + 2 * (size_t)L.Npad, 64);
+      snprintf(nm, sizeof(nm), "gconv%d", ngconv++);
+      step(i, STEP_GCONV, 2.0 * M * L.OC * L.K, in_b + 4.0 * L.K * L.OC + out_b, cur, out);
     }
     cur = out;
   }
@@ -947,6 +960,56 @@ int dnn_plan_add_conv_padded(dnn_plan* p, int kh, int kw, int od, int stride_h, 
                         true, kernel, ep);
 }
 
+int dnn_plan_add_conv_grouped(dnn_plan* p, int kh, int kw, int od, int stride_h, int stride_w, int pad_h, int pad_w,
+                              int groups, const float* kernel, const float* scale, const float* shift, int leaky) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_conv_grouped: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_conv_grouped: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(kh > 0 && kw > 0 && od > 0 && stride_h > 0 && stride_w > 0, "dnn_plan_add_conv_grouped: bad args");
+  DNN_REQUIRE(groups != 1, "dnn_plan_add_conv_grouped: groups == 1 is a dense conv: use dnn_plan_add_conv_padded");
+  DNN_REQUIRE(groups >= 2 && p->cur_c % groups == 0 && od % groups == 0,
+              "dnn_plan_add_conv_grouped: groups %d must be >= 2 and divide the %d input and %d output channels", groups,
+              p->cur_c, od);
+  DNN_REQUIRE(pad_h >= 0 && pad_h < kh && pad_w >= 0 && pad_w < kw,
+              "dnn_plan_add_conv_grouped: pads %d,%d outside [0, kernel) for a %dx%d kernel", pad_h, pad_w, kh, kw);
+  DNN_REQUIRE((scale == nullptr) == (shift == nullptr),
+              "dnn_plan_add_conv_grouped: scale and shift must be both set or both NULL");
+  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "dnn_plan_add_conv_grouped: leaky must be 0, 1 or 2");
+  const int span_h = p->cur_h + 2 * pad_h - kh, span_w = p->cur_w + 2 * pad_w - kw;
+  DNN_REQUIRE(span_h >= 0 && span_w >= 0, "dnn_plan_add_conv_grouped: empty output (%dx%d input, %dx%d kernel, pads %d,%d)",
+              p->cur_h, p->cur_w, kh, kw, pad_h, pad_w);
+  PlanLayer L;
+  L.type = LAYER_GCONV;
+  L.H = p->cur_h;
+  L.W = p->cur_w;
+  L.C = p->cur_c;
+  L.kh = kh;
+  L.kw = kw;
+  L.sh = stride_h;
+  L.sw = stride_w;
+  L.pt = pad_h;
+  L.pl = pad_w;
+  L.OH = span_h / stride_h + 1;
+  L.OW = span_w / stride_w + 1;
+  L.OC = od;
+  L.groups = groups;
+  L.K = kh * kw * (L.C / groups);
+  L.Npad = (int)align_up(od, 64);
+  L.epi_flags = (scale ? EPI_BN_AB : 0) | (leaky == 1 ? EPI_LEAKY_F64 : leaky == 2 ? EPI_LEAKY_F32 : 0);
+  if (kernel) {
+    L.have_host = true;
+    L.w.resize(conv_grouped_weight_floats(L.C, od, groups, kh, kw));
+    conv_grouped_pack(kernel, L.w.data(), L.C, od, groups, kh, kw);
+    L.mean.assign(L.Npad, 1.f);  // alpha = scale, beta = -shift (the negation is exact)
+    L.sq.assign(L.Npad, 0.f);
+    for (int d = 0; scale && d < od; ++d) {
+      L.mean[d] = scale[d];
+      L.sq[d] = -shift[d];
+    }
+  }
+  push_computing(p, std::move(L));
+  return 0;
+}
+
 int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_w, int padding) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_max_pool: plan is NULL or finalized");
   DNN_REQUIRE(kh > 0 && kw > 0 && stride_h > 0 && stride_w > 0, "dnn_plan_add_max_pool: bad args");
@@ -1345,6 +1408,18 @@ static int upload_weights(dnn_plan* p) {
   float* packed32 = tmp + std::max<size_t>(maxw, 1);  // fp16 plans: fp32 pack, then convert
   int rc = 0;
   for (auto& L : p->layers) {
+    if (L.type == LAYER_GCONV) {  // packed on the host when the layer was added
+      const size_t nb = (size_t)L.Npad * sizeof(float);
+      float* e = p->weights + L.epi_off;
+      if (hipMemcpy(p->weights + L.w_off, L.w.data(), L.w.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(e, L.mean.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
+          hipMemcpy(e + L.Npad, L.sq.data(), nb, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("dnn_plan_finalize: weight upload failed");
+        rc = -1;
+        break;
+      }
+      continue;
+    }
     if (!L.is_conv()) continue;
     const size_t wb = L.w.size() * sizeof(float);
     const WeightPack pack = weight_pack(L.variant);
@@ -1444,7 +1519,7 @@ int dnn_plan_finalize(dnn_plan* p, int device, void* weights, void* workspace) {
     DNN_HIP_TRY(hipMemset(p->ws + p->at.tickets, 0, p->ticket_floats * sizeof(float)));
   bool all_host = true;
   for (auto& L : p->layers)
-    if (L.is_conv() && !L.have_host) all_host = false;
+    if (L.has_weights() && !L.have_host) all_host = false;
   if (all_host) {
     int rc = upload_weights(p);
     if (rc) return rc;
@@ -1650,6 +1725,11 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
       return launch_upsample(cur, dst, n, L.H, L.W, L.C, L.factor, s);
     case STEP_SLICE:
       return launch_slice(cur, dst, n, L.H, L.W, L.C, L.first, L.OC, s);
+    case STEP_GCONV: {
+      const float* e = p->weights + L.epi_off;
+      return launch_conv_grouped(cur, p->weights + L.w_off, e, e + L.Npad, dst, n, L.H, L.W, L.C, L.OH, L.OW, L.OC, L.kh,
+                                 L.kw, L.sh, L.sw, L.pt, L.pl, L.groups, L.epi_flags, s);
+    }
     case STEP_SPP:
       return launch_spp(cur, dst, n, L.H, L.W, L.C, L.n_sizes, L.sizes, L.x_first ? 1 : 0, s);
     default:
@@ -1842,6 +1922,10 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
                L.factor);
     } else if (L.type == LAYER_SLICE) {
       snprintf(line, sizeof(line), "slice %dx%dx%d -> %dx%dx%d first=%d\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.first);
+    } else if (L.type == LAYER_GCONV) {
+      snprintf(line, sizeof(line), "conv %dx%dx%d -> %dx%dx%d k%dx%d s%d mode=%s K=%d pad=%d,%d%s%s groups=%d\n", L.H, L.W,
+               L.C, L.OH, L.OW, L.OC, L.kh, L.kw, L.sh, conv_grouped_mfma(L.C, L.OC, L.groups) ? "grouped_mfma" : "grouped_direct",
+               L.K, L.pt, L.pl, (L.epi_flags & EPI_BN_AB) ? " affine" : "", p->latency ? " latency" : "", L.groups);
     } else if (L.type == LAYER_RELEASE) {
       snprintf(line, sizeof(line), "release %dx%dx%d slot=%d\n", L.H, L.W, L.C, L.slot);
     } else if (L.type == LAYER_TAP) {

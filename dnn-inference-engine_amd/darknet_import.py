@@ -44,14 +44,14 @@ definitions).
 Weight files (load_weights / save_weights): three int32 `major, minor, revision`, then `seen` (8
 bytes when major * 10 + minor >= 2, else 4), then per [convolutional] in cfg order biases[n],
 with batch_normalize=1 scales[n], rolling_mean[n], rolling_variance[n], then
-weights[n][c][kh][kw], all fp32 little-endian.  The reader is numpy.frombuffer on the file's
+weights[n][c / groups][kh][kw], all fp32 little-endian (a [convolutional] with groups > 1 is a grouped
+conv: one dnn_plan_add_conv_grouped entry, its kernel [kh][kw][c / groups][n]).  The reader is numpy.frombuffer on the file's
 bytes: nothing in a weight file executes.
 
 Out of scope:
 
   * YOLOv2's [reorg] and [region]: Darknet's reorg channel order is not the route kernel's
     (TensorFlow's space_to_depth), so yolov2.py's weights are not Darknet's either;
-  * grouped convs (`groups` > 1 in a [convolutional]);
   * the mish activation and with it full YOLOv4 (cfg_text("yolov4") raises);
   * [route] with groups > 1 over more than one layer (Darknet slices each layer then; no stock cfg
     does it);
@@ -175,12 +175,21 @@ def conv_params(sec):
     where = f"[convolutional] at line {sec['line']}"
     if act not in ("leaky", "linear"):
         raise DarknetError(f"{where}: activation {act!r} is not supported (leaky, linear)")
-    if _int(sec, "groups", 1) != 1:
-        raise DarknetError(f"{where}: grouped convs are not supported")
     if n < 1 or size < 1 or stride < 1 or not 0 <= pad < size:
         raise DarknetError(f"{where}: filters {n}, size {size}, stride {stride}, padding {pad}: need filters, size, "
                            "stride >= 1 and 0 <= padding < size")
     return n, size, stride, pad, bool(_int(sec, "batch_normalize", 0)), act
+
+
+def conv_groups(sec, c):
+    """`groups` of a [convolutional] section on `c` input channels (default 1): above 1 a grouped
+    conv, one dnn_plan_add_conv_grouped entry whose Darknet weights are [n][c / groups][size][size].
+    DarknetError when it does not divide the input channels or `filters`."""
+    groups, n = _int(sec, "groups", 1), _int(sec, "filters")
+    if groups < 1 or c % groups or n % groups:
+        raise DarknetError(f"[convolutional] at line {sec['line']}: grouped conv with groups = {groups} needs "
+                           f"groups >= 1 dividing the {c} input channels and the {n} filters")
+    return groups
 
 
 def maxpool_params(sec, in_h, in_w):
@@ -252,6 +261,7 @@ def layer_shapes(sections, in_shape=None):
         kind = sec["type"]
         if kind == "convolutional":
             n, size, stride, pad, _, _ = conv_params(sec)
+            conv_groups(sec, c)
             if h + 2 * pad < size or w + 2 * pad < size:
                 raise DarknetError(f"[convolutional] at line {sec['line']}: a {size}x{size} kernel on a "
                                    f"{h} x {w} map with padding {pad} has no output")
@@ -290,7 +300,8 @@ def layer_shapes(sections, in_shape=None):
 
 
 def conv_shapes(sections):
-    """Per [convolutional] section in cfg order: (filters, input channels, size, batch_normalize).
+    """Per [convolutional] section in cfg order: (filters, input channels, size, batch_normalize),
+    the input channels being those of one group (c / groups: the weights' second axis).
     (Channel counts do not depend on the input size.)"""
     net = sections[0]
     shapes = layer_shapes(sections, [1, max(_int(net, "height"), 1), max(_int(net, "width"), 1), _int(net, "channels", 3)])
@@ -299,7 +310,7 @@ def conv_shapes(sections):
     for sec, shape in zip(sections[1:], shapes):
         if sec["type"] == "convolutional":
             n, size, _, _, bn, _ = conv_params(sec)
-            out.append((n, c_in, size, bn))
+            out.append((n, c_in // conv_groups(sec, c_in), size, bn))
         c_in = shape[2]
     return out
 
@@ -447,13 +458,15 @@ def build_graph(builder_cls, sections, layers, in_shape):
         return v
 
     prev = x
+    c_in = int(in_shape[3])
     for at, sec in enumerate(sections[1:]):
         kind = sec["type"]
         if kind == "convolutional":
             n, size, stride, pad, _, act = conv_params(sec)
             layer = next(weights)
             scale, shift = fold_batchnorm(layer)
-            t = g.create_conv2d_padded(node(prev), kernel_hwio(layer), [1, stride, stride, 1], (pad, pad))
+            t = g.create_conv2d_padded(node(prev), kernel_hwio(layer), [1, stride, stride, 1], (pad, pad),
+                                       groups=conv_groups(sec, c_in))
             t = g.create_scale_shift(t, scale, shift)
             cur = g.create_leaky_relu_f32(t) if act == "leaky" else t
         elif kind == "shortcut":
@@ -484,6 +497,7 @@ def build_graph(builder_cls, sections, layers, in_shape):
             cur = prev
         out.append(cur)
         prev = cur
+        c_in = shapes[at][2]
     if not outs:
         raise DarknetError("the cfg has no [yolo] section: nothing to output")
     if outs[-1] is not node(prev):

@@ -72,6 +72,8 @@ def _bind_plan_api(lib):
         "dnn_plan_add_conv": (i, [vp, i, i, i, i, i, i, vp, vp, vp, vp, vp, f, i]),
         "dnn_plan_add_conv_padded": (i, [vp, i, i, i, i, i, i, i, vp, vp, vp, i]),
         "dnn_scale_shift_host": (i, [vp, vp, vp, vp, i, i, i, i, i]),
+        "dnn_plan_add_conv_grouped": (i, [vp, i, i, i, i, i, i, i, i, vp, vp, vp, i]),
+        "dnn_conv_grouped_host": (i, [vp, vp, vp, vp, vp] + [i] * 13),
         "dnn_plan_add_max_pool": (i, [vp, i, i, i, i, i]),
         "dnn_plan_add_stash": (i, [vp, P(i)]),
         "dnn_plan_add_restore": (i, [vp, i]),
@@ -389,10 +391,11 @@ class DnnGraphBuilder(object):
         self.G.add_edge(in_node, out_node)
         return out_node
 
-    def create_conv2d_padded(self, in_node, kernel, strides, pads):
+    def create_conv2d_padded(self, in_node, kernel, strides, pads, groups=1):
         """A conv with explicit zero padding: `pads` = (pad_h, pad_w), each applied on both sides
-        (Darknet's rule; create_conv2d's SAME is TensorFlow's)."""
-        out_node = Conv2DPadded(self.get_name("conv2d_padded"), in_node, kernel, strides, pads)
+        (Darknet's rule; create_conv2d's SAME is TensorFlow's).  `groups` > 1: a grouped conv, the
+        kernel [kh][kw][C / groups][od]."""
+        out_node = Conv2DPadded(self.get_name("conv2d_padded"), in_node, kernel, strides, pads, groups)
         self.G.add_edge(in_node, out_node)
         return out_node
 
@@ -559,12 +562,17 @@ class LeakyReLU(DnnNode):
 class Conv2DPadded(DnnNode):
     """Not in the reference (Darknet's convs need it): Conv2D with `pads` = (pad_h, pad_w) zeros on
     BOTH sides of each axis, out = (in + 2 * pad - k) // stride + 1, 0 <= pad < k.  run() ->
-    conv2d_mul on the np.pad'ed input, like Conv2D."""
+    conv2d_mul on the np.pad'ed input, like Conv2D.  `groups` > 1: a grouped conv (output channel j
+    reads input channels [(j // og) * cg, (j // og + 1) * cg), cg = C / groups, og = od / groups),
+    the kernel [kh][kw][cg][od]; run() -> dnn_conv_grouped_host."""
 
-    def __init__(self, name, in_node, kernel, strides, pads):
+    def __init__(self, name, in_node, kernel, strides, pads, groups=1):
         batch, ih, iw, ic = in_node.result.shape
         kh, kw, kernel_ic, od = kernel.shape
-        if kernel_ic != ic:
+        if groups != int(groups) or groups < 1 or ic % groups or od % groups:
+            raise ValueError
+        self.groups = int(groups)
+        if kernel_ic * self.groups != ic:
             raise ValueError
         try:
             ph, pw = (int(v) for v in pads)
@@ -589,6 +597,14 @@ class Conv2DPadded(DnnNode):
 
     def run(self):
         ph, pw = self.pads
+        if self.groups > 1:
+            x = np.ascontiguousarray(self.in_node.result, dtype=np.float32)
+            kh, kw, _, od = self.kernel.shape
+            rc = mylib.dnn_conv_grouped_host(_vp(x), _vp(self.kernel), None, None, _vp(self.result), *map(int, x.shape),
+                                             kh, kw, od, int(self.strides[1]), int(self.strides[2]), ph, pw,
+                                             self.groups, 0)
+            _check(rc, self.name)
+            return
         in_layer = np.ascontiguousarray(np.pad(self.in_node.result, [(0, 0), (ph, ph), (pw, pw), (0, 0)], 'constant'),
                                         dtype=np.float32)
         mylib.conv2d_mul(
@@ -847,6 +863,14 @@ class PaddedConvEntry(object):
         self.nodes = [conv]
 
 
+class GroupedConvEntry(PaddedConvEntry):
+    """dnn_plan_add_conv_grouped: a Conv2DPadded with groups > 1 and the same fused epilogue."""
+
+    def __init__(self, conv, pads):
+        PaddedConvEntry.__init__(self, conv, pads)
+        self.groups = conv.groups
+
+
 class PoolEntry(object):
     def __init__(self, pool):
         self.pool = pool
@@ -961,7 +985,7 @@ def _lower_one(g, nxt):
         else:
             pads = None
         if pads is not None:
-            e = PaddedConvEntry(nxt, pads)
+            e = GroupedConvEntry(nxt, pads) if getattr(nxt, 'groups', 1) > 1 else PaddedConvEntry(nxt, pads)
             cur = nxt
             for kinds in ((ScaleShift,), (LeakyReLU, LeakyReLUF32)):
                 nn = list(g.G.successors(cur))
@@ -1344,11 +1368,14 @@ class Plan(object):
                 scale = e.affine.scale if e.affine is not None else None
                 shift = e.affine.shift if e.affine is not None else None
                 keep = (c.kernel, scale, shift)  # noqa: F841 (alive across the call)
-                rc = self.lib.dnn_plan_add_conv_padded(
-                    self.h, kh, kw, od, int(c.strides[1]), int(c.strides[2]), e.pads[0], e.pads[1],
-                    _vp(c.kernel) if upload else None, _vp(scale), _vp(shift),
-                    leaky_variant if e.leaky is None else e.leaky)
-                _check(rc, "dnn_plan_add_conv_padded", self.lib)
+                args = (_vp(c.kernel) if upload else None, _vp(scale), _vp(shift),
+                        leaky_variant if e.leaky is None else e.leaky)
+                geom = (self.h, kh, kw, od, int(c.strides[1]), int(c.strides[2]), e.pads[0], e.pads[1])
+                if isinstance(e, GroupedConvEntry):
+                    _check(self.lib.dnn_plan_add_conv_grouped(*geom, e.groups, *args), "dnn_plan_add_conv_grouped",
+                           self.lib)
+                else:
+                    _check(self.lib.dnn_plan_add_conv_padded(*geom, *args), "dnn_plan_add_conv_padded", self.lib)
             elif isinstance(e, ConvEntry):
                 c = e.conv
                 kh, kw, _, od = c.kernel.shape
@@ -1409,10 +1436,12 @@ class Plan(object):
                 if isinstance(e, PaddedConvEntry):
                     kh, kw, _, od = e.conv.kernel.shape
                     sc = _vp(e.affine.scale) if e.affine is not None else None  # (only says: affine or not)
-                    _check(lib.dnn_plan_add_conv_padded(h, kh, kw, od, int(e.conv.strides[1]), int(e.conv.strides[2]),
-                                                        e.pads[0], e.pads[1], None, sc, sc,
-                                                        1 if e.leaky is None else e.leaky),
-                           "dnn_plan_add_conv_padded", lib)
+                    geom = (h, kh, kw, od, int(e.conv.strides[1]), int(e.conv.strides[2]), e.pads[0], e.pads[1])
+                    args = (None, sc, sc, 1 if e.leaky is None else e.leaky)
+                    if isinstance(e, GroupedConvEntry):
+                        _check(lib.dnn_plan_add_conv_grouped(*geom, e.groups, *args), "dnn_plan_add_conv_grouped", lib)
+                    else:
+                        _check(lib.dnn_plan_add_conv_padded(*geom, *args), "dnn_plan_add_conv_padded", lib)
                 elif isinstance(e, ConvEntry):
                     kh, kw, _, od = e.conv.kernel.shape
                     _check(lib.dnn_plan_add_conv(h, kh, kw, od, int(e.conv.strides[1]), int(e.conv.strides[2]),

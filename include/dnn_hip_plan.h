@@ -231,6 +231,35 @@ int dnn_spp_host(const float* a, float* out, int n, int h, int w, int c, int n_s
 int dnn_plan_add_slice(dnn_plan* plan, int first, int channels);
 int dnn_slice_host(const float* a, float* out, int n, int h, int w, int c, int first, int channels);
 
+/* Grouped conv (fp32 plans, batch and latency mode; on an fp16 plan it fails).  The reference has
+ * no such node: it is Darknet's [convolutional] with groups > 1, the 3x3 convs of the ResNeXt
+ * backbones and, with groups == C, the depthwise half of a separable conv.
+ *
+ * dnn_plan_add_conv_grouped: with cg = C / groups and og = od / groups, output channel j reads
+ *   input channels [(j / og) * cg, (j / og) * cg + cg).  kernel is [kh][kw][cg][od] (HWIO with
+ *   I = cg), copied; NULL declares the shape only.  Geometry, pads, scale / shift and leaky are
+ *   exactly dnn_plan_add_conv_padded's, and so are their argument rules; groups >= 2 must divide
+ *   both the current C and od (groups == 1 is refused: that is dnn_plan_add_conv_padded).
+ *   Arithmetic is fp32 throughout.  cg % 4 == 0 and og % 4 == 0 run on the 4x4x1 fp32 MFMA (sixteen
+ *   independent blocks per issue, no block-diagonal zeros), everything else on the direct kernels
+ *   (depthwise 3x3 / 5x5 with C % 4 == 0 on a register-window kernel, the rest one thread per
+ *   output); the choice depends on the shape alone, so a frame's rows are the same bits at every
+ *   batch and in both modes.  One kernel ("gconv%d" in dnn_plan_kernel_info, 2 * M * od * kh * kw *
+ *   cg flops; input, weights and output as bytes).  Input and output are plain NHWC fp32 (the entry
+ *   stops the conv / pool fusions like the fork / join entries: no pool folds into it and no later
+ *   conv asks it for bordered or split planes); the input may be the caller's d_in, the output goes
+ *   to a slot or tap region when a stash or tap follows.  dnn_plan_describe prints a conv line with
+ *   " groups=<g>".  A failed call leaves the plan unchanged.
+ * dnn_conv_grouped_host: the kernel on host tensors (H2D copies, launch, D2H copy, synchronise):
+ *   x [n, h, w, c] -> out [n, OH, OW, od].  Each tensor must be below 2 GiB (refused from the
+ *   arguments, before any allocation). */
+int dnn_plan_add_conv_grouped(dnn_plan* plan, int kh, int kw, int od, int stride_h, int stride_w, int pad_h,
+                              int pad_w, int groups, const float* kernel, const float* scale, const float* shift,
+                              int leaky);
+int dnn_conv_grouped_host(const float* x, const float* kernel, const float* scale, const float* shift, float* out,
+                          int n, int h, int w, int c, int kh, int kw, int od, int stride_h, int stride_w, int pad_h,
+                          int pad_w, int groups, int leaky);
+
 /* Output shape of the plan so far (per image, plus the planned batch). */
 int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int* c);
 
