@@ -34,48 +34,17 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "dnn_common.h"
+#include "letterbox_dev.h"
 #include "../../include/dnn_hip_ingest.h"
 #include "../../include/dnn_hip_post.h"
 
 namespace dnnhip {
 
-// ------------------------------------------------------------------------------ geometry (host)
-struct LbGeom {
-  int new_h, new_w, pad_y, pad_x;
-};
-
-// false: a side of the letterboxed image is below 2 (Darknet divides by new - 1) or, beyond the
-// sizes fp32 quotients can order, above the network's
-static bool letterbox_geom(int src_h, int src_w, int net_h, int net_w, LbGeom* g) {
-  long long nw, nh;
-  if (((float)net_w / (float)src_w) < ((float)net_h / (float)src_h)) {
-    nw = net_w;
-    nh = ((long long)src_h * net_w) / src_w;
-  } else {
-    nh = net_h;
-    nw = ((long long)src_w * net_h) / src_h;
-  }
-  if (nw < 2 || nh < 2 || nw > net_w || nh > net_h) return false;
-  g->new_h = (int)nh;
-  g->new_w = (int)nw;
-  g->pad_x = (net_w - (int)nw) / 2;
-  g->pad_y = (net_h - (int)nh) / 2;
-  return true;
-}
-
 // ------------------------------------------------------------------------------ letterbox kernel
-// What the kernel needs of one frame; the host fills it and a chunk of them travels by value as
-// the kernel's argument (no device-side descriptor table, no copy to wait for).
-struct LbFrame {
-  unsigned long long offset;  // of the frame's first byte in the pixel buffer
-  int H, W;                   // source
-  int h, w;                   // letterboxed image
-  int pad_y, pad_x;
-  float h_scale, w_scale;
-};
-constexpr int LB_CHUNK = 64;  // frames per launch: 64 x 40 B of kernel argument
+// (the size rule, the by-value frame record LbFrame and the sampling of one pixel are in
+// letterbox_dev.h, shared with the NV12 kernel)
 struct LbChunk {
-  LbFrame f[LB_CHUNK];
+  LbFrame f[LB_CHUNK];  // 64 x 40 B of kernel argument
 };
 
 constexpr int LB_THREADS = 256;
@@ -97,49 +66,26 @@ __host__ __device__ __forceinline__ unsigned long long lb_fetch6(const uint8_t* 
   return q;
 }
 
-// pixel (oy, ox) of the network input, its three channels in output order (also host code, so a
-// CPU build can run the same arithmetic)
+// the packed frame's fetch for lb_sample: byte offsets of the two rows, then lb_fetch6 on each
+struct LbPackedFetch {
+  const uint8_t* __restrict__ img;
+  size_t frame_bytes, o0, o1;
+  int W;
+  __host__ __device__ __forceinline__ void frame(const LbFrame& f) { frame_bytes = (size_t)f.H * f.W * 3; W = f.W; }
+  __host__ __device__ __forceinline__ void rows(int iy, int iy1) { o0 = (size_t)iy * W * 3; o1 = (size_t)iy1 * W * 3; }
+  __host__ __device__ __forceinline__ unsigned long long first(int ix, int ix1) const {
+    return lb_fetch6(img, frame_bytes, o0 + (size_t)ix * 3, o0 + (size_t)ix1 * 3);
+  }
+  __host__ __device__ __forceinline__ unsigned long long second(int ix, int ix1) const {
+    return lb_fetch6(img, frame_bytes, o1 + (size_t)ix * 3, o1 + (size_t)ix1 * 3);
+  }
+};
+
 __host__ __device__ __forceinline__ void lb_pixel(const uint8_t* __restrict__ img, const LbFrame& f, const float* lut,
                                                   int oy, int ox, int flip, float* out) {
-  const int r = oy - f.pad_y, c = ox - f.pad_x;
-  if ((unsigned)r >= (unsigned)f.h || (unsigned)c >= (unsigned)f.w) {
-    out[0] = out[1] = out[2] = 0.5f;
-    return;
-  }
-  const size_t frame_bytes = (size_t)f.H * f.W * 3;
-  const float sy = (float)r * f.h_scale;
-  int iy = (int)sy;
-  const float dy = sy - (float)iy;
-  iy = iy < f.H - 1 ? iy : f.H - 1;                      // (addresses only: never taken for a
-  const int iy1 = iy + 1 < f.H ? iy + 1 : f.H - 1;       //  size fp32 indexes exactly)
-  const bool two = !(r == f.h - 1 || f.H == 1);
-  const bool edge = c == f.w - 1 || f.W == 1;            // part(r, c) = S(r, W-1), no interpolation
-  int ix = f.W - 1, ix1 = f.W - 1;
-  float dx = 0.f;
-  if (!edge) {
-    const float sx = (float)c * f.w_scale;
-    ix = (int)sx;
-    dx = sx - (float)ix;
-    ix = ix < f.W - 1 ? ix : f.W - 1;
-    ix1 = ix + 1 < f.W ? ix + 1 : f.W - 1;
-  }
-  const float omdx = 1.f - dx;
-  const size_t o0 = (size_t)iy * f.W * 3, o1 = (size_t)iy1 * f.W * 3;
-  const unsigned long long q0 = lb_fetch6(img, frame_bytes, o0 + (size_t)ix * 3, o0 + (size_t)ix1 * 3);
-  const unsigned long long q1 = two ? lb_fetch6(img, frame_bytes, o1 + (size_t)ix * 3, o1 + (size_t)ix1 * 3) : 0ull;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int sh = 8 * (flip ? 2 - k : k);
-    const float s00 = lut[(q0 >> sh) & 0xff], s01 = lut[(q0 >> (sh + 24)) & 0xff];
-    const float a = edge ? s00 : omdx * s00 + dx * s01;
-    float v = (1.f - dy) * a;
-    if (two) {
-      const float s10 = lut[(q1 >> sh) & 0xff], s11 = lut[(q1 >> (sh + 24)) & 0xff];
-      const float b = edge ? s10 : omdx * s10 + dx * s11;
-      v += dy * b;
-    }
-    out[k] = v;
-  }
+  LbPackedFetch fetch;
+  fetch.img = img;
+  lb_sample(fetch, f, lut, oy, ox, flip, out);
 }
 
 // Grid: x = pieces of one frame's output, y = frames of the chunk.  VEC: a piece is 16 bytes of
@@ -239,18 +185,7 @@ static int launch_letterbox(const uint8_t* d_pixels, const dnn_frame* frames, in
     LbChunk chunk = {};
     for (int k = 0; k < m; ++k) {
       const dnn_frame& fr = frames[c0 + k];
-      LbGeom g;
-      letterbox_geom(fr.h, fr.w, net_h, net_w, &g);
-      LbFrame& f = chunk.f[k];
-      f.offset = fr.offset;
-      f.H = fr.h;
-      f.W = fr.w;
-      f.h = g.new_h;
-      f.w = g.new_w;
-      f.pad_y = g.pad_y;
-      f.pad_x = g.pad_x;
-      f.h_scale = (float)(fr.h - 1) / (float)(g.new_h - 1);
-      f.w_scale = (float)(fr.w - 1) / (float)(g.new_w - 1);
+      chunk.f[k] = lb_frame(fr.offset, fr.h, fr.w, net_h, net_w);
     }
     const dim3 grid((unsigned)gx, (unsigned)m);
     float* dst = d_out + (size_t)c0 * frame_floats;

@@ -588,7 +588,7 @@ class DarknetModel(yolov3.YOLO_V3):
         self.head = head
         self.sess = dnn_hip.DnnInferenceEngine(self.g, debug, device=device, latency=latency)
         self._dev = None
-        self._ingest = {}  # detect_images' RaggedIngest per pixel order
+        self._ingest = {}  # detect_images' RaggedIngest per pixel order, detect_frames_nv12's per matrix
 
     def _need_head(self):
         if self.head is None:
@@ -612,7 +612,6 @@ class DarknetModel(yolov3.YOLO_V3):
         counts in self.buffers, ready for its pack().  (AlexeyAB's detector stretches an image to
         the network's size by default where this letterboxes, so boxes for YOLOv4-tiny compare
         with its -letter_box runs; not pinned by a test.)"""
-        import torch
         import ingest
         self._need_head()
         images = list(images)
@@ -622,6 +621,31 @@ class DarknetModel(yolov3.YOLO_V3):
         if order not in ingest.PIXEL_ORDERS:
             raise ValueError(f"order {order!r}: need one of {sorted(ingest.PIXEL_ORDERS)}")
         _, _, sizes, nbytes = ingest.ragged_layout(images, batch, 1 << 62, net_hw)  # (raises before any device work)
+        return self._detect_ingested(order, dict(order=order), images, sizes, nbytes, raise_errors)
+
+    def detect_frames_nv12(self, frames, matrix="bt601_limited", raise_errors=True):
+        """detect_images for decoder surfaces: up to `batch` NV12 frames of any sizes, each a
+        (y [H, W], uv [(H + 1) // 2, (W + 1) // 2, 2]) pair of uint8 arrays, converted to RGB under
+        `matrix` (ingest.YUV_MATRICES; include/dnn_hip_ingest.h has the integer conversion) and
+        letterboxed in one kernel (dnn_letterbox_frames_nv12).  The rows are those of detect_images on
+        the RGB image that conversion gives, in each frame's own pixels."""
+        import ingest
+        self._need_head()
+        frames = list(frames)
+        batch, net_hw = self.in_shape[0], self.in_shape[1:3]
+        if self.in_shape[3] != 3:
+            raise ValueError(f"detect_frames_nv12 needs a 3-channel network, [net] has channels = {self.in_shape[3]}")
+        ingest._matrix(matrix)
+        _, _, sizes, nbytes = ingest.nv12_layout(frames, batch, 1 << 62, net_hw)  # (raises before any device work)
+        return self._detect_ingested(("nv12", matrix), dict(pixel_format="nv12", matrix=matrix), frames, sizes, nbytes,
+                                     raise_errors)
+
+    def _detect_ingested(self, key, ingest_kw, images, sizes, nbytes, raise_errors):
+        """detect_images' device part: upload + letterbox into the plan's input through the
+        RaggedIngest kept under `key`, the plan, the decode, the correction."""
+        import torch
+        import ingest
+        batch, net_hw = self.in_shape[0], self.in_shape[1:3]
         n = len(images)
         plan = self.sess.plan()
         device = torch.device("cuda", plan.device)
@@ -629,10 +653,10 @@ class DarknetModel(yolov3.YOLO_V3):
         with torch.cuda.device(device):
             compute = torch.cuda.current_stream()
             stream = compute.cuda_stream
-            ing = self._ingest.get(order)
+            ing = self._ingest.get(key)
             if ing is None or ing.max_bytes < nbytes or ing.compute != compute:
-                ing = ingest.RaggedIngest(batch, max(nbytes, 1), net_hw, device, compute, order)
-                self._ingest[order] = ing
+                ing = ingest.RaggedIngest(batch, max(nbytes, 1), net_hw, device, compute, **ingest_kw)
+                self._ingest[key] = ing
             ing.submit(images, out_ptr=d["in"].data_ptr())
             plan.run_device(n, d["in"].data_ptr(), d["out"].data_ptr(), stream)
             self.buffers.run(d["taps"] + [d["out"].data_ptr()], n, stream)

@@ -13,7 +13,9 @@ letterbox instead: the image resized with its aspect kept, centred in a 0.5 canv
 (`dnn_letterbox_frames`; the arithmetic is in csrc/letterbox.hip).  `letterbox_gpu(im)` is the
 one-image call, `RaggedIngest` the same two-slot pipeline for batches of images of DIFFERENT
 sizes; `yolo_post.DetectionBuffers.correct` maps the decoded boxes back into each image's own
-pixels.
+pixels.  With `pixel_format="nv12"` RaggedIngest takes decoder surfaces (a Y plane and an
+interleaved half-resolution UV plane, 1.5 bytes a pixel) instead of packed pixels
+(`dnn_letterbox_frames_nv12`, csrc/letterbox_nv12.hip).
 """
 import collections
 import ctypes
@@ -42,7 +44,25 @@ _lib.dnn_letterbox_frames.argtypes = [ctypes.c_void_p, ctypes.c_ulonglong, ctype
 _lib.dnn_letterbox_frames_host.restype = ctypes.c_int
 _lib.dnn_letterbox_frames_host.argtypes = _lib.dnn_letterbox_frames.argtypes[:-1]
 
+
+class FrameNV12(ctypes.Structure):
+    """dnn_frame_nv12 (include/dnn_hip_ingest.h): the Y plane's h rows of `pitch` bytes at y_offset, the
+    UV plane's (h + 1) // 2 rows of `pitch` bytes at uv_offset."""
+    _fields_ = [("y_offset", ctypes.c_ulonglong), ("uv_offset", ctypes.c_ulonglong), ("h", ctypes.c_int),
+                ("w", ctypes.c_int), ("pitch", ctypes.c_int)]
+
+
+_lib.dnn_letterbox_frames_nv12.restype = ctypes.c_int
+_lib.dnn_letterbox_frames_nv12.argtypes = [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.POINTER(FrameNV12),
+                                           ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_void_p]
+_lib.dnn_letterbox_frames_nv12_host.restype = ctypes.c_int
+_lib.dnn_letterbox_frames_nv12_host.argtypes = _lib.dnn_letterbox_frames_nv12.argtypes[:-1]
+
 IN_SIZE = 416
+YUV_MATRICES = {"bt601_limited": 0, "bt709_limited": 1, "bt601_full": 2}  # DNN_YUV_*
+NV12_FORMS = {None: 0, "gather": 0x100, "staged": 0x200}                   # DNN_NV12_FORCE_*
+PIXEL_FORMATS = ("packed", "nv12")
 PIXEL_ORDERS = {"bgr": 0, "rgb": 1}  # DNN_PIXELS_BGR, DNN_PIXELS_RGB
 
 
@@ -214,6 +234,76 @@ def ragged_layout(images, batch, max_bytes, net_hw):
     return arrays, frames, sizes, at
 
 
+def _matrix(matrix, form=None):
+    if not isinstance(matrix, str) or matrix not in YUV_MATRICES:
+        raise ValueError(f"matrix {matrix!r}: need one of {sorted(YUV_MATRICES)}")
+    if form not in NV12_FORMS:
+        raise ValueError(f"form {form!r}: need None, 'gather' or 'staged'")
+    return YUV_MATRICES[matrix] | NV12_FORMS[form]
+
+
+def letterbox_nv12_device(d_pixels_ptr, pixels_bytes, frames, n, d_out_ptr, stream_ptr, net_hw=(IN_SIZE, IN_SIZE),
+                          matrix="bt601_limited", form=None):
+    """dnn_letterbox_frames_nv12: `frames` a ctypes array of FrameNV12 (host), the pointers device.
+    `form` forces one of the kernel's two forms (tests and measurement; the bits are the same)."""
+    dnn_hip._check(_lib.dnn_letterbox_frames_nv12(d_pixels_ptr, int(pixels_bytes), frames, int(n), d_out_ptr,
+                                                  int(net_hw[0]), int(net_hw[1]), _matrix(matrix, form), stream_ptr),
+                   "dnn_letterbox_frames_nv12")
+
+
+def nv12_layout(frames, batch, max_bytes, net_hw, descriptors=None):
+    """ragged_layout for NV12.  `frames` is a list of (y, uv) pairs, y an H x W and uv a
+    (H + 1) // 2 x (W + 1) // 2 x 2 uint8 array, laid back to back with the tightest pitch,
+    2 * ((W + 1) // 2); or, with `descriptors` (a list of (y_offset, uv_offset, h, w, pitch)), one
+    1-D uint8 surface buffer taken as it is.  Returns ([(offset, flat array), ...] to copy,
+    FrameNV12 array, [(h, w), ...], bytes).  Host only; raises ValueError and touches nothing."""
+    if descriptors is not None:
+        surf = frames
+        if not isinstance(surf, np.ndarray) or surf.dtype != np.uint8 or surf.ndim != 1:
+            raise ValueError("with descriptors, a 1-D uint8 surface buffer expected")
+        descs = [tuple(int(v) for v in d) for d in descriptors]
+        if any(len(d) != 5 for d in descs):
+            raise ValueError("a descriptor is (y_offset, uv_offset, h, w, pitch)")
+        copies, at = [(0, surf)], int(surf.size)
+    else:
+        frames, descs, copies, at = list(frames), [], [], 0
+        for i, fr in enumerate(frames):
+            ok = (isinstance(fr, (tuple, list)) and len(fr) == 2 and all(
+                isinstance(a, np.ndarray) and a.dtype == np.uint8 for a in fr) and fr[0].ndim == 2 and
+                fr[0].size > 0 and fr[1].shape == ((fr[0].shape[0] + 1) // 2, (fr[0].shape[1] + 1) // 2, 2))
+            if not ok:
+                raise ValueError(f"frame {i}: a (y [H, W], uv [(H + 1) // 2, (W + 1) // 2, 2]) pair of uint8 arrays "
+                                 "expected")
+            h, w = int(fr[0].shape[0]), int(fr[0].shape[1])
+            pitch = 2 * ((w + 1) // 2)
+            y = np.zeros((h, pitch), np.uint8)
+            y[:, :w] = fr[0]
+            uv_at = at + h * pitch
+            descs.append((at, uv_at, h, w, pitch))
+            copies += [(at, y.reshape(-1)), (uv_at, np.ascontiguousarray(fr[1]).reshape(-1))]
+            at = uv_at + ((h + 1) // 2) * pitch
+    if len(descs) > batch:
+        raise ValueError(f"{len(descs)} frames > batch {batch}")
+    if at > max_bytes:
+        raise ValueError(f"{at} surface bytes > max_bytes {max_bytes}")
+    arr = (FrameNV12 * max(len(descs), 1))()
+    for i, d in enumerate(descs):
+        y_at, uv_at, h, w, pitch = d
+        if h < 1 or w < 1:
+            raise ValueError(f"frame {i}: size {h} x {w}")
+        row = 2 * ((w + 1) // 2)
+        if pitch < row or min(y_at, uv_at) < 0 or max(y_at + (h - 1) * pitch + w,
+                                                       uv_at + ((h + 1) // 2 - 1) * pitch + row) > at:
+            raise ValueError(f"frame {i}: planes at {y_at} and {uv_at} with pitch {pitch} do not fit a {h} x {w} "
+                             f"frame in {at} bytes")
+        try:
+            letterbox_geometry(d[2], d[3], net_hw[0], net_hw[1])
+        except ValueError as e:
+            raise ValueError(f"frame {i}: {e}")
+        arr[i] = FrameNV12(*d)
+    return copies, arr, [(d[2], d[3]) for d in descs], at
+
+
 def letterbox_gpu(im, net_hw=(IN_SIZE, IN_SIZE), order="bgr", device=0):
     """Darknet's letterbox_image for one H x W x 3 uint8 image -> [net_h, net_w, 3] fp32 RGB
     (numpy); order "bgr" (cv2 frames, flipped) or "rgb"."""
@@ -241,14 +331,23 @@ class RaggedIngest(object):
     dev_u8[k]; the letterbox writing out[k] runs on the compute stream after everything enqueued
     there before it.  release(stream) has FrameIngest's meaning: needed only when the returned
     tensor is consumed on ANOTHER stream.  A rejected submit raises before the slot flips and
-    changes nothing."""
+    changes nothing.
 
-    def __init__(self, batch, max_bytes, net_hw=(IN_SIZE, IN_SIZE), device=0, compute_stream=None, order="bgr"):
+    pixel_format="nv12": submit takes NV12 frames (nv12_layout: (y, uv) pairs, or one surface
+    buffer with descriptors=), uploads their 1.5 bytes a pixel through the same two slots and
+    letterboxes them with dnn_letterbox_frames_nv12 under `matrix` (YUV_MATRICES); `order` is unused."""
+
+    def __init__(self, batch, max_bytes, net_hw=(IN_SIZE, IN_SIZE), device=0, compute_stream=None, order="bgr",
+                 pixel_format="packed", matrix="bt601_limited"):
         import torch
         self.torch = torch
         self.batch, self.max_bytes, self.net_hw = int(batch), int(max_bytes), (int(net_hw[0]), int(net_hw[1]))
         _order(order)
-        self.order = order
+        if pixel_format not in PIXEL_FORMATS:
+            raise ValueError(f"pixel_format {pixel_format!r}: need one of {PIXEL_FORMATS}")
+        if pixel_format == "nv12":
+            _matrix(matrix)
+        self.order, self.pixel_format, self.matrix = order, pixel_format, matrix
         if self.batch < 1 or self.max_bytes < 1 or self.net_hw[0] < 1 or self.net_hw[1] < 1:
             raise ValueError(f"batch {batch}, max_bytes {max_bytes}, net_hw {net_hw}: positive sizes expected")
         self.dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -263,21 +362,29 @@ class RaggedIngest(object):
         self.slot = 0
         self.last = None
 
-    def submit(self, images, out_ptr=None):
-        """images: a list of H x W x 3 uint8 arrays, len <= batch, 3 * sum(H * W) <= max_bytes.
+    def submit(self, images, out_ptr=None, descriptors=None):
+        """images: a list of H x W x 3 uint8 arrays, len <= batch, 3 * sum(H * W) <= max_bytes
+        (pixel_format "nv12": what nv12_layout takes, `descriptors` with it).
         Returns (tensor [n, net_h, net_w, 3], [(h, w), ...]).  With `out_ptr` (a device pointer
         to room for n frames, e.g. a plan's input buffer) the letterbox writes there instead of
         the slot's own tensor and the first value is None."""
         torch = self.torch
-        arrays, frames, sizes, nbytes = ragged_layout(images, self.batch, self.max_bytes, self.net_hw)
-        n = len(arrays)  # (everything above raises before the slot flips)
+        nv12 = self.pixel_format == "nv12"
+        if descriptors is not None and not nv12:
+            raise ValueError("descriptors= goes with pixel_format='nv12'")
+        if nv12:
+            copies, frames, sizes, nbytes = nv12_layout(images, self.batch, self.max_bytes, self.net_hw, descriptors)
+        else:
+            arrays, frames, sizes, nbytes = ragged_layout(images, self.batch, self.max_bytes, self.net_hw)
+            copies = [(f.offset, a.reshape(-1)) for f, a in zip(frames, arrays)]
+        n = len(sizes)  # (everything above raises before the slot flips)
         k = self.slot
         self.slot ^= 1
         if self.uploaded[k] is not None:
             self.uploaded[k].synchronize()  # the copy engine is done reading host[k]
         host = self.host[k].numpy()
-        for f, a in zip(frames, arrays):
-            host[f.offset:f.offset + a.size] = a.reshape(-1)
+        for at, a in copies:
+            host[at:at + a.size] = a
         up = torch.cuda.Event()
         with torch.cuda.stream(self.copy_stream):
             if self.prepped[k] is not None:
@@ -293,8 +400,12 @@ class RaggedIngest(object):
         if out_ptr is None and self.out[k] is None:
             self.out[k] = torch.empty((self.batch,) + self.net_hw + (3,), dtype=torch.float32, device=self.dev)
         dst = self.out[k].data_ptr() if out_ptr is None else int(out_ptr)
-        letterbox_device(self.dev_u8[k].data_ptr(), nbytes, frames, n, dst, self.compute.cuda_stream, self.net_hw,
-                         self.order)
+        if nv12:
+            letterbox_nv12_device(self.dev_u8[k].data_ptr(), nbytes, frames, n, dst, self.compute.cuda_stream,
+                                  self.net_hw, self.matrix)
+        else:
+            letterbox_device(self.dev_u8[k].data_ptr(), nbytes, frames, n, dst, self.compute.cuda_stream,
+                             self.net_hw, self.order)
         pe = torch.cuda.Event()
         pe.record(self.compute)
         self.prepped[k] = pe

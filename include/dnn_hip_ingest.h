@@ -70,6 +70,57 @@ int dnn_letterbox_frames(const uint8_t* d_pixels, unsigned long long pixels_byte
 int dnn_letterbox_frames_host(const uint8_t* pixels, unsigned long long pixels_bytes, const dnn_frame* frames, int n,
                               float* out, int net_h, int net_w, int order);
 
+/* ---- NV12 letterbox ingest: decoder surfaces to the network input ---------------------------
+ * Hardware video decoders and cameras deliver NV12: a full-resolution Y plane with a row pitch and
+ * a half-resolution plane of interleaved U, V pairs.  These entries take such surfaces where the
+ * entries above take packed pixels (csrc/letterbox_nv12.hip; 1.5 bytes a pixel instead of 3).
+ *
+ * The output is bit for bit what dnn_letterbox_frames(..., DNN_PIXELS_RGB) writes for the 8-bit RGB
+ * image that the integer conversion below makes of the surface.  Chroma is the sample of the
+ * pixel's 2 x 2 block, U, V = uv[y >> 1][x >> 1]: no chroma interpolation.  With D = U - 128,
+ * E = V - 128, clip to 0..255 and >> 8 an arithmetic shift:
+ *   matrix          C             R                       G                                B
+ *   BT601_LIMITED   298 (Y - 16)  clip((C+409E+128)>>8)   clip((C-100D-208E+128)>>8)       clip((C+516D+128)>>8)
+ *   BT709_LIMITED   298 (Y - 16)  clip((C+459E+128)>>8)   clip((C- 55D-136E+128)>>8)       clip((C+541D+128)>>8)
+ *   BT601_FULL      256 Y         clip((C+359E+128)>>8)   clip((C- 88D-183E+128)>>8)       clip((C+454D+128)>>8)
+ * These are the usual 8-bit fixed-point forms, stated here as this library's own definition
+ * (tests/nv12_oracle.py restates them in numpy).  Parity with a particular decoder's or library's
+ * converter (rounding, chroma siting, chroma upsampling) is unpinned; the conversion above and
+ * everything after it (the letterbox arithmetic, unchanged) are exact.
+ *
+ * Errors as above: NULL pointers, n < 0, a non-positive size, a network input of 2^31 floats or
+ * more, an unknown matrix, a pitch below the row's bytes, a plane past pixels_bytes, a letterbox
+ * with a side below 2 pixels (the message names the frame) return before any device call. */
+
+/* one NV12 frame of a ragged batch: Y plane h rows of `pitch` bytes at y_offset (w used bytes per
+ * row); UV plane (h + 1) / 2 rows of `pitch` bytes at uv_offset, U and V interleaved, (w + 1) / 2
+ * pairs used per row.  pitch >= 2 * ((w + 1) / 2).  The planes need not be adjacent (decoders align
+ * the Y plane's height) and no alignment of offsets or pitch is required.  Only the used bytes of a
+ * row are read, so a plane's last row may end with them. */
+typedef struct dnn_frame_nv12 {
+  unsigned long long y_offset, uv_offset;
+  int h, w, pitch;
+} dnn_frame_nv12;
+
+#define DNN_YUV_BT601_LIMITED 0 /* video default */
+#define DNN_YUV_BT709_LIMITED 1 /* HD video */
+#define DNN_YUV_BT601_FULL 2    /* JFIF */
+/* For tests and measurement, OR one into `matrix`: the kernel has two forms with identical bits and
+ * picks one per frame (csrc/letterbox_nv12.hip).  Forcing the staged form on a frame whose tiles'
+ * source rectangles do not fit its LDS buffer is an argument error. */
+#define DNN_NV12_FORCE_GATHER 0x100
+#define DNN_NV12_FORCE_STAGED 0x200
+
+/* dnn_letterbox_frames for NV12 surfaces; same contract: `frames` a HOST array fully read before
+ * the call returns, d_out [n][net_h][net_w][3] fp32 RGB with 0.5 outside each frame's image, every
+ * element written exactly once, asynchronous on `stream`, no copy, no synchronisation. */
+int dnn_letterbox_frames_nv12(const uint8_t* d_pixels, unsigned long long pixels_bytes, const dnn_frame_nv12* frames,
+                              int n, float* d_out, int net_h, int net_w, int matrix, void* stream);
+
+/* The same with host pointers, synchronous (allocates, copies in, runs, copies out). */
+int dnn_letterbox_frames_nv12_host(const uint8_t* pixels, unsigned long long pixels_bytes,
+                                   const dnn_frame_nv12* frames, int n, float* out, int net_h, int net_w, int matrix);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
