@@ -434,6 +434,19 @@ constexpr int SPP_MAX_K = 13;
 int launch_spp(const float* a, float* out, int n, int H, int W, int C, int n_sizes, const int* sizes, int x_first,
                hipStream_t stream);
 
+// classify.hip: the tail of a Darknet classifier.  Every tensor < 2 GiB; no atomics
+// global average pool, out [n, 1, 1, C] = (the sum of in [n, H, W, C] over the H * W positions) / (H * W), summed in
+// an order that depends on (H, W) alone; 16-byte loads when C % 4 == 0
+int launch_avgpool(const float* in, float* out, int n, int H, int W, int C, hipStream_t stream);
+// per row of in [n, classes]: exp(x - max x) / sum exp(x - max x); classes <= DNN_SOFTMAX_MAX_CLASSES (the row
+// lives in one workgroup's LDS), refused with a message otherwise
+int launch_softmax(const float* in, float* out, int n, int classes, hipStream_t stream);
+// per row of scores [n, classes] its k largest entries, descending, ties to the lower index: out_index /
+// out_score [n, k], status [n] = 0, or DNN_TOPK_NAN for a row that holds a NaN (its rows are not written).
+// 1 <= k <= min(DNN_TOPK_MAX, classes), classes <= DNN_SOFTMAX_MAX_CLASSES
+int launch_topk(const float* scores, int n, int classes, int k, int* out_index, float* out_score, int* status,
+                hipStream_t stream);
+
 // element-wise ops of the per-op ABI
 int launch_bias_add(const float* in, const float* b, float* out, long long n, int C, hipStream_t s);
 int launch_bn_mvg(const float* in, const float* mean, const float* sq, const float* gamma, float* out,

@@ -1,6 +1,6 @@
 // The join / element-wise kernels on host tensors (include/dnn_hip_plan.h: dnn_spp_host,
 // dnn_route_host, dnn_shortcut_host, dnn_scale_shift_host, dnn_upsample_host, dnn_slice_host,
-// dnn_conv_grouped_host).  Host code only:
+// dnn_conv_grouped_host, dnn_avgpool_host, dnn_softmax_host).  Host code only:
 // each entry checks its arguments and hands on_device() its inputs and a launch.
 #include <hip/hip_runtime.h>
 #include <initializer_list>
@@ -168,6 +168,33 @@ int dnn_slice_host(const float* a, float* out, int n, int h, int w, int c, int f
   return on_device("dnn_slice_host", {{a, af}}, of, out, of, [&](float* const* d, const float** res) {
     *res = d[1];
     return launch_slice(d[0], d[1], n, h, w, c, first, channels, nullptr);
+  });
+}
+
+int dnn_avgpool_host(const float* a, float* out, int n, int h, int w, int c) {
+  DNN_REQUIRE(a && out, "dnn_avgpool_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_avgpool_host: bad shape n=%d %dx%dx%d", n, h, w, c);
+  if (n == 0) return 0;
+  const size_t af = (size_t)n * h * w * c, of = (size_t)n * c;
+  DNN_REQUIRE(af * 4 < k2GiB, "dnn_avgpool_host: a tensor of n=%d %dx%dx%d is >= 2 GiB; split the batch", n, h, w, c);
+  return on_device("dnn_avgpool_host", {{a, af}}, of, out, of, [&](float* const* d, const float** res) {
+    *res = d[1];
+    return launch_avgpool(d[0], d[1], n, h, w, c, nullptr);
+  });
+}
+
+int dnn_softmax_host(const float* a, float* out, int n, int classes) {
+  DNN_REQUIRE(a && out, "dnn_softmax_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && classes > 0, "dnn_softmax_host: bad shape n=%d classes=%d", n, classes);
+  DNN_REQUIRE(classes <= DNN_SOFTMAX_MAX_CLASSES,
+              "dnn_softmax_host: a row of %d classes does not fit the workgroup's LDS (at most DNN_SOFTMAX_MAX_CLASSES = %d)",
+              classes, DNN_SOFTMAX_MAX_CLASSES);
+  if (n == 0) return 0;
+  const size_t f = (size_t)n * classes;
+  DNN_REQUIRE(f * 4 < k2GiB, "dnn_softmax_host: n=%d rows of %d classes are >= 2 GiB; split the batch", n, classes);
+  return on_device("dnn_softmax_host", {{a, f}}, f, out, f, [&](float* const* d, const float** res) {
+    *res = d[1];
+    return launch_softmax(d[0], d[1], n, classes, nullptr);
   });
 }
 

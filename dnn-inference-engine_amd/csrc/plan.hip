@@ -65,6 +65,9 @@
 // Grouped conv: a gconv entry (conv_grouped.hip) is Darknet's [convolutional] with groups > 1, one
 // kernel with its weights and its alpha / beta vectors in the weight arena; plain NHWC fp32 on both
 // sides, so it stops the peepholes too.
+//
+// Classifier tail: an avgpool entry and a softmax entry (classify.hip) are Darknet's [avgpool] and
+// [softmax], one kernel each, plain NHWC fp32 on both sides like the entries above.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -227,7 +230,7 @@ enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, 
 
 enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
                        LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9,
-                       LAYER_SLICE = 10, LAYER_GCONV = 11 };
+                       LAYER_SLICE = 10, LAYER_GCONV = 11, LAYER_AVGPOOL = 12, LAYER_SOFTMAX = 13 };
 
 struct PlanLayer {
   int type = LAYER_CONV;
@@ -299,7 +302,8 @@ enum StepKind : int {
   STEP_POOL,
   STEP_X3_COMBINE_POOL,  // a pool layer's step that also combines the partials of x3 conv `layer - 1`
   STEP_ROUTE, STEP_SHORTCUT, STEP_UPSAMPLE, STEP_SPP, STEP_SLICE, STEP_GCONV,
-  STEP_CVT_OUT           // fp16 plans: the last activation to the fp32 output
+  STEP_CVT_OUT,          // fp16 plans: the last activation to the fp32 output
+  STEP_AVGPOOL, STEP_SOFTMAX
 };
 
 struct Step {
@@ -449,7 +453,7 @@ static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
   place_outputs(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
-  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0, ngconv = 0;
+  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0, ngconv = 0, navg = 0, nsoft = 0;
   // (kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7)
   p->steps.clear();
   const double B = p->batch;
@@ -553,6 +557,12 @@ static void layout(dnn_plan* p) {
       off = align_up(off + 2 * (size_t)L.Npad, 64);
       snprintf(nm, sizeof(nm), "gconv%d", ngconv++);
       step(i, STEP_GCONV, 2.0 * M * L.OC * L.K, in_b + 4.0 * L.K * L.OC + out_b, cur, out);
+    } else if (L.type == LAYER_AVGPOOL) {  // one add per input element
+      snprintf(nm, sizeof(nm), "avgpool%d", navg++);
+      step(i, STEP_AVGPOOL, in_b / 4.0, in_b + out_b, cur, out);
+    } else if (L.type == LAYER_SOFTMAX) {  // per element a compare, a subtract and expf, an add, a division
+      snprintf(nm, sizeof(nm), "softmax%d", nsoft++);
+      step(i, STEP_SOFTMAX, 5.0 * out_b / 4.0, in_b + out_b, cur, out);
     }
     cur = out;
   }
@@ -1378,6 +1388,31 @@ int dnn_plan_add_spp(dnn_plan* p, int n_sizes, const int* sizes, int x_first) {
   return 0;
 }
 
+int dnn_plan_add_avgpool(dnn_plan* p) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_avgpool: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_avgpool: fp32 plans only (this is an fp16 plan)");
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_AVGPOOL);
+  L.OH = L.OW = 1;
+  push_computing(p, std::move(L));
+  return 0;
+}
+
+int dnn_plan_add_softmax(dnn_plan* p) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_softmax: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_softmax: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(p->cur_h == 1 && p->cur_w == 1,
+              "dnn_plan_add_softmax: the current tensor is %dx%dx%d, a 1x1xclasses vector is needed (add an avgpool first)",
+              p->cur_h, p->cur_w, p->cur_c);
+  DNN_REQUIRE(p->cur_c <= DNN_SOFTMAX_MAX_CLASSES,
+              "dnn_plan_add_softmax: %d classes do not fit the workgroup's LDS (at most DNN_SOFTMAX_MAX_CLASSES = %d)",
+              p->cur_c, DNN_SOFTMAX_MAX_CLASSES);
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_SOFTMAX);
+  push_computing(p, std::move(L));
+  return 0;
+}
+
 int dnn_plan_output_shape(const dnn_plan* p, int* batch, int* h, int* w, int* c) {
   DNN_REQUIRE(p, "dnn_plan_output_shape: plan is NULL");
   if (batch) *batch = p->batch;
@@ -1732,6 +1767,10 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
     }
     case STEP_SPP:
       return launch_spp(cur, dst, n, L.H, L.W, L.C, L.n_sizes, L.sizes, L.x_first ? 1 : 0, s);
+    case STEP_AVGPOOL:
+      return launch_avgpool(cur, dst, n, L.H, L.W, L.C, s);
+    case STEP_SOFTMAX:
+      return launch_softmax(cur, dst, n, L.C, s);
     default:
       set_error("dnn_plan_run: fp32 plan has an unsupported step kind %d", (int)st.kind);
       return -2;
@@ -1926,6 +1965,10 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
       snprintf(line, sizeof(line), "conv %dx%dx%d -> %dx%dx%d k%dx%d s%d mode=%s K=%d pad=%d,%d%s%s groups=%d\n", L.H, L.W,
                L.C, L.OH, L.OW, L.OC, L.kh, L.kw, L.sh, conv_grouped_mfma(L.C, L.OC, L.groups) ? "grouped_mfma" : "grouped_direct",
                L.K, L.pt, L.pl, (L.epi_flags & EPI_BN_AB) ? " affine" : "", p->latency ? " latency" : "", L.groups);
+    } else if (L.type == LAYER_AVGPOOL) {
+      snprintf(line, sizeof(line), "avgpool %dx%dx%d -> %dx%dx%d\n", L.H, L.W, L.C, L.OH, L.OW, L.OC);
+    } else if (L.type == LAYER_SOFTMAX) {
+      snprintf(line, sizeof(line), "softmax %dx%dx%d\n", L.H, L.W, L.C);
     } else if (L.type == LAYER_RELEASE) {
       snprintf(line, sizeof(line), "release %dx%dx%d slot=%d\n", L.H, L.W, L.C, L.slot);
     } else if (L.type == LAYER_TAP) {

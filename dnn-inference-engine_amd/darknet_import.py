@@ -41,11 +41,28 @@ scale_x_y other than 1 goes into the head per scale
 Importable stock models: YOLOv3, YOLOv3-SPP, YOLOv3-tiny and YOLOv4-tiny (cfg_text has their public
 definitions).
 
+Classifiers: [avgpool] (a dnn_hip.GlobalAvgPool node, dnn_plan_add_avgpool), [softmax] (groups 1,
+temperature 1, no tree, on a 1 x 1 map: a dnn_hip.Softmax node, dnn_plan_add_softmax), [connected]
+(output, activation linear or leaky, optional batch_normalize; only on a 1 x 1 map, where Darknet's
+CHW flattening and the engine's NHWC agree: a 1x1 padded conv entry), and [dropout] / [cost], which
+count as layers for [route] / [shortcut] indices and compute nothing.  A cfg without [yolo] builds
+with head=None and the last tensor computed as the plan's output: `inference` returns that tensor,
+and for a net ending in a 1 x 1 map
+
+    idx, prob = m.classify(frames, k=5)   # [n, k] best classes and their scores, top-k on the device
+
+cfg_text has the Darknet-19 and Darknet-53 classifier definitions ("darknet19", "darknet53").  The
+frames are [n, h, w, c] fp32 at the network's size: the classifier demo's resize and centre crop are
+the caller's.
+
 Weight files (load_weights / save_weights): three int32 `major, minor, revision`, then `seen` (8
 bytes when major * 10 + minor >= 2, else 4), then per [convolutional] in cfg order biases[n],
 with batch_normalize=1 scales[n], rolling_mean[n], rolling_variance[n], then
 weights[n][c / groups][kh][kw], all fp32 little-endian (a [convolutional] with groups > 1 is a grouped
-conv: one dnn_plan_add_conv_grouped entry, its kernel [kh][kw][c / groups][n]).  The reader is numpy.frombuffer on the file's
+conv: one dnn_plan_add_conv_grouped entry, its kernel [kh][kw][c / groups][n]).  A [connected] section
+has its own order (load_connected_weights): biases[outputs], weights[outputs][inputs], then with
+batch_normalize=1 scales, rolling_mean, rolling_variance; its dict holds 2-D "weights", which is how
+save_weights knows it.  The reader is numpy.frombuffer on the file's
 bytes: nothing in a weight file executes.
 
 Out of scope:
@@ -53,6 +70,8 @@ Out of scope:
   * YOLOv2's [reorg] and [region]: Darknet's reorg channel order is not the route kernel's
     (TensorFlow's space_to_depth), so yolov2.py's weights are not Darknet's either;
   * the mish activation and with it full YOLOv4 (cfg_text("yolov4") raises);
+  * [shortcut] with activation=leaky (Darknet's ResNet / ResNeXt classifiers), [connected] on a map
+    larger than 1 x 1, [softmax] with groups, a temperature or a tree;
   * [route] with groups > 1 over more than one layer (Darknet slices each layer then; no stock cfg
     does it);
   * [yolo] with new_coords = 1 (the scaled-YOLOv4 box form) and nms_kind = diounms (DIoU NMS): both
@@ -75,10 +94,12 @@ import dnn_hip
 import yolo_post
 import yolov3
 
-SECTION_TYPES = ("net", "convolutional", "shortcut", "route", "upsample", "maxpool", "yolo")
+SECTION_TYPES = ("net", "convolutional", "shortcut", "route", "upsample", "maxpool", "yolo", "avgpool", "softmax",
+                 "connected", "dropout", "cost")
 BN_EPS = 1e-6  # normalize_cpu's .000001f, added to sqrt(var)
 SCORE_THR, IOU_THR = 0.5, 0.45  # Darknet's detector defaults (-thresh .5, nms .45)
-MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny", "yolov4-tiny")
+MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny", "yolov4-tiny", "darknet19", "darknet53")
+CLASSIFIERS = {"darknet19": 224, "darknet53": 256}  # the classifier definitions and their default input size
 NMS_KINDS = ("default", "greedynms")  # [yolo] nms_kind values that are the decode's greedy NMS
 
 
@@ -90,7 +111,8 @@ class DarknetError(ValueError):
 def parse_cfg(text):
     """The sections of a Darknet cfg, in order: one dict per section with "type" (the name in
     brackets), "line" (its 1-based line number) and every `key = value` of the section as strings
-    (keys and values stripped).  `#` and `;` start comment lines; blank lines are skipped.  A
+    (keys and values stripped; a key named `type` or `line`, as in [cost]'s `type = sse`, is kept as
+    "type_" / "line_").  `#` and `;` start comment lines; blank lines are skipped.  A
     section type outside SECTION_TYPES raises DarknetError naming the type and the line; unknown
     keys inside a known section are kept and ignored by the importer."""
     sections = []
@@ -112,7 +134,10 @@ def parse_cfg(text):
         if not sections:
             raise DarknetError(f"line {no}: `{line}` before the first section")
         key, value = line.split("=", 1)
-        sections[-1][key.strip()] = value.strip()
+        key = key.strip()
+        if key in ("type", "line"):  # ([cost] has `type = sse`: kept beside the section's own "type")
+            key += "_"
+        sections[-1][key] = value.strip()
     if not sections or sections[0]["type"] != "net":
         raise DarknetError("a cfg starts with a [net] section")
     if any(s["type"] == "net" for s in sections[1:]):
@@ -252,6 +277,42 @@ def yolo_params(sec):
     return s
 
 
+def connected_params(sec, in_h, in_w):
+    """(output, batch_normalize, activation) of a [connected] section on an in_h x in_w map.  Darknet
+    flattens its input as CHW and this engine's tensors are NHWC, so only a 1 x 1 map (after an
+    [avgpool]) has the same element order in both; anything else raises DarknetError."""
+    where = f"[connected] at line {sec['line']}"
+    n = _int(sec, "output")
+    act = sec.get("activation", "logistic")
+    if act not in ("leaky", "linear"):
+        raise DarknetError(f"{where}: activation {act!r} is not supported (leaky, linear)")
+    if n < 1:
+        raise DarknetError(f"{where}: output = {n}: need >= 1")
+    if (in_h, in_w) != (1, 1):
+        raise DarknetError(f"{where}: its input is {in_h} x {in_w}: only a 1 x 1 map is supported (Darknet flattens "
+                           "channels first, the engine's tensors are channels last)")
+    return n, bool(_int(sec, "batch_normalize", 0)), act
+
+
+def softmax_params(sec, in_h, in_w):
+    """Refuses what the softmax kernel does not compute: groups other than 1, a temperature other
+    than 1, a tree, an input that is not 1 x 1 spatially."""
+    where = f"[softmax] at line {sec['line']}"
+    if _int(sec, "groups", 1) != 1:
+        raise DarknetError(f"{where}: groups = {sec['groups']} is not supported (only 1)")
+    try:
+        temperature = float(sec.get("temperature", 1))
+    except ValueError:
+        raise DarknetError(f"{where}: temperature = {sec['temperature']!r} is not a number")
+    if temperature != 1:
+        raise DarknetError(f"{where}: temperature = {temperature} is not supported (only 1)")
+    if "tree" in sec:
+        raise DarknetError(f"{where}: tree = {sec['tree']} (a hierarchical softmax) is not supported")
+    if (in_h, in_w) != (1, 1):
+        raise DarknetError(f"{where}: its input is {in_h} x {in_w}: only a 1 x 1 map is supported (put an [avgpool] "
+                           "before it)")
+
+
 def layer_shapes(sections, in_shape=None):
     """Per layer (every section after [net]) its output's (h, w, c), walking the cfg as Darknet's
     parser does; raises DarknetError for a section that does not fit its input."""
@@ -295,6 +356,15 @@ def layer_shapes(sections, in_shape=None):
             if at == 0 or sections[at]["type"] != "convolutional":
                 raise DarknetError(f"[yolo] at line {sec['line']}: it must follow a [convolutional] section")
             yolo_params(sec)
+        elif kind == "avgpool":
+            h, w = 1, 1
+        elif kind == "softmax":
+            softmax_params(sec, h, w)
+            if c > dnn_hip.SOFTMAX_MAX_CLASSES:
+                raise DarknetError(f"[softmax] at line {sec['line']}: {c} classes, at most {dnn_hip.SOFTMAX_MAX_CLASSES}")
+        elif kind == "connected":
+            c = connected_params(sec, h, w)[0]
+        # (dropout and cost: layers that compute nothing at inference; the tensor passes through)
         shapes.append((h, w, c))
     return shapes
 
@@ -311,6 +381,24 @@ def conv_shapes(sections):
         if sec["type"] == "convolutional":
             n, size, _, _, bn, _ = conv_params(sec)
             out.append((n, c_in // conv_groups(sec, c_in), size, bn))
+        c_in = shape[2]
+    return out
+
+
+def weight_shapes(sections):
+    """Per section with weights, [convolutional] and [connected], in cfg order: (kind, filters or
+    outputs, input channels, size, batch_normalize): conv_shapes' tuples behind the section type,
+    a [connected] with size 0 (its weights are [outputs][inputs])."""
+    net = sections[0]
+    shapes = layer_shapes(sections, [1, max(_int(net, "height"), 1), max(_int(net, "width"), 1), _int(net, "channels", 3)])
+    convs = iter(conv_shapes(sections))
+    out = []
+    c_in = _int(net, "channels", 3)
+    for sec, shape in zip(sections[1:], shapes):
+        if sec["type"] == "convolutional":
+            out.append(("convolutional",) + next(convs))
+        elif sec["type"] == "connected":
+            out.append(("connected", shape[2], c_in, 0, bool(_int(sec, "batch_normalize", 0))))
         c_in = shape[2]
     return out
 
@@ -354,21 +442,26 @@ def load_weights(path, sections, partial=False):
         at = end
         return a
 
-    for k, (n, c, size, bn) in enumerate(conv_shapes(sections)):
+    for k, (kind, n, c, size, bn) in enumerate(weight_shapes(sections)):
         start = at
+        fc = kind == "connected"
+        w_count, w_shape = (n * c, (n, c)) if fc else (n * c * size * size, (n, c, size, size))
         try:
             layer = {"biases": take(n, (n,), "biases")}
+            if fc:  # load_connected_weights: the weights come before the BatchNorm vectors
+                layer["weights"] = take(w_count, w_shape, "weights")
             if bn:
                 for key in ("scales", "rolling_mean", "rolling_variance"):
                     layer[key] = take(n, (n,), key)
-            layer["weights"] = take(n * c * size * size, (n, c, size, size), "weights")
+            if not fc:
+                layer["weights"] = take(w_count, w_shape, "weights")
         except EOFError as e:
             if partial:
                 at = start
                 break
-            raise DarknetError(f"{path}: the file ends inside the {e} of convolutional layer {k} "
-                               f"({n} filters of {c} x {size} x {size}): {len(data)} bytes, at least "
-                               f"{start + 4 * ((4 if bn else 1) * n + n * c * size * size)} expected")
+            raise DarknetError(f"{path}: the file ends inside the {e} of {kind} layer {k} "
+                               f"({n} filters of {' x '.join(map(str, w_shape[1:]))}): {len(data)} bytes, at least "
+                               f"{start + 4 * ((4 if bn else 1) * n + w_count)} expected")
         out.append(layer)
     if at != len(data) and not partial:
         raise DarknetError(f"{path}: {len(data) - at} bytes left after the last convolutional layer "
@@ -377,26 +470,36 @@ def load_weights(path, sections, partial=False):
 
 
 def save_weights(path, layers, major=0, minor=2, revision=0, seen=0):
-    """Write `layers` (dicts as load_weights returns them, in cfg order) as a Darknet weight file."""
+    """Write `layers` (dicts as load_weights returns them, in cfg order) as a Darknet weight file.  A
+    layer whose weights are 2-D, [outputs][inputs], is a [connected] layer and is written in
+    save_connected_weights' order: biases, weights, then the BatchNorm vectors."""
     with open(path, "wb") as f:
         f.write(struct.pack("<3i", major, minor, revision))
         f.write(struct.pack("<q" if _header_seen_bytes(major, minor) == 8 else "<i", seen))
         for k, layer in enumerate(layers):
             w = np.asarray(layer["weights"])
-            if w.ndim != 4 or w.shape[2] != w.shape[3]:
-                raise DarknetError(f"layer {k}: weights of shape {w.shape}, [n][c][size][size] expected")
+            if w.ndim != 2 and (w.ndim != 4 or w.shape[2] != w.shape[3]):
+                raise DarknetError(f"layer {k}: weights of shape {w.shape}, [n][c][size][size] (or a connected layer's "
+                                   "[outputs][inputs]) expected")
             keys = ("biases",) + (("scales", "rolling_mean", "rolling_variance") if "scales" in layer else ())
             for key in keys:
                 a = np.asarray(layer[key])
                 if a.shape != (w.shape[0],):
                     raise DarknetError(f"layer {k}: {key} of shape {a.shape}, ({w.shape[0]},) expected")
                 f.write(np.ascontiguousarray(a, dtype="<f4").tobytes())
-            f.write(np.ascontiguousarray(w, dtype="<f4").tobytes())
+                if key == "biases" and w.ndim == 2:
+                    f.write(np.ascontiguousarray(w, dtype="<f4").tobytes())
+            if w.ndim == 4:
+                f.write(np.ascontiguousarray(w, dtype="<f4").tobytes())
 
 
 def kernel_hwio(layer):
-    """A layer's Darknet weights [n][c][kh][kw] as the engine's HWIO kernel [kh][kw][c][n]."""
-    return np.ascontiguousarray(np.asarray(layer["weights"], np.float32).transpose(2, 3, 1, 0))
+    """A layer's Darknet weights [n][c][kh][kw] as the engine's HWIO kernel [kh][kw][c][n]; a
+    connected layer's [outputs][inputs] as the 1x1 kernel [1][1][inputs][outputs]."""
+    w = np.asarray(layer["weights"], np.float32)
+    if w.ndim == 2:
+        w = w[:, :, None, None]
+    return np.ascontiguousarray(w.transpose(2, 3, 1, 0))
 
 
 def fold_batchnorm(layer):
@@ -416,17 +519,19 @@ def fold_batchnorm(layer):
 
 
 def check_layers(sections, layers):
-    """`layers` (load_weights' format) against the cfg's conv shapes: DarknetError on a mismatch."""
-    shapes = conv_shapes(sections)
+    """`layers` (load_weights' format) against the cfg's conv and connected shapes: DarknetError on
+    a mismatch."""
+    shapes = weight_shapes(sections)
     if len(layers) != len(shapes):
         raise DarknetError(f"{len(layers)} weight layers for {len(shapes)} [convolutional] sections")
-    for k, (layer, (n, c, size, bn)) in enumerate(zip(layers, shapes)):
+    for k, (layer, (kind, n, c, size, bn)) in enumerate(zip(layers, shapes)):
         keys = ("biases", "weights") + (("scales", "rolling_mean", "rolling_variance") if bn else ())
         if any(key not in layer for key in keys):
-            raise DarknetError(f"convolutional layer {k}: expected a dict with {keys}")
-        if tuple(np.asarray(layer["weights"]).shape) != (n, c, size, size):
-            raise DarknetError(f"convolutional layer {k}: weights of shape {np.asarray(layer['weights']).shape}, "
-                               f"{(n, c, size, size)} expected")
+            raise DarknetError(f"{kind} layer {k}: expected a dict with {keys}")
+        want = (n, c) if kind == "connected" else (n, c, size, size)
+        if tuple(np.asarray(layer["weights"]).shape) != want:
+            raise DarknetError(f"{kind} layer {k}: weights of shape {np.asarray(layer['weights']).shape}, "
+                               f"{want} expected")
 
 
 # ------------------------------------------------------------------------------------- the graph
@@ -441,7 +546,9 @@ class _LazyPool(object):
 def build_graph(builder_cls, sections, layers, in_shape):
     """Return (graph, outs, yolos): outs the head nodes (the conv before each [yolo], in cfg
     order; all but the last are the graph's extra outputs, the last its primary one), yolos the
-    [yolo] sections with "grid" = that tensor's (h, w).  `layers` is load_weights' list."""
+    [yolo] sections with "grid" = that tensor's (h, w).  A cfg without [yolo] (a classifier ending
+    in [softmax], or any prefix of a network as a feature extractor) has one output, the last
+    tensor computed, and no yolos.  `layers` is load_weights' list."""
     check_layers(sections, layers)
     shapes = layer_shapes(sections, in_shape)
     g = builder_cls()
@@ -491,6 +598,19 @@ def build_graph(builder_cls, sections, layers, in_shape):
                 cur = _LazyPool(prev, size)
             else:
                 cur = g.create_max_pool2d(node(prev), [1, size, size, 1], [1, stride, stride, 1], "SAME")
+        elif kind == "avgpool":
+            cur = g.create_global_avg_pool(node(prev))
+        elif kind == "softmax":
+            cur = g.create_softmax(node(prev))
+        elif kind == "connected":  # on a 1 x 1 map (connected_params): a 1x1 conv of [outputs][inputs]
+            _, _, act = connected_params(sec, 1, 1)
+            layer = next(weights)
+            scale, shift = fold_batchnorm(layer)
+            t = g.create_conv2d_padded(node(prev), kernel_hwio(layer), [1, 1, 1, 1], (0, 0))
+            t = g.create_scale_shift(t, scale, shift)
+            cur = g.create_leaky_relu_f32(t) if act == "leaky" else t
+        elif kind in ("dropout", "cost"):  # a layer for [route] / [shortcut] indices, nothing at inference
+            cur = prev
         else:  # yolo: the conv before it is an output; the layer itself repeats that tensor
             outs.append(node(prev))
             yolos.append(dict(sec, grid=shapes[at][:2]))
@@ -498,8 +618,11 @@ def build_graph(builder_cls, sections, layers, in_shape):
         out.append(cur)
         prev = cur
         c_in = shapes[at][2]
-    if not outs:
-        raise DarknetError("the cfg has no [yolo] section: nothing to output")
+    if not outs:  # a classifier or a feature extractor: the last tensor computed is the output
+        if prev is x:
+            raise DarknetError("the cfg has no layer that computes: nothing to output")
+        g.set_out_node(node(prev))
+        return g, [node(prev)], []
     if outs[-1] is not node(prev):
         raise DarknetError("the last [yolo] section must end the cfg (the plan's output is the last tensor computed)")
     if len(outs) > yolo_post.MAX_SCALES or len(set(map(id, outs))) != len(outs):
@@ -570,6 +693,11 @@ class DarknetModel(yolov3.YOLO_V3):
             weights, "__fspath__") else list(weights)
         self.g, self.outs, self.yolos = build_graph(dnn_hip.DnnGraphBuilder, self.sections, self.layers, self.in_shape)
         self._head_error = None
+        self._cls = None  # classify's device tensors and its TopK, made on first use
+        if not self.yolos:
+            if head is not _AUTO and head is not None:
+                raise ValueError("the cfg has no [yolo] section: there is nothing for a head to decode")
+            head, self._head_error = None, "the cfg has no [yolo] section: the model has no detection head"
         if head is _AUTO:
             try:
                 head = multi_head(self.yolos, h, w, score_thr, iou_thr, nms, labels, wide)
@@ -593,6 +721,42 @@ class DarknetModel(yolov3.YOLO_V3):
     def _need_head(self):
         if self.head is None:
             raise ValueError(self._head_error or "the model was built with head=None: pass head=")
+
+    def inference(self, im):
+        """One tensor per [yolo] section, in cfg order; for a cfg without [yolo] the one output
+        tensor itself (a classifier's [n, 1, 1, classes] probabilities)."""
+        outs = super().inference(im)
+        return outs if self.yolos else outs[0]
+
+    def classify(self, frames, k=5, raise_errors=True):
+        """(indices [n, k] int32, probabilities [n, k] fp32) of a classifier cfg for [n <= batch, h, w,
+        c] fp32 frames already at the network's size (Darknet's resize and centre crop are the
+        caller's): the plan, then the top-k of its [n, 1, 1, classes] output on the device
+        (classify.TopK), best class first, equal scores in index order.  An image whose scores hold
+        a NaN raises ValueError, or with raise_errors=False gets index -1 and NaN."""
+        import torch
+        import classify as topk
+        plan = self.sess.plan()
+        if self.yolos or plan.out_shape[:2] != (1, 1):
+            raise ValueError(f"classify needs a cfg without [yolo] that ends in a 1 x 1 map, this one's output is "
+                             f"{plan.out_shape}" + (" with [yolo] sections" if self.yolos else ""))
+        x = np.ascontiguousarray(frames, dtype=np.float32)
+        n = x.shape[0]
+        if tuple(x.shape[1:]) != plan.in_shape or n > plan.batch:
+            raise ValueError(f"frames {x.shape} do not fit plan [{plan.batch}, {plan.in_shape}]")
+        device = torch.device("cuda", plan.device)
+        if self._cls is None or self._cls["topk"].k != int(k):
+            self._cls = {"in": torch.empty((plan.batch,) + plan.in_shape, dtype=torch.float32, device=device),
+                         "out": torch.empty((plan.batch,) + plan.out_shape, dtype=torch.float32, device=device),
+                         "topk": topk.TopK(plan.batch, plan.out_shape[2], k, device)}
+        d, tk = self._cls, self._cls["topk"]
+        with torch.cuda.device(device):
+            stream = torch.cuda.current_stream().cuda_stream
+            d["in"][:n].copy_(torch.from_numpy(x))
+            plan.run_device(n, d["in"].data_ptr(), d["out"].data_ptr(), stream)
+            tk.run(d["out"].data_ptr(), n, stream)
+            host = [t[:n].cpu().numpy() for t in (tk.index, tk.score, tk.status)]
+        return topk.TopK.to_rows(*host, raise_errors=raise_errors)
 
     def postprocessing(self, outs):
         self._need_head()
@@ -716,14 +880,30 @@ class _Cfg(object):
         return "\n".join(self.lines)
 
 
-def cfg_text(model, classes=80, width=416, height=416, width_div=1):
-    """The public definition of `model` ("yolov3", "yolov3-spp", "yolov3-tiny" or "yolov4-tiny") as cfg
-    text, for `classes` classes and a width x height input; width_div divides every channel count
-    except the heads' 3 x (5 + classes) (a narrow model of the same topology)."""
+def cfg_text(model, classes=None, width=None, height=None, width_div=1):
+    """The public definition of `model` (one of MODELS) as cfg text, for `classes` classes and a
+    width x height input; width_div divides every channel count except the heads' 3 x (5 + classes)
+    or the classifier conv's `classes` (a narrow model of the same topology).  Defaults: 80 classes
+    at 416 x 416 for the detectors; 1000 classes for the classifiers "darknet19" (224 x 224) and
+    "darknet53" (256 x 256), which end in [avgpool] and [softmax]."""
     if model not in MODELS:
         raise ValueError(f"model {model!r}: one of {MODELS} expected")
-    n_out = 3 * (5 + int(classes))
+    size = CLASSIFIERS.get(model, 416)
+    classes = (1000 if model in CLASSIFIERS else 80) if classes is None else int(classes)
+    width, height = size if width is None else width, size if height is None else height
+    n_out = 3 * (5 + classes)
     c = _Cfg(width, height, int(width_div))
+    if model == "darknet19":
+        for stage, f in enumerate((32, 64, 128, 256, 512, 1024)):
+            for j in range(1 if stage < 2 else 3 if stage < 4 else 5):  # 3x3 f, 1x1 f / 2, 3x3 f, ...
+                c.conv(f // 2 if j % 2 else f, 1 if j % 2 else 3)
+            if stage < 5:
+                c.add("maxpool", ("size", 2), ("stride", 2))
+        c.conv(classes, 1, head=True)
+        c.add("avgpool")
+        c.add("softmax", ("groups", 1))
+        c.add("cost", ("type", "sse"))
+        return c.text()
     if model == "yolov3-tiny":
         for k, f in enumerate((16, 32, 64, 128, 256, 512)):
             at = c.conv(f, 3)
@@ -778,6 +958,11 @@ def cfg_text(model, classes=80, width=416, height=416, width_div=1):
             c.conv(f // 2, 1)
             c.conv(f, 3)
             stage_end.append(c.add("shortcut", ("from", -3), ("activation", "linear")))
+    if model == "darknet53":  # the classifier: the trunk, then the pool, the class conv and the softmax
+        c.add("avgpool")
+        c.conv(classes, 1, head=True)
+        c.add("softmax", ("groups", 1))
+        return c.text()
     ends = []  # the last layer of each stage
     at = 0
     for _, blocks in _STAGES:

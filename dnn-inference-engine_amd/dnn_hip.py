@@ -28,7 +28,9 @@ node, one spp plan entry, one kernel (yolov3_spp.py).  `Conv2DPadded` (`create_c
 a conv with the same zero padding on both sides of each axis (Darknet's), `ScaleShift`
 (`create_scale_shift`) a per-channel y = x * scale + shift (a BatchNorm folded on the host) and
 `LeakyReLUF32` (`create_leaky_relu_f32`) the fp32 leaky max(x, 0.1f x); a conv followed by a
-ScaleShift and either leaky lowers to one dnn_plan_add_conv_padded entry (darknet_import.py).  With
+ScaleShift and either leaky lowers to one dnn_plan_add_conv_padded entry (darknet_import.py).
+`GlobalAvgPool` and `Softmax` (`create_global_avg_pool`, `create_softmax`) are the tail of a Darknet
+classifier, one avgpool / softmax plan entry and one kernel each (csrc/classify.hip).  With
 `debug=True` (or a graph the plan cannot express) it instead runs node by node through
 the per-op C-ABI (`conv2d_mul`, `bias_add`, ... in libdnn_hip.so, include/dnn_hip.h),
 exactly like the reference, and saves every layer to ./intermediate/layer_{k}.npy
@@ -93,6 +95,10 @@ def _bind_plan_api(lib):
         "dnn_plan_add_slice": (i, [vp, i, i]),
         "dnn_slice_host": (i, [vp, vp, i, i, i, i, i, i]),
         "dnn_spp_host": (i, [vp, vp, i, i, i, i, i, P(i), i]),
+        "dnn_plan_add_avgpool": (i, [vp]),
+        "dnn_plan_add_softmax": (i, [vp]),
+        "dnn_avgpool_host": (i, [vp, vp, i, i, i, i]),
+        "dnn_softmax_host": (i, [vp, vp, i, i]),
         "dnn_plan_output_shape": (i, [vp, P(i), P(i), P(i), P(i)]),
         "dnn_plan_describe": (i, [vp, ctypes.c_char_p, i]),
         "dnn_plan_memory": (i, [vp, P(sz), P(sz)]),
@@ -300,7 +306,7 @@ class DnnGraphBuilder(object):
         self.G = nx.DiGraph() if nx is not None else _DiGraph()
         self.name_num = {"conv2d": 0, "bias_add": 0, "max_pool2d": 0, "batch_norm": 0, "leaky_relu": 0,
                          "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0, "spp": 0,
-                         "channel_slice": 0,
+                         "channel_slice": 0, "global_avg_pool": 0, "softmax": 0,
                          "conv2d_padded": 0, "scale_shift": 0, "leaky_relu_f32": 0}
         self.in_node = None
         self.out_node = None
@@ -388,6 +394,16 @@ class DnnGraphBuilder(object):
 
     def create_spp(self, in_node, ksizes, x_first=False):
         out_node = Spp(self.get_name("spp"), in_node, ksizes, x_first)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_global_avg_pool(self, in_node):
+        out_node = GlobalAvgPool(self.get_name("global_avg_pool"), in_node)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_softmax(self, in_node):
+        out_node = Softmax(self.get_name("softmax"), in_node)
         self.G.add_edge(in_node, out_node)
         return out_node
 
@@ -825,6 +841,44 @@ class Spp(DnnNode):
         _check(rc, self.name)
 
 
+SOFTMAX_MAX_CLASSES = 32768  # DNN_SOFTMAX_MAX_CLASSES: the row lives in one workgroup's LDS
+
+
+class GlobalAvgPool(DnnNode):
+    """Not in the reference (a Darknet classifier's [avgpool]): [n, H, W, C] -> [n, 1, 1, C], per
+    channel the fp32 sum over the H x W positions divided once by H * W.  run() -> dnn_avgpool_host."""
+
+    def __init__(self, name, in_node):
+        if len(in_node.result.shape) != 4:
+            raise ValueError
+        batch, _, _, c = in_node.result.shape
+        self.in_node = in_node
+        self.result = np.zeros((batch, 1, 1, c), dtype='float32')
+        self.name = name
+
+    def run(self):
+        a = np.ascontiguousarray(self.in_node.result, dtype=np.float32)
+        _check(mylib.dnn_avgpool_host(_vp(a), _vp(self.result), *map(int, a.shape)), self.name)
+
+
+class Softmax(DnnNode):
+    """Not in the reference (a Darknet classifier's [softmax], temperature 1, one group):
+    [n, 1, 1, classes] -> the same shape, exp(x - max x) / sum exp(x - max x) per image, with
+    classes <= SOFTMAX_MAX_CLASSES.  run() -> dnn_softmax_host."""
+
+    def __init__(self, name, in_node):
+        shape = in_node.result.shape
+        if len(shape) != 4 or shape[1] != 1 or shape[2] != 1 or shape[3] > SOFTMAX_MAX_CLASSES:
+            raise ValueError
+        self.in_node = in_node
+        self.result = np.zeros(shape, dtype='float32')
+        self.name = name
+
+    def run(self):
+        a = np.ascontiguousarray(self.in_node.result, dtype=np.float32)
+        _check(mylib.dnn_softmax_host(_vp(a), _vp(self.result), int(a.shape[0]), int(a.shape[3])), self.name)
+
+
 class Input(DnnNode):
     """proj3/dnn_openblas.py:287-300 (unchanged contract)."""
 
@@ -944,6 +998,20 @@ class SliceEntry(object):
         self.nodes = list(nodes)
 
 
+class AvgPoolEntry(object):
+    """dnn_plan_add_avgpool: the current tensor's global average over its positions."""
+
+    def __init__(self, nodes=()):
+        self.nodes = list(nodes)
+
+
+class SoftmaxEntry(object):
+    """dnn_plan_add_softmax: the softmax of the current 1 x 1 x classes tensor."""
+
+    def __init__(self, nodes=()):
+        self.nodes = list(nodes)
+
+
 class TapEntry(object):
     """dnn_plan_add_tap: the current tensor becomes the plan's extra output `index` (no kernel);
     `node` is the graph node it is the result of (None in plans assembled by hand)."""
@@ -1026,6 +1094,10 @@ def _lower_one(g, nxt):
         return SliceEntry(nxt.first, nxt.channels, nodes=[nxt]), nxt
     if isinstance(nxt, Spp):
         return SppEntry(nxt.ksizes, nxt.x_first, nodes=[nxt]), nxt
+    if isinstance(nxt, GlobalAvgPool):
+        return AvgPoolEntry(nodes=[nxt]), nxt
+    if isinstance(nxt, Softmax):
+        return SoftmaxEntry(nodes=[nxt]), nxt
     return None  # a standalone element-wise op: not expressible as a fused entry
 
 
@@ -1154,7 +1226,7 @@ def _output_branch(g, head):
 def lower_graph(g):
     """Lower a builder graph to fused plan entries, or None if the plan cannot express it (then
     the node-by-node path runs).  Expressible: a chain of Conv2D (with its BiasAdd / BatchNorm /
-    LeakyReLU), MaxPool2D, SpaceToDepth, Upsample, ChannelSlice and Spp, and forks of two such chains (either may be
+    LeakyReLU), MaxPool2D, SpaceToDepth, Upsample, ChannelSlice, Spp, GlobalAvgPool and Softmax, and forks of two such chains (either may be
     empty) joined by one Concat or one Add (with a LeakyReLU directly after it), any number of
     them in sequence within the plan's slots (an Add block gives its slots back, and so does a
     Concat fork lowered inside a pending long skip); forks nested in a fork's branch are not.
@@ -1310,7 +1382,7 @@ def _pad_code(padding):
 
 def _add_structural(lib, h, e, leaky_variant=1):
     """Emit a StashEntry / RestoreEntry / RouteEntry / ShortcutEntry / ReleaseEntry /
-    UpsampleEntry / SppEntry / SliceEntry / TapEntry; False if `e` is none of them."""
+    UpsampleEntry / SppEntry / SliceEntry / AvgPoolEntry / SoftmaxEntry / TapEntry; False if `e` is none of them."""
     if isinstance(e, StashEntry):
         slot = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_stash(h, ctypes.byref(slot)), "dnn_plan_add_stash", lib)
@@ -1331,6 +1403,10 @@ def _add_structural(lib, h, e, leaky_variant=1):
         _check(lib.dnn_plan_add_spp(h, len(e.ksizes), sizes, 1 if e.x_first else 0), "dnn_plan_add_spp", lib)
     elif isinstance(e, SliceEntry):
         _check(lib.dnn_plan_add_slice(h, e.first, e.channels), "dnn_plan_add_slice", lib)
+    elif isinstance(e, AvgPoolEntry):
+        _check(lib.dnn_plan_add_avgpool(h), "dnn_plan_add_avgpool", lib)
+    elif isinstance(e, SoftmaxEntry):
+        _check(lib.dnn_plan_add_softmax(h), "dnn_plan_add_softmax", lib)
     elif isinstance(e, TapEntry):
         index = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_tap(h, ctypes.byref(index)), "dnn_plan_add_tap", lib)

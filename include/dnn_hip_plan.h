@@ -231,6 +231,33 @@ int dnn_spp_host(const float* a, float* out, int n, int h, int w, int c, int n_s
 int dnn_plan_add_slice(dnn_plan* plan, int first, int channels);
 int dnn_slice_host(const float* a, float* out, int n, int h, int w, int c, int first, int channels);
 
+/* The tail of a Darknet classifier (fp32 plans, batch and latency mode; on an fp16 plan both fail).
+ * The reference has no such nodes: darknet19.cfg and darknet53.cfg end in [avgpool], a 1x1
+ * [convolutional] of `classes` filters and [softmax].
+ *
+ * dnn_plan_add_avgpool: current [H, W, C] -> [1, 1, C], Darknet's forward_avgpool_layer: per channel
+ *   the fp32 sum over the H * W positions, then one fp32 division by H * W.  The summation order
+ *   depends on (H, W) alone, so image i has the same bits in a batch-1 and a batch-n plan.  One
+ *   kernel ("avgpool%d" in dnn_plan_kernel_info, H * W * C flops, the input and the output as bytes),
+ *   16-byte loads when C % 4 == 0.
+ * dnn_plan_add_softmax: current [1, 1, classes] -> the same shape, Darknet's softmax() with
+ *   temperature 1 over the whole vector: p[j] = expf(x[j] - max x) / sum_k expf(x[k] - max x) in fp32,
+ *   a division per element.  One kernel ("softmax%d"), one workgroup per image with the row in LDS,
+ *   which bounds it: classes <= DNN_SOFTMAX_MAX_CLASSES.  Fails, leaving the plan unchanged, when the
+ *   current tensor is not 1 x 1 spatially (add an avgpool first) or has more classes than that.
+ * Both read and write plain NHWC fp32 and stop the conv / pool fusions like the fork / join entries;
+ *   the output goes to a slot or tap region when a stash or tap follows and to d_out when the entry
+ *   is the plan's last.  Darknet's [connected] needs no entry of its own: on a [1, 1, inputs] tensor
+ *   it is dnn_plan_add_conv_padded with a [1][1][inputs][outputs] kernel and no padding.
+ * dnn_avgpool_host, dnn_softmax_host: the kernels on host tensors (H2D copy, launch, D2H copy,
+ *   synchronise): a [n, h, w, c] -> out [n, c]; a [n, classes] -> out [n, classes].  Each tensor must
+ *   be below 2 GiB (refused from the arguments, before any allocation). */
+#define DNN_SOFTMAX_MAX_CLASSES 32768 /* 128 KB of the workgroup's 160 KB of LDS */
+int dnn_plan_add_avgpool(dnn_plan* plan);
+int dnn_plan_add_softmax(dnn_plan* plan);
+int dnn_avgpool_host(const float* a, float* out, int n, int h, int w, int c);
+int dnn_softmax_host(const float* a, float* out, int n, int classes);
+
 /* Grouped conv (fp32 plans, batch and latency mode; on an fp16 plan it fails).  The reference has
  * no such node: it is Darknet's [convolutional] with groups > 1, the 3x3 convs of the ResNeXt
  * backbones and, with groups == C, the depthwise half of a separable conv.

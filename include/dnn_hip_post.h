@@ -322,6 +322,27 @@ int dnn_yolo_correct_detections(dnn_detection* dets, const int* counts, int n_im
 int dnn_yolo_correct_detections_host(dnn_detection* dets, const int* counts, int n_images, int max_det,
                                      const dnn_image_size* sizes, int net_h, int net_w);
 
+/* ---- classifiers: the k best classes of a score row -------------------------------------
+ * The reference has no classifier.  Darknet's classifier demo sorts the softmax output on the host
+ * (top_k in utils.c: the k largest entries, unordered ties); here, per image, the k largest entries of
+ * scores [n_images][classes] in descending order, equal scores in ascending index order, written as
+ * index [n_images][k] (int32) and score [n_images][k] (fp32, the entries' own bits).  Any fp32 row
+ * is accepted, probabilities or logits, -inf and +inf included.  1 <= k <= min(DNN_TOPK_MAX,
+ * classes) and classes <= DNN_SOFTMAX_MAX_CLASSES (include/dnn_hip_plan.h: the row is staged in one
+ * workgroup's LDS); anything else returns -2 before any launch.
+ * status[i]: 0, or DNN_TOPK_NAN when row i holds a NaN, which has no place in an order: that image's
+ * index / score rows are then left as they were, and the other images are not touched by it.
+ * Device pointers, asynchronous on `stream` (one launch; it may be captured in a HIP graph). */
+#define DNN_TOPK_MAX 16
+#define DNN_TOPK_NAN (-1)
+
+int dnn_classify_topk(const float* scores, int n_images, int classes, int k, int* index, float* score, int* status,
+                      void* stream);
+
+/* Host pointers, synchronous (copies in, runs, copies out). */
+int dnn_classify_topk_host(const float* scores, int n_images, int classes, int k, int* index, float* score,
+                           int* status);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
