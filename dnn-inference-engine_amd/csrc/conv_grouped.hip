@@ -5,7 +5,7 @@
 //                                                     * w[ky][kx][k][j]  - beta[j])
 //
 // in and out are plain NHWC fp32, w is [kh][kw][cg][OC]; samples outside the frame are zeros; the
-// epilogue is dnn_plan_add_conv_padded's (v * alpha - beta, never contracted, then apply_leaky).
+// epilogue is dnn_plan_add_conv_padded's (v * alpha - beta, never contracted, then apply_act).
 // All arithmetic is fp32.  launch_conv_grouped picks one of two kernels from the shape alone, so a
 // frame's rows are the same bits whatever the batch and the plan's mode.
 //
@@ -48,7 +48,7 @@ struct GroupedGeom {
   int H, W, C, OH, OW, OC;
   int kh, kw, sh, sw, ph, pw;
   int cg, og;
-  int flags;  // EPI_BN_AB | EPI_LEAKY_*
+  int flags;  // EPI_BN_AB | EPI_LEAKY_* or an EPI_ACT_MASK code
 };
 
 constexpr int GC_THREADS = 256;  // 4 waves
@@ -57,7 +57,7 @@ constexpr int GC_BUDGET = 160;   // resident B floats per lane (a K chunk)
 
 __device__ __forceinline__ float gc_epilogue(float v, float a, float b, int flags) {
   if (flags & EPI_BN_AB) v = v * a - b;
-  return apply_leaky(v, flags);
+  return apply_act(v, epi_act(flags));
 }
 
 // One lane's view of its A pixel in each of the P quads of a group: the input offset of tap (0, 0)

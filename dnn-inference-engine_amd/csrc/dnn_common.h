@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <utility>
 #include <vector>
+#include "act_dev.h"
 
 namespace dnnhip {
 
@@ -106,16 +107,15 @@ enum EpiFlags : int {
   EPI_BN_AB = 16,      // v * alpha - beta                       (dnn_avx.c:505-507)
   EPI_OUT_X3 = 32,     // (pool-fused fp32 implicit GEMM) store the exact 3-way bf16 split of the
                        // result into the zero-bordered split planes of an x3 conv's input
+  // bits 6..8: an activation of act_dev.h by its code (ACT_LOGISTIC, ACT_SWISH, ACT_MISH), instead of a leaky
+  EPI_ACT_SHIFT = 6,
+  EPI_ACT_MASK = 7 << EPI_ACT_SHIFT,
 };
 
-// the epilogue's activation (both leaky variants), shared by the conv epilogue and the shortcut
-__device__ __forceinline__ float apply_leaky(float v, int flags) {
-  if (flags & EPI_LEAKY_F64) v = v < 0.f ? (float)(0.1 * (double)v) : v;
-  if (flags & EPI_LEAKY_F32) {
-    float t = v * 0.1f;
-    v = v > t ? v : t;
-  }
-  return v;
+// the epilogue's activation as an act_dev.h code: one of the two leaky bits, or the code in EPI_ACT_MASK
+__host__ __device__ __forceinline__ int epi_act(int flags) {
+  return (flags & EPI_LEAKY_F64) ? ACT_LEAKY_F64 : (flags & EPI_LEAKY_F32) ? ACT_LEAKY_F32
+                                                                             : (flags & EPI_ACT_MASK) >> EPI_ACT_SHIFT;
 }
 
 struct EpiParams {
@@ -400,9 +400,12 @@ int launch_conv1_patch_f16(const Switches& sws, const half_t* in, const half_t* 
 int launch_route(const float* a, const float* b, float* out, int n, int H, int W, int Ca, int block, int Cb,
                  int b_first, hipStream_t stream);
 
-// shortcut.hip: out[i] = act(a[i] + b[i]) over `count` floats (leaky 0 none, 1 / 2 the conv
-// epilogue's two variants; one fp32 add, bit-equal to a float32 a + b); out may alias neither input.
-int launch_shortcut(const float* a, const float* b, float* out, long long count, int leaky, hipStream_t stream);
+// shortcut.hip: out[i] = act(a[i] + b[i]) over `count` floats (act: an act_dev.h code, 0 none, 1 / 2 the
+// conv epilogue's two leaky variants; one fp32 add, bit-equal to a float32 a + b); out may alias neither input.
+int launch_shortcut(const float* a, const float* b, float* out, long long count, int act, hipStream_t stream);
+// activate.hip: out[i] = apply_act(in[i], act) over `count` floats, act one of ACT_LOGISTIC / _SWISH / _MISH;
+// 16-byte accesses when both pointers are 16-byte aligned; in place (out == in) is allowed.  Every tensor < 2 GiB
+int launch_activate(const float* in, float* out, long long count, int act, hipStream_t stream);
 // nearest-neighbour upsample: out [n, H*factor, W*factor, C] = in [n, H, W, C] repeated, factor in
 // 1..8; 16-byte accesses when C % 4 == 0.  Every tensor < 2 GiB
 int launch_upsample(const float* in, float* out, int n, int H, int W, int C, int factor, hipStream_t stream);
@@ -413,7 +416,7 @@ int launch_slice(const float* in, float* out, int n, int H, int W, int C, int fi
                  hipStream_t stream);
 
 // conv_grouped.hip: grouped / depthwise conv, in [n, H, W, C] -> out [n, OH, OW, OC], plain NHWC fp32, pads ph / pw on
-// every side, epilogue v * alpha - beta (flags & EPI_BN_AB) then apply_leaky(flags).  `w` is what
+// every side, epilogue v * alpha - beta (flags & EPI_BN_AB) then apply_act(epi_act(flags)).  `w` is what
 // conv_grouped_pack made of the [kh][kw][C / groups][OC] kernel (conv_grouped_weight_floats floats:
 // lane-ordered 16-byte runs for the MFMA kernel, conv_grouped_mfma; the kernel as it is otherwise).
 // The kernel is chosen from the shape alone.  Every tensor < 2 GiB, 16-byte aligned when C % 4 == 0

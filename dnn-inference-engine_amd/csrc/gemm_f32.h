@@ -141,7 +141,7 @@ __device__ __forceinline__ float apply_epilogue(float v, float bias, float mean,
   if (flags & EPI_BIAS) v = v + bias;
   if (flags & EPI_BN) v = div_rn(v - mean, sq) * gamma;
   if (flags & EPI_BN_AB) v = v * mean - sq;
-  return apply_leaky(v, flags);
+  return apply_act(v, epi_act(flags));
 }
 
 template <int MF>

@@ -1,6 +1,6 @@
 // The join / element-wise kernels on host tensors (include/dnn_hip_plan.h: dnn_spp_host,
 // dnn_route_host, dnn_shortcut_host, dnn_scale_shift_host, dnn_upsample_host, dnn_slice_host,
-// dnn_conv_grouped_host, dnn_avgpool_host, dnn_softmax_host).  Host code only:
+// dnn_conv_grouped_host, dnn_avgpool_host, dnn_softmax_host, dnn_activate_host).  Host code only:
 // each entry checks its arguments and hands on_device() its inputs and a launch.
 #include <hip/hip_runtime.h>
 #include <initializer_list>
@@ -195,6 +195,19 @@ int dnn_softmax_host(const float* a, float* out, int n, int classes) {
   return on_device("dnn_softmax_host", {{a, f}}, f, out, f, [&](float* const* d, const float** res) {
     *res = d[1];
     return launch_softmax(d[0], d[1], n, classes, nullptr);
+  });
+}
+
+int dnn_activate_host(const float* a, float* out, long long n, int act) {
+  DNN_REQUIRE(a && out, "dnn_activate_host: NULL tensor");
+  DNN_REQUIRE(act >= DNN_ACT_LOGISTIC && act <= DNN_ACT_MISH,
+              "dnn_activate_host: act %d is none of DNN_ACT_LOGISTIC, DNN_ACT_SWISH, DNN_ACT_MISH", act);
+  DNN_REQUIRE(n >= 0 && (unsigned long long)n * 4 < k2GiB, "dnn_activate_host: a tensor of %lld floats is >= 2 GiB; split it", n);
+  if (n == 0) return 0;
+  const size_t f = (size_t)n;
+  return on_device("dnn_activate_host", {{a, f}}, f, out, f, [&](float* const* d, const float** res) {
+    *res = d[1];
+    return launch_activate(d[0], d[1], n, act, nullptr);
   });
 }
 

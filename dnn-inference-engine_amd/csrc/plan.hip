@@ -68,6 +68,13 @@
 //
 // Classifier tail: an avgpool entry and a softmax entry (classify.hip) are Darknet's [avgpool] and
 // [softmax], one kernel each, plain NHWC fp32 on both sides like the entries above.
+//
+// Activations: an activation entry (logistic, swish, mish: act_dev.h) is folded into the conv_padded, gconv
+// or shortcut entry that produced the current tensor when that entry has no activation yet and nothing
+// has named or pooled its output (its EPI_ACT_MASK code, or the shortcut's act); it then launches
+// nothing.  Anywhere else it is a layer with one kernel (activate.hip).  Mish and swish are not monotone,
+// so a conv that carries one never fuses a max pool: every pool-fused epilogue pools the raw sums first
+// (nonmonotone() guards dnn_plan_add_max_pool's peepholes and the x3 combine that pools).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -230,7 +237,7 @@ enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, 
 
 enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
                        LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9,
-                       LAYER_SLICE = 10, LAYER_GCONV = 11, LAYER_AVGPOOL = 12, LAYER_SOFTMAX = 13 };
+                       LAYER_SLICE = 10, LAYER_GCONV = 11, LAYER_AVGPOOL = 12, LAYER_SOFTMAX = 13, LAYER_ACT = 14 };
 
 struct PlanLayer {
   int type = LAYER_CONV;
@@ -264,7 +271,8 @@ struct PlanLayer {
   int factor = 1;           // upsample
   int first = 0;            // slice: the first channel taken (OC channels from there)
   int groups = 1;           // gconv
-  int leaky = 0;            // shortcut: 0 none, 1 / 2 the conv epilogue's variants
+  int leaky = 0;            // shortcut: its activation (act_dev.h: 0 none, 1 / 2 the conv epilogue's leaky
+                            // variants, 3..5 a fused activation entry); an activation layer: its code
   int n_sizes = 0, sizes[DNN_SPP_MAX_SIZES] = {0, 0, 0};  // spp: the pools' window sizes, in block order
   bool x_first = false;     // spp: the input's copy is the first channel block
   int dst_loc = 0;          // where this layer writes when its output is plain NHWC (LOC_*; layout())
@@ -275,6 +283,8 @@ struct PlanLayer {
   int out_w() const { return pool == POOL_S2 ? PW : OW; }
   // the GEMM's rows for n images (pool-window-major rows with a fused stride-2 pool)
   long long rows(long long n) const { return pool == POOL_S2 ? 4 * n * PH * PW : n * OH * OW; }
+  // a conv whose activation has a minimum (mish, swish): pooling its raw sums first would be wrong
+  bool nonmonotone() const { return !act_is_monotone(epi_act(epi_flags)); }
 };
 
 constexpr int kMaxSlots = 4;
@@ -303,7 +313,7 @@ enum StepKind : int {
   STEP_X3_COMBINE_POOL,  // a pool layer's step that also combines the partials of x3 conv `layer - 1`
   STEP_ROUTE, STEP_SHORTCUT, STEP_UPSAMPLE, STEP_SPP, STEP_SLICE, STEP_GCONV,
   STEP_CVT_OUT,          // fp16 plans: the last activation to the fp32 output
-  STEP_AVGPOOL, STEP_SOFTMAX
+  STEP_AVGPOOL, STEP_SOFTMAX, STEP_ACT
 };
 
 struct Step {
@@ -453,7 +463,7 @@ static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
   place_outputs(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
-  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0, ngconv = 0, navg = 0, nsoft = 0;
+  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0, ngconv = 0, navg = 0, nsoft = 0, nact = 0;
   // (kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7)
   p->steps.clear();
   const double B = p->batch;
@@ -509,7 +519,7 @@ static void layout(dnn_plan* p) {
       if (is_x3(L.variant)) {
         if (L.splits > 1) {  // raw partials; combined by the next pool's step, or by a step of its own
           slab = std::max(slab, (size_t)L.splits * L.OH * L.OW * L.OC);
-          if (!(i + 1 < nl && p->layers[i + 1].type == LAYER_POOL)) {
+          if (!(i + 1 < nl && p->layers[i + 1].type == LAYER_POOL) || L.nonmonotone()) {
             snprintf(nm, sizeof(nm), "conv%d.combine", nconv);
             step(i, STEP_X3_COMBINE, sum_flops, sum_bytes, LOC_NONE, out);
           }
@@ -532,7 +542,7 @@ static void layout(dnn_plan* p) {
     } else if (L.type == LAYER_POOL) {
       // behind a split x3 conv the pool's kernel sums that conv's partials and applies its epilogue first
       const bool combines = i > 0 && p->layers[i - 1].is_conv() && is_x3(p->layers[i - 1].variant) &&
-                            p->layers[i - 1].splits > 1;
+                            p->layers[i - 1].splits > 1 && !p->layers[i - 1].nonmonotone();
       snprintf(nm, sizeof(nm), "pool%d", npool++);
       step(i, combines ? STEP_X3_COMBINE_POOL : STEP_POOL, 0.0, in_b + out_b, cur, out);
     } else if (L.type == LAYER_ROUTE) {  // reads a and b, writes out: input bytes == output bytes
@@ -563,6 +573,9 @@ static void layout(dnn_plan* p) {
     } else if (L.type == LAYER_SOFTMAX) {  // per element a compare, a subtract and expf, an add, a division
       snprintf(nm, sizeof(nm), "softmax%d", nsoft++);
       step(i, STEP_SOFTMAX, 5.0 * out_b / 4.0, in_b + out_b, cur, out);
+    } else if (L.type == LAYER_ACT) {  // per element an expf, a division and up to four more operations
+      snprintf(nm, sizeof(nm), "activate%d", nact++);
+      step(i, STEP_ACT, 6.0 * out_b / 4.0, in_b + out_b, cur, out);
     }
     cur = out;
   }
@@ -1040,7 +1053,7 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
       L.pl == 0) {
     PlanLayer& prev = p->layers.back();
     // (latency plans: a split implicit conv keeps its split, the combine pools)
-    if (prev.is_conv() && !prev.pool &&
+    if (prev.is_conv() && !prev.pool && !prev.nonmonotone() &&
         (prev.splits == 1 ||
          (prev.variant == CONV_IMPLICIT && !p->fp16 && p->sw.splitk_fused && generic_combine_cfg(prev.cfg)))) {
       bool ok = false;
@@ -1096,7 +1109,7 @@ int dnn_plan_add_max_pool(dnn_plan* p, int kh, int kw, int stride_h, int stride_
   // a 2x2/stride-1 SAME pool (YOLO's pool5) into a single-frame x3_ktile conv before it: the conv
   // computes the row below each tile too and pools before its epilogue
   if (p->sw.fuse && !p->layers.empty() && kh == 2 && kw == 2 && stride_h == 1 && stride_w == 1 && L.pt == 0 &&
-      L.pl == 0 && L.OH == L.H && L.OW == L.W) {
+      L.pl == 0 && L.OH == L.H && L.OW == L.W && !p->layers.back().nonmonotone()) {
     PlanLayer& prev = p->layers.back();
     if (prev.is(CONV_X3_KTILE) && !prev.pool &&
         conv_x3_ktile_supported(p->sw, p->batch, prev.C, prev.OC, prev.H, prev.W, prev.OH, prev.OW, prev.kh, prev.kw,
@@ -1409,6 +1422,40 @@ int dnn_plan_add_softmax(dnn_plan* p) {
               p->cur_c, DNN_SOFTMAX_MAX_CLASSES);
   PlanLayer L;
   shape_only_layer(p, &L, LAYER_SOFTMAX);
+  push_computing(p, std::move(L));
+  return 0;
+}
+
+static const char* act_name(int act) {
+  return act == ACT_LOGISTIC ? "logistic" : act == ACT_SWISH ? "swish" : act == ACT_MISH ? "mish" : "none";
+}
+
+int dnn_plan_add_activation(dnn_plan* p, int act) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_activation: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_activation: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(act == DNN_ACT_LOGISTIC || act == DNN_ACT_SWISH || act == DNN_ACT_MISH,
+              "dnn_plan_add_activation: act %d is none of DNN_ACT_LOGISTIC (%d), DNN_ACT_SWISH (%d), DNN_ACT_MISH (%d)", act,
+              DNN_ACT_LOGISTIC, DNN_ACT_SWISH, DNN_ACT_MISH);
+  // the fused form: the current tensor is the output of the last layer that computes (only release
+  // entries may follow it: a stash, a tap or a restore would have moved cur_src), that layer has no
+  // activation yet and no pool fused behind its epilogue
+  if (p->cur_src == -1 && !p->layers.empty()) {
+    size_t k = p->layers.size() - 1;
+    while (k > 0 && p->layers[k].type == LAYER_RELEASE) --k;
+    PlanLayer& q = p->layers[k];
+    const bool conv = (q.type == LAYER_CONV && q.xpad) || q.type == LAYER_GCONV;
+    if (conv && epi_act(q.epi_flags) == ACT_NONE && q.pool == POOL_NONE && q.to_region < 0 && !q.out_padded) {
+      q.epi_flags |= act << EPI_ACT_SHIFT;
+      return 0;
+    }
+    if (q.type == LAYER_SHORTCUT && q.leaky == ACT_NONE && q.to_region < 0) {
+      q.leaky = act;
+      return 0;
+    }
+  }
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_ACT);
+  L.leaky = act;
   push_computing(p, std::move(L));
   return 0;
 }
@@ -1771,6 +1818,8 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
       return launch_avgpool(cur, dst, n, L.H, L.W, L.C, s);
     case STEP_SOFTMAX:
       return launch_softmax(cur, dst, n, L.C, s);
+    case STEP_ACT:
+      return launch_activate(cur, dst, (long long)n * L.H * L.W * L.C, L.leaky, s);
     default:
       set_error("dnn_plan_run: fp32 plan has an unsupported step kind %d", (int)st.kind);
       return -2;
@@ -1935,10 +1984,13 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
   for (size_t i = 0; i < p->layers.size(); ++i) {
     const PlanLayer& L = p->layers[i];
     if (L.type == LAYER_CONV) {
-      char sk[32] = "", xp[48] = "";
+      char sk[32] = "", xp[64] = "";
       if (L.splits > 1) snprintf(sk, sizeof(sk), " splitK=%d", L.splits);
-      if (L.xpad)  // dnn_plan_add_conv_padded: the pads on every side, and its scale / shift epilogue
-        snprintf(xp, sizeof(xp), " pad=%d,%d%s", L.pt, L.pl, (L.epi_flags & EPI_BN_AB) ? " affine" : "");
+      if (L.xpad) {  // dnn_plan_add_conv_padded: the pads on every side, its scale / shift epilogue, a fused activation entry
+        const int a = epi_act(L.epi_flags);
+        snprintf(xp, sizeof(xp), " pad=%d,%d%s%s%s", L.pt, L.pl, (L.epi_flags & EPI_BN_AB) ? " affine" : "",
+                 a >= ACT_LOGISTIC ? " act=" : "", a >= ACT_LOGISTIC ? act_name(a) : "");
+      }
       snprintf(line, sizeof(line), "conv %dx%dx%d -> %dx%dx%d k%dx%d s%d mode=%s cfg=%d K=%d Kpad=%d%s%s%s%s%s%s\n", L.H,
                L.W, L.C, L.out_h(), L.out_w(), L.OC, L.kh, L.kw, L.sh, kVariantName[L.variant], L.cfg, L.K, L.Kpad,
                L.pool == POOL_S2 ? " +pool2x2s2" : L.pool == POOL_S1 ? " +pool2x2s1" : "", sk,
@@ -1955,20 +2007,24 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
                sb);
     } else if (L.type == LAYER_SHORTCUT) {
       snprintf(line, sizeof(line), "shortcut %dx%dx%d slot=%d act=%s\n", L.H, L.W, L.C, L.slot,
-               L.leaky == 1 ? "leaky" : L.leaky == 2 ? "leaky_f32" : "none");
+               L.leaky == 1 ? "leaky" : L.leaky == 2 ? "leaky_f32" : act_name(L.leaky));
     } else if (L.type == LAYER_UPSAMPLE) {
       snprintf(line, sizeof(line), "upsample %dx%dx%d -> %dx%dx%d factor=%d\n", L.H, L.W, L.C, L.OH, L.OW, L.OC,
                L.factor);
     } else if (L.type == LAYER_SLICE) {
       snprintf(line, sizeof(line), "slice %dx%dx%d -> %dx%dx%d first=%d\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.first);
     } else if (L.type == LAYER_GCONV) {
-      snprintf(line, sizeof(line), "conv %dx%dx%d -> %dx%dx%d k%dx%d s%d mode=%s K=%d pad=%d,%d%s%s groups=%d\n", L.H, L.W,
+      const int a = epi_act(L.epi_flags);
+      snprintf(line, sizeof(line), "conv %dx%dx%d -> %dx%dx%d k%dx%d s%d mode=%s K=%d pad=%d,%d%s%s groups=%d%s%s\n", L.H, L.W,
                L.C, L.OH, L.OW, L.OC, L.kh, L.kw, L.sh, conv_grouped_mfma(L.C, L.OC, L.groups) ? "grouped_mfma" : "grouped_direct",
-               L.K, L.pt, L.pl, (L.epi_flags & EPI_BN_AB) ? " affine" : "", p->latency ? " latency" : "", L.groups);
+               L.K, L.pt, L.pl, (L.epi_flags & EPI_BN_AB) ? " affine" : "", p->latency ? " latency" : "", L.groups,
+               a >= ACT_LOGISTIC ? " act=" : "", a >= ACT_LOGISTIC ? act_name(a) : "");
     } else if (L.type == LAYER_AVGPOOL) {
       snprintf(line, sizeof(line), "avgpool %dx%dx%d -> %dx%dx%d\n", L.H, L.W, L.C, L.OH, L.OW, L.OC);
     } else if (L.type == LAYER_SOFTMAX) {
       snprintf(line, sizeof(line), "softmax %dx%dx%d\n", L.H, L.W, L.C);
+    } else if (L.type == LAYER_ACT) {
+      snprintf(line, sizeof(line), "activate %dx%dx%d act=%s\n", L.H, L.W, L.C, act_name(L.leaky));
     } else if (L.type == LAYER_RELEASE) {
       snprintf(line, sizeof(line), "release %dx%dx%d slot=%d\n", L.H, L.W, L.C, L.slot);
     } else if (L.type == LAYER_TAP) {

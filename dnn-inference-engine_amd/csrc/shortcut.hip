@@ -3,10 +3,11 @@
 // has neither node.  All tensors NHWC fp32, each below 2 GiB (element offsets fit an int).
 //
 //   shortcut   out[i] = act(a[i] + b[i]): one fp32 add, rounded once, then the conv epilogue's
-//              leaky (apply_leaky, dnn_common.h) or nothing.  16 B per lane on all three tensors,
-//              a grid sized to the chip and a grid-stride loop with four vectors of each input
-//              in flight per lane; a scalar loop covers the last n % 4 elements (and everything
-//              when a pointer is not 16-byte aligned).  out must not alias a or b.
+//              activation (apply_act, act_dev.h: a leaky, logistic, swish, mish) or nothing.
+//              16 B per lane on all three tensors, a grid sized to the chip and a grid-stride loop
+//              with four vectors of each input in flight per lane; a scalar loop covers the last
+//              n % 4 elements (and everything when a pointer is not 16-byte aligned).  out must not
+//              alias a or b.
 //   upsample   out[n, h, w, c] = in[n, h / f, w / f, c].  Organised by source pixel, in route.hip's
 //              style: a workgroup owns a chunk of consecutive source pixels and tabulates in LDS
 //              the offset of each one's first destination (the (n, h, w) decomposition: once per
@@ -24,18 +25,18 @@ typedef float sc_f32x4 __attribute__((ext_vector_type(4)));
 constexpr int SC_THREADS = 256;
 constexpr int SC_UNROLL = 4;
 
-template <int FLAGS>
+template <int ACT>
 __device__ __forceinline__ sc_f32x4 shortcut_vec(sc_f32x4 x, sc_f32x4 y) {
   sc_f32x4 r;
-  r.x = apply_leaky(x.x + y.x, FLAGS);
-  r.y = apply_leaky(x.y + y.y, FLAGS);
-  r.z = apply_leaky(x.z + y.z, FLAGS);
-  r.w = apply_leaky(x.w + y.w, FLAGS);
+  r.x = apply_act(x.x + y.x, ACT);
+  r.y = apply_act(x.y + y.y, ACT);
+  r.z = apply_act(x.z + y.z, ACT);
+  r.w = apply_act(x.w + y.w, ACT);
   return r;
 }
 
 // n4 whole 16-byte vectors, then elements [4 * n4, n) one by one
-template <int FLAGS>
+template <int ACT>
 __global__ void __launch_bounds__(SC_THREADS)
 shortcut_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out, int n4, int n) {
   const sc_f32x4* a4 = reinterpret_cast<const sc_f32x4*>(a);
@@ -51,16 +52,16 @@ shortcut_kernel(const float* __restrict__ a, const float* __restrict__ b, float*
       y[u] = b4[i + u * stride];
     }
 #pragma unroll
-    for (int u = 0; u < SC_UNROLL; ++u) o4[i + u * stride] = shortcut_vec<FLAGS>(x[u], y[u]);
+    for (int u = 0; u < SC_UNROLL; ++u) o4[i + u * stride] = shortcut_vec<ACT>(x[u], y[u]);
   }
-  for (; i < n4; i += stride) o4[i] = shortcut_vec<FLAGS>(a4[i], b4[i]);
+  for (; i < n4; i += stride) o4[i] = shortcut_vec<ACT>(a4[i], b4[i]);
   for (int j = 4 * n4 + blockIdx.x * SC_THREADS + threadIdx.x; j < n; j += stride)
-    out[j] = apply_leaky(a[j] + b[j], FLAGS);
+    out[j] = apply_act(a[j] + b[j], ACT);
 }
 
-int launch_shortcut(const float* a, const float* b, float* out, long long count, int leaky, hipStream_t stream) {
+int launch_shortcut(const float* a, const float* b, float* out, long long count, int act, hipStream_t stream) {
   DNN_REQUIRE(a && b && out, "launch_shortcut: NULL tensor");
-  DNN_REQUIRE(leaky >= 0 && leaky <= 2, "launch_shortcut: leaky must be 0, 1 or 2");
+  DNN_REQUIRE(act >= 0 && act < ACT_NUM, "launch_shortcut: activation code %d outside 0..%d", act, ACT_NUM - 1);
   DNN_REQUIRE(count >= 0 && (unsigned long long)count * 4 < 0x80000000ULL,
               "launch_shortcut: a tensor of %lld floats is >= 2 GiB; split the batch", count);
   DNN_REQUIRE(out != a && out != b, "launch_shortcut: out may not alias an input");
@@ -73,12 +74,16 @@ int launch_shortcut(const float* a, const float* b, float* out, long long count,
   const long long lanes = std::max<long long>(n4, n - 4LL * n4);
   const long long blocks = (lanes + SC_THREADS - 1) / SC_THREADS;
   const dim3 grid((unsigned)std::max<long long>(1, std::min<long long>(blocks, (long long)device_cu_count() * 8)));
-  if (leaky == 1)
-    hipLaunchKernelGGL(shortcut_kernel<EPI_LEAKY_F64>, grid, dim3(SC_THREADS), 0, stream, a, b, out, n4, n);
-  else if (leaky == 2)
-    hipLaunchKernelGGL(shortcut_kernel<EPI_LEAKY_F32>, grid, dim3(SC_THREADS), 0, stream, a, b, out, n4, n);
-  else
-    hipLaunchKernelGGL(shortcut_kernel<0>, grid, dim3(SC_THREADS), 0, stream, a, b, out, n4, n);
+#define SC_GO(A) hipLaunchKernelGGL(shortcut_kernel<A>, grid, dim3(SC_THREADS), 0, stream, a, b, out, n4, n)
+  switch (act) {
+    case ACT_LEAKY_F64: SC_GO(ACT_LEAKY_F64); break;
+    case ACT_LEAKY_F32: SC_GO(ACT_LEAKY_F32); break;
+    case ACT_LOGISTIC: SC_GO(ACT_LOGISTIC); break;
+    case ACT_SWISH: SC_GO(ACT_SWISH); break;
+    case ACT_MISH: SC_GO(ACT_MISH); break;
+    default: SC_GO(ACT_NONE); break;
+  }
+#undef SC_GO
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("launch shortcut: %s", hipGetErrorString(e));

@@ -25,7 +25,9 @@ of that forward (tests/darknet_oracle.py), not to Darknet's bits: Darknet rounds
 steps in fp32, the fold rounds once.
 
 Sections: [net] (width, height, channels; the caller's in_shape overrides width and height, as
-Darknet's own resizing does), [convolutional] (activation leaky or linear), [shortcut] (linear),
+Darknet's own resizing does), [convolutional] (activation leaky, linear, mish, swish or logistic: the last
+three a dnn_hip.Activation node, in the plan the conv's epilogue; DarknetModel parses with ACTIVATIONS, parse_cfg
+on its own lets only leaky and linear through unless given the set), [shortcut] (linear, mish, swish, logistic),
 [route] (one layer: that tensor again, or with groups / group_id its channels
 [group_id * c / groups, (group_id + 1) * c / groups), one dnn_hip.ChannelSlice node: the split of a
 CSP block; two: their channel concat; four: the SPP pattern, three stride-1 max pools of one tensor
@@ -38,8 +40,10 @@ yolo_post.MultiHead with logistic class scores, the masked anchors divided by th
 per-class NMS, multi-label output, score 0.5 and IoU 0.45 (Darknet's detector defaults); a
 scale_x_y other than 1 goes into the head per scale
 (yolo_post.MultiHead's scale_x_y: the box centre's logistic becomes sig * s - 0.5 * (s - 1)).
-Importable stock models: YOLOv3, YOLOv3-SPP, YOLOv3-tiny and YOLOv4-tiny (cfg_text has their public
-definitions).
+Importable stock models: YOLOv3, YOLOv3-SPP, YOLOv3-tiny, YOLOv4-tiny and YOLOv4 (cfg_text has their public
+definitions; "yolov4" is CSPDarknet53 with mish, the SPP + PAN neck with leaky and three [yolo] sections with
+scale_x_y 1.2 / 1.1 / 1.05 and greedy NMS; beta_nms, iou_thresh, max_delta and the loss keys are training or
+DIoU matters and are ignored like every unknown key).
 
 Classifiers: [avgpool] (a dnn_hip.GlobalAvgPool node, dnn_plan_add_avgpool), [softmax] (groups 1,
 temperature 1, no tree, on a 1 x 1 map: a dnn_hip.Softmax node, dnn_plan_add_softmax), [connected]
@@ -69,7 +73,7 @@ Out of scope:
 
   * YOLOv2's [reorg] and [region]: Darknet's reorg channel order is not the route kernel's
     (TensorFlow's space_to_depth), so yolov2.py's weights are not Darknet's either;
-  * the mish activation and with it full YOLOv4 (cfg_text("yolov4") raises);
+  * activations other than leaky, linear, mish, swish and logistic (relu, elu, tanh);
   * [shortcut] with activation=leaky (Darknet's ResNet / ResNeXt classifiers), [connected] on a map
     larger than 1 x 1, [softmax] with groups, a temperature or a tree;
   * [route] with groups > 1 over more than one layer (Darknet slices each layer then; no stock cfg
@@ -97,8 +101,10 @@ import yolov3
 SECTION_TYPES = ("net", "convolutional", "shortcut", "route", "upsample", "maxpool", "yolo", "avgpool", "softmax",
                  "connected", "dropout", "cost")
 BN_EPS = 1e-6  # normalize_cpu's .000001f, added to sqrt(var)
+BASE_ACTIVATIONS = ("leaky", "linear")                         # what parse_cfg lets through unless told otherwise
+ACTIVATIONS = BASE_ACTIVATIONS + ("mish", "swish", "logistic")  # of [convolutional]; [shortcut]: all but leaky
 SCORE_THR, IOU_THR = 0.5, 0.45  # Darknet's detector defaults (-thresh .5, nms .45)
-MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny", "yolov4-tiny", "darknet19", "darknet53")
+MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny", "yolov4-tiny", "yolov4", "darknet19", "darknet53")
 CLASSIFIERS = {"darknet19": 224, "darknet53": 256}  # the classifier definitions and their default input size
 NMS_KINDS = ("default", "greedynms")  # [yolo] nms_kind values that are the decode's greedy NMS
 
@@ -108,13 +114,20 @@ class DarknetError(ValueError):
 
 
 # ------------------------------------------------------------------------------------- cfg text
-def parse_cfg(text):
+def parse_cfg(text, activations=BASE_ACTIVATIONS):
     """The sections of a Darknet cfg, in order: one dict per section with "type" (the name in
     brackets), "line" (its 1-based line number) and every `key = value` of the section as strings
     (keys and values stripped; a key named `type` or `line`, as in [cost]'s `type = sse`, is kept as
     "type_" / "line_").  `#` and `;` start comment lines; blank lines are skipped.  A
     section type outside SECTION_TYPES raises DarknetError naming the type and the line; unknown
-    keys inside a known section are kept and ignored by the importer."""
+    keys inside a known section are kept and ignored by the importer.
+
+    `activations`: the `activation` values a [convolutional] (Darknet's default there: logistic) or a
+    [shortcut] (default linear) may have; any other raises DarknetError naming the value and the line.
+    The default is leaky and linear, what every reader of these sections computes: code that walks
+    the sections itself and knows only those two would take a mish layer for a linear one without
+    a word.  DarknetModel parses with ACTIVATIONS; so does a caller whose own code handles mish,
+    swish and logistic."""
     sections = []
     for no, raw in enumerate(text.splitlines(), start=1):
         line = raw.strip()
@@ -142,6 +155,12 @@ def parse_cfg(text):
         raise DarknetError("a cfg starts with a [net] section")
     if any(s["type"] == "net" for s in sections[1:]):
         raise DarknetError("more than one [net] section")
+    for sec in sections:
+        if sec["type"] in ("convolutional", "shortcut"):
+            act = sec.get("activation", "logistic" if sec["type"] == "convolutional" else "linear")
+            if act not in activations:
+                raise DarknetError(f"[{sec['type']}] at line {sec['line']}: activation {act!r} is not supported "
+                                   f"({', '.join(activations)})")
     return sections
 
 
@@ -198,8 +217,8 @@ def conv_params(sec):
     pad = size // 2 if _int(sec, "pad", 0) else _int(sec, "padding", 0)
     act = sec.get("activation", "logistic")
     where = f"[convolutional] at line {sec['line']}"
-    if act not in ("leaky", "linear"):
-        raise DarknetError(f"{where}: activation {act!r} is not supported (leaky, linear)")
+    if act not in ACTIVATIONS:
+        raise DarknetError(f"{where}: activation {act!r} is not supported ({', '.join(ACTIVATIONS)})")
     if n < 1 or size < 1 or stride < 1 or not 0 <= pad < size:
         raise DarknetError(f"{where}: filters {n}, size {size}, stride {stride}, padding {pad}: need filters, size, "
                            "stride >= 1 and 0 <= padding < size")
@@ -215,6 +234,22 @@ def conv_groups(sec, c):
         raise DarknetError(f"[convolutional] at line {sec['line']}: grouped conv with groups = {groups} needs "
                            f"groups >= 1 dividing the {c} input channels and the {n} filters")
     return groups
+
+
+def shortcut_activation(sec):
+    """activation of a [shortcut] section (default linear): linear, mish, swish or logistic."""
+    act = sec.get("activation", "linear")
+    if act not in ACTIVATIONS or act == "leaky":
+        raise DarknetError(f"[shortcut] at line {sec['line']}: activation {act!r} is not supported "
+                           "(linear, mish, swish, logistic)")
+    return act
+
+
+def _activated(g, t, act):
+    """The node of `act` applied to node t: the fp32 leaky, one of dnn_hip.ACTIVATIONS, or t itself (linear)."""
+    if act == "leaky":
+        return g.create_leaky_relu_f32(t)
+    return t if act == "linear" else g.create_activation(t, act)
 
 
 def maxpool_params(sec, in_h, in_w):
@@ -328,9 +363,7 @@ def layer_shapes(sections, in_shape=None):
                                    f"{h} x {w} map with padding {pad} has no output")
             h, w, c = (h + 2 * pad - size) // stride + 1, (w + 2 * pad - size) // stride + 1, n
         elif kind == "shortcut":
-            if sec.get("activation", "linear") != "linear":
-                raise DarknetError(f"[shortcut] at line {sec['line']}: activation {sec['activation']!r} is not "
-                                   "supported (linear)")
+            shortcut_activation(sec)
             src = shapes[_layer_index(sec, _int(sec, "from"), at, "from")]
             if src != (h, w, c):
                 raise DarknetError(f"[shortcut] at line {sec['line']}: layer shapes {src} and {(h, w, c)} differ")
@@ -575,10 +608,10 @@ def build_graph(builder_cls, sections, layers, in_shape):
             t = g.create_conv2d_padded(node(prev), kernel_hwio(layer), [1, stride, stride, 1], (pad, pad),
                                        groups=conv_groups(sec, c_in))
             t = g.create_scale_shift(t, scale, shift)
-            cur = g.create_leaky_relu_f32(t) if act == "leaky" else t
+            cur = _activated(g, t, act)
         elif kind == "shortcut":
             src = out[_layer_index(sec, _int(sec, "from"), at, "from")]
-            cur = g.create_add([node(src), node(prev)])
+            cur = _activated(g, g.create_add([node(src), node(prev)]), shortcut_activation(sec))
         elif kind == "route":
             srcs = [out[_layer_index(sec, v, at, "layers")] for v in _ints(sec, "layers")]
             if len(srcs) == 1:
@@ -686,7 +719,7 @@ class DarknetModel(yolov3.YOLO_V3):
 
     def __init__(self, cfg_text, weights, in_shape=None, debug=False, device=None, head=_AUTO, latency=None,
                  score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per_class", labels="multi", wide=False):
-        self.sections = parse_cfg(cfg_text)
+        self.sections = parse_cfg(cfg_text, ACTIVATIONS)
         h, w, c = net_shape(self.sections, in_shape)
         self.in_shape = (int(in_shape[0]) if in_shape is not None else 1, h, w, c)
         self.layers = load_weights(weights, self.sections) if isinstance(weights, (str, bytes)) or hasattr(
@@ -856,12 +889,12 @@ class _Cfg(object):
         self.n += 1
         return self.n - 1
 
-    def conv(self, filters, size, stride=1, head=False):
+    def conv(self, filters, size, stride=1, head=False, act="leaky"):
         if head:  # a linear conv with a bias, 3 x (5 + classes) filters whatever the width
             pairs = [("size", size), ("stride", stride), ("pad", 1), ("filters", filters), ("activation", "linear")]
         else:
             pairs = [("batch_normalize", 1), ("filters", self.wd(filters)), ("size", size), ("stride", stride),
-                     ("pad", 1), ("activation", "leaky")]
+                     ("pad", 1), ("activation", act)]
         return self.add("convolutional", *pairs)
 
     def yolo(self, mask, anchors, classes):
@@ -869,9 +902,9 @@ class _Cfg(object):
                         ("num", len(anchors.split(",")) // 2), ("jitter", ".3"), ("ignore_thresh", ".7"),
                         ("truth_thresh", 1), ("random", 1))
 
-    def yolo_v4(self, mask, anchors, classes):
+    def yolo_v4(self, mask, anchors, classes, scale_x_y="1.05"):
         return self.add("yolo", ("mask", mask), ("anchors", anchors), ("classes", classes),
-                        ("num", len(anchors.split(",")) // 2), ("jitter", ".3"), ("scale_x_y", "1.05"),
+                        ("num", len(anchors.split(",")) // 2), ("jitter", ".3"), ("scale_x_y", scale_x_y),
                         ("cls_normalizer", "1.0"), ("iou_normalizer", "0.07"), ("iou_loss", "ciou"),
                         ("ignore_thresh", ".7"), ("truth_thresh", 1), ("random", 0), ("resize", "1.5"),
                         ("nms_kind", "greedynms"), ("beta_nms", "0.6"))
@@ -880,14 +913,79 @@ class _Cfg(object):
         return "\n".join(self.lines)
 
 
+_V4_ANCHORS = "12, 16, 19, 36, 40, 28, 36, 75, 76, 55, 72, 146, 142, 110, 192, 243, 459, 401"
+
+
+def _yolov4(c, n_out, classes):
+    """YOLOv4: CSPDarknet53 with mish, the SPP + PAN neck with leaky, three heads from the finest scale up."""
+    def mish(filters, size, stride=1):
+        return c.conv(filters, size, stride, act="mish")
+
+    mish(32, 3)
+    stage_out = []
+    for k, (f, blocks) in enumerate(_STAGES):  # a CSP stage: down, B = 1x1(down); A = 1x1(down), blocks, 1x1; 1x1 of [A, B]
+        half = f if k == 0 else f // 2         # (the first stage keeps the full width in both halves)
+        c.lines.append("# Downsample")
+        mish(f, 3, stride=2)
+        mish(half, 1)
+        c.add("route", ("layers", "-2"))
+        mish(half, 1)
+        for _ in range(blocks):
+            mish(f // 2, 1)
+            mish(half, 3)
+            c.add("shortcut", ("from", -3), ("activation", "linear"))
+        mish(half, 1)
+        c.add("route", ("layers", f"-1,-{3 * blocks + 4}"))
+        stage_out.append(mish(f, 1))
+    c.lines.append("##########################")
+
+    def five(f, first=True):  # 1x1 f, 3x3 2f, 1x1 f(, 3x3 2f, 1x1 f): returns the last layer
+        at = None
+        for j in range(5 if first else 3):
+            at = c.conv(2 * f if j % 2 else f, 3 if j % 2 else 1)
+        return at
+
+    five(512, first=False)
+    c.lines.append("### SPP ###")
+    c.add("maxpool", ("stride", 1), ("size", 5))
+    c.add("route", ("layers", "-2"))
+    c.add("maxpool", ("stride", 1), ("size", 9))
+    c.add("route", ("layers", "-4"))
+    c.add("maxpool", ("stride", 1), ("size", 13))
+    c.add("route", ("layers", "-1,-3,-5,-6"))
+    c.lines.append("### End SPP ###")
+    tops = [five(512, first=False)]  # the neck's tensor of each scale on the way up, coarsest first
+    for f, lateral in ((256, stage_out[3]), (128, stage_out[2])):
+        c.conv(f, 1)
+        c.add("upsample", ("stride", 2))
+        c.add("route", ("layers", lateral))
+        c.conv(f, 1)
+        c.add("route", ("layers", "-1, -3"))
+        tops.append(five(f))
+    for k, (f, mask, sxy) in enumerate(((128, "0,1,2", "1.2"), (256, "3,4,5", "1.1"), (512, "6,7,8", "1.05"))):
+        c.conv(2 * f, 3)
+        c.conv(n_out, 1, head=True)
+        c.yolo_v4(mask, _V4_ANCHORS, classes, sxy)
+        if k < 2:  # the way down: a stride-2 conv of this scale joins the neck's tensor of the next coarser one
+            c.add("route", ("layers", "-4"))
+            at = c.conv(2 * f, 3, stride=2)
+            c.add("route", ("layers", f"-1, {tops[1 - k] - at - 1}"))
+            five(2 * f)
+    return c.text()
+
+
 def cfg_text(model, classes=None, width=None, height=None, width_div=1):
     """The public definition of `model` (one of MODELS) as cfg text, for `classes` classes and a
     width x height input; width_div divides every channel count except the heads' 3 x (5 + classes)
     or the classifier conv's `classes` (a narrow model of the same topology).  Defaults: 80 classes
-    at 416 x 416 for the detectors; 1000 classes for the classifiers "darknet19" (224 x 224) and
+    at 416 x 416 for the detectors ("yolov4" has no default size: ValueError without width and height); 1000 classes for the classifiers "darknet19" (224 x 224) and
     "darknet53" (256 x 256), which end in [avgpool] and [softmax]."""
     if model not in MODELS:
         raise ValueError(f"model {model!r}: one of {MODELS} expected")
+    if model == "yolov4" and (width is None or height is None):
+        # its public cfg is 608 x 608, which has more boxes than the default head decodes (DarknetModel builds it
+        # without a head unless wide=True), and 416 x 416, the other detectors' default here, is not its definition
+        raise ValueError('cfg_text("yolov4") takes no default size: pass width and height (608 x 608 in the public cfg)')
     size = CLASSIFIERS.get(model, 416)
     classes = (1000 if model in CLASSIFIERS else 80) if classes is None else int(classes)
     width, height = size if width is None else width, size if height is None else height
@@ -949,6 +1047,8 @@ def cfg_text(model, classes=None, width=None, height=None, width_div=1):
         c.conv(n_out, 1, head=True)
         c.yolo_v4("1,2,3", _TINY_ANCHORS, classes)
         return c.text()
+    if model == "yolov4":
+        return _yolov4(c, n_out, classes)
     c.conv(32, 3)
     stage_end = []
     for f, blocks in _STAGES:

@@ -99,6 +99,8 @@ def _bind_plan_api(lib):
         "dnn_plan_add_softmax": (i, [vp]),
         "dnn_avgpool_host": (i, [vp, vp, i, i, i, i]),
         "dnn_softmax_host": (i, [vp, vp, i, i]),
+        "dnn_plan_add_activation": (i, [vp, i]),
+        "dnn_activate_host": (i, [vp, vp, ctypes.c_longlong, i]),
         "dnn_plan_output_shape": (i, [vp, P(i), P(i), P(i), P(i)]),
         "dnn_plan_describe": (i, [vp, ctypes.c_char_p, i]),
         "dnn_plan_memory": (i, [vp, P(sz), P(sz)]),
@@ -307,7 +309,7 @@ class DnnGraphBuilder(object):
         self.name_num = {"conv2d": 0, "bias_add": 0, "max_pool2d": 0, "batch_norm": 0, "leaky_relu": 0,
                          "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0, "spp": 0,
                          "channel_slice": 0, "global_avg_pool": 0, "softmax": 0,
-                         "conv2d_padded": 0, "scale_shift": 0, "leaky_relu_f32": 0}
+                         "conv2d_padded": 0, "scale_shift": 0, "leaky_relu_f32": 0, "activation": 0}
         self.in_node = None
         self.out_node = None
         self.extra_out_nodes = []
@@ -404,6 +406,11 @@ class DnnGraphBuilder(object):
 
     def create_softmax(self, in_node):
         out_node = Softmax(self.get_name("softmax"), in_node)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_activation(self, in_node, kind):
+        out_node = Activation(self.get_name("activation"), in_node, kind)
         self.G.add_edge(in_node, out_node)
         return out_node
 
@@ -879,6 +886,28 @@ class Softmax(DnnNode):
         _check(mylib.dnn_softmax_host(_vp(a), _vp(self.result), int(a.shape[0]), int(a.shape[3])), self.name)
 
 
+ACTIVATIONS = {"logistic": 3, "swish": 4, "mish": 5}  # DNN_ACT_LOGISTIC, DNN_ACT_SWISH, DNN_ACT_MISH
+
+
+class Activation(DnnNode):
+    """Not in the reference (Darknet's activation = logistic | swish | mish): element-wise
+    1 / (1 + e^-x), x * logistic(x) or x * tanh(ln(1 + e^x)) in fp32 (csrc/act_dev.h).  In a plan it is
+    dnn_plan_add_activation: the epilogue activation of the conv or shortcut entry before it where that
+    is possible, one element-wise kernel otherwise.  run() -> dnn_activate_host."""
+
+    def __init__(self, name, in_node, kind):
+        if kind not in ACTIVATIONS:
+            raise ValueError
+        self.in_node = in_node
+        self.kind = kind
+        self.result = np.zeros(in_node.result.shape, dtype='float32')
+        self.name = name
+
+    def run(self):
+        x = np.ascontiguousarray(self.in_node.result, dtype=np.float32)
+        _check(mylib.dnn_activate_host(_vp(x), _vp(self.result), x.size, ACTIVATIONS[self.kind]), self.name)
+
+
 class Input(DnnNode):
     """proj3/dnn_openblas.py:287-300 (unchanged contract)."""
 
@@ -1012,6 +1041,15 @@ class SoftmaxEntry(object):
         self.nodes = list(nodes)
 
 
+class ActivationEntry(object):
+    """dnn_plan_add_activation: current = act(current), `kind` one of ACTIVATIONS; the plan folds it into
+    the conv or shortcut entry before it where it can."""
+
+    def __init__(self, kind, nodes=()):
+        self.kind, self.code = kind, ACTIVATIONS[kind]
+        self.nodes = list(nodes)
+
+
 class TapEntry(object):
     """dnn_plan_add_tap: the current tensor becomes the plan's extra output `index` (no kernel);
     `node` is the graph node it is the result of (None in plans assembled by hand)."""
@@ -1098,6 +1136,8 @@ def _lower_one(g, nxt):
         return AvgPoolEntry(nodes=[nxt]), nxt
     if isinstance(nxt, Softmax):
         return SoftmaxEntry(nodes=[nxt]), nxt
+    if isinstance(nxt, Activation):
+        return ActivationEntry(nxt.kind, nodes=[nxt]), nxt
     return None  # a standalone element-wise op: not expressible as a fused entry
 
 
@@ -1226,7 +1266,7 @@ def _output_branch(g, head):
 def lower_graph(g):
     """Lower a builder graph to fused plan entries, or None if the plan cannot express it (then
     the node-by-node path runs).  Expressible: a chain of Conv2D (with its BiasAdd / BatchNorm /
-    LeakyReLU), MaxPool2D, SpaceToDepth, Upsample, ChannelSlice, Spp, GlobalAvgPool and Softmax, and forks of two such chains (either may be
+    LeakyReLU), MaxPool2D, SpaceToDepth, Upsample, ChannelSlice, Spp, GlobalAvgPool, Softmax and Activation, and forks of two such chains (either may be
     empty) joined by one Concat or one Add (with a LeakyReLU directly after it), any number of
     them in sequence within the plan's slots (an Add block gives its slots back, and so does a
     Concat fork lowered inside a pending long skip); forks nested in a fork's branch are not.
@@ -1247,6 +1287,13 @@ def lower_graph(g):
                      23: the end of the third CSP block and the lateral of the top-down merge):
                      Stash(x), then the pending Route(1, slot, ...) and Release(slot); the new skip
                      is resolved where the main line reaches its Concat.
+
+      side branch    one successor starts a plain chain whose result is one input of a Concat that
+                     the main line reaches later with the other input (a CSP stage of YOLOv4: the
+                     1x1 conv beside the residual blocks; a PAN lateral: the 1x1 conv of a backbone
+                     tensor that meets the upsampled neck): Stash(x), the chain, Stash(its result),
+                     Restore(x), Release(x); the Route and the Release of the result's slot follow
+                     where the main line arrives at the Concat.
 
     An extra output on the main line is a Tap after the entry that computes it.  Slots are the
     lowest free numbers; more than MAX_SLOTS live at once gives None.
@@ -1283,6 +1330,35 @@ def lower_graph(g):
         live.add(slot)
         pending[skips[0]] = (slot, node)
         handled.add((node, skips[0]))
+        return True
+
+    def side_branch(succ):
+        """`node` feeds a plain chain that ends as one input of a Concat whose other input the main
+        line produces later: Stash(node), the chain, Stash(its result), Restore(node), Release(node),
+        and the Concat is pending on the chain's slot.  False unless exactly one successor starts such
+        a chain and two slots are free."""
+        found = []
+        for head in succ:
+            chain, cur = [], head
+            while len(list(g.G.predecessors(cur))) == 1 and len(list(g.G.successors(cur))) == 1 and not _is_output(g, cur):
+                chain.append(cur)
+                cur = list(g.G.successors(cur))[0]
+            if chain and isinstance(cur, Concat) and len(list(g.G.predecessors(cur))) == 2 and cur not in pending \
+                    and (cur.in_nodes[0] is chain[-1]) != (cur.in_nodes[1] is chain[-1]):
+                found.append((head, chain, cur))
+        x_slot, b_slot = _free_slots(live, 2)
+        if len(found) != 1 or b_slot >= MAX_SLOTS:
+            return False
+        head, chain, join = found[0]
+        es = _lower_chain(g, chain)
+        if es is None:
+            return False
+        # (the chain's result takes the lower number once node's slot is released: stash order is fixed,
+        # so it keeps b_slot and x_slot is the one given back)
+        entries.extend([StashEntry(x_slot)] + es + [StashEntry(b_slot), RestoreEntry(x_slot), ReleaseEntry(x_slot)])
+        live.add(b_slot)
+        pending[join] = (b_slot, chain[-1])
+        handled.add((node, head))
         return True
 
     node = g.in_node
@@ -1335,7 +1411,7 @@ def lower_graph(g):
                 entries += [RestoreEntry(slot), ReleaseEntry(slot)]
                 handled.add((node, head))
                 continue
-            if not long_skip(succ):
+            if not long_skip(succ) and not side_branch(succ):
                 return None
         elif len(succ) == 3:  # a long skip from a node that also opens a fork (a residual block's input)
             if not long_skip(succ):
@@ -1382,7 +1458,7 @@ def _pad_code(padding):
 
 def _add_structural(lib, h, e, leaky_variant=1):
     """Emit a StashEntry / RestoreEntry / RouteEntry / ShortcutEntry / ReleaseEntry /
-    UpsampleEntry / SppEntry / SliceEntry / AvgPoolEntry / SoftmaxEntry / TapEntry; False if `e` is none of them."""
+    UpsampleEntry / SppEntry / SliceEntry / AvgPoolEntry / SoftmaxEntry / ActivationEntry / TapEntry; False if `e` is none of them."""
     if isinstance(e, StashEntry):
         slot = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_stash(h, ctypes.byref(slot)), "dnn_plan_add_stash", lib)
@@ -1407,6 +1483,8 @@ def _add_structural(lib, h, e, leaky_variant=1):
         _check(lib.dnn_plan_add_avgpool(h), "dnn_plan_add_avgpool", lib)
     elif isinstance(e, SoftmaxEntry):
         _check(lib.dnn_plan_add_softmax(h), "dnn_plan_add_softmax", lib)
+    elif isinstance(e, ActivationEntry):
+        _check(lib.dnn_plan_add_activation(h, e.code), "dnn_plan_add_activation", lib)
     elif isinstance(e, TapEntry):
         index = ctypes.c_int(-1)
         _check(lib.dnn_plan_add_tap(h, ctypes.byref(index)), "dnn_plan_add_tap", lib)

@@ -258,6 +258,34 @@ int dnn_plan_add_softmax(dnn_plan* plan);
 int dnn_avgpool_host(const float* a, float* out, int n, int h, int w, int c);
 int dnn_softmax_host(const float* a, float* out, int n, int classes);
 
+/* Activations beyond leaky (fp32 plans, batch and latency mode; on an fp16 plan the entry fails).  The
+ * reference has none of them: they are Darknet's `activation = logistic | swish | mish` (full YOLOv4's
+ * backbone is mish; EfficientNet and the YOLOv4-csp cfgs use swish and logistic).  In fp32, one expf and
+ * one division per value (csrc/act_dev.h has the evaluation and its cut-offs, DESIGN.md the measured error
+ * against the mathematical function):
+ *   logistic  1 / (1 + e^-v)        swish  v * logistic(v)        mish  v * tanh(ln(1 + e^v))
+ *
+ * dnn_plan_add_activation: current = act(current), element by element.
+ *   Fused form: when the current tensor is the output of a dnn_plan_add_conv_padded,
+ *   dnn_plan_add_conv_grouped or dnn_plan_add_shortcut entry added with leaky = 0, and nothing has
+ *   stashed, tapped or pooled that output yet, the activation becomes that entry's epilogue activation:
+ *   no kernel is added, and dnn_plan_describe shows " act=mish" (logistic, swish) on that entry's line.
+ *   Fused and unfused forms give the same bits.  Otherwise it is one kernel ("activate%d" in
+ *   dnn_plan_kernel_info, 16-byte accesses), plain NHWC fp32 on both sides like the join entries.
+ *   Pool fusion: mish and swish are not monotone (minima near -1.19 and -1.28), so the maximum of a pool
+ *   window does not commute with them.  A conv that carries one of them never takes a fused 2x2 max pool
+ *   (every pool-fused kernel takes the window's maximum, or minimum, of the raw sums and applies the
+ *   epilogue once): the pool runs as its own kernel.  Logistic is monotone and fuses like leaky.
+ *   The `leaky` argument of the other entries keeps its meaning and its 0..2 range.
+ *   Fails, leaving the plan unchanged, on an fp16 plan and for a code outside the three below.
+ * dnn_activate_host: the element-wise kernel on a host tensor of n floats (H2D copy, launch, D2H copy,
+ *   synchronise); below 2 GiB, refused from the arguments before any allocation. */
+#define DNN_ACT_LOGISTIC 3
+#define DNN_ACT_SWISH 4
+#define DNN_ACT_MISH 5
+int dnn_plan_add_activation(dnn_plan* plan, int act);
+int dnn_activate_host(const float* a, float* out, long long n, int act);
+
 /* Grouped conv (fp32 plans, batch and latency mode; on an fp16 plan it fails).  The reference has
  * no such node: it is Darknet's [convolutional] with groups > 1, the 3x3 convs of the ResNeXt
  * backbones and, with groups == C, the depthwise half of a separable conv.

@@ -4,8 +4,9 @@ alone), and the three-scale decode of the 10,647 boxes on typical inputs (a few 
 candidates per image) and on inputs where every box is a candidate.  --model picks the network:
 yolov3 (the default, as above), yolov3_spp (76 convs and the spp entry; the decode is YOLOv3's),
 yolov3_tiny (13 convs, two scales, 2,535 boxes), yolov4_tiny (the Darknet import of the public
-cfg with random weights: 21 convs, 3 slices, 7 routes; its decode with scale_x_y = 1.05) or all
-(the three YOLOv3 models).
+cfg with random weights: 21 convs, 3 slices, 7 routes; its decode with scale_x_y = 1.05), yolov4 (the
+import of the public cfg: 110 convs, 72 of them with mish in the epilogue; its decode with scale_x_y 1.2 /
+1.1 / 1.05) or all (the three YOLOv3 models).
 
   python tools/yolov3_time.py [--model yolov3] [--batch 1] [--reps 20] [--rounds 5] [--decode-only]
 
@@ -110,7 +111,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--decode-only", action="store_true")
-    ap.add_argument("--model", choices=("yolov3", "yolov3_spp", "yolov3_tiny", "yolov4_tiny", "all"), default="yolov3")
+    ap.add_argument("--model", choices=("yolov3", "yolov3_spp", "yolov3_tiny", "yolov4_tiny", "yolov4", "all"), default="yolov3")
     a = ap.parse_args()
     shape = (a.batch, 416, 416, 3)
     res = {"batch": a.batch}
@@ -118,12 +119,13 @@ def main():
         res["decode"] = time_decode(a.batch, a.reps, a.rounds)
     if a.model in ("yolov3_tiny", "all"):
         res["decode_tiny"] = time_decode(a.batch, a.reps, a.rounds, yolo_post.MultiHead.yolov3_tiny(416, 416))
-    if a.model == "yolov4_tiny":
-        secs = darknet_import.parse_cfg(darknet_import.cfg_text("yolov4-tiny"))
+    if a.model in ("yolov4_tiny", "yolov4"):
+        secs = darknet_import.parse_cfg(darknet_import.cfg_text(a.model.replace("_", "-"), width=416, height=416),
+                                        darknet_import.ACTIVATIONS)
         g, _, yolos = darknet_import.build_graph(dnn_hip.DnnGraphBuilder, secs, random_darknet_layers(secs), shape)
-        res["decode_v4_tiny"] = time_decode(a.batch, a.reps, a.rounds, darknet_import.multi_head(yolos, 416, 416))
+        res["decode_" + a.model[4:]] = time_decode(a.batch, a.reps, a.rounds, darknet_import.multi_head(yolos, 416, 416))
         if not a.decode_only:
-            res["yolov4_tiny_plan"] = time_plan(g, a.batch, a.reps, a.rounds)
+            res[a.model + "_plan"] = time_plan(g, a.batch, a.reps, a.rounds)
     if not a.decode_only and a.model in ("yolov3_spp", "all"):
         ws = yolov3_spp.validate(synth.yolov3_spp_weights())
         res["yolov3_spp_plan"] = time_plan(yolov3_spp.build_graph(dnn_hip.DnnGraphBuilder, ws, in_shape=shape)[0],
