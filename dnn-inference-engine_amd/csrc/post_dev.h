@@ -54,13 +54,28 @@ constexpr float VOC_ANCHORS[10] = {1.08f, 1.19f, 3.42f, 4.41f, 6.63f, 11.38f, 9.
 // conf = sigmoid(q[4]).  xs, xb: Darknet's scale_x_y as a pair, one fp32 multiply then one fp32 add
 // (the files are built without contraction); 1.0f, -0.0f where there is none: sig * 1.0f + -0.0f is
 // sig bit for bit for every non-NaN sig.  Shared by all kernels so that they round alike.
+// NEW_COORDS (Darknet's new_coords = 1, include/dnn_hip_post.h): the conv before the head was the
+// logistic, so the values are taken as they are, the sizes are (2 q) ** 2 times the anchor and no
+// transcendental is left; a compile-time variant of every per-box helper, here and in
+// post_multi_dev.h, so that the instantiations without it are the code they were.
+template <bool NEW_COORDS = false>
 __device__ __forceinline__ bool decode_corners(const float* q, int b, int col, int row, const float* anchors_s,
                                                float cell_px, float xs, float xb, long long* out, float* conf) {
-  const float cx = ((float)col + (sigmoid_ref(q[0]) * xs + xb)) * cell_px;
-  const float cy = ((float)row + (sigmoid_ref(q[1]) * xs + xb)) * cell_px;
-  const float rw = (np_expf(q[2]) * anchors_s[2 * b]) * cell_px;
-  const float rh = (np_expf(q[3]) * anchors_s[2 * b + 1]) * cell_px;
-  *conf = sigmoid_ref(q[4]);
+  float cx, cy, rw, rh;
+  if constexpr (NEW_COORDS) {
+    cx = ((float)col + (q[0] * xs + xb)) * cell_px;
+    cy = ((float)row + (q[1] * xs + xb)) * cell_px;
+    const float tw = q[2] * 2.0f, th = q[3] * 2.0f;
+    rw = ((tw * tw) * anchors_s[2 * b]) * cell_px;
+    rh = ((th * th) * anchors_s[2 * b + 1]) * cell_px;
+    *conf = q[4];
+  } else {
+    cx = ((float)col + (sigmoid_ref(q[0]) * xs + xb)) * cell_px;
+    cy = ((float)row + (sigmoid_ref(q[1]) * xs + xb)) * cell_px;
+    rw = (np_expf(q[2]) * anchors_s[2 * b]) * cell_px;
+    rh = (np_expf(q[3]) * anchors_s[2 * b + 1]) * cell_px;
+    *conf = sigmoid_ref(q[4]);
+  }
   const float hw = rw / 2.0f, hh = rh / 2.0f;
   long long l = 0, t = 0, r = 0, bt = 0;
   const bool ok = trunc_i64(cx - hw, &l) && trunc_i64(cx + hw, &r) && trunc_i64(cy - hh, &t) &&
@@ -73,10 +88,21 @@ __device__ __forceinline__ bool decode_corners(const float* q, int b, int col, i
 }
 
 // The ONE label of a box from its C class logits: the arg-max class in *cls and its p(class).
+// NEW_COORDS: p[c] is the value itself (logistic mode only).
+template <bool NEW_COORDS = false>
 __device__ __forceinline__ float class_argmax(const float* lg, int C, bool logistic, int* cls) {
   int best = 0;
   float bp;
-  if (logistic) {
+  if constexpr (NEW_COORDS) {
+    bp = lg[0];
+    for (int c = 1; c < C; ++c) {
+      const float pc = lg[c];
+      if (pc > bp) {  // first index of the largest value
+        bp = pc;
+        best = c;
+      }
+    }
+  } else if (logistic) {
     bp = sigmoid_ref(lg[0]);
     for (int c = 1; c < C; ++c) {
       const float pc = sigmoid_ref(lg[c]);
@@ -192,9 +218,10 @@ __device__ __forceinline__ void reset_state(NmsState& st, int tid) {
 // byte 4 (base + 64) of seg, and the first key still to be read sits at byte 8 (base + 64).  Inside a
 // block every key of the block is read into registers (one per lane) before the first barrier and
 // the list grows only after it.  *n_kept is the list's length after the closing barrier.
-template <int IDX_BITS, int THREADS>
+// rule: the suppression test (post_math.h: IouRule, DiouRule).
+template <int IDX_BITS, int THREADS, class RULE>
 __device__ __forceinline__ void nms_workgroup(unsigned long long* seg, int n, const long long (*box)[4],
-                                              double iou_thr, unsigned long long* hitw, int* n_kept, int* zero_den,
+                                              const RULE rule, unsigned long long* hitw, int* n_kept, int* zero_den,
                                               int lane, int wid) {
   constexpr int WAVES = THREADS / 64;
   // i below is wave-uniform, so a kept candidate's index can be read into a scalar register: its
@@ -219,7 +246,7 @@ __device__ __forceinline__ void nms_workgroup(unsigned long long* seg, int n, co
     for (int j = wid; j < nk; j += WAVES) {
       const int kj = kept[j];  // wave-uniform
       const long long bj[4] = {box[kj][0], box[kj][1], box[kj][2], box[kj][3]};
-      if (live && iou_gt(bi, bj, iou_thr, &zd)) hit = true;
+      if (live && rule(bi, bj, &zd)) hit = true;
     }
     const unsigned long long hw_ = __ballot(hit);
     if (lane == 0) hitw[wid] = hw_;
@@ -235,7 +262,7 @@ __device__ __forceinline__ void nms_workgroup(unsigned long long* seg, int n, co
         // (no key is read here: the list below overwrites them)
         const int ki = SCALAR_INDEX ? __builtin_amdgcn_readlane(mine, i) : __shfl(mine, i);
         const long long bk[4] = {box[ki][0], box[ki][1], box[ki][2], box[ki][3]};
-        const bool h = live && lane > i && iou_gt(bi, bk, iou_thr, &zt);
+        const bool h = live && lane > i && rule(bi, bk, &zt);
         dropped |= __ballot(h);
       }
       const unsigned long long keep = ~dropped;
@@ -256,7 +283,7 @@ __device__ __forceinline__ void nms_any_emit(unsigned long long* keys, int n, co
   int ns = 1;
   while (ns < n) ns <<= 1;
   bitonic_sort<THREADS>(keys, ns, tid);
-  nms_workgroup<32, THREADS>(keys, n, bs.box, iou_thr, st.hitw, &st.n_kept, &st.zero_den, tid & 63, tid >> 6);
+  nms_workgroup<32, THREADS>(keys, n, bs.box, IouRule{iou_thr}, st.hitw, &st.n_kept, &st.zero_den, tid & 63, tid >> 6);
   if (st.zero_den) {
     if (tid == 0) *count = -2;
     return;

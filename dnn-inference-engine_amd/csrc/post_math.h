@@ -94,10 +94,10 @@ __device__ __forceinline__ double i128_to_f64(__int128 v) {
   return neg ? -d : d;
 }
 
-// yolov2tiny.py:179-195: iou(a, b) > thr on integer corners [l, t, r, b].  A zero
-// denominator (possible: overlaps are not clamped) raises ZeroDivisionError in the reference;
-// it sets *zero_den here.
-__device__ __forceinline__ bool iou_gt(const long long* a, const long long* b, double thr, bool* zero_den) {
+// yolov2tiny.py:179-195: iou(a, b) on integer corners [l, t, r, b], the double quotient in *q.  A zero
+// denominator (possible: overlaps are not clamped) raises ZeroDivisionError in the reference; here
+// the function returns false and leaves *q alone.
+__device__ __forceinline__ bool iou_quot(const long long* a, const long long* b, double* q) {
   const long long xa = a[0] > b[0] ? a[0] : b[0], ya = a[1] > b[1] ? a[1] : b[1];
   const long long xb = a[2] < b[2] ? a[2] : b[2], yb = a[3] < b[3] ? a[3] : b[3];
   // fast path: every width below 2^25 -> every product and sum below 2^53, exact in int64 and
@@ -108,21 +108,89 @@ __device__ __forceinline__ bool iou_gt(const long long* a, const long long* b, d
   if (w0 > -lim && w0 < lim && h0 > -lim && h0 < lim && wa > -lim && wa < lim && ha > -lim && ha < lim &&
       wb > -lim && wb < lim && hb > -lim && hb < lim) {
     const long long inter = w0 * h0, den = wa * ha + wb * hb - inter;
-    if (den == 0) {
-      *zero_den = true;
-      return false;
-    }
-    return (double)inter / (double)den > thr;
+    if (den == 0) return false;
+    *q = (double)inter / (double)den;
+    return true;
   }
   const __int128 inter = (__int128)(xb - xa + 1) * (__int128)(yb - ya + 1);
   const __int128 area_a = (__int128)(a[2] - a[0] + 1) * (__int128)(a[3] - a[1] + 1);
   const __int128 area_b = (__int128)(b[2] - b[0] + 1) * (__int128)(b[3] - b[1] + 1);
   const __int128 den = area_a + area_b - inter;
-  if (den == 0) {
+  if (den == 0) return false;
+  *q = i128_to_f64(inter) / i128_to_f64(den);
+  return true;
+}
+
+// iou(a, b) > thr; a zero denominator sets *zero_den.
+__device__ __forceinline__ bool iou_gt(const long long* a, const long long* b, double thr, bool* zero_den) {
+  double q;
+  if (!iou_quot(a, b, &q)) {
     *zero_den = true;
     return false;
   }
-  return i128_to_f64(inter) / i128_to_f64(den) > thr;
+  return q > thr;
 }
+
+// Darknet's diounms_sort test on the same corners (include/dnn_hip_post.h, "DIoU"):
+//   iou(a, b) - (d / c) ** beta > thr
+// d the squared distance of the centres, c the squared diagonal of the smallest box around both, both
+// kept as exact integers: d4 = 4 d from the corner sums, c from the inclusive +1 extents (>= 2 for
+// boxes with r >= l; a zero c, possible only with negative anchors, counts as a zero denominator).  The penalty is never negative, so
+// iou <= thr already decides "not suppressed" and the double pow runs only for the pairs above the
+// threshold, after the zero-denominator bookkeeping: the codes are those of iou_gt.  Every coordinate
+// and extent below 2^25 keeps d4 and c in int64; beyond, int128 and i128_to_f64.  Both conversions
+// round to nearest even, as Python's int -> float.
+__device__ __forceinline__ bool diou_gt(const long long* a, const long long* b, double thr, double beta,
+                                        bool* zero_den) {
+  double q;
+  if (!iou_quot(a, b, &q)) {
+    *zero_den = true;
+    return false;
+  }
+  if (!(q > thr)) return false;
+  const long long l = a[0] < b[0] ? a[0] : b[0], t = a[1] < b[1] ? a[1] : b[1];
+  const long long r = a[2] > b[2] ? a[2] : b[2], bt = a[3] > b[3] ? a[3] : b[3];
+  const long long lim = 1ll << 25;
+  const auto small = [lim](long long v) { return v > -lim && v < lim; };
+  double d4, c;
+  // all eight corners: a negative anchor gives a box with r < l, which min(l) and max(r) do not bound
+  if (small(a[0]) && small(a[1]) && small(a[2]) && small(a[3]) && small(b[0]) && small(b[1]) && small(b[2]) &&
+      small(b[3])) {
+    const long long dx = (a[0] + a[2]) - (b[0] + b[2]), dy = (a[1] + a[3]) - (b[1] + b[3]);
+    const long long w = r - l + 1, h = bt - t + 1;
+    const long long d = dx * dx + dy * dy;  // < 2^55
+    if (d == 0) return true;
+    d4 = (double)d;
+    c = (double)(w * w + h * h);
+  } else {  // corners within +-2^61 (trunc_i64): sums < 2^62, differences < 2^63, d4 < 2^127
+    const __int128 dx = (__int128)(a[0] + a[2]) - (__int128)(b[0] + b[2]);
+    const __int128 dy = (__int128)(a[1] + a[3]) - (__int128)(b[1] + b[3]);
+    const __int128 w = (__int128)r - l + 1, h = (__int128)bt - t + 1;
+    const __int128 d = dx * dx + dy * dy;
+    if (d == 0) return true;
+    d4 = i128_to_f64(d);
+    c = i128_to_f64(w * w + h * h);
+  }
+  if (c == 0.0) {  // only with r < l boxes: the reference's division raises like the IoU's
+    *zero_den = true;
+    return false;
+  }
+  return q - pow(d4 / (4.0 * c), beta) > thr;
+}
+
+// The suppression test of an NMS as a value: what nms_wave, nms_workgroup and nms_segments take where
+// the threshold went.  rule(a, b, &zd): a is suppressed by the kept box b.
+struct IouRule {
+  double thr;
+  __device__ __forceinline__ bool operator()(const long long* a, const long long* b, bool* zero_den) const {
+    return iou_gt(a, b, thr, zero_den);
+  }
+};
+struct DiouRule {
+  double thr, beta;
+  __device__ __forceinline__ bool operator()(const long long* a, const long long* b, bool* zero_den) const {
+    return diou_gt(a, b, thr, beta, zero_den);
+  }
+};
 
 }  // namespace dnnhip

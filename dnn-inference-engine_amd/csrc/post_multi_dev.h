@@ -55,6 +55,7 @@ struct MultiCall {
   void* workspace;
   unsigned long long workspace_bytes;
   int nms_mode, labels_mode;
+  const dnn_yolo_rule* rule = nullptr;  // NULL: all zero, the decode and the NMS of the entries without one
 };
 
 // What the two files' entries differ in: their limits, their workspace and their launcher.
@@ -70,14 +71,30 @@ struct MultiArgs {
   MultiPred mp;
   XyScale xy;
   int nb;  // boxes of one image over all scales
+  bool new_coords, diou;  // the checked rule: which decode, which suppression test
+  double beta;            // DiouRule's exponent
 };
+
+// Calls f(NEW_COORDS as std::bool_constant, the suppression test as IouRule or DiouRule) for the checked
+// rule of a call: the one place that turns the rule's run-time values into template arguments.
+template <class F>
+void with_rule(const MultiArgs& a, double iou_thr, F f) {
+  if (a.new_coords) {
+    if (a.diou) f(std::true_type{}, DiouRule{iou_thr, a.beta});
+    else f(std::true_type{}, IouRule{iou_thr});
+  } else {
+    if (a.diou) f(std::false_type{}, DiouRule{iou_thr, a.beta});
+    else f(std::false_type{}, IouRule{iou_thr});
+  }
+}
 
 // < 0 with the error set, else the boxes of one image over all scales (at most max_boxes)
 int multi_boxes_upto(const dnn_yolo_multi* m, const char* who, long long max_boxes);
 // each mode a value of its own, and not (any class, multi-label): no rule of any entry
 bool multi_modes_ok(int nms_mode, int labels_mode, const char* who);
 // Every argument check of a decode entry, in this order: the description (multi_boxes_upto with the
-// kind's limit), the modes, scale_x_y (each value finite and > 0), counts and pointers, pred[s], and
+// kind's limit), the modes, the rule (new_coords needs class_mode 1, DIoU the per-class NMS and a
+// finite beta_nms > 0), scale_x_y (each value finite and > 0), counts and pointers, pred[s], and
 // unless `host` the workspace's size and alignment.  < 0 with the error set; 0 with nothing to do
 // (no images); 1 with *out filled.
 int check_multi_call(const MultiCall& c, const MultiKind& kind, bool host, MultiArgs* out);
@@ -87,9 +104,11 @@ int yolo_multi_host(const MultiCall& c, const MultiKind& kind);
 // Multi-label score of a class from its logit: conf * p[c], one fp32 multiply, p[c] as class_argmax
 // computes it (m and sum: the box's logit_max and softmax_sum, unused in logistic mode).  The decode
 // and the merge of the multi-label kernels both call this, so an emitted score has the bits it was
-// sorted on.
+// sorted on.  NEW_COORDS (post_dev.h: decode_corners): p[c] is the value itself.
+template <bool NEW_COORDS = false>
 __device__ __forceinline__ float label_score(float logit, bool logistic, float conf, float m, float sum) {
-  const float pc = logistic ? sigmoid_ref(logit) : np_expf(logit - m) / sum;
+  float pc = logit;
+  if constexpr (!NEW_COORDS) pc = logistic ? sigmoid_ref(logit) : np_expf(logit - m) / sum;
   return conf * pc;
 }
 
@@ -164,10 +183,11 @@ __device__ __forceinline__ BoxAt box_at(const ScaleTab& t, int S, int k, int str
 // decode_corners of the box at `at`, the corners stored as box k; a bad corner sets *bad (before
 // the stores, as these kernels always had it: after them the compiler splits the stores over the
 // two outcomes).
+template <bool NEW_COORDS = false>
 __device__ __forceinline__ void decode_corners_at(const ScaleTab& t, const BoxAt& at, const BoxStore& bs, int k,
                                                   float* conf, int* bad) {
   long long c4[4];
-  if (!decode_corners(at.q, at.b, at.col, at.row, t.anchors[at.s], t.sc[at.s].cell, t.sc[at.s].xs, t.sc[at.s].xb, c4, conf))
+  if (!decode_corners<NEW_COORDS>(at.q, at.b, at.col, at.row, t.anchors[at.s], t.sc[at.s].cell, t.sc[at.s].xs, t.sc[at.s].xb, c4, conf))
     *bad = 1;
   bs.box[k][0] = c4[0];
   bs.box[k][1] = c4[1];
@@ -177,20 +197,24 @@ __device__ __forceinline__ void decode_corners_at(const ScaleTab& t, const BoxAt
 
 // One box with ONE label: decode_corners, the arg-max class and the score conf * p(class), all
 // stored as box k; a bad corner sets *bad.  The stores come after the class loop, as they always
-// did in these kernels.
-__device__ __forceinline__ void decode_single_at(const ScaleTab& t, const BoxAt& at, int C, bool logistic,
-                                                 const BoxStore& bs, int k, float* score, int* cls, int* bad) {
+// did in these kernels.  Returns the box's conf: with NEW_COORDS p may exceed 1, and the objectness
+// gate conf > score_thr that the other kernels take first is then a condition of its own.
+template <bool NEW_COORDS = false>
+__device__ __forceinline__ float decode_single_at(const ScaleTab& t, const BoxAt& at, int C, bool logistic,
+                                                  const BoxStore& bs, int k, float* score, int* cls, int* bad) {
   long long c4[4];
   float conf;
-  if (!decode_corners(at.q, at.b, at.col, at.row, t.anchors[at.s], t.sc[at.s].cell, t.sc[at.s].xs, t.sc[at.s].xb, c4, &conf))
+  if (!decode_corners<NEW_COORDS>(at.q, at.b, at.col, at.row, t.anchors[at.s], t.sc[at.s].cell, t.sc[at.s].xs,
+                                  t.sc[at.s].xb, c4, &conf))
     *bad = 1;
-  *score = conf * class_argmax(at.q + 5, C, logistic, cls);
+  *score = conf * class_argmax<NEW_COORDS>(at.q + 5, C, logistic, cls);
   bs.box[k][0] = c4[0];
   bs.box[k][1] = c4[1];
   bs.box[k][2] = c4[2];
   bs.box[k][3] = c4[3];
   bs.score[k] = *score;
   bs.cls[k] = *cls;
+  return conf;
 }
 
 // The sort keys beside key_any (post_dev.h: ~score (32) | index (32), the class-agnostic key and the
@@ -268,8 +292,9 @@ __device__ __forceinline__ void wave_scan_128(const int* in, int C, int* start, 
 // Blocked greedy NMS of the len sorted candidates seg[0 .. len) of one class by ONE wave (all 64
 // lanes call it); the box index is the key's low IDX_BITS bits.  Returns the length of the kept
 // list, written in place over seg; *zd is set when an evaluated IoU had a zero denominator.
-template <int IDX_BITS>
-__device__ __forceinline__ int nms_wave(unsigned long long* seg, int len, const long long (*box)[4], double iou_thr,
+// rule: the suppression test (post_math.h: IouRule, DiouRule).
+template <int IDX_BITS, class RULE>
+__device__ __forceinline__ int nms_wave(unsigned long long* seg, int len, const long long (*box)[4], const RULE rule,
                                         int lane, bool* zd) {
   int* kept = reinterpret_cast<int*>(seg);
   int nk = 0;
@@ -293,7 +318,7 @@ __device__ __forceinline__ int nms_wave(unsigned long long* seg, int len, const 
       const long long g0 = box[kj][0], g1 = box[kj][1], g2 = box[kj][2], g3 = box[kj][3];
       for (int t = 0; t < cnt; ++t) {
         const long long bj[4] = {readlane_i64(g0, t), readlane_i64(g1, t), readlane_i64(g2, t), readlane_i64(g3, t)};
-        if (live && iou_gt(bi, bj, iou_thr, zd)) hit = true;
+        if (live && rule(bi, bj, zd)) hit = true;
       }
     }
     unsigned long long dropped = (m < 64 ? ~((1ull << m) - 1ull) : 0ull) | __ballot(hit);
@@ -301,7 +326,7 @@ __device__ __forceinline__ int nms_wave(unsigned long long* seg, int len, const 
       if ((dropped >> i) & 1ull) continue;  // wave-uniform: candidate i is kept
       const long long bk[4] = {readlane_i64(bi[0], i), readlane_i64(bi[1], i), readlane_i64(bi[2], i),
                                readlane_i64(bi[3], i)};
-      const bool h = live && lane > i && iou_gt(bi, bk, iou_thr, zd);
+      const bool h = live && lane > i && rule(bi, bk, zd);
       dropped |= __ballot(h);
     }
     const unsigned long long keep = ~dropped;
@@ -338,10 +363,11 @@ __device__ __forceinline__ void reset_state(ClassState& st, int tid) {
 // nms_wave on a segment ALONE, no barrier inside, nobody waits; segments longer than PC_BIG are
 // left to 3b, where the whole workgroup runs nms_workgroup on each of them in turn.  Each kept list
 // goes in place over its own segment.  Returns the number kept over all classes, st.out_off the
-// prefix sum of the list lengths; -1 when an IoU denominator was zero.
-template <int IDX_BITS>
+// prefix sum of the list lengths; -1 when an IoU denominator was zero.  rule: the suppression test,
+// handed to both passes.
+template <int IDX_BITS, class RULE>
 __device__ __forceinline__ int nms_segments(unsigned long long* keys, int C, const long long (*box)[4],
-                                            double iou_thr, ClassState& st, int tid) {
+                                            const RULE rule, ClassState& st, int tid) {
   const int lane = tid & 63, wid = tid >> 6;
   {
     bool zd = false;
@@ -353,7 +379,7 @@ __device__ __forceinline__ int nms_segments(unsigned long long* keys, int C, con
       const int s0 = __builtin_amdgcn_readfirstlane(st.seg_start[c]);
       const int len = __builtin_amdgcn_readfirstlane(st.seg_start[c + 1]) - s0;
       if (len == 0 || len > PC_BIG) continue;
-      const int nk = nms_wave<IDX_BITS>(keys + s0, len, box, iou_thr, lane, &zd);
+      const int nk = nms_wave<IDX_BITS>(keys + s0, len, box, rule, lane, &zd);
       if (lane == 0) st.seg_kept[c] = nk;
     }
     if (__any(zd) && lane == 0) st.zero_den = 1;
@@ -363,7 +389,7 @@ __device__ __forceinline__ int nms_segments(unsigned long long* keys, int C, con
     const int s0 = __builtin_amdgcn_readfirstlane(st.seg_start[c]);
     const int len = __builtin_amdgcn_readfirstlane(st.seg_start[c + 1]) - s0;
     if (len <= PC_BIG) continue;  // workgroup-uniform
-    nms_workgroup<IDX_BITS, PM_THREADS>(keys + s0, len, box, iou_thr, st.hitw, &st.n_kept, &st.zero_den, lane, wid);
+    nms_workgroup<IDX_BITS, PM_THREADS>(keys + s0, len, box, rule, st.hitw, &st.n_kept, &st.zero_den, lane, wid);
     if (tid == 0) {
       st.seg_kept[c] = st.n_kept;
       st.n_kept = 0;
@@ -432,7 +458,7 @@ __device__ __forceinline__ void merge_single(unsigned long long* keys, const int
 // only ones still unread.  The padding of the sort starts at byte 8 nk, above the whole list.  The
 // score is recomputed by label_score from the stored conf (and sum) and the box's logits, the bits
 // it was sorted on.  Sorted by (score descending, global index, class), the first max_det emitted.
-template <int IDX_BITS>
+template <int IDX_BITS, bool NEW_COORDS = false>
 __device__ __forceinline__ void merge_labels(unsigned long long* keys, const int (&mine)[16], int nk, const ScaleTab& t,
                                              int S, int C, int stride, bool logistic, const BoxStore& bs,
                                              dnn_detection* rows, int max_det, int* count, int tid) {
@@ -453,7 +479,8 @@ __device__ __forceinline__ void merge_labels(unsigned long long* keys, const int
       const int e = dense[p], k = e & ((1 << IDX_BITS) - 1), c = e >> IDX_BITS;
       const float* lg = box_values(t, scale_of(t, S, k), k, stride) + 5;
       const float sum = logistic ? 1.0f : bs.sum()[k];
-      const float sc = label_score(lg[c], logistic, bs.score[k], logistic ? 0.0f : logit_max(lg, C), sum);
+      const float sc =
+          label_score<NEW_COORDS>(lg[c], logistic, bs.score[k], logistic ? 0.0f : logit_max(lg, C), sum);
       key = key_merge<IDX_BITS>(sc, k, c);
     }
     __syncthreads();

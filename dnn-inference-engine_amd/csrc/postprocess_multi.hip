@@ -30,6 +30,9 @@
 
 namespace dnnhip {
 
+// NEW_COORDS, in all three kernels: the box rule of Darknet's new_coords = 1 (post_dev.h:
+// decode_corners).  RULE, in the two per-class ones: the suppression test (post_math.h).
+template <bool NEW_COORDS>
 __global__ void __launch_bounds__(PM_THREADS)
 yolo_multi_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pred, dnn_detection* __restrict__ dets,
                   int max_det, int* __restrict__ counts, char* workspace, int nb) {
@@ -59,8 +62,8 @@ yolo_multi_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pre
   for (int k = tid; k < nb; k += PM_THREADS) {
     float sc;
     int best;
-    decode_single_at(t, box_at(t, S, k, stride), C, logistic, bs, k, &sc, &best, &bad);
-    if (sc > score_thr) {
+    const float conf = decode_single_at<NEW_COORDS>(t, box_at(t, S, k, stride), C, logistic, bs, k, &sc, &best, &bad);
+    if (sc > score_thr && (!NEW_COORDS || conf > score_thr)) {
       const int pos = atomicAdd(&n_cand, 1);
       keys[pos] = key_any(sc, k);
     }
@@ -92,10 +95,11 @@ yolo_multi_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pre
 //   phase 4  gather_kept, merge_single: the kept lists are gathered into registers (position p of
 //            the concatenated lists, found by a search in the prefix sum of the list lengths), then
 //            written back as dense ~score | index keys, sorted over pow2 >= kept, and emitted.
+template <bool NEW_COORDS, class RULE>
 __global__ void __launch_bounds__(PM_THREADS)
 yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pred,
                             dnn_detection* __restrict__ dets, int max_det, int* __restrict__ counts, char* workspace,
-                            int nb) {
+                            int nb, const RULE rule) {
   __shared__ unsigned long long keys[PM_CAP];
   __shared__ ScaleTab t;
   __shared__ ClassState st;
@@ -122,8 +126,8 @@ yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const XyScale xy, const Mul
   for (int k = tid; k < nb; k += PM_THREADS) {
     float sc;
     int best;
-    decode_single_at(t, box_at(t, S, k, stride), C, logistic, bs, k, &sc, &best, &bad);
-    if (sc > score_thr) {
+    const float conf = decode_single_at<NEW_COORDS>(t, box_at(t, S, k, stride), C, logistic, bs, k, &sc, &best, &bad);
+    if (sc > score_thr && (!NEW_COORDS || conf > score_thr)) {
       const int pos = atomicAdd(&n_cand, 1);
       atomicAdd(&st.cls_cnt[best], 1);
       keys[pos] = key_class<PC_IDX_BITS>(best, sc, k);
@@ -144,7 +148,7 @@ yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const XyScale xy, const Mul
   __syncthreads();  // seg_start too (the sort has no barrier when n <= 1)
 
   // ---- phase 3: every class segment alone; phase 4: merge the kept lists by (score, global index)
-  const int nk = nms_segments<PC_IDX_BITS>(keys, C, bs.box, mh.scale[0].iou_thr, st, tid);
+  const int nk = nms_segments<PC_IDX_BITS>(keys, C, bs.box, rule, st, tid);
   if (nk < 0) {
     if (tid == 0) counts[img] = -2;
     return;
@@ -178,10 +182,11 @@ yolo_multi_classwise_kernel(const dnn_yolo_multi mh, const XyScale xy, const Mul
 //            documented there).
 static_assert(DNN_YOLO_MULTI_MAX_CANDIDATES == PM_CAP, "the candidates of an image are the keys that fit in LDS");
 
+template <bool NEW_COORDS, class RULE>
 __global__ void __launch_bounds__(PM_THREADS)
 yolo_multi_labels_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pred,
                          dnn_detection* __restrict__ dets, int max_det, int* __restrict__ counts, char* workspace,
-                         int nb) {
+                         int nb, const RULE rule) {
   __shared__ unsigned long long keys[PM_CAP];
   __shared__ ScaleTab t;
   __shared__ ClassState st;
@@ -214,9 +219,11 @@ yolo_multi_labels_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiP
   for (int k = tid; k < nb; k += PM_THREADS) {
     const BoxAt at = box_at(t, S, k, stride);
     float conf;
-    decode_corners_at(t, at, bs, k, &conf, &bad);
+    decode_corners_at<NEW_COORDS>(t, at, bs, k, &conf, &bad);
     bs.score[k] = conf;
-    if (!(conf > score_thr)) continue;  // conf * p[c] <= conf: no class of this box is a candidate
+    // no class of this box is a candidate: conf * p[c] <= conf, or under NEW_COORDS, where p[c] may
+    // exceed 1, the gate is a condition of the rule itself (include/dnn_hip_post.h)
+    if (!(conf > score_thr)) continue;
     if (logistic) {
       gated[atomicAdd(&n_gated, 1)] = k | (at.s << PC_IDX_BITS);  // at most nb entries: the box and its scale
       continue;
@@ -241,7 +248,7 @@ yolo_multi_labels_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiP
     int g = tid / C, c = tid % C;
     for (int i = tid; i < pairs; i += PM_THREADS) {
       const int e = gated[g], k = e & ((1 << PC_IDX_BITS) - 1), s = e >> PC_IDX_BITS;
-      const float sc = label_score(box_values(t, s, k, stride)[5 + c], true, bs.score[k], 0.0f, 1.0f);
+      const float sc = label_score<NEW_COORDS>(box_values(t, s, k, stride)[5 + c], true, bs.score[k], 0.0f, 1.0f);
       if (sc > score_thr) append(c, sc, k);
       g += dq;
       c += dr;
@@ -267,14 +274,14 @@ yolo_multi_labels_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiP
   bitonic_sort<PM_THREADS>(keys, ns, tid);
 
   // ---- phase 3: every class segment alone; phase 4: merge by (score, global index, class)
-  const int nk = nms_segments<PC_IDX_BITS>(keys, C, bs.box, mh.scale[0].iou_thr, st, tid);
+  const int nk = nms_segments<PC_IDX_BITS>(keys, C, bs.box, rule, st, tid);
   if (nk < 0) {
     if (tid == 0) counts[img] = -2;
     return;
   }
   int mine[16];
   gather_kept<PC_IDX_BITS, true>(keys, C, nk, st, mine, tid);
-  merge_labels<PC_IDX_BITS>(keys, mine, nk, t, S, C, stride, logistic, bs, dets + (size_t)img * max_det, max_det,
+  merge_labels<PC_IDX_BITS, NEW_COORDS>(keys, mine, nk, t, S, C, stride, logistic, bs, dets + (size_t)img * max_det, max_det,
                             &counts[img], tid);
 }
 
@@ -353,10 +360,43 @@ static bool xy_scale_from(const float* scale_x_y, int n_scales, const char* who,
   return true;
 }
 
+// The rule of a call (NULL: all zero) against its description and modes, into *out; false with the
+// error set.
+static bool rule_ok(const MultiCall& c, MultiArgs* out) {
+  const dnn_yolo_rule none = {0, DNN_YOLO_NMS_KIND_IOU, 0.0};
+  const dnn_yolo_rule& r = c.rule ? *c.rule : none;
+  if ((r.new_coords != 0 && r.new_coords != 1) ||
+      (r.nms_kind != DNN_YOLO_NMS_KIND_IOU && r.nms_kind != DNN_YOLO_NMS_KIND_DIOU)) {
+    set_error("%s: rule new_coords %d, nms_kind %d: need new_coords 0 or 1 and nms_kind %d (IoU) or %d (DIoU)", c.who,
+              r.new_coords, r.nms_kind, DNN_YOLO_NMS_KIND_IOU, DNN_YOLO_NMS_KIND_DIOU);
+    return false;
+  }
+  if (r.new_coords && c.m->class_mode != 1) {
+    set_error("%s: new_coords needs class_mode 1 (logistic): Darknet has no softmax over values that the conv before "
+              "the head already squashed", c.who);
+    return false;
+  }
+  out->new_coords = r.new_coords == 1;
+  out->diou = r.nms_kind == DNN_YOLO_NMS_KIND_DIOU;
+  out->beta = r.beta_nms;
+  if (!out->diou) return true;
+  if (c.nms_mode != DNN_YOLO_NMS_PER_CLASS) {
+    set_error("%s: nms_kind %d (DIoU) needs nms_mode %d (per class): Darknet's diounms_sort has no class-agnostic form",
+              c.who, r.nms_kind, DNN_YOLO_NMS_PER_CLASS);
+    return false;
+  }
+  if (!(r.beta_nms > 0.0) || !(r.beta_nms <= DBL_MAX)) {
+    set_error("%s: beta_nms = %g: must be finite and > 0", c.who, r.beta_nms);
+    return false;
+  }
+  return true;
+}
+
 int check_multi_call(const MultiCall& c, const MultiKind& kind, bool host, MultiArgs* out) {
   out->nb = multi_boxes_upto(c.m, c.who, kind.max_boxes);
   if (out->nb < 0) return out->nb;
   if (!multi_modes_ok(c.nms_mode, c.labels_mode, c.who)) return -2;
+  if (!rule_ok(c, out)) return -2;
   if (!xy_scale_from(c.scale_x_y, c.m->n_scales, c.who, &out->xy)) return -2;
   if (c.n_images < 0 || c.max_det < 0 || (c.n_images > 0 && (!c.pred || !c.counts || (c.max_det > 0 && !c.dets)))) {
     set_error("%s: bad arguments (n_images=%d max_det=%d)", c.who, c.n_images, c.max_det);
@@ -438,13 +478,22 @@ static int launch_yolo_multi(const MultiCall& c, hipStream_t stream) {
   const int go = check_multi_call(c, MULTI, false, &a);
   if (go <= 0) return go;
   // with one class the rules and the label modes are the same function: the class-agnostic kernel
-  // serves them all
-  const bool per_class = c.nms_mode == DNN_YOLO_NMS_PER_CLASS && c.m->scale[0].n_classes > 1;
-  const auto kernel = !per_class                                ? yolo_multi_kernel
-                      : c.labels_mode == DNN_YOLO_LABELS_MULTI ? yolo_multi_labels_kernel
-                                                                : yolo_multi_classwise_kernel;
-  hipLaunchKernelGGL(kernel, dim3(c.n_images), dim3(PM_THREADS), 0, stream, *c.m, a.xy, a.mp, c.dets, c.max_det,
-                     c.counts, static_cast<char*>(c.workspace), a.nb);
+  // serves them all (but for DIoU, which only the per-class kernels have)
+  const bool per_class = c.nms_mode == DNN_YOLO_NMS_PER_CLASS && (c.m->scale[0].n_classes > 1 || a.diou);
+  const bool multi = c.labels_mode == DNN_YOLO_LABELS_MULTI;
+  char* ws = static_cast<char*>(c.workspace);
+  with_rule(a, c.m->scale[0].iou_thr, [&](auto nc, auto rule) {
+    constexpr bool NC = decltype(nc)::value;
+    using RULE = decltype(rule);
+    if (!per_class) {  // (never with DiouRule: rule_ok)
+      hipLaunchKernelGGL(yolo_multi_kernel<NC>, dim3(c.n_images), dim3(PM_THREADS), 0, stream, *c.m, a.xy, a.mp,
+                         c.dets, c.max_det, c.counts, ws, a.nb);
+      return;
+    }
+    const auto kernel = multi ? yolo_multi_labels_kernel<NC, RULE> : yolo_multi_classwise_kernel<NC, RULE>;
+    hipLaunchKernelGGL(kernel, dim3(c.n_images), dim3(PM_THREADS), 0, stream, *c.m, a.xy, a.mp, c.dets, c.max_det,
+                       c.counts, ws, a.nb, rule);
+  });
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("launch yolo_multi: %s", hipGetErrorString(e));
@@ -544,6 +593,21 @@ int dnn_yolo_postprocess_multi_xy_host(const dnn_yolo_multi* m, const float* sca
                                        int labels_mode) {
   return dnnhip::yolo_multi_host({"dnn_yolo_postprocess_multi_xy_host", m, scale_x_y, pred, n_images, dets, max_det,
                                   counts, nullptr, 0, nms_mode, labels_mode}, MULTI);
+}
+
+int dnn_yolo_postprocess_multi_rule(const dnn_yolo_multi* m, const float* scale_x_y, const dnn_yolo_rule* rule,
+                                    const float* const* pred, int n_images, dnn_detection* dets, int max_det,
+                                    int* counts, void* workspace, unsigned long long workspace_bytes, int nms_mode,
+                                    int labels_mode, void* stream) {
+  return MULTI.launch({"dnn_yolo_postprocess_multi_rule", m, scale_x_y, pred, n_images, dets, max_det, counts,
+                       workspace, workspace_bytes, nms_mode, labels_mode, rule}, static_cast<hipStream_t>(stream));
+}
+
+int dnn_yolo_postprocess_multi_rule_host(const dnn_yolo_multi* m, const float* scale_x_y, const dnn_yolo_rule* rule,
+                                         const float* const* pred, int n_images, dnn_detection* dets, int max_det,
+                                         int* counts, int nms_mode, int labels_mode) {
+  return dnnhip::yolo_multi_host({"dnn_yolo_postprocess_multi_rule_host", m, scale_x_y, pred, n_images, dets, max_det,
+                                  counts, nullptr, 0, nms_mode, labels_mode, rule}, MULTI);
 }
 
 }  // extern "C"

@@ -74,7 +74,9 @@ __global__ void __launch_bounds__(PW_DEC_THREADS) yolo_wide_clear_kernel(int* co
   if (i < n_ints) counters[i] = 0;
 }
 
-template <int MODE>
+// NEW_COORDS: the box rule of Darknet's new_coords = 1 (post_dev.h: decode_corners); p[c] is then the
+// value itself, which may exceed 1, so there the gate conf > score_thr is part of the rule.
+template <int MODE, bool NEW_COORDS>
 __global__ void __launch_bounds__(PW_DEC_THREADS)
 yolo_wide_decode_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPred pred, char* workspace, int nb,
                         int n_images) {
@@ -99,7 +101,7 @@ yolo_wide_decode_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPr
   bool gate = false;  // conf > score_thr: only then can a class score be above it
   if (in) {
     at = box_at(t, S, k, stride);
-    decode_corners_at(t, at, bs, k, &conf, &ctr[1]);
+    decode_corners_at<NEW_COORDS>(t, at, bs, k, &conf, &ctr[1]);
     gate = conf > score_thr;
   }
   const float* q = at.q;
@@ -124,17 +126,17 @@ yolo_wide_decode_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPr
       if (MODE == PW_MULTI) {
         for (int c0 = 0; c0 < C; c0 += 64) {
           const int c = c0 + lane;
-          const float sl = c < C ? label_score(lg[c], true, cg, 0.0f, 1.0f) : 0.0f;
+          const float sl = c < C ? label_score<NEW_COORDS>(lg[c], true, cg, 0.0f, 1.0f) : 0.0f;
           const int pos = wave_append(ctr, c < C && sl > score_thr, lane);
           if (pos >= 0 && pos < PM_CAP) keys[pos] = key_class<PW_IDX_BITS>(c, sl, kg);
         }
         continue;
       }
       // class_argmax over the lanes: the largest rounded p, the first index among equals
-      float bp = -1.0f, p0 = 0.0f;  // (every p is >= 0)
+      float bp = NEW_COORDS ? -__builtin_inff() : -1.0f, p0 = 0.0f;  // (every sigmoid is >= 0; a value is any float)
       int bc = 0x7fffffff;
       for (int c = lane; c < C; c += 64) {
-        const float pc = sigmoid_ref(lg[c]);
+        const float pc = NEW_COORDS ? lg[c] : sigmoid_ref(lg[c]);
         if (c == 0) p0 = pc;
         if (pc > bp) {
           bp = pc;
@@ -151,7 +153,9 @@ yolo_wide_decode_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPr
         }
       }
       p0 = __shfl(p0, 0);
-      if (p0 != p0) {  // a NaN in class 0 stays class_argmax's result: no later class compares above it
+      // a NaN in class 0 stays class_argmax's result: no later class compares above it; nor does any
+      // when every value is -inf or NaN (NEW_COORDS only), and no lane has set bc
+      if (p0 != p0 || (NEW_COORDS && bc == 0x7fffffff)) {
         bp = p0;
         bc = 0;
       }
@@ -170,13 +174,13 @@ yolo_wide_decode_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPr
     }
     for (int c = 0; c < C; ++c) {  // wave-uniform trip count: one key per (box, class) above the threshold
       float sl = 0.0f;
-      if (gate) sl = label_score(q[5 + c], logistic, conf, m, sum);
+      if (gate) sl = label_score<NEW_COORDS>(q[5 + c], logistic, conf, m, sum);
       const int pos = wave_append(ctr, gate && sl > score_thr, lane);
       if (pos >= 0 && pos < PM_CAP) keys[pos] = key_class<PW_IDX_BITS>(c, sl, k);
     }
     return;
   } else if (gate) {
-    sc = conf * class_argmax(q + 5, C, logistic, &best);  // decode_box's score
+    sc = conf * class_argmax<NEW_COORDS>(q + 5, C, logistic, &best);  // decode_box's score
   }
 
   if (gate) {
@@ -188,17 +192,18 @@ yolo_wide_decode_kernel(const dnn_yolo_multi mh, const XyScale xy, const MultiPr
     keys[pos] = MODE == PW_ANY ? key_any(sc, k) : key_class<PW_IDX_BITS>(best, sc, k);
 }
 
-template <int MODE>
+// RULE: the suppression test (post_math.h).  NEW_COORDS matters to the multi-label merge alone, which
+// computes the scores again.
+template <int MODE, bool NEW_COORDS, class RULE>
 __global__ void __launch_bounds__(PM_THREADS)
 yolo_wide_nms_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detection* __restrict__ dets, int max_det,
-                     int* __restrict__ counts, char* workspace, int nb, int n_images) {
+                     int* __restrict__ counts, char* workspace, int nb, int n_images, const RULE rule) {
   __shared__ unsigned long long keys[PM_CAP];
   __shared__ ScaleTab t;  // the multi-label merge reads the logits again
   __shared__ typename std::conditional<MODE == PW_ANY, NmsState, ClassState>::type st;
 
   const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int S = mh.n_scales, C = mh.scale[0].n_classes, stride = 5 + C;
-  const double iou_thr = mh.scale[0].iou_thr;
 
   const int* ctr = ws_counters(workspace, img);
   const BoxStore bs = box_store(ws_boxes(workspace, img, nb, n_images), nb);  // multi-label: score is the conf
@@ -230,7 +235,7 @@ yolo_wide_nms_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detectio
   __syncthreads();
 
   if constexpr (MODE == PW_ANY) {
-    nms_any_emit<PM_THREADS>(keys, n, bs, iou_thr, st, rows, max_det, &counts[img], tid);
+    nms_any_emit<PM_THREADS>(keys, n, bs, rule.thr, st, rows, max_det, &counts[img], tid);
   } else {
     if (wid == 0) wave_scan_128(st.cls_cnt, C, st.seg_start, lane);
 
@@ -239,7 +244,7 @@ yolo_wide_nms_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detectio
     __syncthreads();  // seg_start too (the sort has no barrier when n <= 1)
 
     // ---- phase 3: every class segment alone; phase 4: merge by (score, global index[, class])
-    const int nk = nms_segments<PW_IDX_BITS>(keys, C, bs.box, iou_thr, st, tid);
+    const int nk = nms_segments<PW_IDX_BITS>(keys, C, bs.box, rule, st, tid);
     if (nk < 0) {
       if (tid == 0) counts[img] = -2;
       return;
@@ -249,8 +254,8 @@ yolo_wide_nms_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detectio
     if (MODE == PW_PER_CLASS)
       merge_single(keys, mine, nk, bs, rows, max_det, &counts[img], tid);
     else
-      merge_labels<PW_IDX_BITS>(keys, mine, nk, t, S, C, stride, mh.class_mode == 1, bs, rows, max_det, &counts[img],
-                                tid);
+      merge_labels<PW_IDX_BITS, NEW_COORDS>(keys, mine, nk, t, S, C, stride, mh.class_mode == 1, bs, rows, max_det,
+                                            &counts[img], tid);
   }
 }
 
@@ -258,14 +263,15 @@ static unsigned long long wide_workspace(int nb, int n_images) {
   return (unsigned long long)n_images * ((unsigned long long)nb * PM_BOX_BYTES + PW_KEY_BYTES + PW_CTR_BYTES);
 }
 
-template <int MODE>
-static void launch_wide_kernels(const dnn_yolo_multi& m, const XyScale& xy, const MultiPred& mp, int n_images,
-                                dnn_detection* dets, int max_det, int* counts, char* ws, int nb, hipStream_t stream) {
-  const dim3 grid((nb + PW_DEC_THREADS - 1) / PW_DEC_THREADS, n_images);
-  hipLaunchKernelGGL(yolo_wide_decode_kernel<MODE>, grid, dim3(PW_DEC_THREADS), 0, stream, m, xy, mp, ws, nb,
-                     n_images);
-  hipLaunchKernelGGL(yolo_wide_nms_kernel<MODE>, dim3(n_images), dim3(PM_THREADS), 0, stream, m, mp, dets, max_det,
-                     counts, ws, nb, n_images);
+template <int MODE, bool NEW_COORDS, class RULE>
+static void launch_wide_kernels(const MultiCall& c, const MultiArgs& a, const RULE& rule, hipStream_t stream) {
+  char* ws = static_cast<char*>(c.workspace);
+  const dim3 grid((a.nb + PW_DEC_THREADS - 1) / PW_DEC_THREADS, c.n_images);
+  const auto decode = yolo_wide_decode_kernel<MODE, NEW_COORDS>;
+  const auto nms = yolo_wide_nms_kernel<MODE, MODE == PW_MULTI && NEW_COORDS, RULE>;
+  hipLaunchKernelGGL(decode, grid, dim3(PW_DEC_THREADS), 0, stream, *c.m, a.xy, a.mp, ws, a.nb, c.n_images);
+  hipLaunchKernelGGL(nms, dim3(c.n_images), dim3(PM_THREADS), 0, stream, *c.m, a.mp, c.dets, c.max_det, c.counts, ws,
+                     a.nb, c.n_images, rule);
 }
 
 static int launch_yolo_wide(const MultiCall& c, hipStream_t stream);
@@ -281,12 +287,17 @@ static int launch_yolo_wide(const MultiCall& c, hipStream_t stream) {
   hipLaunchKernelGGL(yolo_wide_clear_kernel, dim3((n_ints + PW_DEC_THREADS - 1) / PW_DEC_THREADS),
                      dim3(PW_DEC_THREADS), 0, stream, reinterpret_cast<int*>(ws), n_ints);
   // with one class the rules and the label modes are the same function: the class-agnostic kernels
-  // serve them all
-  const bool one = c.m->scale[0].n_classes == 1;
-  const auto launch = c.labels_mode == DNN_YOLO_LABELS_MULTI && !one   ? launch_wide_kernels<PW_MULTI>
-                      : c.nms_mode == DNN_YOLO_NMS_PER_CLASS && !one ? launch_wide_kernels<PW_PER_CLASS>
-                                                                      : launch_wide_kernels<PW_ANY>;
-  launch(*c.m, a.xy, a.mp, c.n_images, c.dets, c.max_det, c.counts, ws, a.nb, stream);
+  // serve them all (but for DIoU, which only the per-class ones have)
+  const bool one = c.m->scale[0].n_classes == 1 && !a.diou;
+  with_rule(a, c.m->scale[0].iou_thr, [&](auto nc, auto rule) {
+    constexpr bool NC = decltype(nc)::value;
+    if (c.labels_mode == DNN_YOLO_LABELS_MULTI && !one)
+      launch_wide_kernels<PW_MULTI, NC>(c, a, rule, stream);
+    else if (c.nms_mode == DNN_YOLO_NMS_PER_CLASS && !one)
+      launch_wide_kernels<PW_PER_CLASS, NC>(c, a, rule, stream);
+    else  // (never with DiouRule: check_multi_call)
+      launch_wide_kernels<PW_ANY, NC>(c, a, IouRule{rule.thr}, stream);
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_error("launch yolo_wide: %s", hipGetErrorString(e));
@@ -338,6 +349,21 @@ int dnn_yolo_postprocess_wide_xy_host(const dnn_yolo_multi* m, const float* scal
                                       int labels_mode) {
   return dnnhip::yolo_multi_host({"dnn_yolo_postprocess_wide_xy_host", m, scale_x_y, pred, n_images, dets, max_det,
                                   counts, nullptr, 0, nms_mode, labels_mode}, WIDE);
+}
+
+int dnn_yolo_postprocess_wide_rule(const dnn_yolo_multi* m, const float* scale_x_y, const dnn_yolo_rule* rule,
+                                   const float* const* pred, int n_images, dnn_detection* dets, int max_det,
+                                   int* counts, void* workspace, unsigned long long workspace_bytes, int nms_mode,
+                                   int labels_mode, void* stream) {
+  return WIDE.launch({"dnn_yolo_postprocess_wide_rule", m, scale_x_y, pred, n_images, dets, max_det, counts, workspace,
+                      workspace_bytes, nms_mode, labels_mode, rule}, static_cast<hipStream_t>(stream));
+}
+
+int dnn_yolo_postprocess_wide_rule_host(const dnn_yolo_multi* m, const float* scale_x_y, const dnn_yolo_rule* rule,
+                                        const float* const* pred, int n_images, dnn_detection* dets, int max_det,
+                                        int* counts, int nms_mode, int labels_mode) {
+  return dnnhip::yolo_multi_host({"dnn_yolo_postprocess_wide_rule_host", m, scale_x_y, pred, n_images, dets, max_det,
+                                  counts, nullptr, 0, nms_mode, labels_mode, rule}, WIDE);
 }
 
 }  // extern "C"

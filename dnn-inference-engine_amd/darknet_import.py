@@ -33,8 +33,11 @@ on its own lets only leaky and linear through unless given the set), [shortcut] 
 CSP block; two: their channel concat; four: the SPP pattern, three stride-1 max pools of one tensor
 plus the tensor, which is one dnn_hip.Spp node in Darknet's order), [upsample], [maxpool] (where
 Darknet's window placement is the engine's SAME pool's: 2/2, 2/1 and odd sizes at stride 1) and
-[yolo] (mask, anchors, classes, scale_x_y; new_coords must be 0 and nms_kind absent, default or
-greedynms).  The conv before each [yolo] is an output of the plan, in cfg order (at most 4, what
+[yolo] (mask, anchors, classes, scale_x_y; new_coords 0 or 1, the latter only after a conv with
+activation = logistic, whose values the decode then takes as they are; nms_kind absent, default or
+greedynms, or beside new_coords = 1 diounms with beta_nms: the DIoU NMS (diounms with new_coords = 0
+still raises, as it always did here); all [yolo] sections of a cfg must agree on the
+three).  The conv before each [yolo] is an output of the plan, in cfg order (at most 4, what
 the decode takes: the last one the plan's output, the others taps).  The head is a
 yolo_post.MultiHead with logistic class scores, the masked anchors divided by the scale's stride,
 per-class NMS, multi-label output, score 0.5 and IoU 0.45 (Darknet's detector defaults); a
@@ -42,8 +45,8 @@ scale_x_y other than 1 goes into the head per scale
 (yolo_post.MultiHead's scale_x_y: the box centre's logistic becomes sig * s - 0.5 * (s - 1)).
 Importable stock models: YOLOv3, YOLOv3-SPP, YOLOv3-tiny, YOLOv4-tiny and YOLOv4 (cfg_text has their public
 definitions; "yolov4" is CSPDarknet53 with mish, the SPP + PAN neck with leaky and three [yolo] sections with
-scale_x_y 1.2 / 1.1 / 1.05 and greedy NMS; beta_nms, iou_thresh, max_delta and the loss keys are training or
-DIoU matters and are ignored like every unknown key).
+scale_x_y 1.2 / 1.1 / 1.05 and greedy NMS; iou_thresh, max_delta and the loss keys are training matters and
+are ignored like every unknown key; beta_nms is read under nms_kind = diounms only).
 
 Classifiers: [avgpool] (a dnn_hip.GlobalAvgPool node, dnn_plan_add_avgpool), [softmax] (groups 1,
 temperature 1, no tree, on a 1 x 1 map: a dnn_hip.Softmax node, dnn_plan_add_softmax), [connected]
@@ -78,8 +81,9 @@ Out of scope:
     larger than 1 x 1, [softmax] with groups, a temperature or a tree;
   * [route] with groups > 1 over more than one layer (Darknet slices each layer then; no stock cfg
     does it);
-  * [yolo] with new_coords = 1 (the scaled-YOLOv4 box form) and nms_kind = diounms (DIoU NMS): both
-    raise DarknetError, since ignoring either gives wrong boxes;
+  * [route] over more than two layers outside an SPP block (YOLOv7's four-layer concat), so of the
+    cfgs with new_coords = 1 and nms_kind = diounms, which the head decodes, yolov4-csp and its
+    scaled relatives are expected to import and yolov7 is not;
   * image file decoding: detect_images takes H x W x 3 uint8 arrays of any sizes, letterboxes them
     on the device as Darknet's letterbox_image does and returns boxes in each image's own pixels
     (ingest.RaggedIngest, yolo_post.DetectionBuffers.correct); reading a JPEG into such an array
@@ -107,6 +111,7 @@ SCORE_THR, IOU_THR = 0.5, 0.45  # Darknet's detector defaults (-thresh .5, nms .
 MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny", "yolov4-tiny", "yolov4", "darknet19", "darknet53")
 CLASSIFIERS = {"darknet19": 224, "darknet53": 256}  # the classifier definitions and their default input size
 NMS_KINDS = ("default", "greedynms")  # [yolo] nms_kind values that are the decode's greedy NMS
+DIOU_KINDS = ("diounms",)             # ... and those that are its DIoU NMS (yolo_post.MultiHead's nms_kind "diou")
 
 
 class DarknetError(ValueError):
@@ -294,15 +299,41 @@ def route_group(sec, n_layers, c):
     return gid * (c // groups), c // groups
 
 
-def yolo_params(sec):
-    """scale_x_y (default 1) of a [yolo] section, after refusing what the decode does not implement:
-    new_coords other than 0 and an nms_kind outside NMS_KINDS."""
+def yolo_rule(sec, before=None):
+    """(new_coords, nms_kind, beta_nms) of a [yolo] section as yolo_post.MultiHead takes them: new_coords
+    0 or 1, nms_kind "iou" (Darknet's default and greedynms) or "diou" (diounms, accepted beside
+    new_coords = 1 only) with beta_nms (default 0.6; read under diounms only, as every other kind
+    ignores it).  `before`, the section the [yolo] follows, is checked where given: with new_coords = 1
+    Darknet reads the conv's values as they are, so that conv must be activation = logistic."""
     where = f"[yolo] at line {sec['line']}"
-    if _int(sec, "new_coords", 0) != 0:
-        raise DarknetError(f"{where}: new_coords = {sec['new_coords']} is not supported (only 0)")
+    new_coords = _int(sec, "new_coords", 0)
+    if new_coords not in (0, 1):
+        raise DarknetError(f"{where}: new_coords = {sec['new_coords']} is not supported (0 or 1)")
+    if new_coords and before is not None and before.get("activation", "logistic") != "logistic":
+        raise DarknetError(f"{where}: new_coords = 1 after a [convolutional] with activation = "
+                           f"{before.get('activation')}: Darknet reads raw values there, the conv must be logistic")
     kind = sec.get("nms_kind", "default")
-    if kind not in NMS_KINDS:
-        raise DarknetError(f"{where}: nms_kind = {kind} is not supported ({', '.join(NMS_KINDS)})")
+    if kind not in NMS_KINDS + DIOU_KINDS:
+        raise DarknetError(f"{where}: nms_kind = {kind} is not supported ({', '.join(NMS_KINDS + DIOU_KINDS)})")
+    if kind in DIOU_KINDS and not new_coords:
+        # what the importer did before it read the scaled heads stays as it was: DIoU NMS is read with
+        # new_coords = 1 only (yolo_post.MultiHead itself takes nms_kind "diou" with either box form)
+        raise DarknetError(f"{where}: nms_kind = {kind} without new_coords = 1 is not supported (the DIoU NMS is "
+                           "imported for the scaled-YOLOv4 head only)")
+    if kind not in DIOU_KINDS:
+        return bool(new_coords), "iou", 0.6
+    try:
+        beta = float(sec.get("beta_nms", 0.6))
+    except ValueError:
+        raise DarknetError(f"{where}: beta_nms = {sec['beta_nms']!r} is not a number")
+    if not (beta > 0 and beta < float("inf")):
+        raise DarknetError(f"{where}: beta_nms = {beta}: need a finite value > 0")
+    return bool(new_coords), "diou", beta
+
+
+def yolo_params(sec):
+    """scale_x_y (default 1) of a [yolo] section."""
+    where = f"[yolo] at line {sec['line']}"
     try:
         s = float(sec.get("scale_x_y", 1))
     except ValueError:
@@ -389,6 +420,7 @@ def layer_shapes(sections, in_shape=None):
             if at == 0 or sections[at]["type"] != "convolutional":
                 raise DarknetError(f"[yolo] at line {sec['line']}: it must follow a [convolutional] section")
             yolo_params(sec)
+            yolo_rule(sec, sections[at])
         elif kind == "avgpool":
             h, w = 1, 1
         elif kind == "softmax":
@@ -699,6 +731,13 @@ def multi_head(yolos, in_h, in_w, score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per
         scales.append(yolo_post.Scale(gh, gw, len(mask), _int(y, "classes", 20), tuple(a / stride for a in px),
                                       float(stride), score_thr, iou_thr))
     kw = {} if all(s == 1.0 for s in xy) else {"scale_x_y": tuple(xy)}
+    rules = [yolo_rule(y) for y in yolos]
+    for y, r in zip(yolos, rules):  # one decode and one NMS serve every scale (beta_nms matters under DIoU only)
+        if r != rules[0]:
+            raise DarknetError(f"[yolo] at line {y['line']}: new_coords, nms_kind, beta_nms = {r}; the first [yolo] "
+                               f"has {rules[0]} (all sections must agree)")
+    if rules and (rules[0][0] or rules[0][1] != "iou"):
+        kw.update(new_coords=rules[0][0], nms_kind=rules[0][1], beta_nms=rules[0][2])
     return (yolo_post.WideHead if wide else yolo_post.MultiHead)(scales, "logistic", nms, labels, **kw)
 
 
@@ -890,8 +929,9 @@ class _Cfg(object):
         return self.n - 1
 
     def conv(self, filters, size, stride=1, head=False, act="leaky"):
-        if head:  # a linear conv with a bias, 3 x (5 + classes) filters whatever the width
-            pairs = [("size", size), ("stride", stride), ("pad", 1), ("filters", filters), ("activation", "linear")]
+        if head:  # a conv with a bias, 3 x (5 + classes) filters whatever the width: linear, or logistic as given
+            pairs = [("size", size), ("stride", stride), ("pad", 1), ("filters", filters),
+                     ("activation", "logistic" if act == "logistic" else "linear")]
         else:
             pairs = [("batch_normalize", 1), ("filters", self.wd(filters)), ("size", size), ("stride", stride),
                      ("pad", 1), ("activation", act)]
@@ -902,12 +942,13 @@ class _Cfg(object):
                         ("num", len(anchors.split(",")) // 2), ("jitter", ".3"), ("ignore_thresh", ".7"),
                         ("truth_thresh", 1), ("random", 1))
 
-    def yolo_v4(self, mask, anchors, classes, scale_x_y="1.05"):
+    def yolo_v4(self, mask, anchors, classes, scale_x_y="1.05", scaled=False):
         return self.add("yolo", ("mask", mask), ("anchors", anchors), ("classes", classes),
                         ("num", len(anchors.split(",")) // 2), ("jitter", ".3"), ("scale_x_y", scale_x_y),
                         ("cls_normalizer", "1.0"), ("iou_normalizer", "0.07"), ("iou_loss", "ciou"),
                         ("ignore_thresh", ".7"), ("truth_thresh", 1), ("random", 0), ("resize", "1.5"),
-                        ("nms_kind", "greedynms"), ("beta_nms", "0.6"))
+                        ("nms_kind", "diounms" if scaled else "greedynms"), ("beta_nms", "0.6"),
+                        *((("new_coords", 1),) if scaled else ()))
 
     def text(self):
         return "\n".join(self.lines)
@@ -916,8 +957,10 @@ class _Cfg(object):
 _V4_ANCHORS = "12, 16, 19, 36, 40, 28, 36, 75, 76, 55, 72, 146, 142, 110, 192, 243, 459, 401"
 
 
-def _yolov4(c, n_out, classes):
-    """YOLOv4: CSPDarknet53 with mish, the SPP + PAN neck with leaky, three heads from the finest scale up."""
+def _yolov4(c, n_out, classes, scaled=False):
+    """YOLOv4: CSPDarknet53 with mish, the SPP + PAN neck with leaky, three heads from the finest scale up.
+    scaled: the heads of the scaled-YOLOv4 cfgs on that topology (logistic head convs, new_coords,
+    scale_x_y 2.0, DIoU NMS)."""
     def mish(filters, size, stride=1):
         return c.conv(filters, size, stride, act="mish")
 
@@ -964,8 +1007,8 @@ def _yolov4(c, n_out, classes):
         tops.append(five(f))
     for k, (f, mask, sxy) in enumerate(((128, "0,1,2", "1.2"), (256, "3,4,5", "1.1"), (512, "6,7,8", "1.05"))):
         c.conv(2 * f, 3)
-        c.conv(n_out, 1, head=True)
-        c.yolo_v4(mask, _V4_ANCHORS, classes, sxy)
+        c.conv(n_out, 1, head=True, act="logistic" if scaled else "linear")
+        c.yolo_v4(mask, _V4_ANCHORS, classes, "2.0" if scaled else sxy, scaled)
         if k < 2:  # the way down: a stride-2 conv of this scale joins the neck's tensor of the next coarser one
             c.add("route", ("layers", "-4"))
             at = c.conv(2 * f, 3, stride=2)
@@ -974,14 +1017,20 @@ def _yolov4(c, n_out, classes):
     return c.text()
 
 
-def cfg_text(model, classes=None, width=None, height=None, width_div=1):
+def cfg_text(model, classes=None, width=None, height=None, width_div=1, scaled_head=False):
     """The public definition of `model` (one of MODELS) as cfg text, for `classes` classes and a
     width x height input; width_div divides every channel count except the heads' 3 x (5 + classes)
     or the classifier conv's `classes` (a narrow model of the same topology).  Defaults: 80 classes
     at 416 x 416 for the detectors ("yolov4" has no default size: ValueError without width and height); 1000 classes for the classifiers "darknet19" (224 x 224) and
-    "darknet53" (256 x 256), which end in [avgpool] and [softmax]."""
+    "darknet53" (256 x 256), which end in [avgpool] and [softmax].
+    scaled_head ("yolov4" only): YOLOv4's topology with the head of the scaled-YOLOv4 cfgs: the head convs
+    are activation=logistic and each [yolo] carries new_coords=1, scale_x_y=2.0, nms_kind=diounms and
+    beta_nms=0.6.  That is a construction for testing the head, not a public cfg: the public yolov4-csp /
+    yolov7 texts are the caller's to pass in."""
     if model not in MODELS:
         raise ValueError(f"model {model!r}: one of {MODELS} expected")
+    if scaled_head and model != "yolov4":
+        raise ValueError('scaled_head is defined for "yolov4" only')
     if model == "yolov4" and (width is None or height is None):
         # its public cfg is 608 x 608, which has more boxes than the default head decodes (DarknetModel builds it
         # without a head unless wide=True), and 416 x 416, the other detectors' default here, is not its definition
@@ -1048,7 +1097,7 @@ def cfg_text(model, classes=None, width=None, height=None, width_div=1):
         c.yolo_v4("1,2,3", _TINY_ANCHORS, classes)
         return c.text()
     if model == "yolov4":
-        return _yolov4(c, n_out, classes)
+        return _yolov4(c, n_out, classes, scaled_head)
     c.conv(32, 3)
     stage_end = []
     for f, blocks in _STAGES:

@@ -78,6 +78,14 @@ class MultiStruct(ctypes.Structure):
     _fields_ = [("n_scales", ctypes.c_int), ("class_mode", ctypes.c_int), ("scale", HeadStruct * MAX_SCALES)]
 
 
+NMS_KINDS = {"iou": 0, "diou": 1}  # DNN_YOLO_NMS_KIND_IOU, DNN_YOLO_NMS_KIND_DIOU
+
+
+class RuleStruct(ctypes.Structure):
+    """dnn_yolo_rule (include/dnn_hip_post.h)."""
+    _fields_ = [("new_coords", ctypes.c_int), ("nms_kind", ctypes.c_int), ("beta_nms", ctypes.c_double)]
+
+
 class ImageSize(ctypes.Structure):
     """dnn_image_size (include/dnn_hip_post.h)."""
     _fields_ = [("h", ctypes.c_int), ("w", ctypes.c_int)]
@@ -95,6 +103,7 @@ def _bind(lib):
     vp, i, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong
     hp, mp, pp = ctypes.POINTER(HeadStruct), ctypes.POINTER(MultiStruct), ctypes.POINTER(vp)
     fp, sp, bp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ImageSize), ctypes.POINTER(u64)
+    rp = ctypes.POINTER(RuleStruct)
     for name, argtypes in {  # every entry returns int
             "dnn_yolo_head_voc": [i, i, hp],
             "dnn_yolo_head_boxes": [hp],
@@ -122,6 +131,10 @@ def _bind(lib):
             "dnn_yolo_postprocess_multi_xy_host": [mp, fp, pp, i, vp, i, vp, i, i],
             "dnn_yolo_postprocess_wide_xy": [mp, fp, pp, i, vp, i, vp, vp, u64, i, i, vp],
             "dnn_yolo_postprocess_wide_xy_host": [mp, fp, pp, i, vp, i, vp, i, i],
+            "dnn_yolo_postprocess_multi_rule": [mp, fp, rp, pp, i, vp, i, vp, vp, u64, i, i, vp],
+            "dnn_yolo_postprocess_multi_rule_host": [mp, fp, rp, pp, i, vp, i, vp, i, i],
+            "dnn_yolo_postprocess_wide_rule": [mp, fp, rp, pp, i, vp, i, vp, vp, u64, i, i, vp],
+            "dnn_yolo_postprocess_wide_rule_host": [mp, fp, rp, pp, i, vp, i, vp, i, i],
             "dnn_yolo_correct_detections": [vp, vp, i, i, sp, i, i, vp],
             "dnn_yolo_correct_detections_host": [vp, vp, i, i, sp, i, i],
     }.items():
@@ -227,13 +240,34 @@ class MultiHead(object):
     by its first.  scale_x_y is Darknet's [yolo] key of that name (YOLOv4, YOLOv4-tiny): None, or
     one finite float > 0 per scale; the box centre's logistic becomes sig * s - 0.5 * (s - 1) in
     fp32 (the dnn_yolo_postprocess_*_xy entries).  None calls exactly the entries without it.
+    new_coords is Darknet's [yolo] key of that name (scaled-YOLOv4, YOLOv7: the conv before the head
+    is the logistic and the values are decoded as they are; class_mode "logistic" only), nms_kind
+    "diou" its nms_kind = diounms with beta_nms (a candidate is suppressed when iou - (d / c) **
+    beta_nms > iou_thr; nms "per_class" only): the dnn_yolo_postprocess_*_rule entries.  With the
+    defaults a head calls exactly the entries it called without them.
     Validates like the C side (dnn_yolo_multi_boxes) and raises ValueError."""
 
     MAX_BOXES = MULTI_MAX_BOXES         # the most boxes over all scales (WideHead: WIDE_MAX_BOXES)
     BOXES_ENTRY = "dnn_yolo_multi_boxes"  # the C function that validates the description and counts them
 
-    def __init__(self, scales, class_mode="logistic", nms="any", labels="argmax", scale_x_y=None):
+    def __init__(self, scales, class_mode="logistic", nms="any", labels="argmax", scale_x_y=None, new_coords=False,
+                 nms_kind="iou", beta_nms=0.6):
         scales = list(scales)
+        if nms_kind not in NMS_KINDS:
+            raise ValueError(f"nms_kind {nms_kind!r}: need one of {sorted(NMS_KINDS)}")
+        if new_coords not in (False, True, 0, 1):
+            raise ValueError(f"new_coords {new_coords!r}: need False or True")
+        if new_coords and class_mode != "logistic":
+            raise ValueError('new_coords needs class_mode "logistic"')
+        if nms_kind == "diou":
+            if nms != "per_class":
+                raise ValueError('nms_kind "diou" needs nms "per_class": Darknet has no class-agnostic DIoU rule')
+            if not (isinstance(beta_nms, (int, float)) and 0 < beta_nms < float("inf")):
+                raise ValueError(f"beta_nms {beta_nms!r}: a finite value > 0 expected")
+        self.new_coords, self.nms_kind, self.beta_nms = bool(new_coords), nms_kind, float(beta_nms)
+        # the rule the _rule entries read (None: the entries without one)
+        self.rule = (RuleStruct(int(self.new_coords), NMS_KINDS[nms_kind], self.beta_nms)
+                     if self.new_coords or nms_kind != "iou" else None)
         if scale_x_y is not None:
             scale_x_y = tuple(float(v) for v in scale_x_y)
             if len(scale_x_y) != len(scales):
@@ -329,11 +363,11 @@ class MultiHead(object):
 
     def _entry(self, form):
         """form "device", "host" or "workspace" -> (the C entry of that form for this head's modes, its
-        trailing mode arguments): the _xy entry with scale_x_y, else the _labels entry for labels
-        "multi", else the _nms entry."""
+        trailing mode arguments): the _rule entry with a rule, else the _xy entry with scale_x_y, else
+        the _labels entry for labels "multi", else the _nms entry."""
         nms, labels = NMS_MODES[self.nms], LABEL_MODES[self.labels]
-        if self.xy is not None and form != "workspace":
-            kind, tail = "_xy", (nms, labels)
+        if (self.xy is not None or self.rule is not None) and form != "workspace":
+            kind, tail = "_xy" if self.rule is None else "_rule", (nms, labels)
         else:
             kind, tail = ("_labels", (labels,)) if self.labels == "multi" else ("_nms", (nms,))
         if form == "workspace":
@@ -344,7 +378,11 @@ class MultiHead(object):
         """Calls _entry(form): the description (and scale_x_y, where the entry takes it), args, the mode
         arguments, last."""
         name, tail = self._entry(form)
-        lead = (ctypes.byref(self.c),) if self.xy is None or form == "workspace" else (ctypes.byref(self.c), self.xy)
+        lead = (ctypes.byref(self.c),)
+        if form != "workspace" and self.rule is not None:
+            lead += (self.xy, ctypes.byref(self.rule))
+        elif form != "workspace" and self.xy is not None:
+            lead += (self.xy,)
         dnn_hip._check(getattr(_lib, name)(*lead, *args, *tail, *last), name)
 
     def workspace_bytes(self, n_images):
@@ -357,8 +395,10 @@ class MultiHead(object):
         nms = "" if self.nms == "any" else f", NMS {self.nms}"
         labels = "" if self.labels == "argmax" else f", labels {self.labels}"
         xy = "" if self.scale_x_y is None else ", scale_x_y " + ",".join(f"{v:g}" for v in self.scale_x_y)
+        rule = (", new_coords" if self.new_coords else "") + \
+            (f", DIoU beta {self.beta_nms:g}" if self.nms_kind == "diou" else "")
         return (f"{type(self).__name__}({grids}; {self.n_classes} classes, {self.class_mode}, score > {self.score_thr:g}, "
-                f"IoU > {self.iou_thr:g}{nms}{labels}{xy})")
+                f"IoU > {self.iou_thr:g}{nms}{labels}{xy}{rule})")
 
 
 class WideHead(MultiHead):
@@ -375,7 +415,8 @@ class WideHead(MultiHead):
     def _entry(self, form):
         if form == "workspace":
             return "dnn_yolo_wide_workspace", ()
-        return ("dnn_yolo_postprocess_wide" + ("" if self.xy is None else "_xy") + ("_host" if form == "host" else ""),
+        kind = "_rule" if self.rule is not None else "" if self.xy is None else "_xy"
+        return ("dnn_yolo_postprocess_wide" + kind + ("_host" if form == "host" else ""),
                 (NMS_MODES[self.nms], LABEL_MODES[self.labels]))
 
 

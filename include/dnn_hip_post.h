@@ -294,6 +294,72 @@ int dnn_yolo_postprocess_wide_xy_host(const dnn_yolo_multi* multi, const float* 
                                       const float* const* pred, int n_images, dnn_detection* dets, int max_det,
                                       int* counts, int nms_mode, int labels_mode);
 
+/* ---- the scaled-YOLOv4 / YOLOv7 head: new_coords and DIoU NMS ------------------------------
+ * Darknet's [yolo] keys new_coords = 1 and nms_kind = diounms (yolov4-csp, yolov4-p5 / p6, yolov7),
+ * as a rule struct beside scale_x_y.  A NULL or all-zero rule is the decode and the NMS above: the
+ * _rule entries then give the _xy entries' dets, counts and workspace byte for byte.
+ *
+ * new_coords = 1: Darknet applies no activation in the [yolo] layer (the conv before it is
+ * activation = logistic).  For a box with values q[0 .. 5 + C), anchor b and cell (row, col), every
+ * operation one fp32 operation in this order, never contracted (xs, xb: the scale_x_y pair above):
+ *   cx = ((float)col + (q[0] * xs + xb)) * cell        cy = ((float)row + (q[1] * xs + xb)) * cell
+ *   tw = q[2] * 2.0f;  rw = ((tw * tw) * anchor_w[b]) * cell
+ *   th = q[3] * 2.0f;  rh = ((th * th) * anchor_h[b]) * cell
+ *   conf = q[4];       p[c] = q[5 + c], the value itself
+ * Half widths, the truncated corners and the code -1 are those above.  The arg-max label is the
+ * first index of the largest p[c]; the multi-label score is conf * p[c], one fp32 multiply, a
+ * candidate iff it is > score_thr.  Values are not clamped, and a NaN fails the comparisons or the
+ * corner conversion as these rules imply.  Since p[c] may then exceed 1, Darknet's gate on the
+ * objectness is a condition of its own here: a box has candidates only if conf > score_thr (for
+ * values in [0, 1], the logistic's range, that is implied as above).  class_mode must be 1.
+ *
+ * nms_kind DIoU (Darknet's diounms_sort), for nms_mode PER_CLASS with either label mode: a candidate
+ * is suppressed by an earlier kept candidate of its class when
+ *   iou - (d / c) ** beta_nms > iou_thr
+ * on the integer corners [l, t, r, b] of the two boxes a and b:
+ *   iou    the double quotient of the rule above: inclusive + 1 widths, unclamped intersection, a zero
+ *          denominator giving the image -2;
+ *   d4   = ((al + ar) - (bl + br)) ** 2 + ((at + ab) - (bt + bb)) ** 2, four times the squared centre
+ *          distance, an exact integer;
+ *   c    = W ** 2 + H ** 2 with W = max(ar, br) - min(al, bl) + 1 and H likewise, an exact integer, >= 2
+ *          for boxes with r >= l; c == 0 with d4 != 0 (negative anchors only) gives the image -2 as well;
+ *   ratio = (double)d4 / (4.0 * (double)c), both conversions correctly rounded, one double division;
+ *   the penalty is pow(ratio, beta_nms) in double, and 0 when d4 == 0.
+ * The penalty is never negative, so a pair with iou <= iou_thr is not suppressed and its pow is not
+ * evaluated.  Every kept candidate of the class is evaluated, the order, rows and codes are those
+ * above.  beta_nms must be finite and > 0 (Darknet's default: 0.6).
+ *
+ * Returned -2 before any launch, with dnn_last_error() naming the field: a value of new_coords or
+ * nms_kind other than these, new_coords with class_mode 0, DIoU with DNN_YOLO_NMS_ANY_CLASS (Darknet
+ * has no such rule), DIoU with a beta_nms that is not finite and > 0.  rule is a HOST pointer, read
+ * before the call returns.  Limits, workspaces and every other argument are the _xy entries'. */
+#define DNN_YOLO_NMS_KIND_IOU 0
+#define DNN_YOLO_NMS_KIND_DIOU 1
+
+typedef struct dnn_yolo_rule {
+  int new_coords;  /* 0, or 1: the box rule above */
+  int nms_kind;    /* DNN_YOLO_NMS_KIND_IOU or _DIOU */
+  double beta_nms; /* DIoU's exponent; not read for IoU */
+} dnn_yolo_rule;
+
+int dnn_yolo_postprocess_multi_rule(const dnn_yolo_multi* multi, const float* scale_x_y, const dnn_yolo_rule* rule,
+                                    const float* const* pred, int n_images, dnn_detection* dets, int max_det,
+                                    int* counts, void* workspace, unsigned long long workspace_bytes, int nms_mode,
+                                    int labels_mode, void* stream);
+
+int dnn_yolo_postprocess_multi_rule_host(const dnn_yolo_multi* multi, const float* scale_x_y,
+                                         const dnn_yolo_rule* rule, const float* const* pred, int n_images,
+                                         dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode);
+
+int dnn_yolo_postprocess_wide_rule(const dnn_yolo_multi* multi, const float* scale_x_y, const dnn_yolo_rule* rule,
+                                   const float* const* pred, int n_images, dnn_detection* dets, int max_det,
+                                   int* counts, void* workspace, unsigned long long workspace_bytes, int nms_mode,
+                                   int labels_mode, void* stream);
+
+int dnn_yolo_postprocess_wide_rule_host(const dnn_yolo_multi* multi, const float* scale_x_y,
+                                        const dnn_yolo_rule* rule, const float* const* pred, int n_images,
+                                        dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode);
+
 /* ---- boxes back to each image's own pixels ----------------------------------------------
  * The reference's frames are stretched to the network's size and its boxes stay in network
  * pixels.  After a letterbox ingest (include/dnn_hip_ingest.h: dnn_letterbox_frames) image i of
