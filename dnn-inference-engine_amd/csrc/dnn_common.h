@@ -400,6 +400,14 @@ int launch_conv1_patch_f16(const Switches& sws, const half_t* in, const half_t* 
 int launch_route(const float* a, const float* b, float* out, int n, int H, int W, int Ca, int block, int Cb,
                  int b_first, hipStream_t stream);
 
+// reorg.hip: Darknet's [reorg] of a [n, H, W, Ca] (the non-reverse forward on the flat CHW buffer, restated
+// for NHWC; include/dnn_hip_plan.h has the definition), channel concat with b [n, H/stride, W/stride, Cb]
+// (NULL with Cb == 0) in the same pass: out [n, H/stride, W/stride, stride*stride*Ca + Cb], the b channels
+// first with b_first.  stride in 1..8 (1: plain concat), Ca % stride^2 == 0; 16-byte stores when
+// stride*stride*Ca % 4 == 0 and Cb % 4 == 0; every tensor < 2 GiB
+int launch_reorg(const float* a, const float* b, float* out, int n, int H, int W, int Ca, int stride, int Cb,
+                 int b_first, hipStream_t stream);
+
 // shortcut.hip: out[i] = act(a[i] + b[i]) over `count` floats (act: an act_dev.h code, 0 none, 1 / 2 the
 // conv epilogue's two leaky variants; one fp32 add, bit-equal to a float32 a + b); out may alias neither input.
 int launch_shortcut(const float* a, const float* b, float* out, long long count, int act, hipStream_t stream);

@@ -1,5 +1,5 @@
 // The join / element-wise kernels on host tensors (include/dnn_hip_plan.h: dnn_spp_host,
-// dnn_route_host, dnn_shortcut_host, dnn_scale_shift_host, dnn_upsample_host, dnn_slice_host,
+// dnn_route_host, dnn_reorg_host, dnn_shortcut_host, dnn_scale_shift_host, dnn_upsample_host, dnn_slice_host,
 // dnn_conv_grouped_host, dnn_avgpool_host, dnn_softmax_host, dnn_activate_host).  Host code only:
 // each entry checks its arguments and hands on_device() its inputs and a launch.
 #include <hip/hip_runtime.h>
@@ -95,6 +95,34 @@ int dnn_route_host(const float* a, const float* b, float* out, int n, int h, int
   return on_device("dnn_route_host", {{a, af}, {b, bf}}, of, out, of, [&](float* const* d, const float** res) {
     *res = d[2];
     return launch_route(d[0], bf ? d[1] : nullptr, d[2], n, h, w, ca, block, cb, b_first, nullptr);
+  });
+}
+
+int dnn_reorg_host(const float* a, const float* b, float* out, int n, int h, int w, int ca, int stride, int cb,
+                   int b_first) {
+  DNN_REQUIRE(a && out, "dnn_reorg_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && ca > 0 && cb >= 0, "dnn_reorg_host: bad shape n=%d %dx%dx%d cb=%d", n, h, w,
+              ca, cb);
+  DNN_REQUIRE(stride >= 1 && stride <= 8, "dnn_reorg_host: stride %d outside 1..8", stride);
+  DNN_REQUIRE(h % stride == 0 && w % stride == 0, "dnn_reorg_host: %dx%d input is not a multiple of stride %d", h, w,
+              stride);
+  DNN_REQUIRE(ca % (stride * stride) == 0, "dnn_reorg_host: %d channels are not a multiple of stride^2 = %d", ca,
+              stride * stride);
+  DNN_REQUIRE((b != nullptr) == (cb > 0), "dnn_reorg_host: b must be NULL exactly when cb == 0");
+  if (n == 0) return 0;
+  const size_t pix = (size_t)n * (h / stride) * (w / stride);
+  const size_t af = (size_t)n * h * w * ca, bf = pix * cb, of = pix * ((size_t)stride * stride * ca + cb);
+  DNN_REQUIRE(af * 4 < k2GiB && bf * 4 < k2GiB && of * 4 < k2GiB,
+              "dnn_reorg_host: a tensor of n=%d %dx%dx%d stride %d cb=%d is >= 2 GiB; split the batch", n, h, w, ca,
+              stride, cb);
+  return on_device("dnn_reorg_host", {{a, af}, {b, bf}}, of, out, of, [&](float* const* d, const float** res) {
+    *res = d[2];
+    // every output bit set (a NaN) before the launch: an element the kernel leaves out comes back as NaN
+    if (hipMemset(d[2], 0xFF, of * sizeof(float)) != hipSuccess) {
+      set_error("dnn_reorg_host: hipMemset failed");
+      return -1;
+    }
+    return launch_reorg(d[0], bf ? d[1] : nullptr, d[2], n, h, w, ca, stride, cb, b_first, nullptr);
   });
 }
 

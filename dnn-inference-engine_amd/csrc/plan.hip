@@ -59,6 +59,11 @@
 // current tensor and the tensor itself as channel blocks of one output, in one kernel.  Like the
 // other join entries it reads and writes plain NHWC fp32 and stops the conv / pool peepholes.
 //
+// Reorg: a reorg entry (reorg.hip) is Darknet's [reorg] of the current tensor concatenated with a slot's
+// tensor: the route entry's sibling with Darknet's channel order, one kernel, no table in the plan
+// (the kernel tabulates the permutation in LDS per workgroup, so finalize and dnn_plan_memory do not
+// know it).  Plain NHWC fp32 on both sides; it stops the conv / pool peepholes.
+//
 // Channel slice: a slice entry (slice.hip) copies a channel range of the current tensor (Darknet's
 // [route] with groups / group_id), one kernel, plain NHWC fp32 on both sides like the entries above.
 //
@@ -237,7 +242,7 @@ enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, 
 
 enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
                        LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9,
-                       LAYER_SLICE = 10, LAYER_GCONV = 11, LAYER_AVGPOOL = 12, LAYER_SOFTMAX = 13, LAYER_ACT = 14 };
+                       LAYER_SLICE = 10, LAYER_GCONV = 11, LAYER_AVGPOOL = 12, LAYER_SOFTMAX = 13, LAYER_ACT = 14, LAYER_REORG = 15 };
 
 struct PlanLayer {
   int type = LAYER_CONV;
@@ -264,7 +269,7 @@ struct PlanLayer {
   std::vector<float> w, bias, mean, sq, gamma;
   // fork / join: the slot a stash defines, a restore switches to or a route reads as b (-1: none)
   int slot = -1;
-  int block = 1, Cb = 0;    // route: space-to-depth block, channels of b
+  int block = 1, Cb = 0;    // route: space-to-depth block, channels of b; reorg: its stride, channels of b
   bool slot_first = false;  // route: b's channels come first
   int to_region = -1;       // a writing layer followed by a stash: the slot region it writes
   int slot_loc = LOC_NONE;  // where the slot's tensor lives when this entry is added (slot numbers are reused)
@@ -313,7 +318,8 @@ enum StepKind : int {
   STEP_X3_COMBINE_POOL,  // a pool layer's step that also combines the partials of x3 conv `layer - 1`
   STEP_ROUTE, STEP_SHORTCUT, STEP_UPSAMPLE, STEP_SPP, STEP_SLICE, STEP_GCONV,
   STEP_CVT_OUT,          // fp16 plans: the last activation to the fp32 output
-  STEP_AVGPOOL, STEP_SOFTMAX, STEP_ACT
+  STEP_AVGPOOL, STEP_SOFTMAX, STEP_ACT,
+  STEP_REORG             // Darknet's reorg of the current tensor + the concat with a slot (reorg.hip)
 };
 
 struct Step {
@@ -463,7 +469,7 @@ static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
   place_outputs(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
-  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0, ngconv = 0, navg = 0, nsoft = 0, nact = 0;
+  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0, ngconv = 0, navg = 0, nsoft = 0, nact = 0, nreorg = 0;
   // (kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7)
   p->steps.clear();
   const double B = p->batch;
@@ -548,6 +554,9 @@ static void layout(dnn_plan* p) {
     } else if (L.type == LAYER_ROUTE) {  // reads a and b, writes out: input bytes == output bytes
       snprintf(nm, sizeof(nm), "route%d", nroute++);
       step(i, STEP_ROUTE, 0.0, 2.0 * out_b, cur, out);
+    } else if (L.type == LAYER_REORG) {  // a permutation of a beside b's copy: input bytes == output bytes
+      snprintf(nm, sizeof(nm), "reorg%d", nreorg++);
+      step(i, STEP_REORG, 0.0, 2.0 * out_b, cur, out);
     } else if (L.type == LAYER_SHORTCUT) {  // one add per output element; reads a and b, writes out
       snprintf(nm, sizeof(nm), "shortcut%d", nshort++);
       step(i, STEP_SHORTCUT, out_b / 4.0, 3.0 * out_b, cur, out);
@@ -1338,6 +1347,38 @@ int dnn_plan_add_route(dnn_plan* p, int block, int slot, int slot_first) {
   return 0;
 }
 
+int dnn_plan_add_reorg(dnn_plan* p, int stride, int slot, int slot_first) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_reorg: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_reorg: fp32 plans only (this is an fp16 plan)");
+  DNN_REQUIRE(stride >= 1 && stride <= 8, "dnn_plan_add_reorg: stride %d outside 1..8", stride);
+  DNN_REQUIRE(slot == -1 || slot_is_live(p, slot), "dnn_plan_add_reorg: unknown or released slot %d (%d defined)",
+              slot, (int)p->slots.size());
+  DNN_REQUIRE(p->cur_h % stride == 0 && p->cur_w % stride == 0,
+              "dnn_plan_add_reorg: %dx%d input is not a multiple of stride %d", p->cur_h, p->cur_w, stride);
+  DNN_REQUIRE(p->cur_c % (stride * stride) == 0, "dnn_plan_add_reorg: %d channels are not a multiple of stride^2 = %d",
+              p->cur_c, stride * stride);
+  PlanLayer L;
+  L.type = LAYER_REORG;
+  L.H = p->cur_h;
+  L.W = p->cur_w;
+  L.C = p->cur_c;
+  L.OH = L.H / stride;
+  L.OW = L.W / stride;
+  L.block = stride;
+  L.slot = slot;
+  L.slot_first = slot >= 0 && slot_first != 0;
+  if (slot >= 0) {
+    const PlanSlot& S = p->slots[slot];
+    DNN_REQUIRE(S.h == L.OH && S.w == L.OW, "dnn_plan_add_reorg: slot %d is %dx%d, the reorganised input %dx%d", slot,
+                S.h, S.w, L.OH, L.OW);
+    L.Cb = S.c;
+    L.slot_loc = S.loc;
+  }
+  L.OC = stride * stride * L.C + L.Cb;
+  push_computing(p, std::move(L));
+  return 0;
+}
+
 int dnn_plan_add_shortcut(dnn_plan* p, int slot, int leaky) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_shortcut: plan is NULL or finalized");
   DNN_REQUIRE(!p->fp16, "dnn_plan_add_shortcut: fp32 plans only (this is an fp16 plan)");
@@ -1801,6 +1842,9 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
     case STEP_ROUTE:
       return launch_route(cur, L.slot >= 0 ? locate(p, r, L.slot_loc) : nullptr, dst, n, L.H, L.W, L.C, L.block, L.Cb,
                           L.slot_first ? 1 : 0, s);
+    case STEP_REORG:
+      return launch_reorg(cur, L.slot >= 0 ? locate(p, r, L.slot_loc) : nullptr, dst, n, L.H, L.W, L.C, L.block, L.Cb,
+                          L.slot_first ? 1 : 0, s);
     case STEP_SHORTCUT:
       return launch_shortcut(cur, locate(p, r, L.slot_loc), dst, (long long)n * L.H * L.W * L.C, L.leaky, s);
     case STEP_UPSAMPLE:
@@ -2004,6 +2048,12 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
       if (L.slot >= 0)
         snprintf(sb, sizeof(sb), " slot=%d (%dx%dx%d) %s", L.slot, L.OH, L.OW, L.Cb, L.slot_first ? "first" : "last");
       snprintf(line, sizeof(line), "route %dx%dx%d -> %dx%dx%d block=%d%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.block,
+               sb);
+    } else if (L.type == LAYER_REORG) {
+      char sb[64] = "";
+      if (L.slot >= 0)
+        snprintf(sb, sizeof(sb), " slot=%d (%dx%dx%d) %s", L.slot, L.OH, L.OW, L.Cb, L.slot_first ? "first" : "last");
+      snprintf(line, sizeof(line), "reorg %dx%dx%d -> %dx%dx%d stride=%d%s\n", L.H, L.W, L.C, L.OH, L.OW, L.OC, L.block,
                sb);
     } else if (L.type == LAYER_SHORTCUT) {
       snprintf(line, sizeof(line), "shortcut %dx%dx%d slot=%d act=%s\n", L.H, L.W, L.C, L.slot,

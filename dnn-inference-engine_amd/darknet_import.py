@@ -48,6 +48,17 @@ definitions; "yolov4" is CSPDarknet53 with mish, the SPP + PAN neck with leaky a
 scale_x_y 1.2 / 1.1 / 1.05 and greedy NMS; iou_thresh, max_delta and the loss keys are training matters and
 are ignored like every unknown key; beta_nms is read under nms_kind = diounms only).
 
+YOLOv2: [reorg] (stride, default 1: a dnn_hip.Reorg node, Darknet's permutation of the flat CHW buffer, which
+is not space_to_depth; in the plan one dnn_plan_add_reorg entry together with the two-layer [route] that
+follows it, reorg.hip) and [region] as the last section (region_params: coords = 4, softmax = 1, num = the
+anchor count): the conv before it, filters = num * (5 + classes) and activation = linear, is the plan's
+output and the head a one-scale yolo_post.MultiHead with softmax class scores, per-class NMS, multi-label
+output and the thresholds above; its anchors are `anchors` as they stand, since region anchors are in
+cells, and the cell is input / grid.  cfg_text has "yolov2", "yolov2_voc", "yolov2_tiny" and
+"yolov2_tiny_voc" (416 x 416).  yolov2.py's hand-written model keeps TensorFlow's space_to_depth order, so
+its weights are not Darknet's; an imported yolov2.cfg is.  Parity with a Darknet binary is not pinned by a
+test (none is at hand): the tests pin the reorg definition and a float64 restatement of the forward.
+
 Classifiers: [avgpool] (a dnn_hip.GlobalAvgPool node, dnn_plan_add_avgpool), [softmax] (groups 1,
 temperature 1, no tree, on a 1 x 1 map: a dnn_hip.Softmax node, dnn_plan_add_softmax), [connected]
 (output, activation linear or leaky, optional batch_normalize; only on a 1 x 1 map, where Darknet's
@@ -74,8 +85,8 @@ bytes: nothing in a weight file executes.
 
 Out of scope:
 
-  * YOLOv2's [reorg] and [region]: Darknet's reorg channel order is not the route kernel's
-    (TensorFlow's space_to_depth), so yolov2.py's weights are not Darknet's either;
+  * YOLO9000 and the other [region] forms: softmax_tree, background = 1, classfix, softmax = 0, coords
+    other than 4; [reorg] with reverse = 1, flatten = 1 or extra;
   * activations other than leaky, linear, mish, swish and logistic (relu, elu, tanh);
   * [shortcut] with activation=leaky (Darknet's ResNet / ResNeXt classifiers), [connected] on a map
     larger than 1 x 1, [softmax] with groups, a temperature or a tree;
@@ -102,13 +113,15 @@ import dnn_hip
 import yolo_post
 import yolov3
 
-SECTION_TYPES = ("net", "convolutional", "shortcut", "route", "upsample", "maxpool", "yolo", "avgpool", "softmax",
-                 "connected", "dropout", "cost")
+BASE_SECTION_TYPES = ("net", "convolutional", "shortcut", "route", "upsample", "maxpool", "yolo", "avgpool", "softmax",
+                      "connected", "dropout", "cost")              # what parse_cfg lets through unless told otherwise
+SECTION_TYPES = BASE_SECTION_TYPES + ("reorg", "region")  # ... and with YOLOv2's two sections: DarknetModel's set
 BN_EPS = 1e-6  # normalize_cpu's .000001f, added to sqrt(var)
 BASE_ACTIVATIONS = ("leaky", "linear")                         # what parse_cfg lets through unless told otherwise
 ACTIVATIONS = BASE_ACTIVATIONS + ("mish", "swish", "logistic")  # of [convolutional]; [shortcut]: all but leaky
 SCORE_THR, IOU_THR = 0.5, 0.45  # Darknet's detector defaults (-thresh .5, nms .45)
-MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny", "yolov4-tiny", "yolov4", "darknet19", "darknet53")
+MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny", "yolov4-tiny", "yolov4", "darknet19", "darknet53",
+          "yolov2", "yolov2_voc", "yolov2_tiny", "yolov2_tiny_voc")
 CLASSIFIERS = {"darknet19": 224, "darknet53": 256}  # the classifier definitions and their default input size
 NMS_KINDS = ("default", "greedynms")  # [yolo] nms_kind values that are the decode's greedy NMS
 DIOU_KINDS = ("diounms",)             # ... and those that are its DIoU NMS (yolo_post.MultiHead's nms_kind "diou")
@@ -119,13 +132,16 @@ class DarknetError(ValueError):
 
 
 # ------------------------------------------------------------------------------------- cfg text
-def parse_cfg(text, activations=BASE_ACTIVATIONS):
+def parse_cfg(text, activations=BASE_ACTIVATIONS, section_types=BASE_SECTION_TYPES):
     """The sections of a Darknet cfg, in order: one dict per section with "type" (the name in
     brackets), "line" (its 1-based line number) and every `key = value` of the section as strings
     (keys and values stripped; a key named `type` or `line`, as in [cost]'s `type = sse`, is kept as
     "type_" / "line_").  `#` and `;` start comment lines; blank lines are skipped.  A
-    section type outside SECTION_TYPES raises DarknetError naming the type and the line; unknown
-    keys inside a known section are kept and ignored by the importer.
+    section type outside `section_types` raises DarknetError naming the type and the line; unknown
+    keys inside a known section are kept and ignored by the importer.  Like `activations` below, the
+    default is what every walker of the sections knows: [reorg] and [region] pass only when the caller
+    names them (SECTION_TYPES, as DarknetModel does), since code that walks the sections itself would
+    take a [reorg] it does not know for a layer that changes nothing.
 
     `activations`: the `activation` values a [convolutional] (Darknet's default there: logistic) or a
     [shortcut] (default linear) may have; any other raises DarknetError naming the value and the line.
@@ -142,9 +158,9 @@ def parse_cfg(text, activations=BASE_ACTIVATIONS):
             if line[-1] != "]":
                 raise DarknetError(f"line {no}: malformed section header {line!r}")
             kind = line[1:-1].strip()
-            if kind not in SECTION_TYPES:
+            if kind not in section_types:
                 raise DarknetError(f"line {no}: section type [{kind}] is not supported "
-                                   f"(supported: {', '.join(SECTION_TYPES)})")
+                                   f"(supported: {', '.join(section_types)})")
             sections.append({"type": kind, "line": no})
             continue
         if "=" not in line:
@@ -343,6 +359,57 @@ def yolo_params(sec):
     return s
 
 
+def reorg_params(sec, in_h, in_w, in_c):
+    """stride (default 1) of a [reorg] section on an in_h x in_w x in_c map: the non-reverse forward only.
+    DarknetError naming the key for reverse = 1, flatten = 1 or extra, and for a map the stride does not divide."""
+    where = f"[reorg] at line {sec['line']}"
+    for key in ("reverse", "flatten", "extra"):
+        if _int(sec, key, 0):
+            raise DarknetError(f"{where}: {key} = {sec[key]} is not supported (the plain forward reorg only)")
+    s = _int(sec, "stride", 1)
+    if not 1 <= s <= dnn_hip.MAX_ROUTE_BLOCK:
+        raise DarknetError(f"{where}: stride {s} outside 1..{dnn_hip.MAX_ROUTE_BLOCK}")
+    if in_h % s or in_w % s or in_c % (s * s):
+        raise DarknetError(f"{where}: stride {s} does not divide the {in_h} x {in_w} map, or stride^2 its {in_c} channels")
+    return s
+
+
+def region_params(sec, before=None):
+    """(num, classes, anchors) of a [region] section the one-scale softmax decode computes: coords = 4,
+    softmax = 1, num (default 1) pairs in `anchors`, at most yolo_post.MAX_ANCHORS of them and
+    yolo_post.MAX_CLASSES classes.  softmax_tree, background = 1 and classfix (YOLO9000's forms) raise
+    DarknetError naming the key.  `before`, the section the [region] follows, is checked where given: a
+    [convolutional] with filters = num * (5 + classes) and activation = linear."""
+    where = f"[region] at line {sec['line']}"
+    if "softmax_tree" in sec:
+        raise DarknetError(f"{where}: softmax_tree = {sec['softmax_tree']} (YOLO9000's class tree) is not supported")
+    for key in ("background", "classfix"):
+        if _int(sec, key, 0):
+            raise DarknetError(f"{where}: {key} = {sec[key]} is not supported")
+    if _int(sec, "coords", 4) != 4:
+        raise DarknetError(f"{where}: coords = {sec['coords']} is not supported (only 4)")
+    if _int(sec, "softmax", 0) != 1:
+        raise DarknetError(f"{where}: softmax = {sec.get('softmax', 0)} is not supported (only 1: softmax class scores)")
+    num, classes = _int(sec, "num", 1), _int(sec, "classes", 20)
+    try:
+        anchors = tuple(float(v) for v in sec["anchors"].split(",") if v.strip())
+    except (KeyError, ValueError):
+        raise DarknetError(f"{where}: `anchors` is missing or not a list of numbers")
+    if not 1 <= num <= yolo_post.MAX_ANCHORS or len(anchors) != 2 * num:
+        raise DarknetError(f"{where}: num = {num} with {len(anchors)} anchor values: need num (w, h) pairs, num in "
+                           f"1..{yolo_post.MAX_ANCHORS} (DNN_YOLO_MAX_ANCHORS)")
+    if not 1 <= classes <= yolo_post.MAX_CLASSES:
+        raise DarknetError(f"{where}: classes = {classes}: need 1..{yolo_post.MAX_CLASSES} (DNN_YOLO_MAX_CLASSES)")
+    if before is not None:
+        if before["type"] != "convolutional":
+            raise DarknetError(f"{where}: it must follow a [convolutional] section")
+        if _int(before, "filters") != num * (5 + classes) or before.get("activation", "logistic") != "linear":
+            raise DarknetError(f"{where}: the [convolutional] before it has filters = {before.get('filters')}, activation "
+                               f"= {before.get('activation', 'logistic')}: need filters = num * (5 + classes) = "
+                               f"{num * (5 + classes)} and activation = linear")
+    return num, classes, anchors
+
+
 def connected_params(sec, in_h, in_w):
     """(output, batch_normalize, activation) of a [connected] section on an in_h x in_w map.  Darknet
     flattens its input as CHW and this engine's tensors are NHWC, so only a 1 x 1 map (after an
@@ -421,6 +488,13 @@ def layer_shapes(sections, in_shape=None):
                 raise DarknetError(f"[yolo] at line {sec['line']}: it must follow a [convolutional] section")
             yolo_params(sec)
             yolo_rule(sec, sections[at])
+        elif kind == "reorg":
+            s = reorg_params(sec, h, w, c)
+            h, w, c = h // s, w // s, c * s * s
+        elif kind == "region":
+            if at + 2 != len(sections):
+                raise DarknetError(f"[region] at line {sec['line']}: it must be the last section of the cfg")
+            region_params(sec, sections[at] if at else {"type": "net"})
         elif kind == "avgpool":
             h, w = 1, 1
         elif kind == "softmax":
@@ -663,6 +737,9 @@ def build_graph(builder_cls, sections, layers, in_shape):
                 cur = _LazyPool(prev, size)
             else:
                 cur = g.create_max_pool2d(node(prev), [1, size, size, 1], [1, stride, stride, 1], "SAME")
+        elif kind == "reorg":
+            h, w, c = shapes[at - 1] if at else net_shape(sections, in_shape)
+            cur = g.create_reorg(node(prev), reorg_params(sec, h, w, c))
         elif kind == "avgpool":
             cur = g.create_global_avg_pool(node(prev))
         elif kind == "softmax":
@@ -676,7 +753,7 @@ def build_graph(builder_cls, sections, layers, in_shape):
             cur = g.create_leaky_relu_f32(t) if act == "leaky" else t
         elif kind in ("dropout", "cost"):  # a layer for [route] / [shortcut] indices, nothing at inference
             cur = prev
-        else:  # yolo: the conv before it is an output; the layer itself repeats that tensor
+        else:  # yolo / region: the conv before it is an output; the layer itself repeats that tensor
             outs.append(node(prev))
             yolos.append(dict(sec, grid=shapes[at][:2]))
             cur = prev
@@ -714,12 +791,16 @@ def multi_head(yolos, in_h, in_w, score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per
     a yolo_post.WideHead (up to 65,536 boxes, the grid-wide decode), whatever the box count."""
     scales, xy = [], []
     for y in yolos:
-        xy.append(yolo_params(y))
         gh, gw = y["grid"]
         if in_h % gh or in_w % gw or in_h // gh != in_w // gw:
-            raise DarknetError(f"[yolo] at line {y['line']}: a {gh} x {gw} grid does not divide the {in_h} x {in_w} "
+            raise DarknetError(f"[{y['type']}] at line {y['line']}: a {gh} x {gw} grid does not divide the {in_h} x {in_w} "
                                "input into square cells")
         stride = in_h // gh
+        if y["type"] == "region":  # its anchors are in cells already, the unit of the decode
+            num, classes, anchors = region_params(y)
+            scales.append(yolo_post.Scale(gh, gw, num, classes, anchors, float(stride), score_thr, iou_thr))
+            continue
+        xy.append(yolo_params(y))
         try:
             anchors = [float(v) for v in y["anchors"].split(",") if v.strip()]
         except (KeyError, ValueError):
@@ -730,6 +811,8 @@ def multi_head(yolos, in_h, in_w, score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per
         px = [a for m in mask for a in anchors[2 * m:2 * m + 2]]
         scales.append(yolo_post.Scale(gh, gw, len(mask), _int(y, "classes", 20), tuple(a / stride for a in px),
                                       float(stride), score_thr, iou_thr))
+    if [y["type"] for y in yolos] == ["region"]:
+        return (yolo_post.WideHead if wide else yolo_post.MultiHead)(scales, "softmax", nms, labels)
     kw = {} if all(s == 1.0 for s in xy) else {"scale_x_y": tuple(xy)}
     rules = [yolo_rule(y) for y in yolos]
     for y, r in zip(yolos, rules):  # one decode and one NMS serve every scale (beta_nms matters under DIoU only)
@@ -758,7 +841,7 @@ class DarknetModel(yolov3.YOLO_V3):
 
     def __init__(self, cfg_text, weights, in_shape=None, debug=False, device=None, head=_AUTO, latency=None,
                  score_thr=SCORE_THR, iou_thr=IOU_THR, nms="per_class", labels="multi", wide=False):
-        self.sections = parse_cfg(cfg_text, ACTIVATIONS)
+        self.sections = parse_cfg(cfg_text, ACTIVATIONS, SECTION_TYPES)
         h, w, c = net_shape(self.sections, in_shape)
         self.in_shape = (int(in_shape[0]) if in_shape is not None else 1, h, w, c)
         self.layers = load_weights(weights, self.sections) if isinstance(weights, (str, bytes)) or hasattr(
@@ -776,7 +859,8 @@ class DarknetModel(yolov3.YOLO_V3):
             except DarknetError:
                 raise
             except ValueError as e:
-                boxes = sum(y["grid"][0] * y["grid"][1] * (len(_ints(y, "mask")) if "mask" in y else 1)
+                boxes = sum(y["grid"][0] * y["grid"][1] * (_int(y, "num", 1) if y["type"] == "region" else
+                                                           len(_ints(y, "mask")) if "mask" in y else 1)
                             for y in self.yolos)
                 if boxes <= yolo_post.MULTI_MAX_BOXES:
                     raise
@@ -950,10 +1034,20 @@ class _Cfg(object):
                         ("nms_kind", "diounms" if scaled else "greedynms"), ("beta_nms", "0.6"),
                         *((("new_coords", 1),) if scaled else ()))
 
+    def region(self, anchors, classes):
+        return self.add("region", ("anchors", anchors), ("bias_match", 1), ("classes", classes), ("coords", 4),
+                        ("num", len(anchors.split(",")) // 2), ("softmax", 1), ("jitter", ".3"), ("rescore", 1),
+                        ("object_scale", 5), ("noobject_scale", 1), ("class_scale", 1), ("coord_scale", 1),
+                        ("absolute", 1), ("thresh", " .6"), ("random", 1))
+
     def text(self):
         return "\n".join(self.lines)
 
 
+# [region] anchors, in cells of the 13 x 13 grid: yolov2.cfg and yolov2-tiny.cfg (COCO), yolov2-voc.cfg, yolov2-tiny-voc.cfg
+_V2_COCO_ANCHORS = "0.57273, 0.677385, 1.87446, 2.06253, 3.33843, 5.47434, 7.88282, 3.52778, 9.77052, 9.16828"
+_V2_VOC_ANCHORS = "1.3221, 1.73145, 3.19275, 4.00944, 5.05587, 8.09892, 9.47112, 4.84053, 11.2364, 10.0071"
+_V2_TINY_VOC_ANCHORS = "1.08,1.19,  3.42,4.41,  6.63,11.38,  9.42,5.11,  16.62,10.52"
 _V4_ANCHORS = "12, 16, 19, 36, 40, 28, 36, 75, 76, 55, 72, 146, 142, 110, 192, 243, 459, 401"
 
 
@@ -1021,7 +1115,7 @@ def cfg_text(model, classes=None, width=None, height=None, width_div=1, scaled_h
     """The public definition of `model` (one of MODELS) as cfg text, for `classes` classes and a
     width x height input; width_div divides every channel count except the heads' 3 x (5 + classes)
     or the classifier conv's `classes` (a narrow model of the same topology).  Defaults: 80 classes
-    at 416 x 416 for the detectors ("yolov4" has no default size: ValueError without width and height); 1000 classes for the classifiers "darknet19" (224 x 224) and
+    at 416 x 416 for the detectors (20 for "yolov2_voc" and "yolov2_tiny_voc", whose heads are 5 x (5 + classes)) ("yolov4" has no default size: ValueError without width and height); 1000 classes for the classifiers "darknet19" (224 x 224) and
     "darknet53" (256 x 256), which end in [avgpool] and [softmax].
     scaled_head ("yolov4" only): YOLOv4's topology with the head of the scaled-YOLOv4 cfgs: the head convs
     are activation=logistic and each [yolo] carries new_coords=1, scale_x_y=2.0, nms_kind=diounms and
@@ -1036,10 +1130,40 @@ def cfg_text(model, classes=None, width=None, height=None, width_div=1, scaled_h
         # without a head unless wide=True), and 416 x 416, the other detectors' default here, is not its definition
         raise ValueError('cfg_text("yolov4") takes no default size: pass width and height (608 x 608 in the public cfg)')
     size = CLASSIFIERS.get(model, 416)
-    classes = (1000 if model in CLASSIFIERS else 80) if classes is None else int(classes)
+    voc = model in ("yolov2_voc", "yolov2_tiny_voc")
+    classes = (1000 if model in CLASSIFIERS else 20 if voc else 80) if classes is None else int(classes)
     width, height = size if width is None else width, size if height is None else height
     n_out = 3 * (5 + classes)
     c = _Cfg(width, height, int(width_div))
+    if model in ("yolov2_tiny", "yolov2_tiny_voc"):  # six conv + pool stages (the last pool stride 1), two 3x3 convs
+        for k, f in enumerate((16, 32, 64, 128, 256, 512)):
+            c.conv(f, 3)
+            c.add("maxpool", ("size", 2), ("stride", 2 if k < 5 else 1))
+        c.conv(1024, 3)
+        c.lines.append("###########")
+        c.conv(1024 if voc else 512, 3)
+        c.conv(5 * (5 + classes), 1, head=True)
+        c.region(_V2_TINY_VOC_ANCHORS if voc else _V2_COCO_ANCHORS, classes)
+        return c.text()
+    if model in ("yolov2", "yolov2_voc"):  # Darknet-19's trunk, two 3x3 convs, the passthrough of layer 16
+        for stage, f in enumerate((32, 64, 128, 256, 512, 1024)):
+            for j in range(1 if stage < 2 else 3 if stage < 4 else 5):  # 3x3 f, 1x1 f / 2, 3x3 f, ...
+                at = c.conv(f // 2 if j % 2 else f, 1 if j % 2 else 3)
+            if stage == 4:
+                fine = at  # the 26 x 26 x 512 map (at 416 x 416)
+            if stage < 5:
+                c.add("maxpool", ("size", 2), ("stride", 2))
+        c.lines.append("#######")
+        c.conv(1024, 3)
+        trunk = c.conv(1024, 3)
+        c.add("route", ("layers", fine - c.n))
+        c.conv(64, 1)
+        c.add("reorg", ("stride", 2))
+        c.add("route", ("layers", f"-1,{trunk - c.n}"))
+        c.conv(1024, 3)
+        c.conv(5 * (5 + classes), 1, head=True)
+        c.region(_V2_VOC_ANCHORS if voc else _V2_COCO_ANCHORS, classes)
+        return c.text()
     if model == "darknet19":
         for stage, f in enumerate((32, 64, 128, 256, 512, 1024)):
             for j in range(1 if stage < 2 else 3 if stage < 4 else 5):  # 3x3 f, 1x1 f / 2, 3x3 f, ...

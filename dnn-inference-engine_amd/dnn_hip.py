@@ -16,7 +16,8 @@ one im2col + fp32-MFMA GEMM with the element-wise ops in its epilogue, every Max
 one pool kernel; weights are uploaded once and activations stay in HBM.  Two node kinds the
 reference lacks, `SpaceToDepth` and `Concat` (`create_space_to_depth`, `create_concat`), express
 YOLOv2's passthrough: a fork joined by a Concat lowers to stash / restore / route plan entries
-(the route kernel does the fold and the concat in one pass).  Two more, `Add` and `Upsample`
+(the route kernel does the fold and the concat in one pass); `Reorg` (`create_reorg`) is the same
+passthrough in Darknet's channel order, one reorg entry with its Concat (reorg.hip).  Two more, `Add` and `Upsample`
 (`create_add`, `create_upsample`), express the residual block y = x + f(x) and the top-down
 merge: a fork joined by an Add lowers to stash / shortcut / release entries (a release hands the
 slot and its workspace region back, so any number of blocks fit in one plan).  A graph may have
@@ -81,6 +82,8 @@ def _bind_plan_api(lib):
         "dnn_plan_add_restore": (i, [vp, i]),
         "dnn_plan_add_route": (i, [vp, i, i, i]),
         "dnn_route_host": (i, [vp, vp, vp, i, i, i, i, i, i, i]),
+        "dnn_plan_add_reorg": (i, [vp, i, i, i]),
+        "dnn_reorg_host": (i, [vp, vp, vp, i, i, i, i, i, i, i]),
         "dnn_plan_add_shortcut": (i, [vp, i, i]),
         "dnn_plan_add_upsample": (i, [vp, i]),
         "dnn_plan_add_release": (i, [vp, i]),
@@ -309,7 +312,7 @@ class DnnGraphBuilder(object):
         self.name_num = {"conv2d": 0, "bias_add": 0, "max_pool2d": 0, "batch_norm": 0, "leaky_relu": 0,
                          "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0, "spp": 0,
                          "channel_slice": 0, "global_avg_pool": 0, "softmax": 0,
-                         "conv2d_padded": 0, "scale_shift": 0, "leaky_relu_f32": 0, "activation": 0}
+                         "conv2d_padded": 0, "scale_shift": 0, "leaky_relu_f32": 0, "activation": 0, "reorg": 0}
         self.in_node = None
         self.out_node = None
         self.extra_out_nodes = []
@@ -369,6 +372,11 @@ class DnnGraphBuilder(object):
 
     def create_space_to_depth(self, in_node, block):
         out_node = SpaceToDepth(self.get_name("space_to_depth"), in_node, block)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_reorg(self, in_node, stride):
+        out_node = Reorg(self.get_name("reorg"), in_node, stride)
         self.G.add_edge(in_node, out_node)
         return out_node
 
@@ -715,6 +723,46 @@ class SpaceToDepth(DnnNode):
         _route_host(self.name, self.in_node.result, None, self.result, self.block)
 
 
+def reorg_numpy(a, stride):
+    """Darknet's [reorg] (the non-reverse forward) of an NHWC array [n, h, w, c] -> [n, h/stride, w/stride,
+    stride*stride*c], by its definition on the flat CHW buffers of an image (include/dnn_hip_plan.h,
+    dnn_plan_add_reorg): out_flat[i + w (j + h k)] = in_flat[w2 + w s (h2 + h s c2)] with c2 = k mod out_c,
+    off = k div out_c, w2 = i s + off mod s, h2 = j s + off div s, out_c = c / s^2."""
+    a = np.asarray(a)
+    n, h, w, c = a.shape
+    s = int(stride)
+    out_c = c // (s * s)
+    o = np.arange(c * h * w)
+    i, j, k = o % w, (o // w) % h, o // (w * h)
+    c2, off = k % out_c, k // out_c
+    f = (i * s + off % s) + w * s * ((j * s + off // s) + h * s * c2)
+    in_flat = a.transpose(0, 3, 1, 2).reshape(n, c * h * w)
+    out_flat = np.empty_like(in_flat)
+    out_flat[:, o] = in_flat[:, f]
+    return np.ascontiguousarray(out_flat.reshape(n, c * s * s, h // s, w // s).transpose(0, 2, 3, 1))
+
+
+class Reorg(DnnNode):
+    """Not in the reference (YOLOv2's Darknet weights need it): Darknet's [reorg] layer, [n, H, W, C] ->
+    [n, H/stride, W/stride, stride*stride*C] in Darknet's channel order (reorg_numpy; not SpaceToDepth's).
+    In a plan it is a dnn_plan_add_reorg entry (reorg.hip), fused with the Concat it feeds; run(), the
+    node-by-node path, is the numpy restatement of the definition."""
+
+    def __init__(self, name, in_node, stride):
+        if len(in_node.result.shape) != 4 or int(stride) != stride or not 1 <= stride <= MAX_ROUTE_BLOCK:
+            raise ValueError
+        batch, h, w, c = in_node.result.shape
+        if h % stride or w % stride or c % (stride * stride):
+            raise ValueError
+        self.in_node = in_node
+        self.stride = int(stride)
+        self.result = np.zeros((batch, h // self.stride, w // self.stride, self.stride * self.stride * c), dtype='float32')
+        self.name = name
+
+    def run(self):
+        self.result[...] = reorg_numpy(self.in_node.result, self.stride)
+
+
 class Concat(DnnNode):
     """Not in the reference: channel concat of exactly two NHWC tensors of the same batch and
     spatial size, in the order given.  run() -> dnn_route_host with block 1."""
@@ -985,6 +1033,15 @@ class RouteEntry(object):
         self.nodes = list(nodes)
 
 
+class ReorgEntry(object):
+    """dnn_plan_add_reorg: Darknet's reorg(current, stride) concatenated with slot `slot`'s tensor
+    (-1: none), the slot's channels first with slot_first."""
+
+    def __init__(self, stride, slot=-1, slot_first=False, nodes=()):
+        self.stride, self.slot, self.slot_first = int(stride), int(slot), bool(slot_first)
+        self.nodes = list(nodes)
+
+
 class ShortcutEntry(object):
     """dnn_plan_add_shortcut: current = act(current + slot `slot`'s tensor); `leaky` when a
     LeakyReLU directly after the Add is folded in."""
@@ -1126,6 +1183,8 @@ def _lower_one(g, nxt):
         return PoolEntry(nxt), nxt
     if isinstance(nxt, SpaceToDepth):
         return RouteEntry(nxt.block, nodes=[nxt]), nxt
+    if isinstance(nxt, Reorg):
+        return ReorgEntry(nxt.stride, nodes=[nxt]), nxt
     if isinstance(nxt, Upsample):
         return UpsampleEntry(nxt.factor, nodes=[nxt]), nxt
     if isinstance(nxt, ChannelSlice):
@@ -1190,8 +1249,8 @@ def _lower_fork(g, x, heads, live, nested=False):
     if isinstance(join, Add):
         return _emit_add_block(g, join, lowered, live)
 
-    def ends_in_s2d(es):
-        return bool(es) and isinstance(es[-1], RouteEntry) and es[-1].slot < 0
+    def ends_in_s2d(es):  # a SpaceToDepth or a Reorg of its own: it fuses into the join
+        return bool(es) and isinstance(es[-1], (RouteEntry, ReorgEntry)) and es[-1].slot < 0
 
     # the branch lowered last is the route's `a` (the other one waits in a slot): the non-empty
     # one, then the one that ends in a SpaceToDepth (it fuses into the route), then the second
@@ -1214,10 +1273,14 @@ def _lower_fork(g, x, heads, live, nested=False):
         return None
     tail = list(lowered[last])
     block, nodes = 1, [join]
-    if ends_in_s2d(tail):
-        s2d = tail.pop()
-        block, nodes = s2d.block, s2d.nodes + [join]
-    entries += tail + [RouteEntry(block, b_slot, slot_first=(first == 0), nodes=nodes)]
+    if ends_in_s2d(tail) and isinstance(tail[-1], ReorgEntry):
+        reorg = tail.pop()
+        entries += tail + [ReorgEntry(reorg.stride, b_slot, slot_first=(first == 0), nodes=reorg.nodes + [join])]
+    else:
+        if ends_in_s2d(tail):
+            s2d = tail.pop()
+            block, nodes = s2d.block, s2d.nodes + [join]
+        entries += tail + [RouteEntry(block, b_slot, slot_first=(first == 0), nodes=nodes)]
     if nested:  # the route has read both, and nothing later names them
         return entries + [ReleaseEntry(s) for s in sorted(used)], join, live
     return entries, join, live | used
@@ -1266,7 +1329,7 @@ def _output_branch(g, head):
 def lower_graph(g):
     """Lower a builder graph to fused plan entries, or None if the plan cannot express it (then
     the node-by-node path runs).  Expressible: a chain of Conv2D (with its BiasAdd / BatchNorm /
-    LeakyReLU), MaxPool2D, SpaceToDepth, Upsample, ChannelSlice, Spp, GlobalAvgPool, Softmax and Activation, and forks of two such chains (either may be
+    LeakyReLU), MaxPool2D, SpaceToDepth, Reorg, Upsample, ChannelSlice, Spp, GlobalAvgPool, Softmax and Activation, and forks of two such chains (either may be
     empty) joined by one Concat or one Add (with a LeakyReLU directly after it), any number of
     them in sequence within the plan's slots (an Add block gives its slots back, and so does a
     Concat fork lowered inside a pending long skip); forks nested in a fork's branch are not.
@@ -1457,7 +1520,7 @@ def _pad_code(padding):
 
 
 def _add_structural(lib, h, e, leaky_variant=1):
-    """Emit a StashEntry / RestoreEntry / RouteEntry / ShortcutEntry / ReleaseEntry /
+    """Emit a StashEntry / RestoreEntry / RouteEntry / ReorgEntry / ShortcutEntry / ReleaseEntry /
     UpsampleEntry / SppEntry / SliceEntry / AvgPoolEntry / SoftmaxEntry / ActivationEntry / TapEntry; False if `e` is none of them."""
     if isinstance(e, StashEntry):
         slot = ctypes.c_int(-1)
@@ -1468,6 +1531,8 @@ def _add_structural(lib, h, e, leaky_variant=1):
         _check(lib.dnn_plan_add_restore(h, e.slot), "dnn_plan_add_restore", lib)
     elif isinstance(e, RouteEntry):
         _check(lib.dnn_plan_add_route(h, e.block, e.slot, 1 if e.slot_first else 0), "dnn_plan_add_route", lib)
+    elif isinstance(e, ReorgEntry):
+        _check(lib.dnn_plan_add_reorg(h, e.stride, e.slot, 1 if e.slot_first else 0), "dnn_plan_add_reorg", lib)
     elif isinstance(e, ShortcutEntry):
         _check(lib.dnn_plan_add_shortcut(h, e.slot, leaky_variant if e.leaky else 0), "dnn_plan_add_shortcut", lib)
     elif isinstance(e, ReleaseEntry):

@@ -128,6 +128,35 @@ int dnn_plan_add_route(dnn_plan* plan, int block, int slot, int slot_first);
 int dnn_route_host(const float* a, const float* b, float* out, int n, int h, int w, int ca, int block, int cb,
                    int b_first);
 
+/* Darknet's [reorg] (fp32 plans, batch and latency mode; on an fp16 plan it fails): the route
+ * entry's sibling with Darknet's channel order, which YOLOv2's Darknet weights are trained on.
+ *
+ * dnn_plan_add_reorg: current = [ reorg(current [H, W, C], stride) , slot's tensor ] on channels
+ *   (the slot's channels first if slot_first; slot == -1: no concat; stride == 1: plain concat).
+ *   reorg is the non-reverse forward of Darknet's reorg layer, defined on one image's flat CHW
+ *   buffers with c = C, h = H, w = W, s = stride, out_c = c / s^2: for every k < c, j < h, i < w
+ *     o  = i + w (j + h k)                       flat index into the OUTPUT buffer
+ *     c2 = k mod out_c ;  off = k div out_c
+ *     w2 = i s + off mod s ;  h2 = j s + off div s
+ *     f  = w2 + w s (h2 + h s c2)                flat index into the INPUT buffer
+ *     out_flat[o] = in_flat[f]
+ *   with in_flat read as [c][h][w] and out_flat as [c s^2][h/s][w/s]: a bijection on c h w
+ *   elements, the same for every image, and not space_to_depth.  The plan's tensors are NHWC: the
+ *   source offset is (yi w + xi) c + ci where f = (ci h + yi) w + xi, the destination offset
+ *   (yo (w/s) + xo)(c s^2) + co where o = (co (h/s) + yo)(w/s) + xo.
+ *   stride in 1..8, H % stride == 0, W % stride == 0, C % stride^2 == 0; the slot checks are
+ *   dnn_plan_add_route's (live, of spatial size H/stride x W/stride).  Output H/stride x W/stride x
+ *   (stride^2 C + Cb).  One kernel ("reorg%d" in dnn_plan_kernel_info, 0 flops, two output tensors
+ *   of bytes); dnn_plan_describe prints "reorg HxWxC -> HxWxC stride=s[ slot=k (HxWxC) first|last]".
+ *   Pure data movement: the result is the definition's, bit for bit.
+ * dnn_reorg_host: the kernel on host tensors (H2D copies, launch, D2H copy, synchronise): a
+ *   [n, h, w, ca], b [n, h/stride, w/stride, cb] (NULL with cb == 0), out [n, h/stride, w/stride,
+ *   stride^2 ca + cb], b_first = slot_first.  The device output is filled with NaN before the
+ *   launch, so an element the kernel did not write comes back as NaN.  Each tensor below 2 GiB. */
+int dnn_plan_add_reorg(dnn_plan* plan, int stride, int slot, int slot_first);
+int dnn_reorg_host(const float* a, const float* b, float* out, int n, int h, int w, int ca, int stride, int cb,
+                   int b_first);
+
 /* Residual and top-down entries (fp32 plans, batch and latency mode; on an fp16 plan each of the
  * three fails).  The reference has no such nodes: they extend its chain to the residual block
  * y = x + f(x) of Darknet-53 and to the upsample + concat merge of detection necks.
