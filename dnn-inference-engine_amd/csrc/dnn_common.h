@@ -458,6 +458,23 @@ int launch_softmax(const float* in, float* out, int n, int classes, hipStream_t 
 int launch_topk(const float* scores, int n, int classes, int k, int* out_index, float* out_score, int* status,
                 hipStream_t stream);
 
+// squeeze_excite.hip: the squeeze-and-excitation gate, y = x * act2(W2^T act1(W1^T mean(x) + b1) + b2) per image, x and
+// y [n, H, W, C] (y == x is allowed), in two launches.  `packed` is se_pack()'s block of se_weight_floats(C, Cr)
+// floats ([W1 transposed [Cr][C] | W2 [Cr][C] | b1 | b2], from W1 [C][Cr], W2 [Cr][C]; a NULL bias packs zeros);
+// `partial` is scratch of n * se_partial_floats(H, W, C) floats (the squeeze's per-range sums; the ranges depend on
+// H * W and C alone).  act1 / act2: act_dev.h codes 0, 2, 3, 4, 5.  C <= DNN_SE_MAX_C, 1 <= Cr <= DNN_SE_MAX_CR,
+// every tensor < 2 GiB; 16-byte accesses when C % 4 == 0 and the three tensors are 16-byte aligned
+int se_range_pixels(int HW, int C);
+int se_ranges(int HW, int C);
+size_t se_partial_floats(int H, int W, int C);
+size_t se_weight_floats(int C, int Cr);
+void se_pack(const float* w1, const float* b1, const float* w2, const float* b2, int C, int Cr, float* packed);
+// `phases`: SE_SQUEEZE (x -> partial), SE_EXCITE (x, partial -> y) or both, each one kernel; a plan launches them as
+// two steps with the same arguments
+enum SePhase : int { SE_SQUEEZE = 1, SE_EXCITE = 2 };
+int launch_squeeze_excite(const float* x, float* y, float* partial, const float* packed, int n, int H, int W, int C,
+                          int Cr, int act1, int act2, int phases, hipStream_t stream);
+
 // element-wise ops of the per-op ABI
 int launch_bias_add(const float* in, const float* b, float* out, long long n, int C, hipStream_t s);
 int launch_bn_mvg(const float* in, const float* mean, const float* sq, const float* gamma, float* out,

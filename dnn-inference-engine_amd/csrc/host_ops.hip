@@ -1,6 +1,6 @@
 // The join / element-wise kernels on host tensors (include/dnn_hip_plan.h: dnn_spp_host,
 // dnn_route_host, dnn_reorg_host, dnn_shortcut_host, dnn_scale_shift_host, dnn_upsample_host, dnn_slice_host,
-// dnn_conv_grouped_host, dnn_avgpool_host, dnn_softmax_host, dnn_activate_host).  Host code only:
+// dnn_conv_grouped_host, dnn_avgpool_host, dnn_softmax_host, dnn_activate_host, dnn_squeeze_excite_host).  Host code only:
 // each entry checks its arguments and hands on_device() its inputs and a launch.
 #include <hip/hip_runtime.h>
 #include <initializer_list>
@@ -237,6 +237,25 @@ int dnn_activate_host(const float* a, float* out, long long n, int act) {
     *res = d[1];
     return launch_activate(d[0], d[1], n, act, nullptr);
   });
+}
+
+int dnn_squeeze_excite_host(const float* x, const float* w1, const float* b1, int act1, const float* w2, const float* b2,
+                            int act2, float* out, int n, int h, int w, int c, int cr) {
+  DNN_REQUIRE(x && w1 && w2 && out, "dnn_squeeze_excite_host: NULL tensor");
+  DNN_REQUIRE(n >= 0 && h > 0 && w > 0 && c > 0, "dnn_squeeze_excite_host: bad shape n=%d %dx%dx%d", n, h, w, c);
+  if (int rc = se_args_ok("dnn_squeeze_excite_host", c, cr, act1, act2)) return rc;
+  if (n == 0) return 0;
+  const size_t f = (size_t)n * h * w * c;
+  DNN_REQUIRE(f * 4 < k2GiB, "dnn_squeeze_excite_host: a tensor of n=%d %dx%dx%d is >= 2 GiB; split the batch", n, h, w, c);
+  std::vector<float> packed(se_weight_floats(c, cr));
+  se_pack(w1, b1, w2, b2, c, cr, packed.data());
+  const size_t part = align_up((size_t)n * se_partial_floats(h, w, c), 64);  // behind the output, in the scratch
+  return on_device("dnn_squeeze_excite_host", {{x, f}, {packed.data(), packed.size()}}, align_up(f, 64) + part, out, f,
+                   [&](float* const* d, const float** res) {
+                     *res = d[2];
+                     return launch_squeeze_excite(d[0], d[2], d[2] + align_up(f, 64), d[1], n, h, w, c, cr, act1, act2,
+                                                  SE_SQUEEZE | SE_EXCITE, nullptr);
+                   });
 }
 
 int dnn_conv_grouped_host(const float* x, const float* kernel, const float* scale, const float* shift, float* out, int n,

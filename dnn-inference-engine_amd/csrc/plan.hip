@@ -80,6 +80,10 @@
 // nothing.  Anywhere else it is a layer with one kernel (activate.hip).  Mish and swish are not monotone,
 // so a conv that carries one never fuses a max pool: every pool-fused epilogue pools the raw sums first
 // (nonmonotone() guards dnn_plan_add_max_pool's peepholes and the x3 combine that pools).
+//
+// Squeeze-and-excitation: an se entry (squeeze_excite.hip) multiplies the current tensor by a per-image, per-channel
+// gate made from its own global average and two small matrices; two kernels, its weights in the weight arena
+// and the squeeze's partial sums in the split-K slab (no slot); plain NHWC fp32 on both sides.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <climits>
@@ -242,7 +246,7 @@ enum TensorLoc : int { LOC_NONE = -2, LOC_OUT = -1, LOC_ACT0 = 0, LOC_ACT1 = 1, 
 
 enum LayerType : int { LAYER_CONV = 0, LAYER_POOL = 1, LAYER_STASH = 2, LAYER_RESTORE = 3, LAYER_ROUTE = 4,
                        LAYER_SHORTCUT = 5, LAYER_UPSAMPLE = 6, LAYER_RELEASE = 7, LAYER_TAP = 8, LAYER_SPP = 9,
-                       LAYER_SLICE = 10, LAYER_GCONV = 11, LAYER_AVGPOOL = 12, LAYER_SOFTMAX = 13, LAYER_ACT = 14, LAYER_REORG = 15 };
+                       LAYER_SLICE = 10, LAYER_GCONV = 11, LAYER_AVGPOOL = 12, LAYER_SOFTMAX = 13, LAYER_ACT = 14, LAYER_REORG = 15, LAYER_SE = 16 };
 
 struct PlanLayer {
   int type = LAYER_CONV;
@@ -280,9 +284,10 @@ struct PlanLayer {
                             // variants, 3..5 a fused activation entry); an activation layer: its code
   int n_sizes = 0, sizes[DNN_SPP_MAX_SIZES] = {0, 0, 0};  // spp: the pools' window sizes, in block order
   bool x_first = false;     // spp: the input's copy is the first channel block
+  int se_cr = 0, se_act1 = 0, se_act2 = 0;  // se: the squeezed width and the two activations (act_dev.h codes)
   int dst_loc = 0;          // where this layer writes when its output is plain NHWC (LOC_*; layout())
   bool is_conv() const { return type == LAYER_CONV; }
-  bool has_weights() const { return type == LAYER_CONV || type == LAYER_GCONV; }
+  bool has_weights() const { return type == LAYER_CONV || type == LAYER_GCONV || type == LAYER_SE; }
   bool is(int v) const { return type == LAYER_CONV && variant == v; }
   int out_h() const { return pool == POOL_S2 ? PH : OH; }
   int out_w() const { return pool == POOL_S2 ? PW : OW; }
@@ -319,7 +324,9 @@ enum StepKind : int {
   STEP_ROUTE, STEP_SHORTCUT, STEP_UPSAMPLE, STEP_SPP, STEP_SLICE, STEP_GCONV,
   STEP_CVT_OUT,          // fp16 plans: the last activation to the fp32 output
   STEP_AVGPOOL, STEP_SOFTMAX, STEP_ACT,
-  STEP_REORG             // Darknet's reorg of the current tensor + the concat with a slot (reorg.hip)
+  STEP_REORG,            // Darknet's reorg of the current tensor + the concat with a slot (reorg.hip)
+  STEP_SE_SQUEEZE,       // an se entry's per-range channel sums into the slab
+  STEP_SE_EXCITE         // ... its gate from those sums and the multiply -> dst (squeeze_excite.hip)
 };
 
 struct Step {
@@ -469,7 +476,7 @@ static void layout(dnn_plan* p) {
   p->direct_out = fp16_direct_out(p);
   place_outputs(p);
   size_t off = 0, act = (size_t)p->in_h * p->in_w * p->in_c, col = 0, slab = 0, slab_fused = 0, tickets = 0;
-  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0, ngconv = 0, navg = 0, nsoft = 0, nact = 0, nreorg = 0;
+  int nconv = 0, npool = 0, nroute = 0, nshort = 0, nup = 0, nspp = 0, nslice = 0, ngconv = 0, navg = 0, nsoft = 0, nact = 0, nreorg = 0, nse = 0;
   // (kernel names use conv / pool ordinals: "conv7.gemm" is YOLO's conv7)
   p->steps.clear();
   const double B = p->batch;
@@ -585,6 +592,16 @@ static void layout(dnn_plan* p) {
     } else if (L.type == LAYER_ACT) {  // per element an expf, a division and up to four more operations
       snprintf(nm, sizeof(nm), "activate%d", nact++);
       step(i, STEP_ACT, 6.0 * out_b / 4.0, in_b + out_b, cur, out);
+    } else if (L.type == LAYER_SE) {  // [W1t | W2 | b1 | b2]; the partial sums share the slab with the split-K layers
+      L.w_off = L.epi_off = off;
+      off = align_up(off + se_weight_floats(L.C, L.se_cr), 64);
+      const size_t part = se_partial_floats(L.H, L.W, L.C);
+      slab = std::max(slab, part);
+      const double part_b = 4.0 * B * part, gate_f = 4.0 * B * L.C * L.se_cr;
+      snprintf(nm, sizeof(nm), "se%d.squeeze", nse);
+      step(i, STEP_SE_SQUEEZE, in_b / 4.0, in_b + part_b, cur, LOC_NONE);
+      snprintf(nm, sizeof(nm), "se%d.excite", nse++);
+      step(i, STEP_SE_EXCITE, gate_f + in_b / 4.0, in_b + out_b + part_b + 4.0 * se_weight_floats(L.C, L.se_cr), cur, out);
     }
     cur = out;
   }
@@ -1452,6 +1469,26 @@ int dnn_plan_add_avgpool(dnn_plan* p) {
   return 0;
 }
 
+int dnn_plan_add_squeeze_excite(dnn_plan* p, int cr, const float* w1, const float* b1, int act1, const float* w2,
+                                const float* b2, int act2) {
+  DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_squeeze_excite: plan is NULL or finalized");
+  DNN_REQUIRE(!p->fp16, "dnn_plan_add_squeeze_excite: fp32 plans only (this is an fp16 plan)");
+  if (int rc = se_args_ok("dnn_plan_add_squeeze_excite", p->cur_c, cr, act1, act2)) return rc;
+  DNN_REQUIRE((w1 == nullptr) == (w2 == nullptr), "dnn_plan_add_squeeze_excite: w1 and w2 must be both set or both NULL");
+  PlanLayer L;
+  shape_only_layer(p, &L, LAYER_SE);
+  L.se_cr = cr;
+  L.se_act1 = act1;
+  L.se_act2 = act2;
+  if (w1) {
+    L.have_host = true;
+    L.w.resize(se_weight_floats(L.C, cr));
+    se_pack(w1, b1, w2, b2, L.C, cr, L.w.data());
+  }
+  push_computing(p, std::move(L));
+  return 0;
+}
+
 int dnn_plan_add_softmax(dnn_plan* p) {
   DNN_REQUIRE(p && !p->finalized, "dnn_plan_add_softmax: plan is NULL or finalized");
   DNN_REQUIRE(!p->fp16, "dnn_plan_add_softmax: fp32 plans only (this is an fp16 plan)");
@@ -1537,6 +1574,14 @@ static int upload_weights(dnn_plan* p) {
       if (hipMemcpy(p->weights + L.w_off, L.w.data(), L.w.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
           hipMemcpy(e, L.mean.data(), nb, hipMemcpyHostToDevice) != hipSuccess ||
           hipMemcpy(e + L.Npad, L.sq.data(), nb, hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("dnn_plan_finalize: weight upload failed");
+        rc = -1;
+        break;
+      }
+      continue;
+    }
+    if (L.type == LAYER_SE) {  // packed on the host when the layer was added
+      if (hipMemcpy(p->weights + L.w_off, L.w.data(), L.w.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
         set_error("dnn_plan_finalize: weight upload failed");
         rc = -1;
         break;
@@ -1864,6 +1909,10 @@ static int launch_step32(dnn_plan* p, const Step& st, const RunArgs& r) {
       return launch_softmax(cur, dst, n, L.C, s);
     case STEP_ACT:
       return launch_activate(cur, dst, (long long)n * L.H * L.W * L.C, L.leaky, s);
+    case STEP_SE_SQUEEZE:
+    case STEP_SE_EXCITE:
+      return launch_squeeze_excite(cur, dst, slab, p->weights + L.w_off, n, L.H, L.W, L.C, L.se_cr, L.se_act1, L.se_act2,
+                                   st.kind == STEP_SE_SQUEEZE ? SE_SQUEEZE : SE_EXCITE, s);
     default:
       set_error("dnn_plan_run: fp32 plan has an unsupported step kind %d", (int)st.kind);
       return -2;
@@ -2075,6 +2124,10 @@ int dnn_plan_describe(const dnn_plan* p, char* buf, int buf_len) {
       snprintf(line, sizeof(line), "softmax %dx%dx%d\n", L.H, L.W, L.C);
     } else if (L.type == LAYER_ACT) {
       snprintf(line, sizeof(line), "activate %dx%dx%d act=%s\n", L.H, L.W, L.C, act_name(L.leaky));
+    } else if (L.type == LAYER_SE) {
+      auto nm = [](int a) { return a == ACT_NONE ? "linear" : a == ACT_LEAKY_F32 ? "leaky_f32" : act_name(a); };
+      snprintf(line, sizeof(line), "squeeze_excite %dx%dx%d cr=%d act=%s,%s\n", L.H, L.W, L.C, L.se_cr, nm(L.se_act1),
+               nm(L.se_act2));
     } else if (L.type == LAYER_RELEASE) {
       snprintf(line, sizeof(line), "release %dx%dx%d slot=%d\n", L.H, L.W, L.C, L.slot);
     } else if (L.type == LAYER_TAP) {

@@ -9,4 +9,8 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // the checks dnn_plan_add_spp and dnn_spp_host make of their window sizes (0, or -2 with the error set)
 int spp_sizes_ok(const char* who, int n_sizes, const int* sizes);
 
+// the checks dnn_plan_add_squeeze_excite, dnn_squeeze_excite_host and the launcher make of the gate's widths and
+// activation codes (squeeze_excite.hip; 0, or -2 with the error set, naming the limit)
+int se_args_ok(const char* who, int C, int Cr, int act1, int act2);
+
 }  // namespace dnnhip

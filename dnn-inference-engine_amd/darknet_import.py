@@ -69,6 +69,13 @@ and for a net ending in a 1 x 1 map
 
     idx, prob = m.classify(frames, k=5)   # [n, k] best classes and their scores, top-k on the device
 
+Squeeze-and-excitation: [scale_channels] (activation linear, no scale_wh) is read only as the end of the SE block
+of the MBConv networks, [avgpool], two 1x1 stride-1 [convolutional] sections (a bias or a folded BatchNorm, any
+supported activation), then [scale_channels] with `from` naming the [avgpool]'s input (se_block).  The four sections
+count as four layers and the two convs' weights are read in file order like any conv's, but they make ONE
+dnn_hip.SqueezeExcite node (dnn_plan_add_squeeze_excite: two kernels, no slot, squeeze_excite.hip); nothing else
+may read the three inner layers.  cfg_text("efficientnet_b0") is EfficientNet-B0 built from the paper's table.
+
 cfg_text has the Darknet-19 and Darknet-53 classifier definitions ("darknet19", "darknet53").  The
 frames are [n, h, w, c] fp32 at the network's size: the classifier demo's resize and centre crop are
 the caller's.
@@ -88,6 +95,7 @@ Out of scope:
   * YOLO9000 and the other [region] forms: softmax_tree, background = 1, classfix, softmax = 0, coords
     other than 4; [reorg] with reverse = 1, flatten = 1 or extra;
   * activations other than leaky, linear, mish, swish and logistic (relu, elu, tanh);
+  * [sam] (spatial attention) and [scale_channels] with scale_wh = 1 or outside the SE block above;
   * [shortcut] with activation=leaky (Darknet's ResNet / ResNeXt classifiers), [connected] on a map
     larger than 1 x 1, [softmax] with groups, a temperature or a tree;
   * [route] with groups > 1 over more than one layer (Darknet slices each layer then; no stock cfg
@@ -115,14 +123,15 @@ import yolov3
 
 BASE_SECTION_TYPES = ("net", "convolutional", "shortcut", "route", "upsample", "maxpool", "yolo", "avgpool", "softmax",
                       "connected", "dropout", "cost")              # what parse_cfg lets through unless told otherwise
-SECTION_TYPES = BASE_SECTION_TYPES + ("reorg", "region")  # ... and with YOLOv2's two sections: DarknetModel's set
+SECTION_TYPES = BASE_SECTION_TYPES + ("reorg", "region", "scale_channels")  # ... and with YOLOv2's two sections and the
+#                                                     squeeze-and-excitation gate's closing one: DarknetModel's set
 BN_EPS = 1e-6  # normalize_cpu's .000001f, added to sqrt(var)
 BASE_ACTIVATIONS = ("leaky", "linear")                         # what parse_cfg lets through unless told otherwise
 ACTIVATIONS = BASE_ACTIVATIONS + ("mish", "swish", "logistic")  # of [convolutional]; [shortcut]: all but leaky
 SCORE_THR, IOU_THR = 0.5, 0.45  # Darknet's detector defaults (-thresh .5, nms .45)
 MODELS = ("yolov3", "yolov3-spp", "yolov3-tiny", "yolov4-tiny", "yolov4", "darknet19", "darknet53",
-          "yolov2", "yolov2_voc", "yolov2_tiny", "yolov2_tiny_voc")
-CLASSIFIERS = {"darknet19": 224, "darknet53": 256}  # the classifier definitions and their default input size
+          "yolov2", "yolov2_voc", "yolov2_tiny", "yolov2_tiny_voc", "efficientnet_b0")
+CLASSIFIERS = {"darknet19": 224, "darknet53": 256, "efficientnet_b0": 224}  # the classifier definitions and their default input size
 NMS_KINDS = ("default", "greedynms")  # [yolo] nms_kind values that are the decode's greedy NMS
 DIOU_KINDS = ("diounms",)             # ... and those that are its DIoU NMS (yolo_post.MultiHead's nms_kind "diou")
 
@@ -446,6 +455,37 @@ def softmax_params(sec, in_h, in_w):
                            "before it)")
 
 
+def se_block(sections, at):
+    """The squeeze-and-excitation block that the [scale_channels] section at layer `at` closes: the layer index of
+    its input x.  The one supported form is
+
+        x, [avgpool], [convolutional] 1x1 stride 1, [convolutional] 1x1 stride 1, [scale_channels] from = x
+
+    with activation = linear and no scale_wh on the closing section, groups = 1 on both convs and `from` naming the
+    layer right before the [avgpool].  Anything else (a gate of another depth, a `from` elsewhere, scale_wh = 1,
+    Darknet's [sam]) raises DarknetError with the line and the rule."""
+    sec = sections[at + 1]
+    where = f"[scale_channels] at line {sec['line']} (layer {at})"
+    rule = ("it is supported only as the end of a squeeze-and-excitation block: [avgpool], two 1x1 stride-1 "
+            "[convolutional] sections, then [scale_channels] with `from` naming the [avgpool]'s input")
+    if _int(sec, "scale_wh", 0):
+        raise DarknetError(f"{where}: scale_wh = {sec['scale_wh']} (a spatial gate) is not supported; {rule}")
+    if sec.get("activation", "linear") != "linear":
+        raise DarknetError(f"{where}: activation {sec['activation']!r} is not supported (linear only); {rule}")
+    src = _layer_index(sec, _int(sec, "from"), at, "from")
+    kinds = [s["type"] for s in sections[max(at - 2, 1):at + 1]]  # the three layers before this one
+    if at < 4 or kinds != ["avgpool", "convolutional", "convolutional"]:
+        raise DarknetError(f"{where}: the three layers before it are {kinds}; {rule}")
+    if src != at - 4:
+        raise DarknetError(f"{where}: from = {sec['from']} names layer {src}, the [avgpool]'s input is layer {at - 4}; {rule}")
+    for conv in sections[at - 1:at + 1]:
+        _, size, stride, _, _, _ = conv_params(conv)
+        if size != 1 or stride != 1 or _int(conv, "groups", 1) != 1:
+            raise DarknetError(f"{where}: the [convolutional] at line {conv['line']} has size {size}, stride {stride}, "
+                               f"groups {_int(conv, 'groups', 1)}; {rule}")
+    return src
+
+
 def layer_shapes(sections, in_shape=None):
     """Per layer (every section after [net]) its output's (h, w, c), walking the cfg as Darknet's
     parser does; raises DarknetError for a section that does not fit its input."""
@@ -497,6 +537,13 @@ def layer_shapes(sections, in_shape=None):
             region_params(sec, sections[at] if at else {"type": "net"})
         elif kind == "avgpool":
             h, w = 1, 1
+        elif kind == "scale_channels":
+            src = shapes[se_block(sections, at)]
+            if (h, w, c) != (1, 1, src[2]) or not 1 <= shapes[at - 2][2] <= dnn_hip.SE_MAX_CR or c > dnn_hip.SE_MAX_C:
+                raise DarknetError(f"[scale_channels] at line {sec['line']}: a {h} x {w} x {c} gate (squeezed width "
+                                   f"{shapes[at - 2][2]}) on a {src} tensor: need 1 x 1 x {src[2]}, at most "
+                                   f"{dnn_hip.SE_MAX_C} channels and a squeezed width of at most {dnn_hip.SE_MAX_CR}")
+            h, w, c = src
         elif kind == "softmax":
             softmax_params(sec, h, w)
             if c > dnn_hip.SOFTMAX_MAX_CLASSES:
@@ -682,6 +729,25 @@ class _LazyPool(object):
         self.src, self.size, self.node = src, size, None
 
 
+class _SePart(object):
+    """A layer inside a squeeze-and-excitation block (its [avgpool] or one of its two convs, with that conv's
+    weights): no node of its own, and nothing but the block's [scale_channels] may read it."""
+
+    def __init__(self, sec, layer):
+        self.sec, self.layer = sec, layer
+
+
+def _se_fc(layer):
+    """(matrix [inputs, outputs], bias [outputs]) fp32 of a 1x1 conv on a 1 x 1 map as one of the gate's two small
+    matrices: y = x @ matrix + bias.  A folded BatchNorm's per-output scale (fold_batchnorm) goes into the matrix's
+    columns, in float64 and rounded once; without BatchNorm the matrix is the conv's weights as they are."""
+    scale, shift = fold_batchnorm(layer)
+    w = kernel_hwio(layer)[0, 0]
+    if "scales" in layer:
+        w = (w.astype(np.float64) * scale.astype(np.float64)).astype(np.float32)
+    return np.ascontiguousarray(w), shift
+
+
 def build_graph(builder_cls, sections, layers, in_shape):
     """Return (graph, outs, yolos): outs the head nodes (the conv before each [yolo], in cfg
     order; all but the last are the graph's extra outputs, the last its primary one), yolos the
@@ -696,7 +762,14 @@ def build_graph(builder_cls, sections, layers, in_shape):
     outs, yolos = [], []
     weights = iter(layers)
 
+    # the [avgpool] and the two convs of every squeeze-and-excitation block: layers that exist only inside the
+    # SqueezeExcite node their [scale_channels] makes (se_block has checked the pattern in layer_shapes)
+    se_parts = {k for at, sec in enumerate(sections[1:]) if sec["type"] == "scale_channels" for k in (at - 3, at - 2, at - 1)}
+
     def node(v):
+        if isinstance(v, _SePart):
+            raise DarknetError(f"[{v.sec['type']}] at line {v.sec['line']} is inside a squeeze-and-excitation block: only "
+                               "the block's [scale_channels] may read it")
         if isinstance(v, _LazyPool):
             if v.node is None:
                 v.node = g.create_max_pool2d(node(v.src), [1, v.size, v.size, 1], [1, 1, 1, 1], "SAME")
@@ -707,7 +780,14 @@ def build_graph(builder_cls, sections, layers, in_shape):
     c_in = int(in_shape[3])
     for at, sec in enumerate(sections[1:]):
         kind = sec["type"]
-        if kind == "convolutional":
+        if at in se_parts:  # (its conv's weights are read here, in file order like any conv's)
+            cur = _SePart(sec, next(weights) if kind == "convolutional" else None)
+        elif kind == "scale_channels":
+            fc1, fc2 = out[at - 2], out[at - 1]
+            (w1, b1), (w2, b2) = _se_fc(fc1.layer), _se_fc(fc2.layer)
+            cur = g.create_squeeze_excite(node(out[se_block(sections, at)]), w1, b1, conv_params(fc1.sec)[5],
+                                          w2, b2, conv_params(fc2.sec)[5])
+        elif kind == "convolutional":
             n, size, stride, pad, _, act = conv_params(sec)
             layer = next(weights)
             scale, shift = fold_batchnorm(layer)
@@ -1111,12 +1191,58 @@ def _yolov4(c, n_out, classes, scaled=False):
     return c.text()
 
 
+# EfficientNet-B0's seven stages (Tan & Le 2019, table 1): (expansion, kernel, output width, blocks, first stride)
+_B0_STAGES = ((1, 3, 16, 1, 1), (6, 3, 24, 2, 2), (6, 5, 40, 2, 2), (6, 3, 80, 3, 2), (6, 5, 112, 3, 1),
+              (6, 5, 192, 4, 2), (6, 3, 320, 1, 1))
+
+
+def _efficientnet_b0(c, classes):
+    """EfficientNet-B0 in Darknet sections, built from the paper's table: the 3x3 stride-2 stem of 32, sixteen MBConv
+    blocks, the 1x1 head of 1280, [avgpool], a 1x1 conv to `classes` and [softmax].  An MBConv block is a 1x1
+    expansion (left out where the expansion is 1), a depthwise k x k conv, the squeeze-and-excitation block
+    ([avgpool], a 1x1 conv with a bias and swish to a quarter of the BLOCK's input width, a 1x1 conv with a bias and
+    logistic back to the expanded width, [scale_channels]), a linear 1x1 projection, and a linear [shortcut] from the
+    block's input where the stride is 1 and the widths agree.  Every other conv has batch_normalize=1 and swish."""
+    def conv(filters, size, stride=1, act="swish", groups=1, bn=True):
+        pairs = ([("batch_normalize", 1)] if bn else []) + [("filters", filters), ("size", size), ("stride", stride),
+                                                            ("pad", 1)]
+        return c.add("convolutional", *pairs, *([("groups", groups)] if groups > 1 else []), ("activation", act))
+
+    conv(c.wd(32), 3, stride=2)
+    cin = c.wd(32)
+    for expand, k, width, blocks, stride in _B0_STAGES:
+        for b in range(blocks):
+            c.lines.append(f"# MBConv{expand} {k}x{k}")
+            start, cout, s = c.n, c.wd(width), stride if b == 0 else 1
+            mid = cin * expand
+            if expand != 1:
+                conv(mid, 1)
+            conv(mid, k, stride=s, groups=mid)
+            c.add("avgpool")
+            conv(max(1, cin // 4), 1, bn=False)
+            conv(mid, 1, act="logistic", bn=False)
+            c.add("scale_channels", ("from", -4), ("activation", "linear"))
+            conv(cout, 1, act="linear")
+            if s == 1 and cin == cout:
+                c.add("shortcut", ("from", start - 1 - c.n), ("activation", "linear"))
+            cin = cout
+    conv(c.wd(1280), 1)
+    c.add("avgpool")
+    c.conv(classes, 1, head=True)
+    c.add("softmax", ("groups", 1))
+    return c.text()
+
+
 def cfg_text(model, classes=None, width=None, height=None, width_div=1, scaled_head=False):
     """The public definition of `model` (one of MODELS) as cfg text, for `classes` classes and a
     width x height input; width_div divides every channel count except the heads' 3 x (5 + classes)
     or the classifier conv's `classes` (a narrow model of the same topology).  Defaults: 80 classes
     at 416 x 416 for the detectors (20 for "yolov2_voc" and "yolov2_tiny_voc", whose heads are 5 x (5 + classes)) ("yolov4" has no default size: ValueError without width and height); 1000 classes for the classifiers "darknet19" (224 x 224) and
     "darknet53" (256 x 256), which end in [avgpool] and [softmax].
+    "efficientnet_b0" (224 x 224, 1000 classes) is a CONSTRUCTION after the table of the EfficientNet paper
+    (_efficientnet_b0: stem, seven MBConv stages with squeeze-and-excitation, the 1280-wide head), not the text of
+    AlexeyAB's efficientnet_b0.cfg, which is not in this repository and may differ in details (its SE widths, its
+    dropout sections); a user's own cfg and .weights are theirs to pass to DarknetModel.
     scaled_head ("yolov4" only): YOLOv4's topology with the head of the scaled-YOLOv4 cfgs: the head convs
     are activation=logistic and each [yolo] carries new_coords=1, scale_x_y=2.0, nms_kind=diounms and
     beta_nms=0.6.  That is a construction for testing the head, not a public cfg: the public yolov4-csp /
@@ -1164,6 +1290,8 @@ def cfg_text(model, classes=None, width=None, height=None, width_div=1, scaled_h
         c.conv(5 * (5 + classes), 1, head=True)
         c.region(_V2_VOC_ANCHORS if voc else _V2_COCO_ANCHORS, classes)
         return c.text()
+    if model == "efficientnet_b0":
+        return _efficientnet_b0(c, classes)
     if model == "darknet19":
         for stage, f in enumerate((32, 64, 128, 256, 512, 1024)):
             for j in range(1 if stage < 2 else 3 if stage < 4 else 5):  # 3x3 f, 1x1 f / 2, 3x3 f, ...

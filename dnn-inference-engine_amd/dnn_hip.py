@@ -31,7 +31,10 @@ a conv with the same zero padding on both sides of each axis (Darknet's), `Scale
 `LeakyReLUF32` (`create_leaky_relu_f32`) the fp32 leaky max(x, 0.1f x); a conv followed by a
 ScaleShift and either leaky lowers to one dnn_plan_add_conv_padded entry (darknet_import.py).
 `GlobalAvgPool` and `Softmax` (`create_global_avg_pool`, `create_softmax`) are the tail of a Darknet
-classifier, one avgpool / softmax plan entry and one kernel each (csrc/classify.hip).  With
+classifier, one avgpool / softmax plan entry and one kernel each (csrc/classify.hip).  `SqueezeExcite`
+(`create_squeeze_excite`) is the squeeze-and-excitation gate of the MBConv networks, x times a per-image,
+per-channel gate made from x's own global average and two small matrices: one plan entry, two kernels and no
+slot (csrc/squeeze_excite.hip).  With
 `debug=True` (or a graph the plan cannot express) it instead runs node by node through
 the per-op C-ABI (`conv2d_mul`, `bias_add`, ... in libdnn_hip.so, include/dnn_hip.h),
 exactly like the reference, and saves every layer to ./intermediate/layer_{k}.npy
@@ -104,6 +107,8 @@ def _bind_plan_api(lib):
         "dnn_softmax_host": (i, [vp, vp, i, i]),
         "dnn_plan_add_activation": (i, [vp, i]),
         "dnn_activate_host": (i, [vp, vp, ctypes.c_longlong, i]),
+        "dnn_plan_add_squeeze_excite": (i, [vp, i, vp, vp, i, vp, vp, i]),
+        "dnn_squeeze_excite_host": (i, [vp, vp, vp, i, vp, vp, i, vp, i, i, i, i, i]),
         "dnn_plan_output_shape": (i, [vp, P(i), P(i), P(i), P(i)]),
         "dnn_plan_describe": (i, [vp, ctypes.c_char_p, i]),
         "dnn_plan_memory": (i, [vp, P(sz), P(sz)]),
@@ -312,7 +317,8 @@ class DnnGraphBuilder(object):
         self.name_num = {"conv2d": 0, "bias_add": 0, "max_pool2d": 0, "batch_norm": 0, "leaky_relu": 0,
                          "input": 0, "space_to_depth": 0, "concat": 0, "add": 0, "upsample": 0, "spp": 0,
                          "channel_slice": 0, "global_avg_pool": 0, "softmax": 0,
-                         "conv2d_padded": 0, "scale_shift": 0, "leaky_relu_f32": 0, "activation": 0, "reorg": 0}
+                         "conv2d_padded": 0, "scale_shift": 0, "leaky_relu_f32": 0, "activation": 0, "reorg": 0,
+                         "squeeze_excite": 0}
         self.in_node = None
         self.out_node = None
         self.extra_out_nodes = []
@@ -419,6 +425,13 @@ class DnnGraphBuilder(object):
 
     def create_activation(self, in_node, kind):
         out_node = Activation(self.get_name("activation"), in_node, kind)
+        self.G.add_edge(in_node, out_node)
+        return out_node
+
+    def create_squeeze_excite(self, in_node, w1, b1, act1, w2, b2, act2):
+        """The squeeze-and-excitation gate x * act2(act1(mean(x) @ w1 + b1) @ w2 + b2): w1 [C, Cr], w2 [Cr, C], the
+        biases [Cr] and [C] or None, the activations names of SE_ACTIVATIONS."""
+        out_node = SqueezeExcite(self.get_name("squeeze_excite"), in_node, w1, b1, act1, w2, b2, act2)
         self.G.add_edge(in_node, out_node)
         return out_node
 
@@ -956,6 +969,63 @@ class Activation(DnnNode):
         _check(mylib.dnn_activate_host(_vp(x), _vp(self.result), x.size, ACTIVATIONS[self.kind]), self.name)
 
 
+SE_ACTIVATIONS = dict(ACTIVATIONS, linear=0, leaky=2)  # act_dev.h codes: what a SqueezeExcite's two FCs may carry
+SE_MAX_C, SE_MAX_CR = 4096, 1024                       # DNN_SE_MAX_C, DNN_SE_MAX_CR
+
+
+def _act_numpy(v, kind):
+    """One of SE_ACTIVATIONS on a float32 array: evaluated in float64, rounded once."""
+    v = np.asarray(v, np.float64)
+    with np.errstate(over="ignore"):
+        sig = np.where(v >= 0, 1.0 / (1.0 + np.exp(-np.abs(v))), np.exp(-np.abs(v)) / (1.0 + np.exp(-np.abs(v))))
+        out = {"linear": lambda: v, "leaky": lambda: np.maximum(v, 0.1 * v), "logistic": lambda: sig,
+               "swish": lambda: v * sig, "mish": lambda: v * np.tanh(np.logaddexp(0.0, v))}[kind]()
+    return out.astype(np.float32)
+
+
+def squeeze_excite_numpy(x, w1, b1, act1, w2, b2, act2):
+    """The squeeze-and-excitation gate by its definition (include/dnn_hip_plan.h, dnn_plan_add_squeeze_excite) on an
+    NHWC float32 array: the channel means, the two small matrix products with their activations, the broadcast
+    multiply; sums in float32, numpy's order."""
+    x = np.asarray(x, np.float32)
+    m = x.sum(axis=(1, 2), dtype=np.float32) / np.float32(x.shape[1] * x.shape[2])
+    h = _act_numpy(m @ w1 + (0 if b1 is None else b1), act1)
+    g = _act_numpy(h @ w2 + (0 if b2 is None else b2), act2)
+    return x * g[:, None, None, :]
+
+
+class SqueezeExcite(DnnNode):
+    """Not in the reference (Darknet's [avgpool] [convolutional] [convolutional] [scale_channels], the SE block of the
+    MBConv networks): y = x * g, g = act2(act1(mean_hw(x) @ w1 + b1) @ w2 + b2) per image, w1 [C, Cr], w2 [Cr, C].  In
+    a plan it is one dnn_plan_add_squeeze_excite entry, two kernels and no slot (csrc/squeeze_excite.hip); run(),
+    the node-by-node path, is the numpy restatement of the definition."""
+
+    def __init__(self, name, in_node, w1, b1, act1, w2, b2, act2):
+        if len(in_node.result.shape) != 4 or act1 not in SE_ACTIVATIONS or act2 not in SE_ACTIVATIONS:
+            raise ValueError
+        c = in_node.result.shape[3]
+        w1, w2 = np.asarray(w1), np.asarray(w2)
+        if w1.ndim != 2 or w1.shape[0] != c or w2.shape != w1.shape[::-1]:
+            raise ValueError
+        cr = w1.shape[1]
+        if not (1 <= c <= SE_MAX_C and 1 <= cr <= SE_MAX_CR):
+            raise ValueError
+        if any(b is not None and np.asarray(b).shape != (k,) for b, k in ((b1, cr), (b2, c))):
+            raise ValueError
+        self.in_node = in_node
+        self.w1 = np.ascontiguousarray(w1, dtype=np.float32)
+        self.w2 = np.ascontiguousarray(w2, dtype=np.float32)
+        self.b1 = None if b1 is None else np.ascontiguousarray(b1, dtype=np.float32)
+        self.b2 = None if b2 is None else np.ascontiguousarray(b2, dtype=np.float32)
+        self.act1, self.act2 = act1, act2
+        self.result = np.zeros(in_node.result.shape, dtype='float32')
+        self.name = name
+
+    def run(self):
+        self.result[...] = squeeze_excite_numpy(self.in_node.result, self.w1, self.b1, self.act1, self.w2, self.b2,
+                                                self.act2)
+
+
 class Input(DnnNode):
     """proj3/dnn_openblas.py:287-300 (unchanged contract)."""
 
@@ -1107,6 +1177,21 @@ class ActivationEntry(object):
         self.nodes = list(nodes)
 
 
+class SqueezeExciteEntry(object):
+    """dnn_plan_add_squeeze_excite: current = current * gate(current), `node` the SqueezeExcite that holds the two
+    matrices, the biases and the activation names."""
+
+    def __init__(self, node):
+        self.node = node
+        self.nodes = [node]
+
+    def add(self, lib, h, upload=True):
+        n = self.node
+        w1, w2 = (_vp(n.w1), _vp(n.w2)) if upload else (None, None)
+        _check(lib.dnn_plan_add_squeeze_excite(h, int(n.w1.shape[1]), w1, _vp(n.b1), SE_ACTIVATIONS[n.act1], w2,
+                                               _vp(n.b2), SE_ACTIVATIONS[n.act2]), "dnn_plan_add_squeeze_excite", lib)
+
+
 class TapEntry(object):
     """dnn_plan_add_tap: the current tensor becomes the plan's extra output `index` (no kernel);
     `node` is the graph node it is the result of (None in plans assembled by hand)."""
@@ -1197,6 +1282,8 @@ def _lower_one(g, nxt):
         return SoftmaxEntry(nodes=[nxt]), nxt
     if isinstance(nxt, Activation):
         return ActivationEntry(nxt.kind, nodes=[nxt]), nxt
+    if isinstance(nxt, SqueezeExcite):
+        return SqueezeExciteEntry(nxt), nxt
     return None  # a standalone element-wise op: not expressible as a fused entry
 
 
@@ -1329,7 +1416,7 @@ def _output_branch(g, head):
 def lower_graph(g):
     """Lower a builder graph to fused plan entries, or None if the plan cannot express it (then
     the node-by-node path runs).  Expressible: a chain of Conv2D (with its BiasAdd / BatchNorm /
-    LeakyReLU), MaxPool2D, SpaceToDepth, Reorg, Upsample, ChannelSlice, Spp, GlobalAvgPool, Softmax and Activation, and forks of two such chains (either may be
+    LeakyReLU), MaxPool2D, SpaceToDepth, Reorg, Upsample, ChannelSlice, Spp, GlobalAvgPool, Softmax, Activation and SqueezeExcite, and forks of two such chains (either may be
     empty) joined by one Concat or one Add (with a LeakyReLU directly after it), any number of
     them in sequence within the plan's slots (an Add block gives its slots back, and so does a
     Concat fork lowered inside a pending long skip); forks nested in a fork's branch are not.
@@ -1581,7 +1668,9 @@ class Plan(object):
         for e in entries:
             if _add_structural(self.lib, self.h, e, leaky_variant):
                 continue
-            if isinstance(e, PaddedConvEntry):
+            if isinstance(e, SqueezeExciteEntry):
+                e.add(self.lib, self.h, upload)
+            elif isinstance(e, PaddedConvEntry):
                 c = e.conv
                 kh, kw, _, od = c.kernel.shape
                 scale = e.affine.scale if e.affine is not None else None
@@ -1652,7 +1741,9 @@ class Plan(object):
             for e in entries:
                 if _add_structural(lib, h, e):
                     continue
-                if isinstance(e, PaddedConvEntry):
+                if isinstance(e, SqueezeExciteEntry):
+                    e.add(lib, h, upload=False)
+                elif isinstance(e, PaddedConvEntry):
                     kh, kw, _, od = e.conv.kernel.shape
                     sc = _vp(e.affine.scale) if e.affine is not None else None  # (only says: affine or not)
                     geom = (h, kh, kw, od, int(e.conv.strides[1]), int(e.conv.strides[2]), e.pads[0], e.pads[1])

@@ -344,6 +344,37 @@ int dnn_conv_grouped_host(const float* x, const float* kernel, const float* scal
                           int n, int h, int w, int c, int kh, int kw, int od, int stride_h, int stride_w, int pad_h,
                           int pad_w, int groups, int leaky);
 
+/* Squeeze-and-excitation gate (fp32 plans, batch and latency mode; on an fp16 plan it fails).  The reference has
+ * no such node: it is Darknet's [avgpool] [convolutional 1x1] [convolutional 1x1] [scale_channels], the SE block of
+ * the MBConv networks (efficientnet_b0.cfg, enet-coco.cfg).  For the current tensor x [H, W, C] of an image:
+ *   m[c] = (sum of x[h, w, c] over the H * W positions) / (H * W)
+ *   h[j] = act1(sum_c m[c] * w1[c][j] + b1[j])     j < cr
+ *   g[c] = act2(sum_j h[j] * w2[j][c] + b2[c])
+ *   y[h, w, c] = x[h, w, c] * g[c]
+ * in fp32, products and sums rounded separately, in an order that depends on (H, W, C, cr) alone: image i has the
+ * same bits at every batch and in both modes.  csrc/squeeze_excite.hip has the work split and the orders.
+ *
+ * dnn_plan_add_squeeze_excite: current [H, W, C] -> the same shape.  w1 is [C][cr] and w2 [cr][C] (the HWIO
+ *   kernels of the two 1x1 convs), b1 [cr] and b2 [C] or NULL (zeros); all copied.  w1 == NULL declares the shape
+ *   only (the values arrive with the weight arena).  act1 and act2 are 0 (linear), 2 (leaky in fp32), DNN_ACT_LOGISTIC,
+ *   DNN_ACT_SWISH or DNN_ACT_MISH.  Limits, each named in the error: C <= DNN_SE_MAX_C, 1 <= cr <= DNN_SE_MAX_CR.
+ *   Two kernels ("se%d.squeeze" and "se%d.excite" in dnn_plan_kernel_info: H * W * C flops and the input plus the
+ *   partial sums as bytes; 4 * C * cr + H * W * C flops and input, output, partial sums and weights as bytes), no
+ *   slot: the partial sums live in the workspace's split-K slab (dnn_plan_memory counts them).  Input and output
+ *   are plain NHWC fp32 (the entry stops the conv / pool fusions like the fork / join entries); the input may be the
+ *   caller's d_in, the output goes to a slot or tap region when a stash or tap follows and to d_out when the entry
+ *   is the plan's last.  dnn_plan_describe prints "squeeze_excite HxWxC cr=<cr> act=<act1>,<act2>".  A failed call
+ *   leaves the plan unchanged.
+ * dnn_squeeze_excite_host: the two kernels on host tensors (H2D copies, launches, D2H copy, synchronise):
+ *   x [n, h, w, c] -> out of the same shape.  Each tensor below 2 GiB (refused from the arguments, before any
+ *   allocation). */
+#define DNN_SE_MAX_C 4096
+#define DNN_SE_MAX_CR 1024
+int dnn_plan_add_squeeze_excite(dnn_plan* plan, int cr, const float* w1, const float* b1, int act1, const float* w2,
+                                const float* b2, int act2);
+int dnn_squeeze_excite_host(const float* x, const float* w1, const float* b1, int act1, const float* w2,
+                            const float* b2, int act2, float* out, int n, int h, int w, int c, int cr);
+
 /* Output shape of the plan so far (per image, plus the planned batch). */
 int dnn_plan_output_shape(const dnn_plan* plan, int* batch, int* h, int* w, int* c);
 
