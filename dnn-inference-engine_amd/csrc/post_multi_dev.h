@@ -9,6 +9,8 @@
 //   per box     label_score; ScaleTab / fill_scale_tab (the per-scale parameters in LDS), box_at
 //               (global box index -> scale, cell, anchor, values), decode_corners_at /
 //               decode_single_at (decode and store), the class-major and merge key layouts
+//   grid-wide   the workspace layout (counters, boxes, keys) and wave_append, for the two files whose
+//               decode runs over the whole grid (postprocess_wide.hip, postprocess_dfl.hip)
 //   phase 3     nms_wave; nms_segments with its state ClassState (per class: waves on tickets, then
 //               the long segments by the workgroup)
 //   phase 4     gather_kept, merge_single, merge_labels (the in-place expansion and its invariant)
@@ -255,6 +257,38 @@ __device__ __forceinline__ int key_merge_index(unsigned long long key) {
   return (int)(key >> PC_CLS_BITS) & ((1 << IDX_BITS) - 1);
 }
 __device__ __forceinline__ int key_merge_class(unsigned long long key) { return (int)key & ((1 << PC_CLS_BITS) - 1); }
+
+// ---- the workspace of the grid-wide decodes (postprocess_wide.hip, postprocess_dfl.hip): n images of nb
+// boxes are n counter blocks of 64 bytes, then per image 40 nb bytes of boxes (the layout of
+// postprocess_multi.hip), then per image PM_CAP keys.
+constexpr int PW_CTR_BYTES = 64;  // int 0: candidates, int 1: a corner was not finite or out of range
+constexpr unsigned long long PW_KEY_BYTES = (unsigned long long)PM_CAP * 8ull;
+
+inline unsigned long long wide_workspace(int nb, int n_images) {
+  return (unsigned long long)n_images * ((unsigned long long)nb * PM_BOX_BYTES + PW_KEY_BYTES + PW_CTR_BYTES);
+}
+__device__ __forceinline__ int* ws_counters(char* ws, int img) {
+  return reinterpret_cast<int*>(ws + (size_t)img * PW_CTR_BYTES);
+}
+__device__ __forceinline__ char* ws_boxes(char* ws, int img, int nb, int n_images) {
+  return ws + (size_t)n_images * PW_CTR_BYTES + (size_t)img * nb * PM_BOX_BYTES;
+}
+__device__ __forceinline__ unsigned long long* ws_keys(char* ws, int img, int nb, int n_images) {
+  return reinterpret_cast<unsigned long long*>(ws + (size_t)n_images * (PW_CTR_BYTES + (size_t)nb * PM_BOX_BYTES) +
+                                               (size_t)img * PW_KEY_BYTES);
+}
+
+// Position of this lane's candidate in the image's list, or -1 without one: one atomic per wave
+// with the number of lanes that have a candidate.  Every lane of the wave calls it together.
+__device__ __forceinline__ int wave_append(int* counter, bool want, int lane) {
+  const unsigned long long m = __ballot(want);
+  if (m == 0) return -1;  // wave-uniform
+  const int leader = __ffsll((long long)m) - 1;
+  int base = 0;
+  if (lane == leader) base = atomicAdd(counter, __popcll(m));  // device scope
+  base = __shfl(base, leader);
+  return want ? base + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+}
 
 // Candidates of one class above which the whole workgroup takes the segment.  A wave alone pays for
 // every kept box of its segment itself, so long chains are cheaper split over 16 waves even with

@@ -34,8 +34,6 @@
 namespace dnnhip {
 
 constexpr int PW_DEC_THREADS = 256;
-constexpr int PW_CTR_BYTES = 64;  // int 0: candidates, int 1: a corner was not finite or out of range
-constexpr unsigned long long PW_KEY_BYTES = (unsigned long long)PM_CAP * 8ull;
 constexpr int PW_ANY = 0, PW_PER_CLASS = 1, PW_MULTI = 2;
 // Logistic class scores: 1 = a wave with few gated boxes shares their classes across its lanes,
 // 0 = a box's thread always loops over its classes itself.  The results are the same bits;
@@ -45,29 +43,8 @@ constexpr int PW_ANY = 0, PW_PER_CLASS = 1, PW_MULTI = 2;
 #endif
 static_assert(PW_DEC_THREADS % 64 == 0 && PW_DEC_THREADS >= 2 * DNN_YOLO_MAX_ANCHORS, "whole waves; the anchor copy");
 
-// the parts of an image's workspace (see the top of the file)
-__device__ __forceinline__ int* ws_counters(char* ws, int img) {
-  return reinterpret_cast<int*>(ws + (size_t)img * PW_CTR_BYTES);
-}
-__device__ __forceinline__ char* ws_boxes(char* ws, int img, int nb, int n_images) {
-  return ws + (size_t)n_images * PW_CTR_BYTES + (size_t)img * nb * PM_BOX_BYTES;
-}
-__device__ __forceinline__ unsigned long long* ws_keys(char* ws, int img, int nb, int n_images) {
-  return reinterpret_cast<unsigned long long*>(ws + (size_t)n_images * (PW_CTR_BYTES + (size_t)nb * PM_BOX_BYTES) +
-                                               (size_t)img * PW_KEY_BYTES);
-}
-
-// Position of this lane's candidate in the image's list, or -1 without one: one atomic per wave
-// with the number of lanes that have a candidate.  Every lane of the wave calls it together.
-__device__ __forceinline__ int wave_append(int* counter, bool want, int lane) {
-  const unsigned long long m = __ballot(want);
-  if (m == 0) return -1;  // wave-uniform
-  const int leader = __ffsll((long long)m) - 1;
-  int base = 0;
-  if (lane == leader) base = atomicAdd(counter, __popcll(m));  // device scope
-  base = __shfl(base, leader);
-  return want ? base + __popcll(m & ((1ull << lane) - 1ull)) : -1;
-}
+// (the parts of an image's workspace, ws_counters / ws_boxes / ws_keys, and wave_append: post_multi_dev.h,
+// shared with postprocess_dfl.hip)
 
 __global__ void __launch_bounds__(PW_DEC_THREADS) yolo_wide_clear_kernel(int* counters, int n_ints) {
   const int i = blockIdx.x * PW_DEC_THREADS + threadIdx.x;
@@ -257,10 +234,6 @@ yolo_wide_nms_kernel(const dnn_yolo_multi mh, const MultiPred pred, dnn_detectio
       merge_labels<PW_IDX_BITS, NEW_COORDS>(keys, mine, nk, t, S, C, stride, mh.class_mode == 1, bs, rows, max_det,
                                             &counts[img], tid);
   }
-}
-
-static unsigned long long wide_workspace(int nb, int n_images) {
-  return (unsigned long long)n_images * ((unsigned long long)nb * PM_BOX_BYTES + PW_KEY_BYTES + PW_CTR_BYTES);
 }
 
 template <int MODE, bool NEW_COORDS, class RULE>

@@ -86,6 +86,20 @@ class RuleStruct(ctypes.Structure):
     _fields_ = [("new_coords", ctypes.c_int), ("nms_kind", ctypes.c_int), ("beta_nms", ctypes.c_double)]
 
 
+DFL_MIN_REG, DFL_MAX_REG = 2, 16  # DNN_YOLO_DFL_MIN_REG, DNN_YOLO_DFL_MAX_REG
+
+
+class DflScaleStruct(ctypes.Structure):
+    """dnn_yolo_dfl_scale (include/dnn_hip_post.h)."""
+    _fields_ = [("grid_h", ctypes.c_int), ("grid_w", ctypes.c_int), ("stride", ctypes.c_float)]
+
+
+class DflStruct(ctypes.Structure):
+    """dnn_yolo_dfl (include/dnn_hip_post.h)."""
+    _fields_ = [("n_scales", ctypes.c_int), ("n_classes", ctypes.c_int), ("reg_max", ctypes.c_int),
+                ("score_thr", ctypes.c_float), ("iou_thr", ctypes.c_double), ("scale", DflScaleStruct * MAX_SCALES)]
+
+
 class ImageSize(ctypes.Structure):
     """dnn_image_size (include/dnn_hip_post.h)."""
     _fields_ = [("h", ctypes.c_int), ("w", ctypes.c_int)]
@@ -103,8 +117,12 @@ def _bind(lib):
     vp, i, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong
     hp, mp, pp = ctypes.POINTER(HeadStruct), ctypes.POINTER(MultiStruct), ctypes.POINTER(vp)
     fp, sp, bp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ImageSize), ctypes.POINTER(u64)
-    rp = ctypes.POINTER(RuleStruct)
+    rp, dp = ctypes.POINTER(RuleStruct), ctypes.POINTER(DflStruct)
     for name, argtypes in {  # every entry returns int
+            "dnn_yolo_dfl_boxes": [dp],
+            "dnn_yolo_dfl_workspace": [dp, i, bp],
+            "dnn_yolo_postprocess_dfl": [dp, pp, i, vp, i, vp, vp, u64, i, i, vp],
+            "dnn_yolo_postprocess_dfl_host": [dp, pp, i, vp, i, vp, i, i],
             "dnn_yolo_head_voc": [i, i, hp],
             "dnn_yolo_head_boxes": [hp],
             "dnn_yolo_head_workspace": [hp, i, bp],
@@ -418,6 +436,100 @@ class WideHead(MultiHead):
         kind = "_rule" if self.rule is not None else "" if self.xy is None else "_xy"
         return ("dnn_yolo_postprocess_wide" + kind + ("_host" if form == "host" else ""),
                 (NMS_MODES[self.nms], LABEL_MODES[self.labels]))
+
+
+DflScale = collections.namedtuple("DflScale", "grid_h grid_w stride")
+DflScale.__doc__ = """One scale of a DflHead: its grid and the network-input pixels per cell."""
+
+
+class DflHead(object):
+    """An anchor-free head with distribution-focal-loss boxes (YOLOv8, YOLO11; dnn_yolo_dfl,
+    csrc/postprocess_dfl.hip): `scales` is a sequence of 1..4 (grid_h, grid_w, stride), scale 0's grid
+    points first; a point has 4 * reg_max box logits (reg_max bins for each of left, top, right,
+    bottom) and then one logit per class, so scale s is predicted as [B, grid_h, grid_w,
+    4 * reg_max + classes].  The score of (point, class) is the sigmoid of its logit, there is no
+    objectness; boxes are decoded for the points with a score above score_thr only.  nms and labels
+    are MultiHead's ("multi" needs "per_class"), rows and codes too; at most 65536 points and 16384
+    candidates an image.  detect_batch_multi, MultiDetectionBuffers and label_boxes take it as they
+    take a MultiHead.  Validates like the C side (dnn_yolo_dfl_boxes) and raises ValueError."""
+
+    def __init__(self, scales, classes, reg_max=16, score_thr=0.25, iou_thr=0.45, nms="per_class", labels="argmax"):
+        scales = [tuple(s) for s in scales]
+        if not 1 <= len(scales) <= MAX_SCALES:
+            raise ValueError(f"{len(scales)} scales: need 1..{MAX_SCALES}")
+        if isinstance(classes, (int, np.integer)):
+            self.names, self.n_classes = None, int(classes)
+        else:
+            self.names = tuple(classes)
+            self.n_classes = len(self.names)
+        if not 1 <= self.n_classes <= MAX_CLASSES:
+            raise ValueError(f"{self.n_classes} classes: need 1..{MAX_CLASSES}")
+        if int(reg_max) != reg_max or not DFL_MIN_REG <= reg_max <= DFL_MAX_REG:
+            raise ValueError(f"reg_max {reg_max!r}: need {DFL_MIN_REG}..{DFL_MAX_REG}")
+        if nms not in NMS_MODES:
+            raise ValueError(f"nms {nms!r}: need one of {sorted(NMS_MODES)}")
+        if not isinstance(labels, str) or labels not in LABEL_MODES:
+            raise ValueError(f"labels {labels!r}: need one of {sorted(LABEL_MODES)}")
+        if labels == "multi" and nms != "per_class":
+            raise ValueError('labels "multi" needs nms "per_class": under the class-agnostic rule a box\'s second '
+                             "label is always suppressed by its first")
+        self.score_thr, self.iou_thr = float(score_thr), float(iou_thr)
+        if not (np.float32(self.score_thr) >= 0) or math.isnan(self.iou_thr):
+            raise ValueError(f"score_thr {score_thr!r} must be >= 0 and iou_thr {iou_thr!r} a number")
+        self.reg_max, self.nms, self.labels = int(reg_max), nms, labels
+        self.scales = []
+        for s in scales:
+            if len(s) != 3:
+                raise ValueError(f"scale {s!r}: (grid_h, grid_w, stride) expected")
+            gh, gw, stride = s
+            if int(gh) != gh or int(gw) != gw or gh < 1 or gw < 1:
+                raise ValueError(f"grid {gh} x {gw}: whole numbers of cells >= 1 expected")
+            if not (np.float32(stride) > 0 and np.isfinite(np.float32(stride))):
+                raise ValueError(f"stride {stride!r} must be a finite number of pixels > 0")
+            self.scales.append(DflScale(int(gh), int(gw), float(stride)))
+        self.scale_boxes = [s.grid_h * s.grid_w for s in self.scales]
+        self.boxes = sum(self.scale_boxes)
+        if self.boxes > WIDE_MAX_BOXES:
+            raise ValueError(f"{self.boxes} points over {len(self.scales)} scales: need <= {WIDE_MAX_BOXES}")
+        self.max_det = min(self.boxes * (1 if labels == "argmax" else self.n_classes), MULTI_MAX_CANDIDATES)
+        self.n_out = 4 * self.reg_max + self.n_classes
+        self.pred_shapes = [(s.grid_h, s.grid_w, self.n_out) for s in self.scales]
+        self.pred_floats = [h * w * c for h, w, c in self.pred_shapes]
+        self.c = DflStruct(len(self.scales), self.n_classes, self.reg_max, self.score_thr, self.iou_thr)
+        for k, s in enumerate(self.scales):
+            self.c.scale[k] = DflScaleStruct(*s)
+        n = _lib.dnn_yolo_dfl_boxes(ctypes.byref(self.c))
+        if n != self.boxes:
+            raise ValueError(f"dnn_yolo_dfl_boxes: {n}: {dnn_hip.last_error()}")
+
+    @classmethod
+    def for_input(cls, in_h, in_w, strides=(8, 16, 32), classes=80, **kw):
+        """The head of an in_h x in_w input: one scale per stride, in that order; both sizes must be
+        multiples of every stride."""
+        if any(st < 1 or int(st) != st or in_h < st or in_w < st or in_h % st or in_w % st for st in strides):
+            raise ValueError(f"input {in_h} x {in_w}: height and width must be multiples of the strides {tuple(strides)}")
+        return cls([(in_h // int(st), in_w // int(st), float(st)) for st in strides], classes, **kw)
+
+    def _entry(self, form):
+        """form "device", "host" or "workspace" -> (the C entry, its trailing mode arguments)."""
+        if form == "workspace":
+            return "dnn_yolo_dfl_workspace", ()
+        return ("dnn_yolo_postprocess_dfl" + ("_host" if form == "host" else ""),
+                (NMS_MODES[self.nms], LABEL_MODES[self.labels]))
+
+    def _call(self, form, args, last=()):
+        name, tail = self._entry(form)
+        dnn_hip._check(getattr(_lib, name)(ctypes.byref(self.c), *args, *tail, *last), name)
+
+    def workspace_bytes(self, n_images):
+        b = ctypes.c_ulonglong(0)
+        self._call("workspace", (n_images,), (ctypes.byref(b),))
+        return int(b.value)
+
+    def __repr__(self):
+        grids = ", ".join(f"{s.grid_h}x{s.grid_w}/{s.stride:g}" for s in self.scales)
+        return (f"DflHead({grids}; {self.n_classes} classes, reg_max {self.reg_max}, score > {self.score_thr:g}, "
+                f"IoU > {self.iou_thr:g}, NMS {self.nms}, labels {self.labels})")
 
 
 def detect_batch_multi(preds, head, max_det=None, raise_errors=True):

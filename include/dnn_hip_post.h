@@ -360,6 +360,85 @@ int dnn_yolo_postprocess_wide_rule_host(const dnn_yolo_multi* multi, const float
                                         const dnn_yolo_rule* rule, const float* const* pred, int n_images,
                                         dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode);
 
+/* ---- anchor-free heads: distribution focal loss (DFL) boxes, YOLOv8 / YOLO11 ------------------
+ * Such a head has no anchors and no objectness.  Per grid point it gives four discrete distributions
+ * over reg_max bins, one per box side (the distance from the point to the left, top, right and bottom
+ * edge, in cells), and one logit per class.  A dnn_yolo_dfl lists 1..DNN_YOLO_MAX_SCALES scales, each
+ * (grid_h, grid_w, stride) with stride the finite, positive number of network-input pixels per cell.
+ *
+ * Input: one tensor per scale, NHWC fp32, [n_images][grid_h][grid_w][4 * reg_max + n_classes].  The box
+ * logits come first, side-major: channel s * reg_max + k is bin k of side s in (left, top, right, bottom);
+ * the n_classes class logits follow (a Concat of the box and the class branch).
+ *
+ * Box index: the scales' points concatenated, scale 0 first, each scale in (row, col) order: the rule of
+ * the multi-scale entries above with one box per cell.
+ *
+ * Scores: p[c] = 1 / (1 + e ** -logit[c]) in fp32, the function of class_mode 1 above; there is no
+ * objectness factor, the score of (point, c) is p[c] itself.
+ *   DNN_YOLO_LABELS_ARGMAX  the point's class is the first index of the largest computed p (the rounded
+ *     values are compared; a NaN p never compares above another, and a NaN p[0] leaves the point
+ *     without a candidate, as in class_mode 1), and the point is a candidate iff that p > score_thr.
+ *   DNN_YOLO_LABELS_MULTI   every (point, c) with p[c] > score_thr is a candidate.
+ *
+ * Distance of a side from its reg_max logits x[0 .. reg_max), every operation one fp32 operation, never
+ * contracted, every sum ASCENDING in the bin index from bin 0 (((v0 + v1) + v2) + ...):
+ *   m = max x;  e[k] = exp(x[k] - m) (the fp32 exp of the class_mode 0 softmax);  sum = e[0] + e[1] + ...
+ *   p[k] = e[k] / sum;  d = p[0] * 0.0f + p[1] * 1.0f + ... (each product rounded, then added)
+ * Box of a candidate point at (row, col) of a scale, in network-input pixels:
+ *   x1 = (((float)col + 0.5f) - d_left) * stride     y1 = (((float)row + 0.5f) - d_top) * stride
+ *   x2 = (((float)col + 0.5f) + d_right) * stride    y2 = (((float)row + 0.5f) + d_bottom) * stride
+ * and the corners of its rows are these truncated toward zero, as above.  Only candidate points are
+ * decoded: counts[i] = -1 when a corner of a CANDIDATE point of image i is not finite or beyond +-2^61 (a
+ * NaN or +inf box logit, or a side whose logits are all -inf); the box logits of the other points are
+ * not read.
+ *
+ * Sort order, NMS rules (nms_mode / labels_mode: the wide entry's three pairs; (ANY_CLASS, MULTI)
+ * returns -2), rows and the codes -1, then -3, then -2 are those above, run by the same device code.
+ * Limits: DNN_YOLO_WIDE_MAX_BOXES points per image (640 x 640 at strides 8, 16, 32: 8,400; 1280 x 1280:
+ * 33,600) and DNN_YOLO_MULTI_MAX_CANDIDATES candidates per image in every mode, an image with more
+ * getting -3 and no rows.  With n_classes == 1 all three pairs are the same function.
+ *
+ * A call clears the per-image counters, runs the decode kernel over the grid and one NMS workgroup per
+ * image: three launches in that order on `stream`; it may be captured in a HIP graph.  An image's rows
+ * do not depend on the batch it is in.  Workspace: the wide entries' (per image 40 bytes per point,
+ * DNN_YOLO_MULTI_MAX_CANDIDATES 8-byte keys, a 64-byte counter block), 8-byte aligned.
+ * Returned -2 before any launch, dnn_last_error() naming the field: n_scales, n_classes, reg_max outside
+ * their ranges, a grid below one cell, a stride that is not finite and > 0, score_thr < 0 or NaN, a NaN
+ * iou_thr, more points than the limit, nms_mode / labels_mode as above, and the argument checks of the
+ * wide entries. */
+#define DNN_YOLO_DFL_MIN_REG 2
+#define DNN_YOLO_DFL_MAX_REG 16 /* a side's bins are one 16-lane row of a wave */
+
+typedef struct dnn_yolo_dfl_scale {
+  int grid_h, grid_w; /* cells */
+  float stride;       /* network-input pixels per cell; finite, > 0 */
+} dnn_yolo_dfl_scale;
+
+typedef struct dnn_yolo_dfl {
+  int n_scales;    /* 1..DNN_YOLO_MAX_SCALES */
+  int n_classes;   /* 1..DNN_YOLO_MAX_CLASSES */
+  int reg_max;     /* DNN_YOLO_DFL_MIN_REG..DNN_YOLO_DFL_MAX_REG bins per side */
+  float score_thr; /* >= 0 */
+  double iou_thr;
+  dnn_yolo_dfl_scale scale[DNN_YOLO_MAX_SCALES];
+} dnn_yolo_dfl;
+
+/* Grid points of one image, summed over the scales, or < 0 (message in dnn_last_error()) for an invalid
+ * description.  Host only: no device is touched. */
+int dnn_yolo_dfl_boxes(const dnn_yolo_dfl* dfl);
+
+int dnn_yolo_dfl_workspace(const dnn_yolo_dfl* dfl, int n_images, unsigned long long* bytes);
+
+/* Device pointers, asynchronous on `stream`; pred: a HOST array of n_scales device pointers.  Arguments
+ * and their checks are those of dnn_yolo_postprocess_wide. */
+int dnn_yolo_postprocess_dfl(const dnn_yolo_dfl* dfl, const float* const* pred, int n_images, dnn_detection* dets,
+                             int max_det, int* counts, void* workspace, unsigned long long workspace_bytes,
+                             int nms_mode, int labels_mode, void* stream);
+
+/* Host pointers, synchronous (allocates its scratch, copies in, runs, copies out). */
+int dnn_yolo_postprocess_dfl_host(const dnn_yolo_dfl* dfl, const float* const* pred, int n_images,
+                                  dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode);
+
 /* ---- boxes back to each image's own pixels ----------------------------------------------
  * The reference's frames are stretched to the network's size and its boxes stay in network
  * pixels.  After a letterbox ingest (include/dnn_hip_ingest.h: dnn_letterbox_frames) image i of
