@@ -277,9 +277,11 @@ __device__ __forceinline__ void nms_workgroup(unsigned long long* seg, int n, co
 // Phases 2 and 3 of the class-agnostic rule, and the emit, by the whole workgroup of THREADS: sorts
 // the n candidates of keys (key_any, padded with ~0ull to pow2 >= n), runs nms_workgroup and writes
 // the first max_det kept boxes to rows and their number (-2: a zero IoU denominator) to *count.
+// points (may be NULL): points[r] = the global box index that row r came from, by the thread that writes the row.
 template <int THREADS>
 __device__ __forceinline__ void nms_any_emit(unsigned long long* keys, int n, const BoxStore& bs, double iou_thr,
-                                             NmsState& st, dnn_detection* rows, int max_det, int* count, int tid) {
+                                             NmsState& st, dnn_detection* rows, int max_det, int* count, int tid,
+                                             int* points = nullptr) {
   int ns = 1;
   while (ns < n) ns <<= 1;
   bitonic_sort<THREADS>(keys, ns, tid);
@@ -293,6 +295,7 @@ __device__ __forceinline__ void nms_any_emit(unsigned long long* keys, int n, co
   for (int r = tid; r < nw; r += THREADS) {
     const int k = kept[r];
     emit_row(rows + r, bs.cls[k], bs.score[k], bs.box[k]);
+    if (points) points[r] = k;
   }
   if (tid == 0) *count = nk;
 }

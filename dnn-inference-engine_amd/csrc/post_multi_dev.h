@@ -460,9 +460,11 @@ __device__ __forceinline__ void gather_kept(const unsigned long long* keys, int 
 }
 
 // Phase 4 with one label a box: the gathered box indices (no class) back as dense key_any keys,
-// sorted over pow2 >= nk by (score descending, global index), the first max_det emitted.
+// sorted over pow2 >= nk by (score descending, global index), the first max_det emitted.  points: as
+// nms_any_emit's (post_dev.h).
 __device__ __forceinline__ void merge_single(unsigned long long* keys, const int (&mine)[16], int nk, const BoxStore& bs,
-                                             dnn_detection* rows, int max_det, int* count, int tid) {
+                                             dnn_detection* rows, int max_det, int* count, int tid,
+                                             int* points = nullptr) {
   int ns2 = 1;
   while (ns2 < nk) ns2 <<= 1;
 #pragma unroll
@@ -479,6 +481,7 @@ __device__ __forceinline__ void merge_single(unsigned long long* keys, const int
   for (int r = tid; r < nw; r += PM_THREADS) {
     const int k = key_any_index(keys[r]);
     emit_row(rows + r, bs.cls[k], bs.score[k], bs.box[k]);
+    if (points) points[r] = k;
   }
   if (tid == 0) *count = nk;
 }
@@ -492,10 +495,12 @@ __device__ __forceinline__ void merge_single(unsigned long long* keys, const int
 // only ones still unread.  The padding of the sort starts at byte 8 nk, above the whole list.  The
 // score is recomputed by label_score from the stored conf (and sum) and the box's logits, the bits
 // it was sorted on.  Sorted by (score descending, global index, class), the first max_det emitted.
+// points: as nms_any_emit's (post_dev.h); two rows may share a point.
 template <int IDX_BITS, bool NEW_COORDS = false>
 __device__ __forceinline__ void merge_labels(unsigned long long* keys, const int (&mine)[16], int nk, const ScaleTab& t,
                                              int S, int C, int stride, bool logistic, const BoxStore& bs,
-                                             dnn_detection* rows, int max_det, int* count, int tid) {
+                                             dnn_detection* rows, int max_det, int* count, int tid,
+                                             int* points = nullptr) {
   int* dense = reinterpret_cast<int*>(keys);
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
@@ -526,6 +531,7 @@ __device__ __forceinline__ void merge_labels(unsigned long long* keys, const int
   for (int r = tid; r < nw; r += PM_THREADS) {
     const unsigned long long key = keys[r];
     emit_row(rows + r, key_merge_class(key), key_merge_score<IDX_BITS>(key), bs.box[key_merge_index<IDX_BITS>(key)]);
+    if (points) points[r] = key_merge_index<IDX_BITS>(key);
   }
   if (tid == 0) *count = nk;
 }

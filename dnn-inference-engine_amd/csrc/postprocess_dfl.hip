@@ -54,7 +54,7 @@
 // pointer, (row, col, scale), a score and a class, and sigmoid_ref's double exp2 takes the rest: 66 to 74
 // VGPRs, six waves a SIMD.  NMS: 128 KiB of keys + the table + ClassState, as postprocess_wide.hip.
 #include <cfloat>
-#include "post_multi_dev.h"
+#include "post_dfl_host.h"
 
 namespace dnnhip {
 
@@ -290,7 +290,7 @@ yolo_dfl_decode_kernel(const dnn_yolo_dfl h, const MultiPred pred, char* workspa
 template <int MODE>
 __global__ void __launch_bounds__(PM_THREADS)
 yolo_dfl_nms_kernel(const dnn_yolo_dfl h, const MultiPred pred, dnn_detection* __restrict__ dets, int max_det,
-                    int* __restrict__ counts, char* workspace, int nb, int n_images) {
+                    int* __restrict__ counts, char* workspace, int nb, int n_images, int* __restrict__ points) {
   __shared__ unsigned long long keys[PM_CAP];
   __shared__ ScaleTab t;  // the multi-label merge reads the class logits again
   __shared__ typename std::conditional<MODE == PD_ANY, NmsState, ClassState>::type st;
@@ -303,6 +303,7 @@ yolo_dfl_nms_kernel(const dnn_yolo_dfl h, const MultiPred pred, dnn_detection* _
   const BoxStore bs = box_store(ws_boxes(workspace, img, nb, n_images), nb);
   const unsigned long long* gkeys = ws_keys(workspace, img, nb, n_images);
   dnn_detection* rows = dets + (size_t)img * max_det;
+  int* pts = points ? points + (size_t)img * max_det : nullptr;  // row r came from grid point pts[r]
 
   const int n = ctr[0];  // workgroup-uniform, like the two exits below
   if (ctr[1]) {
@@ -328,7 +329,7 @@ yolo_dfl_nms_kernel(const dnn_yolo_dfl h, const MultiPred pred, dnn_detection* _
   __syncthreads();
 
   if constexpr (MODE == PD_ANY) {
-    nms_any_emit<PM_THREADS>(keys, n, bs, rule.thr, st, rows, max_det, &counts[img], tid);
+    nms_any_emit<PM_THREADS>(keys, n, bs, rule.thr, st, rows, max_det, &counts[img], tid, pts);
   } else {
     if (wid == 0) wave_scan_128(st.cls_cnt, C, st.seg_start, lane);
     bitonic_sort<PM_THREADS>(keys, ns, tid);
@@ -341,15 +342,15 @@ yolo_dfl_nms_kernel(const dnn_yolo_dfl h, const MultiPred pred, dnn_detection* _
     int mine[16];
     gather_kept<PW_IDX_BITS, MODE == PD_MULTI>(keys, C, nk, st, mine, tid);
     if (MODE == PD_PER_CLASS)
-      merge_single(keys, mine, nk, bs, rows, max_det, &counts[img], tid);
+      merge_single(keys, mine, nk, bs, rows, max_det, &counts[img], tid, pts);
     else
-      merge_labels<PW_IDX_BITS>(keys, mine, nk, t, S, C, 4 * h.reg_max + C, true, bs, rows, max_det, &counts[img], tid);
+      merge_labels<PW_IDX_BITS>(keys, mine, nk, t, S, C, 4 * h.reg_max + C, true, bs, rows, max_det, &counts[img], tid,
+                                pts);
   }
 }
 
 // ---- host side -------------------------------------------------------------------------------------
-// < 0 with the error set (it names the field), else the grid points of one image over all scales
-static int dfl_boxes(const dnn_yolo_dfl* h, const char* who) {
+int dfl_boxes(const dnn_yolo_dfl* h, const char* who) {
   DNN_REQUIRE(h, "%s: NULL description", who);
   DNN_REQUIRE(h->n_scales >= 1 && h->n_scales <= DNN_YOLO_MAX_SCALES, "%s: %d scales: need 1..%d", who, h->n_scales,
               DNN_YOLO_MAX_SCALES);
@@ -375,22 +376,7 @@ static int dfl_boxes(const dnn_yolo_dfl* h, const char* who) {
   return (int)total;
 }
 
-struct DflCall {  // the arguments of an entry as its caller gave them (the host form: no workspace)
-  const char* who;
-  const dnn_yolo_dfl* h;
-  const float* const* pred;
-  int n_images;
-  dnn_detection* dets;
-  int max_det;
-  int* counts;
-  void* workspace;
-  unsigned long long workspace_bytes;
-  int nms_mode, labels_mode;
-};
-
-// Every argument check, in the wide entries' order: the description, the modes, counts and pointers, pred[s],
-// and unless `host` the workspace.  < 0 with the error set; 0 with nothing to do; 1 with *nb and *mp filled.
-static int check_dfl_call(const DflCall& c, bool host, int* nb, MultiPred* mp) {
+int check_dfl_call(const DflCall& c, bool host, int* nb, MultiPred* mp) {
   *nb = dfl_boxes(c.h, c.who);
   if (*nb < 0) return *nb;
   if (!multi_modes_ok(c.nms_mode, c.labels_mode, c.who)) return -2;
@@ -418,10 +404,10 @@ static void launch_dfl_kernels(const DflCall& c, const MultiPred& mp, int nb, bo
   const auto decode = vec ? yolo_dfl_decode_kernel<MODE, true> : yolo_dfl_decode_kernel<MODE, false>;
   hipLaunchKernelGGL(decode, grid, dim3(PD_THREADS), 0, stream, *c.h, mp, ws, nb, c.n_images);
   hipLaunchKernelGGL(yolo_dfl_nms_kernel<MODE>, dim3(c.n_images), dim3(PM_THREADS), 0, stream, *c.h, mp, c.dets,
-                     c.max_det, c.counts, ws, nb, c.n_images);
+                     c.max_det, c.counts, ws, nb, c.n_images, c.points);
 }
 
-static int launch_yolo_dfl(const DflCall& c, hipStream_t stream) {
+int launch_yolo_dfl(const DflCall& c, hipStream_t stream) {
   int nb;
   MultiPred mp;
   const int go = check_dfl_call(c, false, &nb, &mp);

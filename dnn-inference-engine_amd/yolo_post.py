@@ -100,6 +100,15 @@ class DflStruct(ctypes.Structure):
                 ("score_thr", ctypes.c_float), ("iou_thr", ctypes.c_double), ("scale", DflScaleStruct * MAX_SCALES)]
 
 
+SEG_COEFS, SEG_MAX_SIDE = (16, 32, 48, 64), 1024  # dnn_yolo_seg's n_coef values, DNN_YOLO_SEG_MAX_SIDE
+
+
+class SegStruct(ctypes.Structure):
+    """dnn_yolo_seg (include/dnn_hip_post.h)."""
+    _fields_ = [("n_coef", ctypes.c_int), ("mask_h", ctypes.c_int), ("mask_w", ctypes.c_int),
+                ("net_h", ctypes.c_int), ("net_w", ctypes.c_int), ("max_masks", ctypes.c_int)]
+
+
 class ImageSize(ctypes.Structure):
     """dnn_image_size (include/dnn_hip_post.h)."""
     _fields_ = [("h", ctypes.c_int), ("w", ctypes.c_int)]
@@ -117,12 +126,16 @@ def _bind(lib):
     vp, i, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_ulonglong
     hp, mp, pp = ctypes.POINTER(HeadStruct), ctypes.POINTER(MultiStruct), ctypes.POINTER(vp)
     fp, sp, bp = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ImageSize), ctypes.POINTER(u64)
-    rp, dp = ctypes.POINTER(RuleStruct), ctypes.POINTER(DflStruct)
+    rp, dp, gp = ctypes.POINTER(RuleStruct), ctypes.POINTER(DflStruct), ctypes.POINTER(SegStruct)
     for name, argtypes in {  # every entry returns int
             "dnn_yolo_dfl_boxes": [dp],
             "dnn_yolo_dfl_workspace": [dp, i, bp],
             "dnn_yolo_postprocess_dfl": [dp, pp, i, vp, i, vp, vp, u64, i, i, vp],
             "dnn_yolo_postprocess_dfl_host": [dp, pp, i, vp, i, vp, i, i],
+            "dnn_yolo_seg_mask_words": [gp],
+            "dnn_yolo_dfl_seg_workspace": [dp, gp, i, i, bp],
+            "dnn_yolo_postprocess_dfl_seg": [dp, gp, pp, pp, vp, i, vp, i, vp, vp, vp, u64, i, i, vp],
+            "dnn_yolo_postprocess_dfl_seg_host": [dp, gp, pp, pp, vp, i, vp, i, vp, vp, i, i],
             "dnn_yolo_head_voc": [i, i, hp],
             "dnn_yolo_head_boxes": [hp],
             "dnn_yolo_head_workspace": [hp, i, bp],
@@ -451,10 +464,17 @@ class DflHead(object):
     objectness; boxes are decoded for the points with a score above score_thr only.  nms and labels
     are MultiHead's ("multi" needs "per_class"), rows and codes too; at most 65536 points and 16384
     candidates an image.  detect_batch_multi, MultiDetectionBuffers and label_boxes take it as they
-    take a MultiHead.  Validates like the C side (dnn_yolo_dfl_boxes) and raises ValueError."""
+    take a MultiHead.  mask_dim (None, or 16, 32, 48 or 64: the mask coefficients per grid point of a
+    segmentation model, 32 in the public ones) adds `coef_shapes`, the coefficient branch per scale, and
+    `seg()`; detect_batch_masks and MaskDetectionBuffers then give the rows with their instance masks.
+    Validates like the C side (dnn_yolo_dfl_boxes) and raises ValueError."""
 
-    def __init__(self, scales, classes, reg_max=16, score_thr=0.25, iou_thr=0.45, nms="per_class", labels="argmax"):
+    def __init__(self, scales, classes, reg_max=16, score_thr=0.25, iou_thr=0.45, nms="per_class", labels="argmax",
+                 mask_dim=None):
         scales = [tuple(s) for s in scales]
+        if mask_dim is not None and mask_dim not in SEG_COEFS:
+            raise ValueError(f"mask_dim {mask_dim!r}: need None or one of {SEG_COEFS}")
+        self.mask_dim = None if mask_dim is None else int(mask_dim)
         if not 1 <= len(scales) <= MAX_SCALES:
             raise ValueError(f"{len(scales)} scales: need 1..{MAX_SCALES}")
         if isinstance(classes, (int, np.integer)):
@@ -501,6 +521,15 @@ class DflHead(object):
         n = _lib.dnn_yolo_dfl_boxes(ctypes.byref(self.c))
         if n != self.boxes:
             raise ValueError(f"dnn_yolo_dfl_boxes: {n}: {dnn_hip.last_error()}")
+        if self.mask_dim is not None:
+            self.coef_shapes = [(s.grid_h, s.grid_w, self.mask_dim) for s in self.scales]
+
+    def seg(self, mask_hw, net_hw, max_masks=300):
+        """The SegSpec of a mask_hw = (h, w) prototype map for a net_hw = (h, w) network input, masks for
+        the first max_masks rows of an image."""
+        if self.mask_dim is None:
+            raise ValueError("this head has no mask coefficients: construct it with mask_dim")
+        return SegSpec(self.mask_dim, mask_hw, net_hw, max_masks)
 
     @classmethod
     def for_input(cls, in_h, in_w, strides=(8, 16, 32), classes=80, **kw):
@@ -528,8 +557,48 @@ class DflHead(object):
 
     def __repr__(self):
         grids = ", ".join(f"{s.grid_h}x{s.grid_w}/{s.stride:g}" for s in self.scales)
+        masks = "" if self.mask_dim is None else f", mask_dim {self.mask_dim}"
         return (f"DflHead({grids}; {self.n_classes} classes, reg_max {self.reg_max}, score > {self.score_thr:g}, "
-                f"IoU > {self.iou_thr:g}, NMS {self.nms}, labels {self.labels})")
+                f"IoU > {self.iou_thr:g}, NMS {self.nms}, labels {self.labels}{masks})")
+
+
+class SegSpec(object):
+    """dnn_yolo_seg: n_coef mask coefficients, a mask_hw = (h, w) prototype map, the net_hw = (h, w) frame the
+    rows' corners are in, and masks for rows 0..min(count, max_masks)-1 (max_masks must not exceed the max_det
+    of the call).  A mask is mask_h rows of w32 = ceil(mask_w / 32) words.  Validates like the C side
+    (dnn_yolo_seg_mask_words) and raises ValueError."""
+
+    def __init__(self, n_coef, mask_hw, net_hw, max_masks=300):
+        (mh, mw), (nh, nw) = mask_hw, net_hw
+        if n_coef not in SEG_COEFS:
+            raise ValueError(f"n_coef {n_coef!r}: need one of {SEG_COEFS}")
+        for name, v, hi in (("mask_h", mh, SEG_MAX_SIDE), ("mask_w", mw, SEG_MAX_SIDE), ("net_h", nh, 2 ** 31 - 1),
+                            ("net_w", nw, 2 ** 31 - 1), ("max_masks", max_masks, MULTI_MAX_CANDIDATES)):
+            if int(v) != v or not 1 <= v <= hi:
+                raise ValueError(f"{name} {v!r}: need a whole number in 1..{hi}")
+        self.n_coef, self.mask_h, self.mask_w, self.net_h, self.net_w = int(n_coef), int(mh), int(mw), int(nh), int(nw)
+        self.max_masks, self.w32 = int(max_masks), (int(mw) + 31) // 32
+        self.c = SegStruct(self.n_coef, self.mask_h, self.mask_w, self.net_h, self.net_w, self.max_masks)
+        n = _lib.dnn_yolo_seg_mask_words(ctypes.byref(self.c))
+        if n != self.mask_h * self.w32:
+            raise ValueError(f"dnn_yolo_seg_mask_words: {n}: {dnn_hip.last_error()}")
+        self.proto_shape = (self.mask_h, self.mask_w, self.n_coef)
+
+    def workspace_bytes(self, head, n_images, max_det):
+        b = ctypes.c_ulonglong(0)
+        dnn_hip._check(_lib.dnn_yolo_dfl_seg_workspace(ctypes.byref(head.c), ctypes.byref(self.c), n_images, max_det,
+                                                       ctypes.byref(b)), "dnn_yolo_dfl_seg_workspace")
+        return int(b.value)
+
+    def unpack(self, words, n_rows):
+        """uint32 [max_masks, mask_h, w32] of one image -> bool [n_rows, mask_h, mask_w]."""
+        w = np.ascontiguousarray(words[:n_rows], dtype="<u4")
+        bits = np.unpackbits(w.view(np.uint8).reshape(n_rows, self.mask_h, self.w32 * 4), axis=2, bitorder="little")
+        return bits[:, :, :self.mask_w].astype(bool)
+
+    def __repr__(self):
+        return (f"SegSpec({self.n_coef} coefficients, {self.mask_h}x{self.mask_w} masks of a {self.net_h}x{self.net_w} "
+                f"input, {self.max_masks} masks)")
 
 
 def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
@@ -551,6 +620,38 @@ def detect_batch_multi(preds, head, max_det=None, raise_errors=True):
     ptrs = (ctypes.c_void_p * len(ps))(*[p.ctypes.data for p in ps])
     head._call("host", (ptrs, n, dets.ctypes.data, max_det, counts.ctypes.data))
     return _rows(dets, counts, max_det, raise_errors)
+
+
+def detect_batch_masks(preds, coefs, protos, head, spec, max_det=None, raise_errors=True):
+    """detect_batch_multi for a DflHead with mask_dim, with the instance masks: coefs is one fp32 host array
+    per scale, [B, *head.coef_shapes[s]], protos [B, *spec.proto_shape] -> (rows, masks): rows exactly
+    detect_batch_multi's, masks[i] a bool array [min(count_i, spec.max_masks), mask_h, mask_w] at prototype
+    resolution (empty for an image with a code).  Upsampling to image pixels is the caller's."""
+    if head.mask_dim != spec.n_coef:
+        raise ValueError(f"head.mask_dim {head.mask_dim} and the spec's {spec.n_coef} coefficients differ")
+    if len(preds) != len(head.scales) or len(coefs) != len(head.scales):
+        raise ValueError(f"{len(preds)} prediction and {len(coefs)} coefficient tensors for {len(head.scales)} scales")
+    ps = [np.ascontiguousarray(p, dtype=np.float32) for p in preds]
+    cs = [np.ascontiguousarray(c, dtype=np.float32) for c in coefs]
+    pr = np.ascontiguousarray(protos, dtype=np.float32)
+    n = ps[0].size // head.pred_floats[0]
+    if any(p.size != n * f for p, f in zip(ps, head.pred_floats)) or \
+            any(c.size != n * int(np.prod(sh)) for c, sh in zip(cs, head.coef_shapes)) or \
+            pr.size != n * int(np.prod(spec.proto_shape)):
+        raise ValueError(f"predictions {[p.shape for p in ps]}, coefficients {[c.shape for c in cs]} and prototypes "
+                         f"{pr.shape} are not {n} images of {head.pred_shapes}, {head.coef_shapes}, {spec.proto_shape}")
+    max_det = head.max_det if max_det is None else max_det
+    dets = np.zeros((n, max_det), DETECTION_DTYPE)
+    counts = np.zeros(n, np.int32)
+    words = np.zeros((n, spec.max_masks, spec.mask_h, spec.w32), np.uint32)
+    pp = (ctypes.c_void_p * len(ps))(*[p.ctypes.data for p in ps])
+    cp = (ctypes.c_void_p * len(cs))(*[c.ctypes.data for c in cs])
+    dnn_hip._check(_lib.dnn_yolo_postprocess_dfl_seg_host(
+        ctypes.byref(head.c), ctypes.byref(spec.c), pp, cp, pr.ctypes.data, n, dets.ctypes.data, max_det,
+        counts.ctypes.data, words.ctypes.data, NMS_MODES[head.nms], LABEL_MODES[head.labels]),
+        "dnn_yolo_postprocess_dfl_seg_host")
+    rows = _rows(dets, counts, max_det, raise_errors)
+    return rows, [spec.unpack(words[i], max(0, min(int(c), spec.max_masks))) for i, c in enumerate(counts)]
 
 
 def _rows(dets, counts, max_det, raise_errors=True):
@@ -724,3 +825,38 @@ class MultiDetectionBuffers(DetectionBuffers):
         ptrs = (ctypes.c_void_p * len(pred_ptrs))(*[int(p) for p in pred_ptrs])
         self.head._call("device", (ptrs, n, self.dets.data_ptr(), self.max_det, self.counts.data_ptr(),
                                    self.workspace.data_ptr(), self.workspace.numel()), (stream,))
+
+
+class MaskDetectionBuffers(MultiDetectionBuffers):
+    """MultiDetectionBuffers for a DflHead with mask_dim and a SegSpec: also owns masks, uint32
+    [n, max_masks, mask_h, w32] on the device, and the larger workspace; `run(pred_ptrs, coef_ptrs, proto_ptr, n,
+    stream)` goes through dnn_yolo_postprocess_dfl_seg (device pointers, 16-byte aligned, asynchronous), and
+    `masks_to_host(n)` unpacks what it wrote."""
+
+    def __init__(self, n, device, head, spec, max_det=None):
+        import torch
+        MultiDetectionBuffers.__init__(self, n, device, head, max_det)
+        if head.mask_dim != spec.n_coef:
+            raise ValueError(f"head.mask_dim {head.mask_dim} and the spec's {spec.n_coef} coefficients differ")
+        self.spec = spec
+        self.workspace = torch.zeros(spec.workspace_bytes(head, n, self.max_det), dtype=torch.uint8, device=device)
+        self.masks = torch.zeros((n, spec.max_masks, spec.mask_h, spec.w32), dtype=torch.int32, device=device)
+
+    def run(self, pred_ptrs, coef_ptrs, proto_ptr, n, stream):
+        S = len(self.head.scales)
+        if n > self.n or len(pred_ptrs) != S or len(coef_ptrs) != S:
+            raise ValueError(f"{n} images, {len(pred_ptrs)} prediction and {len(coef_ptrs)} coefficient pointers for "
+                             f"buffers of {self.n} images and {S} scales")
+        pp = (ctypes.c_void_p * S)(*[int(p) for p in pred_ptrs])
+        cp = (ctypes.c_void_p * S)(*[int(p) for p in coef_ptrs])
+        dnn_hip._check(_lib.dnn_yolo_postprocess_dfl_seg(
+            ctypes.byref(self.head.c), ctypes.byref(self.spec.c), pp, cp, int(proto_ptr), n, self.dets.data_ptr(),
+            self.max_det, self.counts.data_ptr(), self.masks.data_ptr(), self.workspace.data_ptr(),
+            self.workspace.numel(), NMS_MODES[self.head.nms], LABEL_MODES[self.head.labels], stream),
+            "dnn_yolo_postprocess_dfl_seg")
+
+    def masks_to_host(self, n):
+        """Synchronises: per image the bool masks detect_batch_masks returns."""
+        counts = self.counts[:n].cpu().numpy()
+        words = self.masks[:n].cpu().numpy().view(np.uint32)
+        return [self.spec.unpack(words[i], max(0, min(int(c), self.spec.max_masks))) for i, c in enumerate(counts)]

@@ -439,6 +439,65 @@ int dnn_yolo_postprocess_dfl(const dnn_yolo_dfl* dfl, const float* const* pred, 
 int dnn_yolo_postprocess_dfl_host(const dnn_yolo_dfl* dfl, const float* const* pred, int n_images,
                                   dnn_detection* dets, int max_det, int* counts, int nms_mode, int labels_mode);
 
+/* ---- instance masks for the anchor-free heads (YOLOv8-seg / YOLO11-seg) -----------------------
+ * A segmentation model adds, per scale, a branch of n_coef mask coefficients per grid point, and one
+ * prototype tensor of n_coef channels at a quarter of the input resolution.  The mask of a detection is
+ * the sign of coef . proto at every prototype pixel, cropped to the detection's box.
+ *
+ * Inputs beyond the DFL decode's: coef, a HOST array of n_scales device pointers, coef[s] =
+ * [n_images][grid_h][grid_w][n_coef] fp32 NHWC, and proto, [n_images][mask_h][mask_w][n_coef] fp32 NHWC;
+ * every coef[s] and proto 16-byte aligned.
+ *
+ * dets and counts are, bit for bit, what dnn_yolo_postprocess_dfl writes for the same pred and modes, and
+ * the per-image codes are exactly its codes.  Masks are made for rows k < min(counts[i], max_masks) of an
+ * image with counts[i] >= 0:
+ *   logit(k, y, x) = sum_c coef[point(k)][c] * proto[y][x][c] in fp32, in the kernel's own order (fp32
+ *     MFMA 16x16x4, four channel quarters side by side); point(k) is the grid point row k came from, in
+ *     the global point order (two multi-label rows may share one).
+ *   crop (ultralytics' crop_mask rule without its rounding): left, right clamped to [0, net_w] and top,
+ *     bottom to [0, net_h]; pixel (x, y) is inside iff x * net_w >= left * mask_w, x * net_w < right *
+ *     mask_w, y * net_h >= top * mask_h and y * net_h < bottom * mask_h, in 64-bit integers.  An empty
+ *     or outside box gives an all-zero mask.
+ *   masks: unsigned int [n_images][max_masks][mask_h][W32], W32 = (mask_w + 31) / 32; bit x % 32 of word
+ *     x / 32 of row y is 1 iff the pixel is inside the crop and logit > 0 (a NaN logit gives 0).  Every
+ *     word of rows k < min(counts[i], max_masks) is written, zeros outside the crop and in the padding
+ *     bits; the other rows, and every row of an image with a negative code, are not touched.
+ *
+ * Workspace: dnn_yolo_dfl_seg_workspace bytes (the DFL decode's, then per image max_det point indices and
+ * max_masks coefficient rows and crop rectangles), 16-byte aligned.  A call runs the DFL decode's three
+ * kernels, a gather kernel and the mask kernel on `stream`, nothing but kernels; it may be captured in a
+ * HIP graph.  Returned nonzero before any device call, dnn_last_error() naming the field: n_coef not 16,
+ * 32, 48 or 64; mask_h or mask_w outside 1..DNN_YOLO_SEG_MAX_SIDE; net_h or net_w not positive; max_masks
+ * outside 1..max_det; coef, coef[s], proto or masks NULL or (the inputs) misaligned; a workspace that is
+ * too small or misaligned; and every check of dnn_yolo_postprocess_dfl.  Upsampling a mask to image
+ * pixels and mapping it through a letterbox are the caller's. */
+#define DNN_YOLO_SEG_MAX_SIDE 1024
+
+typedef struct dnn_yolo_seg {
+  int n_coef;         /* nm: 16, 32, 48 or 64 (public models: 32) */
+  int mask_h, mask_w; /* prototype map, pixels; each 1..DNN_YOLO_SEG_MAX_SIDE */
+  int net_h, net_w;   /* network input, pixels: the frame the rows' corners are in */
+  int max_masks;      /* 1..max_det: masks are made for rows 0..min(count, max_masks)-1 */
+} dnn_yolo_seg;
+
+/* mask_h * W32, the words of one mask, or < 0 (message in dnn_last_error()).  Host only. */
+int dnn_yolo_seg_mask_words(const dnn_yolo_seg* seg);
+
+int dnn_yolo_dfl_seg_workspace(const dnn_yolo_dfl* dfl, const dnn_yolo_seg* seg, int n_images, int max_det,
+                               unsigned long long* bytes);
+
+/* Device pointers (pred, coef: HOST arrays of device pointers), asynchronous on `stream`. */
+int dnn_yolo_postprocess_dfl_seg(const dnn_yolo_dfl* dfl, const dnn_yolo_seg* seg, const float* const* pred,
+                                 const float* const* coef, const float* proto, int n_images, dnn_detection* dets,
+                                 int max_det, int* counts, unsigned int* masks, void* workspace,
+                                 unsigned long long workspace_bytes, int nms_mode, int labels_mode, void* stream);
+
+/* Host pointers, synchronous (allocates its scratch, copies in, masks included, runs, copies out). */
+int dnn_yolo_postprocess_dfl_seg_host(const dnn_yolo_dfl* dfl, const dnn_yolo_seg* seg, const float* const* pred,
+                                      const float* const* coef, const float* proto, int n_images,
+                                      dnn_detection* dets, int max_det, int* counts, unsigned int* masks,
+                                      int nms_mode, int labels_mode);
+
 /* ---- boxes back to each image's own pixels ----------------------------------------------
  * The reference's frames are stretched to the network's size and its boxes stay in network
  * pixels.  After a letterbox ingest (include/dnn_hip_ingest.h: dnn_letterbox_frames) image i of
